@@ -11,9 +11,18 @@ window is part of the metric and is printed in `config`).  value = steps * windo
 whole job.  With N > 1 the SAME matrix is row-partitioned over the N GPUs (BASELINE config 4) => "scaling": "strong".
 Inputs are synthetic (SURVEY 8d generators), resident in HBM before the timed region starts.
 
-Extra objects on the JSON line: `roofline` (the CSR SpMV kernel: algorithmic bytes / HIP-event time on the stream
-it is launched on, against the 8 TB/s HBM peak), `roofline_orth` (the Gram-Schmidt kernels of the timed windows) and
-`cpu_baseline` (the real reference — or the oracle port — on the host cores of the same machine, bounded sample).
+A plain run sets up, warms up, times the steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`,
+`dtype`, ...).  `--full` adds everything else, each measured in the same process: `roofline` (the CSR SpMV kernel:
+algorithmic bytes / HIP-event time on the stream it is launched on, against the 8 TB/s HBM peak and the measured
+streaming ceilings), `roofline_orth` and `phases` (the Gram-Schmidt kernels and the per-phase split of instrumented
+steps after the timed region), `value_host_io` / `value_device_io` (the same steps through the other I/O boundary),
+`cpu_baseline*` (the real reference — or the oracle port — on the host cores of the same machine, bounded sample) and,
+for config 3, `callback_path` and `other_configs` (configs 2 and 5).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float64): eigenvalues,
+iteration counts and the eigenvector (LambdaLanczos), or the output vector and its iteration count (Exponentiator).
+Vectors larger than DUMP_FULL_BYTES are written as a fixed, seeded sample of DUMP_SAMPLE entries plus the sampled
+indices (<name>_index.npy).  The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -83,7 +92,18 @@ def parse_args():
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="CPU-only check of the multi-process plumbing (rendezvous, id broadcast, partition, shard "
                          "generation, reductions over ranks); no device work, prints one JSON line per job")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (SpMV roofline and streaming ceilings, the other "
+                         "I/O boundary, per-phase timers, CPU baselines and parity, callback path, configs 2 / 5); the "
+                         "options above that tune those legs only take effect with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def spmv_bytes(n, nnz, complex_):
@@ -144,6 +164,35 @@ def pmc_orth_traffic(workload, window):
     if d.get("window_iterations") != window or "orth_bytes_per_window" not in d:
         return None, None
     return d["orth_bytes_per_window"], os.path.relpath(files[-1], ROOT)
+
+
+DUMP_FULL_BYTES = 32 << 20  # a vector up to this size is dumped whole ...
+DUMP_SAMPLE = 1 << 21       # ... a larger one as this many entries at fixed indices (DUMP_SEED) plus the indices
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, arrays, n, row_begin, n_local, rank, world):
+    """Write {name: array} as dirname/<name>.npy in float64 (complex: <name>_real and <name>_imag).  Scalars and short
+    arrays go from rank 0; a vector of the local row shard (length n_local) is written whole when the whole vector is small
+    and as a seeded sample of global rows otherwise; with several ranks every rank writes its own rows under
+    <name>_rank<r>."""
+    os.makedirs(dirname, exist_ok=True)
+    sample = None
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        is_vector = a.ndim == 1 and a.shape[0] == n_local
+        if not is_vector and rank != 0:
+            continue
+        parts = {name + "_real": a.real, name + "_imag": a.imag} if np.iscomplexobj(a) else {name: a}
+        suffix = "_rank%d" % rank if (is_vector and world > 1) else ""
+        if is_vector and len(parts) * n * 8 > DUMP_FULL_BYTES:   # size of the whole vector over all ranks
+            if sample is None:
+                rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+                sample = rows[(rows >= row_begin) & (rows < row_begin + n_local)]
+            parts = {k: p[sample - row_begin] for k, p in parts.items()}
+            parts[name + "_index"] = sample
+        for k, p in parts.items():
+            np.save(os.path.join(dirname, k + suffix + ".npy"), np.ascontiguousarray(p, dtype=np.float64))
 
 
 STAGE = ["start"]  # where the job is, for the watchdog's diagnostic
@@ -543,41 +592,44 @@ def main():
                            "how": "3 SpMVs per combination behind one warm-up, HIP events on the library stream, max over ranks; "
                                   "the operator of the timed steps is the picked one"}
 
-    spmv_ms = time_spmv(op)
-    spmv_variants = {"%s [%s]" % (kernel_names[selected], phase2_form) if selected == L.capi.SPMV_PB else kernel_names[selected]: spmv_ms}
-    spmv_gbs = b_spmv / (spmv_ms * 1e-3) / 1e9
-    if selected == L.capi.SPMV_PB and world == 1 and not args.no_spmv_variants:
-        # The other two phase-2 forms on the SAME matrix in the SAME process (each its own image, built and released here),
-        # so that a slow box and a slow kernel can be told apart from one JSON line.
-        STAGE[0] = "SpMV timing of the other phase-2 forms"
-        saved = {k: os.environ.get(k) for k in ("LL_PB_PHASE2", "LL_SPMV_KERNEL")}
-        try:
-            for form in ("fixed", "ordered", "atomic"):
-                if form == phase2_form:
-                    continue
-                os.environ["LL_PB_PHASE2"], os.environ["LL_SPMV_KERNEL"] = form, "pb"
+    # ------------------------------------------------------------ --full: the SpMV kernel alone and the streaming ceilings
+    spmv_ms = spmv_variants = spmv_gbs = ceiling = None
+    if args.full:
+        spmv_ms = time_spmv(op)
+        spmv_variants = {"%s [%s]" % (kernel_names[selected], phase2_form) if selected == L.capi.SPMV_PB else kernel_names[selected]: spmv_ms}
+        spmv_gbs = b_spmv / (spmv_ms * 1e-3) / 1e9
+        if selected == L.capi.SPMV_PB and world == 1 and not args.no_spmv_variants:
+            # The other two phase-2 forms on the SAME matrix in the SAME process (each its own image, built and released here),
+            # so that a slow box and a slow kernel can be told apart from one JSON line.
+            STAGE[0] = "SpMV timing of the other phase-2 forms"
+            saved = {k: os.environ.get(k) for k in ("LL_PB_PHASE2", "LL_SPMV_KERNEL")}
+            try:
+                for form in ("fixed", "ordered", "atomic"):
+                    if form == phase2_form:
+                        continue
+                    os.environ["LL_PB_PHASE2"], os.environ["LL_SPMV_KERNEL"] = form, "pb"
+                    ctx.reload_env()
+                    alt = L.CsrOperator(ctx, *csr, n_cols=n, row_begin=rb)
+                    nm = "pb_phase1+%s [%s]" % ("pb_phase2" if form != "fixed" else "pb_phase2_fixed", form)
+                    spmv_variants[nm] = time_spmv(alt)
+                    alt.close()
+            finally:
+                for k, v in saved.items():
+                    if v is None:
+                        os.environ.pop(k, None)
+                    else:
+                        os.environ[k] = v
                 ctx.reload_env()
-                alt = L.CsrOperator(ctx, *csr, n_cols=n, row_begin=rb)
-                nm = "pb_phase1+%s [%s]" % ("pb_phase2" if form != "fixed" else "pb_phase2_fixed", form)
-                spmv_variants[nm] = time_spmv(alt)
-                alt.close()
-        finally:
-            for k, v in saved.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-            ctx.reload_env()
-        spmv_variants["%s [%s] again, after the others" % (kernel_names[selected], phase2_form)] = time_spmv(op)
+            spmv_variants["%s [%s] again, after the others" % (kernel_names[selected], phase2_form)] = time_spmv(op)
 
-    # ------------------------------------------------------------ measured streaming ceilings of THIS device, same process (SURVEY 8d "Bound")
-    STAGE[0] = "bandwidth ceilings"
-    probe_bytes = 2 << 30
-    read_ceiling, copy_ceiling = ctx.bandwidth_probe(probe_bytes)
-    ceiling = {"read_GBps": read_ceiling, "copy_GBps": copy_ceiling, "bytes": probe_bytes,
-               "how": "ll_bandwidth_probe: a read-only sum and a copy kernel over 2 GiB, 16-byte accesses, best grid of four, three "
-                      "launches each by HIP events on the library stream, in this process right after the SpMV timing; copy = bytes read + "
-                      "bytes written per second"}
+        # ------------------------------------------------------------ measured streaming ceilings of THIS device, same process (SURVEY 8d "Bound")
+        STAGE[0] = "bandwidth ceilings"
+        probe_bytes = 2 << 30
+        read_ceiling, copy_ceiling = ctx.bandwidth_probe(probe_bytes)
+        ceiling = {"read_GBps": read_ceiling, "copy_GBps": copy_ceiling, "bytes": probe_bytes,
+                   "how": "ll_bandwidth_probe: a read-only sum and a copy kernel over 2 GiB, 16-byte accesses, best grid of four, three "
+                          "launches each by HIP events on the library stream, in this process right after the SpMV timing; copy = bytes read + "
+                          "bytes written per second"}
 
     # ------------------------------------------------------------ timed steps
     STAGE[0] = "timed Lanczos windows"
@@ -586,6 +638,7 @@ def main():
                  "seconds_host_wait": 0.0, "seconds_setup": 0.0, "seconds_finish": 0.0, "seconds_total": 0.0,
                  "seconds_comm_gather": 0.0, "seconds_comm_allreduce": 0.0}
 
+    last = {}   # what the latest step returned to its caller (--dump-outputs)
     if wl == "c5":
         eng = L.Exponentiator(op, n)
         eng.max_iteration = args.window
@@ -593,12 +646,14 @@ def main():
         if args.host_io:
             def step():
                 out, it = eng.run(-1j * 5.0, init)
+                last["output"], last["iterations"] = out, it
                 return it
         else:
             d_in, d_out = ctx.to_device(init), ctx.empty((nl,), dtype)
 
             def step():
                 out, it = eng.run(-1j * 5.0, d_in, out=d_out)
+                last["output"], last["iterations"] = out, it
                 return it
     else:
         eng = L.LambdaLanczos(op, n, find_max, 1)
@@ -616,13 +671,14 @@ def main():
             eng.eigenvectors_out = ctx.empty((1, nl), dtype)
 
         def step():
-            eng.run()
-            return eng.getIterationCounts()[0]
+            last["eigenvalues"], last["eigenvectors"] = eng.run()
+            last["iteration_counts"] = eng.getIterationCounts()
+            return last["iteration_counts"][0]
 
     # The timed steps run WITHOUT the library's per-phase HIP events (three event records per iteration cost 5 % at
     # n = 1e6 and 20 % on the launch-bound config 5); the per-phase split comes from the same number of steps (at most
     # three) repeated WITH them right after the timed region.  --phase-timers-inline restores the old single pass.
-    inline = args.phase_timers_inline and not args.no_phase_timers
+    inline = args.full and args.phase_timers_inline and not args.no_phase_timers
     ctx.set_profiling(inline)
     for _ in range(args.warmup):
         step()
@@ -642,235 +698,246 @@ def main():
     total_iters = int(sum(itern))
     value = total_iters / elapsed
     itern_phases = list(itern)
-    # The same steps through the OTHER boundary, in the same process: `value` is the device-buffer figure unless --host-io
-    # was given; value_host_io is always the reference's std::vector boundary (LL:330: start vector up through the pinned
-    # staging buffer, eigenvector / output back), value_device_io always the HBM-resident one.
-    STAGE[0] = "timed windows through the other I/O boundary"
-    if wl == "c5":
-        if args.host_io:
-            d_in2, d_out2 = ctx.to_device(init), ctx.empty((nl,), dtype)
-
-            def step_other():
-                return eng.run(-1j * 5.0, d_in2, out=d_out2)[1]
-        else:
-            def step_other():
-                return eng.run(-1j * 5.0, init)[1]
-    else:
-        keep_io = (eng.init_vector, getattr(eng, "eigenvectors_out", None))
-        other_io = ((ctx.to_device(init), ctx.empty((1, nl), dtype)) if args.host_io else
-                    ((lambda v, *_: np.copyto(v, init)), None))
-
-        def step_other():
-            eng.init_vector, eng.eigenvectors_out = other_io
-            try:
-                eng.run()
-            finally:
-                eng.init_vector, eng.eigenvectors_out = keep_io
-            return eng.getIterationCounts()[0]
-    step_other()
-    barrier()
-    t0o = time.perf_counter()
-    iters_other = sum(step_other() for _ in range(args.steps))
-    barrier()
-    elapsed_other = max_over_ranks(time.perf_counter() - t0o)
-    value_other = iters_other / elapsed_other
-    value_host_io, value_device_io = (value, value_other) if args.host_io else (value_other, value)
-    if not inline and not args.no_phase_timers:
-        STAGE[0] = "instrumented steps (per-phase timers)"
-        ctx.set_profiling(True)
-        itern_phases = []
-        for _ in range(min(args.steps, 3)):
-            itern_phases.append(step())
-            for key in stats_acc:
-                stats_acc[key] += eng.last_stats[key]
-        barrier()
-
-    # Gram-Schmidt kernels of the instrumented windows: algorithmic bytes (minimal-pass model minus the SpMV) / device time
-    s = 16 if complex_ else 8
-    two_sweep_bytes = sum(s * n * (2 * k + 9) for it in itern_phases for k in range(1, it + 1))
     lagged_gs = lagged_timed > 0   # the Gram-Schmidt form of the TIMED steps (ll_run_stats.lagged_iterations)
-    if wl == "c5":
-        orth_bytes = sum(s * n * 9 for it in itern_phases for _k in range(1, it + 1))
-        orth_model = "s*n*9 bytes per iteration (no Gram-Schmidt against the basis: Exponentiator default)"
-    elif lagged_gs and pair_timed > 0:
-        # pair form: iterations 1 and 2 single (s*n*(k+4)), then pairs (k, k+1): the first three-term kernel (3R 1W) + ONE sweep
-        # that reads the k-2 stored vectors and the four raw ones and writes u_{k-2}, u_{k-1} and the compensated r4
-        def pair_window(it):
-            tot, k = 0, 1
-            while k <= it:
-                if k >= 3:
-                    tot += s * n * (k + 9)
-                    k += 2
-                else:
-                    tot += s * n * (k + 4)
-                    k += 1
-            return tot
-        orth_bytes = sum(pair_window(it) for it in itern_phases)
-        orth_model = ("TWO iterations per sweep (pair form, %d of the %d timed iterations): s*n*(k+9) bytes per pair (k, k+1) = "
-                      "three-term kernel (3R 1W) + one sweep over k-2 stored and 4 raw vectors (3 written); the one-sweep form needs "
-                      "s*n*(k+4) per iteration, the two-sweep form of SURVEY 8d s*n*(2k+9)" % (pair_timed, total_iters))
-    elif lagged_gs:
-        # one-sweep (lagged) form: reads y, r, u_{k-2} and the k-1 complete basis vectors, writes w and u_{k-1}
-        orth_bytes = sum(s * n * (k + 4) for it in itern_phases for k in range(1, it + 1))
-        orth_model = ("s*n*(k+4) bytes per iteration: the one-sweep (lagged) Gram-Schmidt form this run used; the two-sweep "
-                      "form of SURVEY 8d needs s*n*(2k+9)")
-    else:
-        orth_bytes = two_sweep_bytes
-        orth_model = "s*n*(2k+9) bytes per iteration (SURVEY 8d minimal-pass model)"
-    orth_s = max_over_ranks(stats_acc["seconds_orth"])
-    spmv_loop_s = max_over_ranks(stats_acc["seconds_spmv"])
-    comm_gather_s = max_over_ranks(stats_acc["seconds_comm_gather"])
-    comm_allreduce_s = max_over_ranks(stats_acc["seconds_comm_allreduce"])
-    setup_by_rank = [t_gen]
-    upload_by_rank = [t_up]
-    gather_by_rank = [stats_acc["seconds_comm_gather"]]
-    if dist is not None:
-        import torch
+    if args.dump_outputs:
+        STAGE[0] = "writing the outputs of the last timed step"
+        got = {k: (v.get() if isinstance(v, L.DeviceArray) else v) for k, v in last.items()}
+        if wl == "c5":
+            outputs = {"output": got["output"], "iterations": np.array([got["iterations"]], np.float64)}
+        else:
+            outputs = {"eigenvalues": got["eigenvalues"], "eigenvector": np.asarray(got["eigenvectors"])[0],
+                       "iteration_counts": np.array(got["iteration_counts"], np.float64)}
+        dump_outputs(args.dump_outputs, outputs, n, rb, nl, rank, world)
 
-        tt = [torch.zeros(3, dtype=torch.float64) for _ in range(world)]
-        dist.all_gather(tt, torch.tensor([t_gen, t_up, stats_acc["seconds_comm_gather"]], dtype=torch.float64))
-        setup_by_rank = [float(t[0]) for t in tt]
-        upload_by_rank = [float(t[1]) for t in tt]
-        gather_by_rank = [float(t[2]) for t in tt]
+    if args.full:
+        # The same steps through the OTHER boundary, in the same process: `value` is the device-buffer figure unless --host-io
+        # was given; value_host_io is always the reference's std::vector boundary (LL:330: start vector up through the pinned
+        # staging buffer, eigenvector / output back), value_device_io always the HBM-resident one.
+        STAGE[0] = "timed windows through the other I/O boundary"
+        if wl == "c5":
+            if args.host_io:
+                d_in2, d_out2 = ctx.to_device(init), ctx.empty((nl,), dtype)
 
-    # ------------------------------------------------------------ CPU baseline (rank 0, N = 1 only; bounded sample)
-    STAGE[0] = "CPU baseline"
-    cpu = None
-    if world == 1 and args.cpu_window != 0 and wl == "c5":
-        # config 5 runs fully on the CPU in seconds: the real Exponentiator<T>::run (EX:87-173) through
-        # oracle/_ref, same matrix, same input, same a = -5i; the whole run is the sample
-        import oracle_lib
+                def step_other():
+                    return eng.run(-1j * 5.0, d_in2, out=d_out2)[1]
+            else:
+                def step_other():
+                    return eng.run(-1j * 5.0, init)[1]
+        else:
+            keep_io = (eng.init_vector, getattr(eng, "eigenvectors_out", None))
+            other_io = ((ctx.to_device(init), ctx.empty((1, nl), dtype)) if args.host_io else
+                        ((lambda v, *_: np.copyto(v, init)), None))
 
-        kind = "reference" if oracle_lib.have_reference() else "port"
-        chk = oracle_lib.reference() if kind == "reference" else oracle_lib.oracle()
-        o_out, o_it, o_t = chk.expo((csr[0], csr[1], csr[2]), -5.0j, init, max_iteration=args.window)
+            def step_other():
+                eng.init_vector, eng.eigenvectors_out = other_io
+                try:
+                    eng.run()
+                finally:
+                    eng.init_vector, eng.eigenvectors_out = keep_io
+                return eng.getIterationCounts()[0]
+        step_other()
         barrier()
-        tg = time.perf_counter()
-        g_out, g_it = eng.run(-1j * 5.0, init)
+        t0o = time.perf_counter()
+        iters_other = sum(step_other() for _ in range(args.steps))
         barrier()
-        tg = time.perf_counter() - tg
-        err = float(np.max(np.abs(g_out - o_out)) / np.linalg.norm(init))
-        ovl = float(abs(np.vdot(o_out, g_out)) / (np.linalg.norm(o_out) * np.linalg.norm(g_out)))
-        cpu = {
-            "value": o_it / o_t["t_total"],
-            "unit": "Lanczos iterations/s",
-            "cores": 1,
-            "kind": kind,
-            "sample": "the whole run: Exponentiator::run, exp(-5iH)v on the same matrix and input, %d iterations, "
-                      "single thread like the reference" % o_it,
-            "seconds": o_t["t_total"],
-            "spmv_GBps": b_spmv * o_it / max(o_t["t_mv"], 1e-12) / 1e9,
-            "gpu_same_window_value": g_it / tg,
-            "parity_same_window": {"iterations_cpu": int(o_it), "iterations_gpu": int(g_it),
-                                   "max_abs_diff_over_input_norm": err, "one_minus_overlap": 1.0 - ovl,
-                                   "tolerance": "|out_gpu - out_cpu| <= 1e-10 |in|, 1 - overlap <= 10 eps, iterations within 1",
-                                   "ok": bool(err <= 1e-10 and 1.0 - ovl <= 10 * 2.3e-16 + 1e-15 and abs(int(o_it) - int(g_it)) <= 1)},
-            "host_cores_available": os.cpu_count(),
-        }
-    cpu_short = None
-    if world == 1 and args.cpu_window != 0 and wl != "c5":
-        import oracle_lib
+        elapsed_other = max_over_ranks(time.perf_counter() - t0o)
+        value_other = iters_other / elapsed_other
+        value_host_io, value_device_io = (value, value_other) if args.host_io else (value_other, value)
+        if not inline and not args.no_phase_timers:
+            STAGE[0] = "instrumented steps (per-phase timers)"
+            ctx.set_profiling(True)
+            itern_phases = []
+            for _ in range(min(args.steps, 3)):
+                itern_phases.append(step())
+                for key in stats_acc:
+                    stats_acc[key] += eng.last_stats[key]
+            barrier()
 
-        kind = "reference" if oracle_lib.have_reference() else "port"
-        chk = oracle_lib.reference() if kind == "reference" else oracle_lib.oracle()
-        full = (csr[0], csr[1], csr[2])
+        # Gram-Schmidt kernels of the instrumented windows: algorithmic bytes (minimal-pass model minus the SpMV) / device time
+        s = 16 if complex_ else 8
+        two_sweep_bytes = sum(s * n * (2 * k + 9) for it in itern_phases for k in range(1, it + 1))
+        if wl == "c5":
+            orth_bytes = sum(s * n * 9 for it in itern_phases for _k in range(1, it + 1))
+            orth_model = "s*n*9 bytes per iteration (no Gram-Schmidt against the basis: Exponentiator default)"
+        elif lagged_gs and pair_timed > 0:
+            # pair form: iterations 1 and 2 single (s*n*(k+4)), then pairs (k, k+1): the first three-term kernel (3R 1W) + ONE sweep
+            # that reads the k-2 stored vectors and the four raw ones and writes u_{k-2}, u_{k-1} and the compensated r4
+            def pair_window(it):
+                tot, k = 0, 1
+                while k <= it:
+                    if k >= 3:
+                        tot += s * n * (k + 9)
+                        k += 2
+                    else:
+                        tot += s * n * (k + 4)
+                        k += 1
+                return tot
+            orth_bytes = sum(pair_window(it) for it in itern_phases)
+            orth_model = ("TWO iterations per sweep (pair form, %d of the %d timed iterations): s*n*(k+9) bytes per pair (k, k+1) = "
+                          "three-term kernel (3R 1W) + one sweep over k-2 stored and 4 raw vectors (3 written); the one-sweep form needs "
+                          "s*n*(k+4) per iteration, the two-sweep form of SURVEY 8d s*n*(2k+9)" % (pair_timed, total_iters))
+        elif lagged_gs:
+            # one-sweep (lagged) form: reads y, r, u_{k-2} and the k-1 complete basis vectors, writes w and u_{k-1}
+            orth_bytes = sum(s * n * (k + 4) for it in itern_phases for k in range(1, it + 1))
+            orth_model = ("s*n*(k+4) bytes per iteration: the one-sweep (lagged) Gram-Schmidt form this run used; the two-sweep "
+                          "form of SURVEY 8d needs s*n*(2k+9)")
+        else:
+            orth_bytes = two_sweep_bytes
+            orth_model = "s*n*(2k+9) bytes per iteration (SURVEY 8d minimal-pass model)"
+        orth_s = max_over_ranks(stats_acc["seconds_orth"])
+        spmv_loop_s = max_over_ranks(stats_acc["seconds_spmv"])
+        comm_gather_s = max_over_ranks(stats_acc["seconds_comm_gather"])
+        comm_allreduce_s = max_over_ranks(stats_acc["seconds_comm_allreduce"])
+        setup_by_rank = [t_gen]
+        upload_by_rank = [t_up]
+        gather_by_rank = [stats_acc["seconds_comm_gather"]]
+        if dist is not None:
+            import torch
 
-        def cpu_leg(w):
-            """LambdaLanczos::run of the real reference (or the oracle port) with max_iteration = w on the host, then the same window
-            on the GPU: like-for-like rate and eigenpair parity."""
-            r = chk.lanczos(full, init, find_max, max_iteration=w, offset=offset, trace=False)
-            cpu_its = r["iter_counts"][0]
-            eng.max_iteration = w
-            step()
+            tt = [torch.zeros(3, dtype=torch.float64) for _ in range(world)]
+            dist.all_gather(tt, torch.tensor([t_gen, t_up, stats_acc["seconds_comm_gather"]], dtype=torch.float64))
+            setup_by_rank = [float(t[0]) for t in tt]
+            upload_by_rank = [float(t[1]) for t in tt]
+            gather_by_rank = [float(t[2]) for t in tt]
+
+        # ------------------------------------------------------------ CPU baseline (rank 0, N = 1 only; bounded sample)
+        STAGE[0] = "CPU baseline"
+        cpu = None
+        if world == 1 and args.cpu_window != 0 and wl == "c5":
+            # config 5 runs fully on the CPU in seconds: the real Exponentiator<T>::run (EX:87-173) through
+            # oracle/_ref, same matrix, same input, same a = -5i; the whole run is the sample
+            import oracle_lib
+
+            kind = "reference" if oracle_lib.have_reference() else "port"
+            chk = oracle_lib.reference() if kind == "reference" else oracle_lib.oracle()
+            o_out, o_it, o_t = chk.expo((csr[0], csr[1], csr[2]), -5.0j, init, max_iteration=args.window)
             barrier()
             tg = time.perf_counter()
-            vals_g, vecs_g = eng.run()
+            g_out, g_it = eng.run(-1j * 5.0, init)
             barrier()
             tg = time.perf_counter() - tg
-            d_lam = float(abs(vals_g[0] - r["eigenvalues"][0]))
-            vecs_g = vecs_g if isinstance(vecs_g, np.ndarray) else vecs_g.get()
-            defect = float(1.0 - abs(np.vdot(r["eigenvectors"][0], vecs_g[0])))
-            return {
-                "value": cpu_its / r["t_total"],
+            err = float(np.max(np.abs(g_out - o_out)) / np.linalg.norm(init))
+            ovl = float(abs(np.vdot(o_out, g_out)) / (np.linalg.norm(o_out) * np.linalg.norm(g_out)))
+            cpu = {
+                "value": o_it / o_t["t_total"],
                 "unit": "Lanczos iterations/s",
                 "cores": 1,
                 "kind": kind,
-                "sample": "same matrix and start vector, LambdaLanczos::run with max_iteration=%d (mean k=%.1f), "
-                          "single thread like the reference" % (w, (w + 1) / 2),
-                "seconds": r["t_total"],
-                "note": ("the cost of an iteration grows with k: this sample IS the headline window, `value` and "
-                         "`gpu_same_window_value` are like-for-like with the line's `value`" if w == args.window else
-                         "the cost of an iteration grows with k: compare `value` (window of %d iterations) with "
-                         "`gpu_same_window_value`, NOT with the headline value (window of %d)" % (w, args.window)),
-                "spmv_GBps": b_spmv * cpu_its / max(r["t_mv"], 1e-12) / 1e9,
-                "gpu_same_window_value": cpu_its / tg,
-                "parity_same_window": {"eigenvalue_cpu": float(r["eigenvalues"][0]), "eigenvalue_gpu": float(vals_g[0]),
-                                       "abs_diff": d_lam, "eigenvector_one_minus_overlap": defect,
-                                       "tolerance": "|dlambda| <= 1e-10*max(1,|lambda|), 1-|<v_cpu,v_gpu>| <= 1e-8",
-                                       "ok": bool(d_lam <= 1e-10 * max(1.0, abs(vals_g[0])) and defect <= 1e-8)},
+                "sample": "the whole run: Exponentiator::run, exp(-5iH)v on the same matrix and input, %d iterations, "
+                          "single thread like the reference" % o_it,
+                "seconds": o_t["t_total"],
+                "spmv_GBps": b_spmv * o_it / max(o_t["t_mv"], 1e-12) / 1e9,
+                "gpu_same_window_value": g_it / tg,
+                "parity_same_window": {"iterations_cpu": int(o_it), "iterations_gpu": int(g_it),
+                                       "max_abs_diff_over_input_norm": err, "one_minus_overlap": 1.0 - ovl,
+                                       "tolerance": "|out_gpu - out_cpu| <= 1e-10 |in|, 1 - overlap <= 10 eps, iterations within 1",
+                                       "ok": bool(err <= 1e-10 and 1.0 - ovl <= 10 * 2.3e-16 + 1e-15 and abs(int(o_it) - int(g_it)) <= 1)},
                 "host_cores_available": os.cpu_count(),
             }
+        cpu_short = None
+        if world == 1 and args.cpu_window != 0 and wl != "c5":
+            import oracle_lib
 
-        w_main = args.window if args.cpu_window < 0 else args.cpu_window
-        if args.cpu_short_window > 0 and args.cpu_short_window != w_main:
-            STAGE[0] = "CPU baseline (short sample)"
-            cpu_short = cpu_leg(args.cpu_short_window)
-        STAGE[0] = "CPU baseline (headline window)"
-        cpu = cpu_leg(w_main)
-        eng.max_iteration = args.window
-    short_w = args.cpu_short_window if args.cpu_short_window > 0 else 14
+            kind = "reference" if oracle_lib.have_reference() else "port"
+            chk = oracle_lib.reference() if kind == "reference" else oracle_lib.oracle()
+            full = (csr[0], csr[1], csr[2])
 
-    traffic, traffic_src, traffic_age = (None, None, None)
-    orth_traffic, orth_traffic_src = (None, None)
-    if world == 1 and not args.n and not lattice:
-        traffic, traffic_src, traffic_age = pmc_traffic(wl, kernel_names[selected].split("+"), "ll::zc" if complex_ else "double")
-        if args.eps is None and wl != "c5":
-            orth_traffic, orth_traffic_src = pmc_orth_traffic(wl, args.window)
+            def cpu_leg(w):
+                """LambdaLanczos::run of the real reference (or the oracle port) with max_iteration = w on the host, then the same window
+                on the GPU: like-for-like rate and eigenpair parity."""
+                r = chk.lanczos(full, init, find_max, max_iteration=w, offset=offset, trace=False)
+                cpu_its = r["iter_counts"][0]
+                eng.max_iteration = w
+                step()
+                barrier()
+                tg = time.perf_counter()
+                vals_g, vecs_g = eng.run()
+                barrier()
+                tg = time.perf_counter() - tg
+                d_lam = float(abs(vals_g[0] - r["eigenvalues"][0]))
+                vecs_g = vecs_g if isinstance(vecs_g, np.ndarray) else vecs_g.get()
+                defect = float(1.0 - abs(np.vdot(r["eigenvectors"][0], vecs_g[0])))
+                return {
+                    "value": cpu_its / r["t_total"],
+                    "unit": "Lanczos iterations/s",
+                    "cores": 1,
+                    "kind": kind,
+                    "sample": "same matrix and start vector, LambdaLanczos::run with max_iteration=%d (mean k=%.1f), "
+                              "single thread like the reference" % (w, (w + 1) / 2),
+                    "seconds": r["t_total"],
+                    "note": ("the cost of an iteration grows with k: this sample IS the headline window, `value` and "
+                             "`gpu_same_window_value` are like-for-like with the line's `value`" if w == args.window else
+                             "the cost of an iteration grows with k: compare `value` (window of %d iterations) with "
+                             "`gpu_same_window_value`, NOT with the headline value (window of %d)" % (w, args.window)),
+                    "spmv_GBps": b_spmv * cpu_its / max(r["t_mv"], 1e-12) / 1e9,
+                    "gpu_same_window_value": cpu_its / tg,
+                    "parity_same_window": {"eigenvalue_cpu": float(r["eigenvalues"][0]), "eigenvalue_gpu": float(vals_g[0]),
+                                           "abs_diff": d_lam, "eigenvector_one_minus_overlap": defect,
+                                           "tolerance": "|dlambda| <= 1e-10*max(1,|lambda|), 1-|<v_cpu,v_gpu>| <= 1e-8",
+                                           "ok": bool(d_lam <= 1e-10 * max(1.0, abs(vals_g[0])) and defect <= 1e-8)},
+                    "host_cores_available": os.cpu_count(),
+                }
 
-    cpu_all = None
-    if cpu is not None and wl != "c5":
-        # courtesy upper bound (SURVEY 8d): the oracle port with OpenMP over all host cores, same sample
-        import oracle_lib
+            w_main = args.window if args.cpu_window < 0 else args.cpu_window
+            if args.cpu_short_window > 0 and args.cpu_short_window != w_main:
+                STAGE[0] = "CPU baseline (short sample)"
+                cpu_short = cpu_leg(args.cpu_short_window)
+            STAGE[0] = "CPU baseline (headline window)"
+            cpu = cpu_leg(w_main)
+            eng.max_iteration = args.window
+        short_w = args.cpu_short_window if args.cpu_short_window > 0 else 14
 
-        orc = oracle_lib.oracle()
-        best = None
-        try:
-            for want in (16, 32, 64):  # more threads than ~32 got slower on the GPU box's host (measured)
-                if want > (os.cpu_count() or 1):
-                    break
-                threads = orc.set_threads(want)
-                r2 = orc.lanczos((csr[0], csr[1], csr[2]), init, find_max, max_iteration=short_w, offset=offset,
-                                 trace=False)
-                if best is None or r2["t_total"] < best[1]["t_total"]:
-                    best = (threads, r2)
-        finally:
-            orc.set_threads(1)
-        if best is not None:
-            threads, r2 = best
-            cpu_all = {"value": r2["iter_counts"][0] / r2["t_total"], "unit": "Lanczos iterations/s", "cores": threads,
-                       "kind": "port", "seconds": r2["t_total"],
-                       "sample": (cpu_short or cpu)["sample"].replace("single thread like the reference",
-                                                                      "OpenMP threads (best of 16/32/64; not how the reference runs)"),
-                       "spmv_GBps": b_spmv * r2["iter_counts"][0] / max(r2["t_mv"], 1e-12) / 1e9}
+        traffic, traffic_src, traffic_age = (None, None, None)
+        orth_traffic, orth_traffic_src = (None, None)
+        if world == 1 and not args.n and not lattice:
+            traffic, traffic_src, traffic_age = pmc_traffic(wl, kernel_names[selected].split("+"), "ll::zc" if complex_ else "double")
+            if args.eps is None and wl != "c5":
+                orth_traffic, orth_traffic_src = pmc_orth_traffic(wl, args.window)
 
-    # ------------------------------------------------------------ the other single-GPU configs and the callback path
-    other, cb_leg = None, None
-    if world == 1 and wl == "c3" and not args.n and not args.no_other_configs:
-        STAGE[0] = "host-callback leg"
-        try:
-            cb_leg = callback_leg(ctx, L, csr, n, init, find_max, offset, max(short_w, 8),
-                                  (cpu_short or cpu)["gpu_same_window_value"] if (cpu_short or cpu) else None)
-        except Exception as e:  # noqa: BLE001 - reported, never fatal for the headline line
-            cb_leg = {"error": repr(e)}
-        other = {}
-        for key, fn in (("c2", other_config_c2), ("c5", other_config_c5)):
-            STAGE[0] = "other config " + key
-            t_leg = time.perf_counter()
+        cpu_all = None
+        if cpu is not None and wl != "c5":
+            # courtesy upper bound (SURVEY 8d): the oracle port with OpenMP over all host cores, same sample
+            import oracle_lib
+
+            orc = oracle_lib.oracle()
+            best = None
             try:
-                other[key] = fn(ctx, L, G)
-            except Exception as e:  # noqa: BLE001
-                other[key] = {"error": repr(e)}
-            other[key]["leg_wall_s"] = time.perf_counter() - t_leg
+                for want in (16, 32, 64):  # more threads than ~32 got slower on the GPU box's host (measured)
+                    if want > (os.cpu_count() or 1):
+                        break
+                    threads = orc.set_threads(want)
+                    r2 = orc.lanczos((csr[0], csr[1], csr[2]), init, find_max, max_iteration=short_w, offset=offset,
+                                     trace=False)
+                    if best is None or r2["t_total"] < best[1]["t_total"]:
+                        best = (threads, r2)
+            finally:
+                orc.set_threads(1)
+            if best is not None:
+                threads, r2 = best
+                cpu_all = {"value": r2["iter_counts"][0] / r2["t_total"], "unit": "Lanczos iterations/s", "cores": threads,
+                           "kind": "port", "seconds": r2["t_total"],
+                           "sample": (cpu_short or cpu)["sample"].replace("single thread like the reference",
+                                                                          "OpenMP threads (best of 16/32/64; not how the reference runs)"),
+                           "spmv_GBps": b_spmv * r2["iter_counts"][0] / max(r2["t_mv"], 1e-12) / 1e9}
+
+        # ------------------------------------------------------------ the other single-GPU configs and the callback path
+        other, cb_leg = None, None
+        if world == 1 and wl == "c3" and not args.n and not args.no_other_configs:
+            STAGE[0] = "host-callback leg"
+            try:
+                cb_leg = callback_leg(ctx, L, csr, n, init, find_max, offset, max(short_w, 8),
+                                      (cpu_short or cpu)["gpu_same_window_value"] if (cpu_short or cpu) else None)
+            except Exception as e:  # noqa: BLE001 - reported, never fatal for the headline line
+                cb_leg = {"error": repr(e)}
+            other = {}
+            for key, fn in (("c2", other_config_c2), ("c5", other_config_c5)):
+                STAGE[0] = "other config " + key
+                t_leg = time.perf_counter()
+                try:
+                    other[key] = fn(ctx, L, G)
+                except Exception as e:  # noqa: BLE001
+                    other[key] = {"error": repr(e)}
+                other[key]["leg_wall_s"] = time.perf_counter() - t_leg
 
     if rank == 0:
         line = {
@@ -879,8 +946,6 @@ def main():
                        if wl == "c3" and not args.n else
                        "Lanczos iterations/sec (fixed window) + SpMV GB/s, %s" % ("complex fp64" if complex_ else "fp64")),
             "value": value,
-            "value_host_io": value_host_io,      # the same steps with std::vector-style host buffers at the boundary (LL:330)
-            "value_device_io": value_device_io,  # ... with the start vector / result resident in HBM (what `value` is by default)
             "unit": "Lanczos iterations/s",
             "n_gpus": world,
             "steps": args.steps,
@@ -925,76 +990,82 @@ def main():
             "comm_ranks_seen": ranks_seen,
             "transport": transport,
             "exchange_tuning": exchange_tuning,
-            "spmv": {"GBps": spmv_gbs, "ms": spmv_ms, "algorithmic_bytes": b_spmv, "frac_of_8TBps": spmv_gbs / HBM_PEAK_GBS,
-                     "kernel": kernel_names[selected] + " (picked by timing the candidates at upload; the other images are released)",
-                     "ms_by_kernel": spmv_variants, "creation_time_autotune_ms": tune,
-                     "includes_exchange": world > 1},
-            "roofline": {
-                "kernel": kernel_names[selected],
-                "launch": "one ll_spmv call y = A x (pb: two back-to-back kernels, phase 2 with order-independent fixed-point "
-                          "sums), HIP events on the library stream, %d launches averaged" % args.spmv_reps,
-                "bound": "hbm",
-                "achieved": spmv_gbs,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": spmv_gbs / HBM_PEAK_GBS,
-                "measured_ceiling": ceiling,
-                "frac_of_measured": spmv_gbs / read_ceiling,        # against the read-only stream (96 % of the algorithmic bytes are reads)
-                "frac_of_measured_copy": spmv_gbs / copy_ceiling,   # against the copy stream (read + write mix)
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_age": traffic_age,
-                "achieved_actual_traffic_GBps": (traffic / (spmv_ms * 1e-3) / 1e9) if traffic else None,
-            },
-            "roofline_orth": {
-                "kernel": ("pair_three_term + pair_sweep + folds (two iterations per sweep)" if (lagged_gs and pair_timed > 0) else
-                           "lagged sweep + folds (three-term, one-sweep Gram-Schmidt, norm)" if lagged_gs else
-                           "mdot+maxpy+scale (three-term, Gram-Schmidt, norm, normalise)"),
-                "bound": "hbm",
-                "achieved": (orth_bytes / orth_s / 1e9) if orth_s > 0 else None,  # None: --no-phase-timers
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": (orth_bytes / orth_s / 1e9 / HBM_PEAK_GBS) if orth_s > 0 else None,
-                "frac_of_measured": (orth_bytes / orth_s / 1e9 / read_ceiling) if orth_s > 0 else None,
-                "traffic": orth_traffic,
-                "traffic_source": orth_traffic_src,
-                "traffic_note": "measured HBM bytes of the Gram-Schmidt kernels (one-sweep form: lagged sweep + folds; two-sweep "
-                                "form: mdot + maxpy + scale) per step (one window), PMC counters; "
-                                "achieved = algorithmic bytes of the timed steps / their device time",
-                "algorithmic_bytes_per_step": orth_bytes / max(len(itern_phases), 1),
-                "model": orth_model,
-                "lagged_iterations_timed_steps": lagged_timed,
-                "pair_iterations_timed_steps": pair_timed,
-                "two_sweep_model_bytes_per_step": (two_sweep_bytes / max(len(itern_phases), 1)) if wl != "c5" else None,
-            },
-            "phases": {
-                "steps": len(itern_phases) if not args.no_phase_timers else 0,
-                "source": ("the timed steps themselves" if inline else
-                           "the same step repeated with per-phase HIP events after the timed region"),
-                "device_s_operator": spmv_loop_s,
-                "device_s_orth": orth_s,
-                "host_s_tridiag": stats_acc["seconds_host_tridiag"],
-                "host_s_enqueue": stats_acc["seconds_host_enqueue"],
-                "host_s_wait_scalars": stats_acc["seconds_host_wait"],
-                "host_s_setup": stats_acc["seconds_setup"],
-                "host_s_ritz_finish": stats_acc["seconds_finish"],
-                "library_s_total": stats_acc["seconds_total"],
-                "wall_s": elapsed,
-                "device_s_comm_gather": comm_gather_s,
-                "device_s_comm_gather_min_over_ranks": min(gather_by_rank),
-                "device_s_comm_gather_max_over_ranks": max(gather_by_rank),
-                "device_s_comm_gather_by_rank": gather_by_rank,
-                "device_s_comm_allreduce": comm_allreduce_s,
-                "setup_s_generate_upload": max(setup_by_rank),
-                "setup_s_generate_upload_by_rank": setup_by_rank,
-                "setup_s_operator_create_by_rank": upload_by_rank,
-            },
-            "cpu_baseline": cpu,
-            "cpu_baseline_short": cpu_short,
-            "cpu_baseline_all_cores": cpu_all,
-            "callback_path": cb_leg,
-            "other_configs": other,
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "value_host_io": value_host_io,      # the same steps with std::vector-style host buffers at the boundary (LL:330)
+                "value_device_io": value_device_io,  # ... with the start vector / result resident in HBM (what `value` is by default)
+                "spmv": {"GBps": spmv_gbs, "ms": spmv_ms, "algorithmic_bytes": b_spmv, "frac_of_8TBps": spmv_gbs / HBM_PEAK_GBS,
+                         "kernel": kernel_names[selected] + " (picked by timing the candidates at upload; the other images are released)",
+                         "ms_by_kernel": spmv_variants, "creation_time_autotune_ms": tune,
+                         "includes_exchange": world > 1},
+                "roofline": {
+                    "kernel": kernel_names[selected],
+                    "launch": "one ll_spmv call y = A x (pb: two back-to-back kernels, phase 2 with order-independent fixed-point "
+                              "sums), HIP events on the library stream, %d launches averaged" % args.spmv_reps,
+                    "bound": "hbm",
+                    "achieved": spmv_gbs,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": spmv_gbs / HBM_PEAK_GBS,
+                    "measured_ceiling": ceiling,
+                    "frac_of_measured": spmv_gbs / read_ceiling,        # against the read-only stream (96 % of the algorithmic bytes are reads)
+                    "frac_of_measured_copy": spmv_gbs / copy_ceiling,   # against the copy stream (read + write mix)
+                    "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "traffic_age": traffic_age,
+                    "achieved_actual_traffic_GBps": (traffic / (spmv_ms * 1e-3) / 1e9) if traffic else None,
+                },
+                "roofline_orth": {
+                    "kernel": ("pair_three_term + pair_sweep + folds (two iterations per sweep)" if (lagged_gs and pair_timed > 0) else
+                               "lagged sweep + folds (three-term, one-sweep Gram-Schmidt, norm)" if lagged_gs else
+                               "mdot+maxpy+scale (three-term, Gram-Schmidt, norm, normalise)"),
+                    "bound": "hbm",
+                    "achieved": (orth_bytes / orth_s / 1e9) if orth_s > 0 else None,  # None: --no-phase-timers
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": (orth_bytes / orth_s / 1e9 / HBM_PEAK_GBS) if orth_s > 0 else None,
+                    "frac_of_measured": (orth_bytes / orth_s / 1e9 / read_ceiling) if orth_s > 0 else None,
+                    "traffic": orth_traffic,
+                    "traffic_source": orth_traffic_src,
+                    "traffic_note": "measured HBM bytes of the Gram-Schmidt kernels (one-sweep form: lagged sweep + folds; two-sweep "
+                                    "form: mdot + maxpy + scale) per step (one window), PMC counters; "
+                                    "achieved = algorithmic bytes of the timed steps / their device time",
+                    "algorithmic_bytes_per_step": orth_bytes / max(len(itern_phases), 1),
+                    "model": orth_model,
+                    "lagged_iterations_timed_steps": lagged_timed,
+                    "pair_iterations_timed_steps": pair_timed,
+                    "two_sweep_model_bytes_per_step": (two_sweep_bytes / max(len(itern_phases), 1)) if wl != "c5" else None,
+                },
+                "phases": {
+                    "steps": len(itern_phases) if not args.no_phase_timers else 0,
+                    "source": ("the timed steps themselves" if inline else
+                               "the same step repeated with per-phase HIP events after the timed region"),
+                    "device_s_operator": spmv_loop_s,
+                    "device_s_orth": orth_s,
+                    "host_s_tridiag": stats_acc["seconds_host_tridiag"],
+                    "host_s_enqueue": stats_acc["seconds_host_enqueue"],
+                    "host_s_wait_scalars": stats_acc["seconds_host_wait"],
+                    "host_s_setup": stats_acc["seconds_setup"],
+                    "host_s_ritz_finish": stats_acc["seconds_finish"],
+                    "library_s_total": stats_acc["seconds_total"],
+                    "wall_s": elapsed,
+                    "device_s_comm_gather": comm_gather_s,
+                    "device_s_comm_gather_min_over_ranks": min(gather_by_rank),
+                    "device_s_comm_gather_max_over_ranks": max(gather_by_rank),
+                    "device_s_comm_gather_by_rank": gather_by_rank,
+                    "device_s_comm_allreduce": comm_allreduce_s,
+                    "setup_s_generate_upload": max(setup_by_rank),
+                    "setup_s_generate_upload_by_rank": setup_by_rank,
+                    "setup_s_operator_create_by_rank": upload_by_rank,
+                },
+                "cpu_baseline": cpu,
+                "cpu_baseline_short": cpu_short,
+                "cpu_baseline_all_cores": cpu_all,
+                "callback_path": cb_leg,
+                "other_configs": other,
+            })
         print(json.dumps(line), flush=True)
 
     op.close()

@@ -13,9 +13,11 @@ outputs the reference produced for them.  No reference source is stored.  Cases 
   run_iteration.json     LambdaLanczos::run_iteration called directly (LL:216-322): nroot pairs, caller's orthogonalizeTo
   long_runs.json         runs of several hundred iterations to convergence / exhaustion (the Gram-Schmidt forms of the HIP path
                          against the reference's sequential MGS, LL:260): alpha/beta, counts, values, sampled vector entries
+  live_reference.json    the cases of test_oracle_golden.test_live_against_reference: counts, values, every eigenvector
 
     python tests/golden/make_golden.py run_iteration      # regenerate one file only
     python tests/golden/make_golden.py long_runs          # (about 6 minutes of single-core reference time)
+    python tests/golden/make_golden.py live_reference
 """
 import json
 import os
@@ -179,8 +181,31 @@ def make_long_runs(ref, only=None):
     dump("long_runs.json", out)
 
 
+def live_reference_specs():
+    """Several pairs, the smallest and the largest end, real and complex (splitmix start vector, seed 3)."""
+    return {
+        "randsym2000_max_k2": dict(gen="randsym_np", args=[2000], find_max=True, offset=0.0, num_eigs=2),
+        "laplace24_min_k1": dict(gen="laplace2d_np", args=[24], find_max=False, offset=-8.0, num_eigs=1),
+        "torus12_min_k3": dict(gen="torus_np", args=[12], find_max=False, offset=-10.0, num_eigs=3),
+    }
+
+
+def make_live_reference(ref):
+    out = {}
+    for name, s in live_reference_specs().items():
+        csr = getattr(G, s["gen"])(*s["args"])
+        n = csr[0].shape[0] - 1
+        r = ref.lanczos(csr, G.start_vector(n, 3, csr[2].dtype), s["find_max"], num_eigs=s["num_eigs"], offset=s["offset"])
+        out[name] = dict(s, n=n, start="generators.start_vector(n, seed=3)", iter_counts=r["iter_counts"],
+                         eigenvalues=r["eigenvalues"].tolist(), eigenvectors=[c2list(v) for v in r["eigenvectors"]])
+    dump("live_reference.json", out)
+
+
 def main():
     ref = oracle_lib.reference()
+    if len(sys.argv) > 1 and sys.argv[1] == "live_reference":
+        make_live_reference(ref)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "run_iteration":
         make_run_iteration(ref)
         return
@@ -262,6 +287,7 @@ def main():
         ex["torus32_dt%g" % dt] = {"gen": "torus_np(32)", "start": "generators.start_vector(1024, 1, complex128)",
                                    "a": c2list(np.array([-1j * dt])), "output": c2list(o), "itern": it}
     dump("exponentiator.json", ex)
+    make_live_reference(ref)
     make_long_runs(ref)
 
 

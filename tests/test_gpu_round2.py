@@ -299,7 +299,7 @@ def test_c4_full_size_bench_eight_ranks_on_one_gpu(tmp_path):
     env = dict(os.environ, LL_COMM_PLUGIN=SHM_TRANSPORT, LL_BENCH_DEVICE="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-           "--window", "20", "--spmv-reps", "3"]
+           "--window", "20", "--spmv-reps", "3", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
