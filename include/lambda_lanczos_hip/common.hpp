@@ -46,6 +46,10 @@ template <typename T> struct abi;
                               const T* va, const ll_csr_options* opt, ll_operator** o) {                                 \
       return ll_op_create_csr_opt_##SFX(c, nr, nc, rb, rp, ci, va, opt, o);                                              \
     }                                                                                                                    \
+    static int create_csr_sym(ll_context* c, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const T* va,     \
+                              const ll_csr_options* opt, ll_operator** o) {                                              \
+      return ll_op_create_csr_sym_##SFX(c, n, uplo, rp, ci, va, opt, o);                                                 \
+    }                                                                                                                    \
     static int create_dense(ll_context* c, int64_t nr, int64_t nc, int64_t rb, const T* a, ll_operator** o) {            \
       return ll_op_create_dense_##SFX(c, nr, nc, rb, a, o);                                                              \
     }                                                                                                                    \
@@ -179,6 +183,35 @@ template <typename T> class CsrMatrix : public DeviceOperator<T> {
     int a = 0;
     check(ll_op_accuracy(this->get(), &a));
     return (Accuracy)a;
+  }
+};
+
+// A symmetric (real T) / Hermitian (complex T) matrix given as ONE stored triangle (ll_op_create_csr_sym_*): a MatrixMarket
+// symmetric / hermitian file, scipy.sparse.triu, an FEM assembly.  A = T + T^H - diag(T); the library keeps the one-triangle
+// image (LL_SPMV_SYM) when the triangle is eligible, the expanded full matrix otherwise.  Single-rank contexts only.
+enum class Triangle { Upper = LL_UPPER, Lower = LL_LOWER };
+template <typename T> class SymmetricCsrMatrix : public DeviceOperator<T> {
+ public:
+  SymmetricCsrMatrix(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& col, const std::vector<T>& val,
+                     Triangle uplo, Context ctx = Context::default_context(), Accuracy accuracy = Accuracy::Default)
+      : DeviceOperator<T>(ctx) {
+    const int64_t n = (int64_t)row_ptr.size() - 1;
+    ll_operator* op = nullptr;
+    ll_csr_options opt;
+    check(ll_csr_options_default(&opt));
+    opt.accuracy = (int32_t)accuracy;
+    check(abi<T>::create_csr_sym(ctx.get(), n, (int)uplo, row_ptr.data(), col.data(), val.data(), &opt, &op));
+    this->adopt(op, n, n);
+  }
+  int selected_spmv() const {
+    int k = 0;
+    check(ll_op_selected_spmv(this->get(), &k));
+    return k;
+  }
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
   }
 };
 

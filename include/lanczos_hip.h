@@ -50,7 +50,9 @@ extern "C" {
                              * 4: additive — ll_csr_options / ll_op_create_csr_opt_*, ll_op_set_accuracy, ll_op_accuracy, the tiled
                              *    SpMV kernel id; no struct changed, callers built against minor 3 keep working
                              * 5: additive — ll_ctx_set_tuning (the test hooks and geometry overrides left the environment),
-                             *    ll_comm_transport, ll_bandwidth_probe, ll_op_tiled_layout; no struct changed */
+                             *    ll_comm_transport, ll_bandwidth_probe, ll_op_tiled_layout; no struct changed;
+                             *    also additive under minor 5 — ll_op_create_csr_sym_* (one stored triangle), the one-triangle
+                             *    SpMV kernel id, ll_op_device_bytes; no struct changed */
 
 enum {
   LL_OK = 0,
@@ -276,7 +278,7 @@ int ll_op_create_stencil_z(ll_context* ctx, const ll_stencil_desc* desc, int64_t
  *   3-5 % slower); the environment's LL_PB_PHASE2=ordered or LL_SPMV_KERNEL=csr does the same for every operator of a context.
  *   Rows that meet an Inf / NaN are reported as NaN.  float / complex float storage: the product a_ij x_j is rounded to
  *   the storage type once (exactly what a float multiply gives) before it is summed in fixed point / double. */
-enum { LL_SPMV_CSR_STREAM = 0, LL_SPMV_PB = 1, LL_SPMV_TILED = 2 };
+enum { LL_SPMV_CSR_STREAM = 0, LL_SPMV_PB = 1, LL_SPMV_TILED = 2, LL_SPMV_SYM = 3 /* ll_op_create_csr_sym_* only, see below */ };
 /* The ACCURACY CLASS above as a per-operator choice of the caller (who knows whether the vectors are localised), not of
  * the environment:
  *   LL_ACCURACY_DEFAULT        what the context's environment says (LL_PB_PHASE2; norm-wise when unset)
@@ -304,6 +306,47 @@ int ll_op_create_csr_opt_s(ll_context* ctx, int64_t n_rows, int64_t n_cols, int6
                            const int32_t* col, const float* val, const ll_csr_options* opt, ll_operator** out);
 int ll_op_create_csr_opt_c(ll_context* ctx, int64_t n_rows, int64_t n_cols, int64_t row_begin, const int64_t* row_ptr,
                            const int32_t* col, const void* val, const ll_csr_options* opt, ll_operator** out);
+/* A symmetric (real types) or Hermitian (complex types) matrix given as ONE stored triangle T (n x n, CSR, global indices):
+ *   A = T + T^T - diag(T)   (real),      A = T + T^H - diag(T)   (complex; the diagonal entries are used as given, as the
+ *                                                                  full-storage kernels use them).
+ * uplo = LL_UPPER: every entry has col >= row; LL_LOWER: col <= row.  An entry on the wrong side of the diagonal, a column out
+ * of range or another uplo is LL_ERR_INVALID.  Duplicates are kept (as in the CSR path); rows may be empty.  opt may be NULL
+ * (= ll_csr_options_default); arrays_on_device = 1 takes device arrays.
+ * Kernel choice (opt->kernel):
+ *   -1            LL_SPMV_SYM when the triangle is eligible and the norm-wise class applies (LL_ACCURACY_COMPONENTWISE, or the
+ *                 environment's LL_PB_PHASE2=ordered|atomic, asks for floating-point sums, which LL_SPMV_SYM does not have);
+ *                 otherwise the full matrix is expanded and created exactly like ll_op_create_csr_opt_* (timing or LL_SPMV_KERNEL).
+ *   LL_SPMV_SYM   an error when the triangle is not eligible or the component-wise class is asked for: never a silent fallback.
+ *   LL_SPMV_CSR_STREAM / _PB / _TILED: the expanded full matrix with that kernel.
+ * LL_SPMV_SYM: one workgroup per row block keeps y of its rows in LDS (64-bit fixed point, the NORM-wise class below: y is
+ *   bit-identical to LL_SPMV_PB / LL_SPMV_TILED on the expanded matrix) and streams every stored entry with an end in its rows
+ *   — a_ij x_j into row i, conj(a_ij) x_i into row j — with the x window of its rows +- h staged in LDS, where h is the
+ *   half-bandwidth of all but at most 1/16 of the entries (the others, e.g. the corners of a periodic band, read x from memory).
+ *   ELIGIBLE: h is at most the row block — the largest power of two <= 16384 rows whose accumulators and x window (rows + 2 h
+ *   elements) fit the LDS — and h <= 2048, or h <= n / 4, or one row block holds the whole matrix.  Every triangle of
+ *   half-bandwidth <= 2048 is eligible for all four types (float: 8192-row blocks, double and complex float: 4096, complex
+ *   double: 2048); a random matrix is not.  n is limited to 2^31 - 2 like every CSR operator (32-bit column indices).
+ * Creation reads the triangle on the host (device arrays are copied down); for LL_SPMV_SYM the row exponents and ll_op_inf_norm
+ * of A are summed there in the order of the expanded rows (increasing column order when the triangle's rows are sorted) and
+ * only the one-triangle image goes to the device (about half the full matrix: ll_op_device_bytes); the other kernels get the
+ * matrix expanded on the host.
+ * Queries: ll_op_info reports the STORED entries as nnz_local; ll_op_inf_norm is the max absolute row sum of A;
+ * ll_op_selected_spmv reports LL_SPMV_SYM or the kernel of the expanded image; ll_op_select_spmv can only keep the kernel
+ * that was selected (the other images are not built); ll_op_tiled_layout reports (0, 0) and ll_op_autotune_ms_of(LL_SPMV_SYM)
+ * -1 (not timed) for a LL_SPMV_SYM operator; ll_op_set_accuracy(LL_ACCURACY_COMPONENTWISE) on it is LL_ERR_INVALID.
+ * SHARDED contexts (more than one rank) are refused: a rank's rows of the triangle do not hold its rows of A — create the full
+ * matrix with ll_op_create_csr_* there. */
+enum { LL_UPPER = 0, LL_LOWER = 1 };
+int ll_op_create_csr_sym_d(ll_context* ctx, int64_t n, int uplo, const int64_t* row_ptr, const int32_t* col, const double* val,
+                           const ll_csr_options* opt, ll_operator** out);
+int ll_op_create_csr_sym_z(ll_context* ctx, int64_t n, int uplo, const int64_t* row_ptr, const int32_t* col, const void* val,
+                           const ll_csr_options* opt, ll_operator** out);
+int ll_op_create_csr_sym_s(ll_context* ctx, int64_t n, int uplo, const int64_t* row_ptr, const int32_t* col, const float* val,
+                           const ll_csr_options* opt, ll_operator** out);
+int ll_op_create_csr_sym_c(ll_context* ctx, int64_t n, int uplo, const int64_t* row_ptr, const int32_t* col, const void* val,
+                           const ll_csr_options* opt, ll_operator** out);
+/* Device bytes the operator's images hold (what its creation allocated and still holds; the context's caches are not counted). */
+int ll_op_device_bytes(const ll_operator* op, int64_t* bytes);
 int ll_op_set_accuracy(ll_operator* op, int accuracy);        /* LL_ACCURACY_NORMWISE | LL_ACCURACY_COMPONENTWISE */
 int ll_op_accuracy(const ll_operator* op, int* accuracy_out);
 int ll_op_select_spmv(ll_operator* op, int kind);

@@ -14,7 +14,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lanczos_hip.h")
 LL_OK, LL_ERR_INVALID, LL_ERR_HIP, LL_ERR_RCCL, LL_ERR_ALLOC, LL_ERR_CALLBACK = range(6)
 ORTH_CGS_DGKS, ORTH_CGS2, ORTH_MGS = 0, 1, 2
 TRIDIAG_QR, TRIDIAG_BISECT, TRIDIAG_AUTO = 0, 1, 2
-SPMV_CSR_STREAM, SPMV_PB, SPMV_TILED = 0, 1, 2
+SPMV_CSR_STREAM, SPMV_PB, SPMV_TILED, SPMV_SYM = 0, 1, 2, 3
+UPPER, LOWER = 0, 1
 ACCURACY_DEFAULT, ACCURACY_NORMWISE, ACCURACY_COMPONENTWISE = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 
@@ -145,6 +146,9 @@ PROTOTYPES = {
     "ll_csr_options_default": (C.c_int, [P(CsrOptions)]),
     "ll_op_create_csr_opt_d": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, P(CsrOptions), P(vp)]),
     "ll_op_create_csr_opt_z": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, P(CsrOptions), P(vp)]),
+    "ll_op_create_csr_sym_d": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, P(CsrOptions), P(vp)]),
+    "ll_op_create_csr_sym_z": (C.c_int, [vp, i64, C.c_int, vp, vp, vp, P(CsrOptions), P(vp)]),
+    "ll_op_device_bytes": (C.c_int, [vp, P(i64)]),
     "ll_op_set_accuracy": (C.c_int, [vp, C.c_int]),
     "ll_op_accuracy": (C.c_int, [vp, P(C.c_int)]),
     "ll_op_create_coo_d": (C.c_int, [vp, i64, i64, vp, vp, vp, P(vp)]),

@@ -234,7 +234,9 @@ ll_operator::~ll_operator() {
                   (void*)d_pb_rptr, (void*)d_pb_xoff, (void*)d_pb_ncols, d_pb_arena, (void*)d_pb_rexp, d_pb_diag,
                   (void*)d_pb_blockmax, d_rp_own, d_rp_rem, (void*)d_col_own, (void*)d_col_rem, d_val_own, d_val_rem,
                   (void*)d_tiles_own, (void*)d_tiles_rem, (void*)d_tl_first, (void*)d_tl_col, (void*)d_tl_quad, d_tl_val,
-                  (void*)d_tl_idx, (void*)d_tl_rexp, (void*)d_tl_xmax, (void*)d_tl_rbmap})
+                  (void*)d_tl_idx, (void*)d_tl_rexp, (void*)d_tl_xmax, (void*)d_tl_rbmap, (void*)d_sym_qptr, d_sym_val,
+                  (void*)d_sym_idx, (void*)d_sym_rexp, (void*)d_sym_xmax, (void*)d_sym_fptr, d_sym_fval, (void*)d_sym_fdst,
+                  (void*)d_sym_fsrc, d_sym_diag})
     if (q) (void)hipFree(q);
   if (owns_arrays) {
     if (d_col) (void)hipFree(d_col);
@@ -633,6 +635,15 @@ inline double abs2_host(double v) { return v * v; }
 inline double abs2_host(float v) { return (double)v * (double)v; }
 inline double abs2_host(zc v) { return v.re * v.re + v.im * v.im; }
 inline double abs2_host(cf v) { return (double)v.re * (double)v.re + (double)v.im * (double)v.im; }
+// the device's abs1 / abs2 (dev_helpers.hpp) on the host, operation for operation (row exponents and norm of a stored triangle)
+inline double abs1_host(double v) { return std::fabs(v); }
+inline double abs1_host(float v) { return std::fabs((double)v); }
+inline double abs1_host(zc v) { return std::fabs(v.re) + std::fabs(v.im); }
+inline double abs1_host(cf v) { return std::fabs((double)v.re) + std::fabs((double)v.im); }
+inline double abs2_fma_host(double v) { return v * v; }
+inline double abs2_fma_host(float v) { return (double)v * (double)v; }
+inline double abs2_fma_host(zc v) { return std::fma(v.re, v.re, v.im * v.im); }
+inline double abs2_fma_host(cf v) { return std::fma((double)v.re, (double)v.re, (double)v.im * (double)v.im); }
 
 // SpMV tiles: runs of whole rows with <= cap nonzeros and <= kBlock rows; a longer row is alone.
 void build_tiles_cap(const int64_t* rp, int64_t nrows, int64_t cap, std::vector<int32_t>& tiles) {
@@ -852,6 +863,7 @@ void release_image(ll_operator* op, int keep_kind) {
     op->pb_ncb = op->pb_nrb = 0;
   }
   if (keep_kind != LL_SPMV_TILED) tl_release(op);
+  if (keep_kind != LL_SPMV_SYM) sym_release(op);
 }
 // the part of the PB image that is allocated so far (a failed or refused build)
 void release_pb_image(ll_operator* op) {
@@ -1336,8 +1348,203 @@ void create_coo(ll_context* ctx, int64_t n, int64_t nnz, const int32_t* rows, co
   }
   create_csr<T>(ctx, n, n, 0, rp.data(), ci.data(), va.data(), false, out);
 }
+
+// One stored triangle -> the operator.  Every row of A is taken in the order of the expansion a caller would build (upper:
+// the mirrored entries of the rows above, by row, then the row's own; lower: the row's own, then the mirrored entries of the
+// rows below, by row) — increasing column order when the triangle's rows are sorted by column.  The row exponents of the
+// fixed-point grid and the infinity norm are summed in that order.  The one-triangle image is built from the triangle alone
+// (nothing but the image reaches the device); any other choice expands the matrix on the host and goes through create_csr.
+template <typename T>
+void create_csr_sym(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const void* va,
+                    const ll_csr_options* opt, ll_operator** out) {
+  use(ctx);
+  LL_REQUIRE(out != nullptr && rp != nullptr, "null argument");
+  LL_REQUIRE(ctx->nranks <= 1 && ctx->comm == nullptr,
+             "a matrix stored as one triangle cannot be created on a sharded context (a rank's rows of the triangle do not hold "
+             "its rows of the matrix): create the full matrix there");
+  LL_REQUIRE(uplo == LL_UPPER || uplo == LL_LOWER, "uplo must name the upper (0) or the lower (1) triangle");
+  LL_REQUIRE(n >= 1 && n < (int64_t)0x7fffffff, "bad shape");
+  ll_csr_options o;
+  ll_csr_options_default(&o);
+  if (opt != nullptr) o = *opt;
+  LL_REQUIRE(o.accuracy >= LL_ACCURACY_DEFAULT && o.accuracy <= LL_ACCURACY_COMPONENTWISE, "ll_csr_options.accuracy");
+  LL_REQUIRE(o.kernel >= -1 && o.kernel <= LL_SPMV_SYM, "ll_csr_options.kernel");
+  const bool on_device = o.arrays_on_device != 0;
+  // the triangle on the host
+  std::vector<int64_t> rp_h((size_t)n + 1);
+  if (on_device) LL_HIP(hipMemcpy(rp_h.data(), rp, rp_h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  else std::copy(rp, rp + n + 1, rp_h.begin());
+  LL_REQUIRE(rp_h[0] == 0, "row_ptr must start at 0");
+  for (int64_t i = 0; i < n; ++i) LL_REQUIRE(rp_h[(size_t)i + 1] >= rp_h[(size_t)i], "row_ptr must be non-decreasing");
+  const int64_t nnz = rp_h[(size_t)n];
+  LL_REQUIRE(nnz == 0 || (ci != nullptr && va != nullptr), "null argument");
+  std::vector<int32_t> ci_copy;
+  std::vector<T> va_copy;
+  const int32_t* ci_h = ci;
+  const T* va_h = (const T*)va;
+  if (on_device && nnz > 0) {
+    ci_copy.resize((size_t)nnz);
+    va_copy.resize((size_t)nnz);
+    LL_HIP(hipMemcpy(ci_copy.data(), ci, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LL_HIP(hipMemcpy(va_copy.data(), va, (size_t)nnz * sizeof(T), hipMemcpyDeviceToHost));
+    ci_h = ci_copy.data();
+    va_h = va_copy.data();
+  }
+  // checks, entries per column outside the diagonal
+  std::vector<int64_t> mirrored((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t p = rp_h[(size_t)i]; p < rp_h[(size_t)i + 1]; ++p) {
+      const int64_t j = ci_h[p];
+      LL_REQUIRE(j >= 0 && j < n, "column index out of range");
+      LL_REQUIRE(uplo == LL_UPPER ? j >= i : j <= i,
+                 uplo == LL_UPPER ? "an entry lies below the diagonal of an upper triangle"
+                                  : "an entry lies above the diagonal of a lower triangle");
+      if (j != i) ++mirrored[(size_t)j];
+    }
+  // which kernel
+  const bool componentwise =
+      o.accuracy == LL_ACCURACY_COMPONENTWISE || (o.accuracy == LL_ACCURACY_DEFAULT && ctx->tune.pb_phase2 != LL_PB_FIXED);
+  const int64_t win_halo = sym_halo_for(rp_h.data(), ci_h, n);  // (entries beyond it are read with x from memory)
+  const int rb_rows = win_halo >= 0 ? sym_rows_for<T>(n, win_halo) : 0;
+  if (o.kernel == LL_SPMV_SYM) {
+    LL_REQUIRE(!componentwise, "the one-triangle kernel sums in fixed point only (norm-wise class): it has no component-wise form");
+    LL_REQUIRE(nnz > 0, "the one-triangle kernel was asked for by name but the triangle has no entries");
+    LL_REQUIRE(rb_rows > 0, "this triangle is not eligible for the one-triangle kernel (its half-bandwidth exceeds the row block "
+                            "whose x window fits the LDS)");
+  }
+  const bool use_sym = o.kernel == LL_SPMV_SYM || (o.kernel == -1 && !componentwise && nnz > 0 && rb_rows > 0);
+  if (use_sym) {
+    // The expanded matrix is never built.  Its row sums are taken in one sweep over the triangle's rows in increasing order:
+    // every row's mirrored entries then arrive by source row, before (upper) or after (lower) its own entries — the order of
+    // the expanded rows above, in which the full-storage kernels sum them (pb_rowexp_kernel, csr_check_kernel; the same IEEE
+    // operations, so the same bits).
+    std::vector<double> s1((size_t)n, 0.0), s2((size_t)n, 0.0);  // sum |re| + |im| (row exponents), sum of moduli (inf norm)
+    int64_t fnnz = 0;
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t p = rp_h[(size_t)i]; p < rp_h[(size_t)i + 1]; ++p) {
+        const int64_t j = ci_h[p];
+        const double a1 = abs1_host(va_h[p]), a2 = std::sqrt(abs2_fma_host(va_h[p]));
+        s1[(size_t)i] += a1;
+        s2[(size_t)i] += a2;
+        ++fnnz;
+        if (j != i) {
+          s1[(size_t)j] += a1;
+          s2[(size_t)j] += a2;
+          ++fnnz;
+        }
+      }
+    std::vector<int16_t> rexp((size_t)n);
+    double mx = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = s1[(size_t)i];
+      int e = -1100;
+      if (v > 0.0 && std::isfinite(v)) (void)std::frexp(v, &e);
+      else if (!(v == 0.0)) e = 32767;
+      rexp[(size_t)i] = (int16_t)e;
+      mx = std::fmax(mx, s2[(size_t)i]);
+    }
+    std::unique_ptr<ll_operator> op(new ll_operator);
+    op->kind = ll_operator::CSR;
+    op->is_complex = scalar_traits<T>::is_complex;
+    op->elem_bytes = (int)sizeof(T);
+    op->ctx = ctx;
+    op->accuracy_req = o.accuracy;
+    set_partition(ctx, op.get(), n, 0, n);
+    op->nnz = fnnz;
+    op->inf_norm = mx;
+    op->sym_stored = nnz;
+    op->sym_halo = (int)win_halo;
+    op->sym_rb_rows = rb_rows;
+    sym_build<T>(op.get(), rp_h.data(), ci_h, va_h);
+    LL_HIP(hipMemcpy(op->d_sym_rexp, rexp.data(), rexp.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    op->spmv_kind = LL_SPMV_SYM;
+    *out = op.release();
+    return;
+  }
+  // the expansion (stable: rows are visited in increasing order, so every row's mirrored entries arrive by source row)
+  std::vector<int64_t> frp((size_t)n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) frp[(size_t)i + 1] = frp[(size_t)i] + (rp_h[(size_t)i + 1] - rp_h[(size_t)i]) + mirrored[(size_t)i];
+  const int64_t fnnz = frp[(size_t)n];
+  std::vector<int32_t> fci((size_t)std::max<int64_t>(fnnz, 1));
+  std::vector<T> fva((size_t)std::max<int64_t>(fnnz, 1));
+  std::vector<int64_t> mcur((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    mcur[(size_t)i] = uplo == LL_UPPER ? frp[(size_t)i] : frp[(size_t)i] + (rp_h[(size_t)i + 1] - rp_h[(size_t)i]);
+  for (int64_t i = 0; i < n; ++i) {
+    int64_t d = uplo == LL_UPPER ? frp[(size_t)i] + mirrored[(size_t)i] : frp[(size_t)i];
+    for (int64_t p = rp_h[(size_t)i]; p < rp_h[(size_t)i + 1]; ++p) {
+      const int32_t j = ci_h[p];
+      fci[(size_t)d] = j;
+      fva[(size_t)d++] = va_h[p];
+      if (j != i) {
+        const int64_t q = mcur[(size_t)j]++;
+        fci[(size_t)q] = (int32_t)i;
+        if constexpr (scalar_traits<T>::is_complex) fva[(size_t)q] = T{va_h[p].re, -va_h[p].im};
+        else fva[(size_t)q] = va_h[p];
+      }
+    }
+  }
+  // (the caller's copies, if any, are released with this scope, after their last reader)
+  ll_csr_options fo = o;
+  fo.arrays_on_device = 0;
+  ll_operator* raw = nullptr;
+  create_csr<T>(ctx, n, n, 0, frp.data(), fci.data(), fva.data(), false, &raw, &fo);
+  raw->sym_stored = nnz;
+  *out = raw;
+}
+
+// device bytes of every allocation the operator holds (interior pointers of the PB arena are not allocations)
+int64_t op_device_bytes(const ll_operator* op) {
+  int64_t total = 0;
+  auto add = [&](const void* p) {
+    if (p == nullptr) return;
+    size_t b = 0;
+    LL_HIP(hipMemPtrGetInfo(const_cast<void*>(p), &b));
+    total += (int64_t)b;
+  };
+  for (const void* q : std::initializer_list<const void*>{op->d_row_ptr, (const void*)op->d_tile_rows, (const void*)op->d_dense, op->d_onsite, (const void*)op->d_pb_segq,
+                        (const void*)op->d_pb_segdest, (const void*)op->d_pb_rptr, (const void*)op->d_pb_xoff,
+                        (const void*)op->d_pb_ncols, op->d_pb_arena, (const void*)op->d_pb_rexp, op->d_pb_diag,
+                        (const void*)op->d_pb_blockmax, op->d_rp_own, op->d_rp_rem, (const void*)op->d_col_own,
+                        (const void*)op->d_col_rem, op->d_val_own, op->d_val_rem, (const void*)op->d_tiles_own,
+                        (const void*)op->d_tiles_rem, (const void*)op->d_tl_first, (const void*)op->d_tl_col,
+                        (const void*)op->d_tl_quad, op->d_tl_val, (const void*)op->d_tl_idx, (const void*)op->d_tl_rexp,
+                        (const void*)op->d_tl_xmax, (const void*)op->d_tl_rbmap, (const void*)op->d_sym_qptr, op->d_sym_val,
+                        (const void*)op->d_sym_idx, (const void*)op->d_sym_rexp, (const void*)op->d_sym_xmax,
+                        (const void*)op->d_sym_fptr, op->d_sym_fval, (const void*)op->d_sym_fdst, (const void*)op->d_sym_fsrc,
+                        op->d_sym_diag})
+    add(q);
+  if (op->owns_arrays) {
+    add(op->d_col);
+    add(op->d_val);
+  }
+  return total;
+}
 }  // namespace
 }  // extern "C++"
+int ll_op_create_csr_sym_d(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const double* va,
+                           const ll_csr_options* opt, ll_operator** out) {
+  return guarded([&] { create_csr_sym<double>(ctx, n, uplo, rp, ci, va, opt, out); });
+}
+int ll_op_create_csr_sym_z(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const void* va,
+                           const ll_csr_options* opt, ll_operator** out) {
+  return guarded([&] { create_csr_sym<zc>(ctx, n, uplo, rp, ci, va, opt, out); });
+}
+int ll_op_create_csr_sym_s(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const float* va,
+                           const ll_csr_options* opt, ll_operator** out) {
+  return guarded([&] { create_csr_sym<float>(ctx, n, uplo, rp, ci, va, opt, out); });
+}
+int ll_op_create_csr_sym_c(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const void* va,
+                           const ll_csr_options* opt, ll_operator** out) {
+  return guarded([&] { create_csr_sym<cf>(ctx, n, uplo, rp, ci, va, opt, out); });
+}
+int ll_op_device_bytes(const ll_operator* op, int64_t* bytes) {
+  return guarded([&] {
+    LL_REQUIRE(op != nullptr && bytes != nullptr, "null argument");
+    if (op->ctx) LL_HIP(hipSetDevice(op->ctx->device));
+    *bytes = op_device_bytes(op);
+  });
+}
 int ll_op_create_coo_d(ll_context* ctx, int64_t n, int64_t nnz, const int32_t* rows, const int32_t* cols,
                        const double* vals, ll_operator** out) {
   return guarded([&] { create_coo<double>(ctx, n, nnz, rows, cols, vals, out); });
@@ -1405,7 +1612,9 @@ int ll_op_destroy(ll_operator* op) {
 int ll_op_select_spmv(ll_operator* op, int kind) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr && op->kind == ll_operator::CSR, "not a CSR operator");
-    LL_REQUIRE(kind == LL_SPMV_CSR_STREAM || kind == LL_SPMV_PB || kind == LL_SPMV_TILED, "unknown SpMV kernel");
+    LL_REQUIRE(kind == LL_SPMV_CSR_STREAM || kind == LL_SPMV_PB || kind == LL_SPMV_TILED || kind == LL_SPMV_SYM, "unknown SpMV kernel");
+    LL_REQUIRE(kind != LL_SPMV_SYM || op->sym_nrb > 0,
+               "operator has no one-triangle image (only ll_op_create_csr_sym_* builds it, when it selects that kernel)");
     LL_REQUIRE(kind != LL_SPMV_PB || op->d_pb_val != nullptr,
                "operator has no propagation-blocked image (not selected at creation; LL_SPMV_KEEP_BOTH=1 keeps every image)");
     LL_REQUIRE(kind != LL_SPMV_CSR_STREAM || (op->d_row_ptr != nullptr && (op->d_col != nullptr || op->nnz == 0 || op->csr_split)),
@@ -1420,6 +1629,8 @@ int ll_op_set_accuracy(ll_operator* op, int accuracy) {
     LL_REQUIRE(op != nullptr && op->kind == ll_operator::CSR, "not a CSR operator");
     LL_REQUIRE(accuracy == LL_ACCURACY_NORMWISE || accuracy == LL_ACCURACY_COMPONENTWISE,
                "accuracy must be LL_ACCURACY_NORMWISE or LL_ACCURACY_COMPONENTWISE");
+    LL_REQUIRE(!(op->spmv_kind == LL_SPMV_SYM && accuracy == LL_ACCURACY_COMPONENTWISE),
+               "the one-triangle kernel sums in fixed point only (norm-wise class): it has no component-wise form");
     if (op->tl_nrb > 0) op->tl_ordered = accuracy == LL_ACCURACY_COMPONENTWISE;  // the tiled image serves both classes
     op->accuracy_req = accuracy;
     if (op->d_pb_val == nullptr) return;  // no PB image: CSR-stream is component-wise whatever is asked, the tiled kernel was set above
@@ -1436,7 +1647,8 @@ int ll_op_accuracy(const ll_operator* op, int* accuracy_out) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr && accuracy_out != nullptr, "null argument");
     const bool fixed = op->kind == ll_operator::CSR && ((op->spmv_kind == LL_SPMV_PB && op->pb_phase2 == LL_PB_FIXED) ||
-                                                        (op->spmv_kind == LL_SPMV_TILED && !op->tl_ordered));
+                                                        (op->spmv_kind == LL_SPMV_TILED && !op->tl_ordered) ||
+                                                        op->spmv_kind == LL_SPMV_SYM);
     *accuracy_out = fixed ? LL_ACCURACY_NORMWISE : LL_ACCURACY_COMPONENTWISE;
   });
 }
@@ -1455,8 +1667,8 @@ int ll_op_autotune_ms(const ll_operator* op, double* csr_stream_ms, double* pb_m
 }
 int ll_op_autotune_ms_of(const ll_operator* op, int kind, double* ms) {
   return guarded([&] {
-    LL_REQUIRE(op != nullptr && ms != nullptr && kind >= LL_SPMV_CSR_STREAM && kind <= LL_SPMV_TILED, "bad argument");
-    *ms = (double)op->tune_ms[kind];
+    LL_REQUIRE(op != nullptr && ms != nullptr && kind >= LL_SPMV_CSR_STREAM && kind <= LL_SPMV_SYM, "bad argument");
+    *ms = kind == LL_SPMV_SYM ? -1.0 : (double)op->tune_ms[kind];  // (the one-triangle kernel is never timed)
   });
 }
 int ll_op_tiled_layout(const ll_operator* op, int* row_blocks, int* own_column_row_blocks) {
@@ -1471,7 +1683,7 @@ int ll_op_info(const ll_operator* op, int64_t* n, int64_t* n_local, int64_t* nnz
     LL_REQUIRE(op != nullptr, "null operator");
     if (n) *n = op->n;
     if (n_local) *n_local = op->n_local;
-    if (nnz) *nnz = op->nnz;
+    if (nnz) *nnz = op->sym_stored >= 0 ? op->sym_stored : op->nnz;  // created from one triangle: the entries stored
   });
 }
 

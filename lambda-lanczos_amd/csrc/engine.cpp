@@ -208,13 +208,14 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
   LL_REQUIRE(sc == nullptr || can_defer_scale(), "internal: this operator cannot normalise its input on the fly");
   LL_REQUIRE(xnorm2 == nullptr || (can_scale_input() && sc == nullptr), "internal: this operator cannot scale its input");
   ScaleIn<T> from_norm;  // the non-PB kernels take the norm as a one-element list of "partials" (nothing published)
-  if (xnorm2 && !(op->kind == ll_operator::CSR && (op->spmv_kind == LL_SPMV_PB || op->spmv_kind == LL_SPMV_TILED))) {
+  if (xnorm2 && !(op->kind == ll_operator::CSR && (op->spmv_kind == LL_SPMV_PB || op->spmv_kind == LL_SPMV_TILED ||
+                                                    op->spmv_kind == LL_SPMV_SYM))) {
     from_norm.partials = xnorm2;
     from_norm.nparts = 1;
     sc = &from_norm;
   }
   hipStream_t s = ctx->stream;
-  ctx->ensure_alpha_partials(std::max<size_t>(kMaxSpmvGrid, (size_t)std::max(op->pb_nrb, op->tl_nrb)));
+  ctx->ensure_alpha_partials(std::max<size_t>(kMaxSpmvGrid, (size_t)std::max({op->pb_nrb, op->tl_nrb, op->sym_nrb})));
   double* const dotp = d_alpha ? ctx->d_alpha_partials : nullptr;
   int nparts = 0;
   if (op->kind == ll_operator::STENCIL) {
@@ -337,6 +338,8 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
       nparts = launch_dense_mv<T>(*op, x_full, x_local, y, offset, dotp, s, sc);
     else if (pb)
       nparts = launch_spmv_pb<T>(*op, x_full, x_own, x_local, y, offset, dotp, s, xnorm2);
+    else if (op->spmv_kind == LL_SPMV_SYM)  // one-triangle image: single GPU only (creation refuses sharded contexts)
+      nparts = launch_spmv_sym<T>(*op, x_local, y, offset, dotp, s, xnorm2);
     else if (op->spmv_kind == LL_SPMV_TILED)  // single GPU (sharded contexts took the two-launch form above): x_local is the whole x
       nparts = launch_spmv_tiled<T>(*op, x_local, y, offset, dotp, s, xnorm2);
     else {

@@ -102,6 +102,7 @@ constexpr int kXcds = 8;
 constexpr int kMaxGrid = kCUs * 8;   // persistent grids: at most 8 workgroups per CU (multiple of 8 XCDs)
 constexpr int kMaxSpmvGrid = kCUs * 16;  // CSR-stream SpMV with 16-byte values (its partial dot products: d_alpha_partials)
 constexpr int kSpmvTileNnz = 1024;   // nonzeros staged through LDS per SpMV tile
+constexpr int kXmaxParts = 512;      // maxima of |x| the pre-pass of the tiled and one-triangle kernels leaves (one per workgroup)
 constexpr int kMaxSegs = 26;         // basis segments (slabs) per multi-dot / multi-axpy launch: 5000 vectors in slabs of 200
 
 // A run of basis vectors stored with a common leading dimension: vector j at base + j*ld.
@@ -356,6 +357,22 @@ struct ll_operator {
   int pb_chunk_first[ll::kMaxGatherChunks] = {0};  // remote blocks of gather chunk c: [first, first + count)
   int pb_chunk_count[ll::kMaxGatherChunks] = {0};
   ll::GatherPlan gather;             // how a sharded vector is all-gathered when the PB kernels are selected
+  // one-triangle image of a symmetric / Hermitian matrix (spmv_sym.hip; LL_SPMV_SYM, ll_op_create_csr_sym_*): one stream per
+  // row block of every stored entry with an end in the block; an entry whose two ends lie in different blocks is in both streams
+  int64_t sym_stored = -1;           // entries of the triangle the operator was created from (ll_op_info); -1: full storage
+  int sym_nrb = 0, sym_rb_rows = 0, sym_halo = 0;  // row blocks, rows per block, half-bandwidth max |i - j| of the triangle
+  int64_t* d_sym_qptr = nullptr;     // [nrb + 1] first quad (4 entries) of each row block's stream
+  void* d_sym_val = nullptr;         // values as stored (T)
+  uint32_t* d_sym_idx = nullptr;     // window index of the entry's row | of its column << 16 (0xffffffff: padding)
+  int16_t* d_sym_rexp = nullptr;     // exponent of every row's absolute sum over the FULL row of A
+  double* d_sym_xmax = nullptr;      // kXmaxParts maxima of |x| (pre-pass)
+  void* d_sym_diag = nullptr;        // [n] the first diagonal entry of every row, kept outside the streams (0: none)
+  // entries whose other end lies outside the row block's x window (the few beyond the halo, e.g. the wrap-around corners of a
+  // periodic band): one product each, x read from memory — destination local row | 1 << 31 for the mirrored product, source row
+  int64_t* d_sym_fptr = nullptr;     // [nrb + 1] first far entry of each row block
+  void* d_sym_fval = nullptr;
+  uint32_t* d_sym_fdst = nullptr;
+  int32_t* d_sym_fsrc = nullptr;
   // dense row-major block (kind DENSE): n_local x n values of T
   void* d_dense = nullptr;
   // lattice operator (kind STENCIL)
@@ -437,6 +454,19 @@ int launch_spmv_tiled_pass(const ll_operator& op, int pass, const T* x, int64_t 
                            double offset, double* dot_partials, hipStream_t s, const double* xnorm2, int n_xmax);
 // Column range check + max absolute row sum of the local rows (sets op->inf_norm), on the device.
 template <typename T> void csr_check_device(ll_operator* op);
+// maxima of |x| over n elements, one per workgroup, into parts [kXmaxParts]; returns how many were written (tl_xmax_kernel)
+template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hipStream_t s);
+// The one-triangle kernel (spmv_sym.hip).  sym_rows_for: rows per row block for a triangle of that half-bandwidth, 0 when
+// the triangle is not eligible.  sym_build: the image from the HOST triangle (op->n, sym_halo, sym_rb_rows set; the row
+// exponents are filled by the caller).  launch_spmv_sym: y = A x + offset x on a single GPU, same contract as launch_spmv.
+template <typename T> int sym_rows_for(int64_t n, int64_t halo);
+// the x window's halo for a triangle: the smallest h that leaves at most 1/16 of the entries with |i - j| > h (-1: none <= 32767)
+int64_t sym_halo_for(const int64_t* rp, const int32_t* ci, int64_t n);
+template <typename T> void sym_build(ll_operator* op, const int64_t* rp, const int32_t* ci, const T* va);
+template <typename T>
+int launch_spmv_sym(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                    const double* xnorm2);
+void sym_release(ll_operator* op);
 // Same contract for the dense row block (op.kind == DENSE).
 template <typename T>
 int launch_dense_mv(const ll_operator& op, const T* x_full, const T* x_local, T* y, double offset, double* dot_partials,

@@ -197,6 +197,12 @@ class _Operator:
         check(lib().ll_op_info(self.handle, C.byref(n), C.byref(nl), C.byref(nnz)))
         return n.value, nl.value, nnz.value
 
+    def device_bytes(self):
+        """Device bytes the operator's images hold (ll_op_device_bytes; the context's caches are not counted)."""
+        b = C.c_int64()
+        check(lib().ll_op_device_bytes(self.handle, C.byref(b)))
+        return b.value
+
     def close(self):
         if self.handle:
             check(lib().ll_op_destroy(self.handle))
@@ -244,6 +250,45 @@ class CsrOperator(_Operator):
         h = C.c_void_p()
         fn = getattr(lib(), "ll_op_create_coo_" + _suffix(vals.dtype))
         check(fn(ctx.handle, int(n), len(vals), ptr(rows), ptr(cols), ptr(vals), C.byref(h)))
+        self.handle = h
+        return self
+
+    @classmethod
+    def from_triangle(cls, ctx, row_ptr, col, val, uplo="U", accuracy=None, kernel=None):
+        """A symmetric (real) / Hermitian (complex) n x n matrix given as ONE stored triangle (ll_op_create_csr_sym_*):
+        A = T + T^T - diag(T), or T + T^H - diag(T) for complex types.  uplo: "U" (col >= row) or "L" (col <= row).
+        kernel: None (capi.SPMV_SYM when the triangle is eligible, else the expanded full matrix, timed), capi.SPMV_SYM (an
+        error when not eligible), or another capi.SPMV_* for the expanded matrix; accuracy as for the constructor.
+        row_ptr / col / val may also be DeviceArrays (int64 / int32 / values already in HBM)."""
+        if uplo not in ("U", "L", capi.UPPER, capi.LOWER):
+            raise ValueError("uplo must be 'U' or 'L'")
+        self = cls.__new__(cls)
+        on_device = isinstance(row_ptr, DeviceArray)
+        if on_device:  # device arrays (int64 row_ptr, int32 col, values): ll_csr_options.arrays_on_device = 1
+            if not (isinstance(col, DeviceArray) and isinstance(val, DeviceArray)):
+                raise TypeError("row_ptr, col and val must all be DeviceArrays, or all host arrays")
+            if row_ptr.dtype != np.int64 or col.dtype != np.int32:
+                raise TypeError("device row_ptr must be int64 and col int32")
+            n = row_ptr.shape[0] - 1
+            self.nnz = int(col.shape[0])
+            args = (row_ptr.ptr, col.ptr, val.ptr)
+        else:
+            row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+            col = np.ascontiguousarray(col, dtype=np.int32)
+            val = np.ascontiguousarray(val)
+            n = row_ptr.shape[0] - 1
+            self.nnz = int(row_ptr[-1])
+            args = (ptr(row_ptr), ptr(col), ptr(val))
+        self.ctx, self.dtype, self.n, self.n_local, self.row_begin = ctx, val.dtype, n, n, 0
+        opt = capi.CsrOptions()
+        check(lib().ll_csr_options_default(C.byref(opt)))
+        opt.accuracy = capi.ACCURACY_DEFAULT if accuracy is None else int(accuracy)
+        opt.kernel = -1 if kernel is None else int(kernel)
+        opt.arrays_on_device = 1 if on_device else 0
+        code = capi.UPPER if uplo in ("U", capi.UPPER) else capi.LOWER
+        h = C.c_void_p()
+        fn = getattr(lib(), "ll_op_create_csr_sym_" + _suffix(val.dtype))
+        check(fn(ctx.handle, n, code, *args, C.byref(opt), C.byref(h)))
         self.handle = h
         return self
 

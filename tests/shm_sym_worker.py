@@ -1,0 +1,43 @@
+"""One rank of tests/test_gpu_sym.py's sharded-context check: two of these processes share the test box's GPU through the
+host-staged test transport (LL_COMM_PLUGIN) and ask for a one-triangle operator, which a sharded context refuses.
+argv: rank world shm_name out_dir"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import lambda_lanczos_amd as L  # noqa: E402
+from util import install_hook_sync  # noqa: E402
+from lambda_lanczos_amd import generators as G  # noqa: E402
+
+install_hook_sync()
+
+
+def main():
+    rank, world, name, out_dir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4]
+    ctx = L.Context(0)
+    ctx.init_comm(name.encode() + b"\0" * (128 - len(name)), rank, world)
+    rp, ci, va = G.laplace2d_np(40)
+    rows = np.repeat(np.arange(rp.shape[0] - 1), np.diff(rp))
+    keep = ci >= rows
+    trp = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=rp.shape[0] - 1))]).astype(np.int64)
+    res = {}
+    try:
+        L.CsrOperator.from_triangle(ctx, trp, ci[keep], va[keep], uplo="U")
+        res["code"] = 0
+    except L.capi.LanczosHipError as e:
+        res["code"] = e.code
+        res["msg"] = str(e)
+    ctx.close()
+    with open(os.path.join(out_dir, "rank%d.json" % rank), "w") as f:
+        json.dump(res, f)
+
+
+if __name__ == "__main__":
+    main()
