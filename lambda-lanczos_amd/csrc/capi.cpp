@@ -139,76 +139,44 @@ void ll_context::cache_put(void* p, size_t bytes) {
     slab_cache.erase(slab_cache.begin() + (long)victim);
   }
 }
-void ll_context::ensure_partials(size_t doubles) {
-  if (doubles <= partials_cap) return;
-  if (d_partials) LL_HIP(hipFree(d_partials));
-  d_partials = nullptr;
-  partials_cap = grow(partials_cap, doubles);
-  dev_malloc((void**)&d_partials, partials_cap * sizeof(double), "partial sums");
+template <typename T> T* ll_context::ensure(Workspace<T>& w, size_t count, bool geometric, const char* what) {
+  if (count <= w.cap) return w.get();
+  LL_HIP(w.buf.free_now());
+  const size_t cap = geometric ? grow(w.cap, count) : count;
+  w.buf = dev_alloc<T>(cap, what);
+  w.cap = cap;
+  return w.get();
 }
-void ll_context::ensure_alpha_partials(size_t doubles) {
-  if (doubles <= alpha_partials_cap) return;
-  if (d_alpha_partials) LL_HIP(hipFree(d_alpha_partials));
-  d_alpha_partials = nullptr;
-  alpha_partials_cap = grow(alpha_partials_cap, doubles);
-  dev_malloc((void**)&d_alpha_partials, alpha_partials_cap * sizeof(double), "alpha partial sums");
-}
-void ll_context::ensure_h(size_t doubles) {
-  if (doubles <= h_cap) return;
-  if (d_h) LL_HIP(hipFree(d_h));
-  d_h = nullptr;
-  h_cap = grow(h_cap, doubles);
-  dev_malloc((void**)&d_h, h_cap * sizeof(double), "projection coefficients");
-}
+template double* ll_context::ensure<double>(Workspace<double>&, size_t, bool, const char*);
+template void* ll_context::ensure<void>(Workspace<void>&, size_t, bool, const char*);
 void ll_context::ensure_pinned(size_t doubles) {
-  if (doubles <= pinned_cap) return;
-  if (h_pinned) LL_HIP(hipHostFree(h_pinned));
-  h_pinned = nullptr;
-  pinned_cap = grow(pinned_cap, doubles);
+  if (doubles <= pinned.cap) return;
+  LL_HIP(pinned.buf.free_now());
+  const size_t cap = grow(pinned.cap, doubles);
   // device-mapped, coherent host memory: the publish kernel stores the per-iteration scalars straight into it
-  hipError_t e = hipHostMalloc((void**)&h_pinned, pinned_cap * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
+  double* p = nullptr;
+  hipError_t e = hipHostMalloc((void**)&p, cap * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    LL_HIP(hipHostMalloc((void**)&h_pinned, pinned_cap * sizeof(double), hipHostMallocDefault));
+    LL_HIP(hipHostMalloc((void**)&p, cap * sizeof(double), hipHostMallocDefault));
   }
+  pinned.buf = HostArray<double>(p);
+  pinned.cap = cap;
 }
-void ll_context::ensure_coeff(size_t bytes) {
-  if (bytes <= coeff_cap) return;
-  if (d_coeff) LL_HIP(hipFree(d_coeff));
-  d_coeff = nullptr;
-  coeff_cap = grow(coeff_cap, bytes);
-  dev_malloc(&d_coeff, coeff_cap, "Ritz coefficients");
+static void* ensure_host(Workspace<void, hipHostFree>& w, size_t bytes) {
+  LL_HIP(w.buf.free_now());
+  const size_t cap = grow(w.cap, bytes);
+  void* p = nullptr;
+  LL_HIP(hipHostMalloc(&p, cap, hipHostMallocDefault));
+  w.buf = HostArray<void>(p);
+  w.cap = cap;
+  return p;
 }
-void ll_context::ensure_xfull(size_t bytes) {
-  if (bytes <= xfull_cap) return;
-  if (d_xfull) LL_HIP(hipFree(d_xfull));
-  d_xfull = nullptr;
-  xfull_cap = bytes;
-  dev_malloc(&d_xfull, xfull_cap, "gathered vector");
-}
-void ll_context::ensure_halo(size_t bytes) {
-  if (bytes <= halo_cap) return;
-  if (d_halo) LL_HIP(hipFree(d_halo));
-  d_halo = nullptr;
-  halo_cap = bytes;
-  dev_malloc(&d_halo, halo_cap, "halo buffer");
-}
-void* ll_context::ensure_stage(size_t bytes) {
-  if (bytes <= stage_cap) return h_stage;
-  if (h_stage) LL_HIP(hipHostFree(h_stage));
-  h_stage = nullptr;
-  stage_cap = grow(stage_cap, bytes);
-  LL_HIP(hipHostMalloc(&h_stage, stage_cap, hipHostMallocDefault));
-  return h_stage;
-}
+void* ll_context::ensure_stage(size_t bytes) { return bytes <= stage.cap ? stage.get() : ensure_host(stage, bytes); }
 void* ll_context::ensure_cb_stage(size_t bytes) {
-  if (bytes <= cb_cap) return h_cb;
+  if (bytes <= cb.cap) return cb.get();
   LL_HIP(hipStreamSynchronize(stream));  // an H2D copy out of the old buffer may still be in flight
-  if (h_cb) LL_HIP(hipHostFree(h_cb));
-  h_cb = nullptr;
-  cb_cap = grow(cb_cap, bytes);
-  LL_HIP(hipHostMalloc(&h_cb, cb_cap, hipHostMallocDefault));
-  return h_cb;
+  return ensure_host(cb, bytes);
 }
 void ll_context::sync() { LL_HIP(hipStreamSynchronize(stream)); }
 void ll_context::drain_comm_events(double* gather_s, double* allreduce_s) {
@@ -229,19 +197,7 @@ void ll_context::drain_comm_events(double* gather_s, double* allreduce_s) {
 
 // ---------------------------------------------------------------- operator storage
 ll_operator::~ll_operator() {
-  if (ctx) (void)hipSetDevice(ctx->device);
-  for (void* q : {d_row_ptr, (void*)d_tile_rows, d_dense, d_onsite, (void*)d_pb_segq, (void*)d_pb_segdest,
-                  (void*)d_pb_rptr, (void*)d_pb_xoff, (void*)d_pb_ncols, d_pb_arena, (void*)d_pb_rexp, d_pb_diag,
-                  (void*)d_pb_blockmax, d_rp_own, d_rp_rem, (void*)d_col_own, (void*)d_col_rem, d_val_own, d_val_rem,
-                  (void*)d_tiles_own, (void*)d_tiles_rem, (void*)d_tl_first, (void*)d_tl_col, (void*)d_tl_quad, d_tl_val,
-                  (void*)d_tl_idx, (void*)d_tl_rexp, (void*)d_tl_xmax, (void*)d_tl_rbmap, (void*)d_sym_qptr, d_sym_val,
-                  (void*)d_sym_idx, (void*)d_sym_rexp, (void*)d_sym_xmax, (void*)d_sym_fptr, d_sym_fval, (void*)d_sym_fdst,
-                  (void*)d_sym_fsrc, d_sym_diag})
-    if (q) (void)hipFree(q);
-  if (owns_arrays) {
-    if (d_col) (void)hipFree(d_col);
-    if (d_val) (void)hipFree(d_val);
-  }
+  if (ctx) (void)hipSetDevice(ctx->device);  // before the images free their arrays
 }
 
 // ---------------------------------------------------------------- exception -> status
@@ -304,8 +260,10 @@ static int ctx_create_impl(int device, void* stream, bool own, ll_context** out)
     } else {
       c->stream = (hipStream_t)stream;
     }
-    LL_HIP(hipMalloc((void**)&c->d_scal, kScalCount * sizeof(double)));
-    LL_HIP(hipMemset(c->d_scal, 0, kScalCount * sizeof(double)));
+    double* scal = nullptr;
+    LL_HIP(hipMalloc((void**)&scal, kScalCount * sizeof(double)));
+    c->scal = DevArray<double>(scal);
+    LL_HIP(hipMemset(scal, 0, kScalCount * sizeof(double)));
     *out = c.release();
   });
 }
@@ -325,24 +283,13 @@ int ll_ctx_destroy(ll_context* ctx) {
     for (auto e : ctx->ev_chunk)
       if (e) (void)hipEventDestroy(e);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
-    if (ctx->d_partials) (void)hipFree(ctx->d_partials);
-    if (ctx->d_alpha_partials) (void)hipFree(ctx->d_alpha_partials);
-    if (ctx->d_h) (void)hipFree(ctx->d_h);
-    if (ctx->d_scal) (void)hipFree(ctx->d_scal);
-    if (ctx->d_norm_partials) (void)hipFree(ctx->d_norm_partials);
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_cb) (void)hipHostFree(ctx->h_cb);
     if (ctx->ev_cb) (void)hipEventDestroy(ctx->ev_cb);
-    if (ctx->d_coeff) (void)hipFree(ctx->d_coeff);
-    if (ctx->d_xfull) (void)hipFree(ctx->d_xfull);
-    if (ctx->d_halo) (void)hipFree(ctx->d_halo);
     for (auto& c : ctx->slab_cache) (void)hipFree(c.first);
     for (auto e : ctx->timer_events) (void)hipEventDestroy(e);
     if (ctx->t0) (void)hipEventDestroy(ctx->t0);
     if (ctx->t1) (void)hipEventDestroy(ctx->t1);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // (the workspace buffers free themselves)
   });
 }
 int ll_ctx_reload_env(ll_context* ctx) {
@@ -416,24 +363,19 @@ int ll_bandwidth_probe(ll_context* ctx, size_t bytes, double* read_GBps, double*
     use(ctx);
     LL_REQUIRE(bytes >= ((size_t)1 << 20) && read_GBps && copy_GBps, "ll_bandwidth_probe: at least 1 MiB and two outputs");
     bytes &= ~(size_t)4095;
-    struct Buf {
-      void *a = nullptr, *b = nullptr;
-      double* out = nullptr;
+    struct Events {
       hipEvent_t e0 = nullptr, e1 = nullptr;
-      ~Buf() {
-        if (a) (void)hipFree(a);
-        if (b) (void)hipFree(b);
-        if (out) (void)hipFree(out);
+      ~Events() {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
       }
     } w;
     hipStream_t s = ctx->stream;
-    ctx->dev_malloc(&w.a, bytes, "bandwidth probe (source)");
-    ctx->dev_malloc(&w.b, bytes, "bandwidth probe (destination)");
-    ctx->dev_malloc((void**)&w.out, 16, "bandwidth probe (sink)");
-    LL_HIP(hipMemsetAsync(w.a, 0, bytes, s));
-    LL_HIP(hipMemsetAsync(w.b, 0, bytes, s));
+    const DevArray<void> a = ctx->dev_alloc<void>(bytes, "bandwidth probe (source)");
+    const DevArray<void> b = ctx->dev_alloc<void>(bytes, "bandwidth probe (destination)");
+    const DevArray<double> out = ctx->dev_alloc<double>(2, "bandwidth probe (sink)");
+    LL_HIP(hipMemsetAsync(a.get(), 0, bytes, s));
+    LL_HIP(hipMemsetAsync(b.get(), 0, bytes, s));
     LL_HIP(hipEventCreate(&w.e0));
     LL_HIP(hipEventCreate(&w.e1));
     auto timed = [&](auto launch) {  // best grid of a few, three launches each behind one warm-up
@@ -450,8 +392,8 @@ int ll_bandwidth_probe(ll_context* ctx, size_t bytes, double* read_GBps, double*
       }
       return best;
     };
-    const double ms_r = timed([&](int g) { launch_bw_read(w.a, bytes, w.out, g, s); });
-    const double ms_c = timed([&](int g) { launch_bw_copy(w.a, w.b, bytes, g, s); });
+    const double ms_r = timed([&](int g) { launch_bw_read(a.get(), bytes, out.get(), g, s); });
+    const double ms_c = timed([&](int g) { launch_bw_copy(a.get(), b.get(), bytes, g, s); });
     *read_GBps = (double)bytes / (ms_r * 1e-3) / 1e9;
     *copy_GBps = 2.0 * (double)bytes / (ms_c * 1e-3) / 1e9;  // bytes read + bytes written
   });
@@ -474,12 +416,10 @@ void finish_comm_setup_impl(ll_context* ctx) {
   LL_HIP(hipEventCreateWithFlags(&ctx->ev_x_ready, hipEventDisableTiming));
   for (auto& e : ctx->ev_chunk) LL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   const int P = ctx->nranks;
-  double* d = nullptr;
-  LL_HIP(hipMalloc((void**)&d, (size_t)(P + 2) * sizeof(double)));
-  struct Free {
-    void* p;
-    ~Free() { (void)hipFree(p); }
-  } guard{d};
+  double* p = nullptr;
+  LL_HIP(hipMalloc((void**)&p, (size_t)(P + 2) * sizeof(double)));
+  const DevArray<double> buf(p);
+  double* const d = buf.get();
   std::vector<double> h((size_t)P + 2, 0.0);
   h[(size_t)P] = (double)(ctx->rank + 1);  // send slot
   h[(size_t)P + 1] = 1.0;                  // all-reduce slot
@@ -686,27 +626,28 @@ void build_tiles(const int64_t* rp, int64_t nrows, std::vector<int32_t>& tiles, 
   }
 }
 
+// The row offsets and tiles of a CSR image whose columns and values are in place (op->csr).
 template <typename T>
 void finish_csr(ll_operator* op, const int64_t* rp_host) {
   ll_context* ctx = op->ctx;
+  CsrImage& im = op->csr;
   const int64_t nr = op->n_local;
   std::vector<int32_t> tiles;
   build_tiles(rp_host, nr, tiles, sizeof(T) >= 16 ? kMaxSpmvGrid : kMaxGrid, ctx->tune.spmv_tile_balance);
-  op->ntiles = (int)tiles.size() - 1;
-  ctx->dev_malloc((void**)&op->d_tile_rows, tiles.size() * sizeof(int32_t), "SpMV tiles");
-  LL_HIP(hipMemcpy(op->d_tile_rows, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  im.ntiles = (int)tiles.size() - 1;
+  im.tiles = ctx->dev_alloc<int32_t>(tiles.size(), "SpMV tiles");
+  LL_HIP(hipMemcpy(im.tiles.get(), tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   // 64-bit row offsets once nnz exceeds int32 (LL_FORCE_RP64=1: exercise that kernel variant on small test matrices)
-  op->rp64 = op->nnz > (int64_t)0x7fffffff || ctx->tune.force_rp64;
-  if (op->rp64) {
-    ctx->dev_malloc(&op->d_row_ptr, (size_t)(nr + 1) * sizeof(int64_t), "row offsets");
-    LL_HIP(hipMemcpy(op->d_row_ptr, rp_host, (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  im.rp64 = op->nnz > (int64_t)0x7fffffff || ctx->tune.force_rp64;
+  if (im.rp64) {
+    im.row_ptr = ctx->dev_alloc<int64_t>((size_t)nr + 1, "row offsets");
+    LL_HIP(hipMemcpy(im.row_ptr.get(), rp_host, (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   } else {
     std::vector<int32_t> rp32((size_t)nr + 1);
     for (int64_t i = 0; i <= nr; ++i) rp32[i] = (int32_t)rp_host[i];
-    ctx->dev_malloc(&op->d_row_ptr, (size_t)(nr + 1) * sizeof(int32_t), "row offsets");
-    LL_HIP(hipMemcpy(op->d_row_ptr, rp32.data(), (size_t)(nr + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    im.row_ptr = ctx->dev_alloc<int32_t>((size_t)nr + 1, "row offsets");
+    LL_HIP(hipMemcpy(im.row_ptr.get(), rp32.data(), (size_t)(nr + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  (void)ctx;
 }
 
 // Sharded contexts that keep the CSR-stream kernel: split the image by column ownership so that the own-column product
@@ -716,23 +657,19 @@ template <typename T> void build_csr_split(ll_operator* op) {
   ll_context* ctx = op->ctx;
   hipStream_t s = ctx->stream;
   const int64_t nr = op->n_local;
-  if (nr <= 0 || op->d_row_ptr == nullptr) return;
-  int32_t* d_cnt = nullptr;
-  ctx->dev_malloc((void**)&d_cnt, (size_t)nr * sizeof(int32_t), "own-column counts");
-  struct Free1 {
-    void* p;
-    ~Free1() { (void)hipFree(p); }
-  } free_cnt{d_cnt};
-  launch_csr_count_own<T>(*op, d_cnt, s);
+  const bool rp64 = op->csr.rp64;
+  if (nr <= 0 || !op->csr.row_ptr) return;
+  const DevArray<int32_t> d_cnt = ctx->dev_alloc<int32_t>((size_t)nr, "own-column counts");
+  launch_csr_count_own<T>(*op, d_cnt.get(), s);
   std::vector<int32_t> cnt((size_t)nr);
   std::vector<int64_t> rp((size_t)nr + 1);
-  LL_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (op->rp64) {
-    LL_HIP(hipMemcpyAsync(rp.data(), op->d_row_ptr, (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  LL_HIP(hipMemcpyAsync(cnt.data(), d_cnt.get(), (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (rp64) {
+    LL_HIP(hipMemcpyAsync(rp.data(), op->csr.row_ptr.get(), (size_t)(nr + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     LL_HIP(hipStreamSynchronize(s));
   } else {
     std::vector<int32_t> rp32((size_t)nr + 1);
-    LL_HIP(hipMemcpyAsync(rp32.data(), op->d_row_ptr, (size_t)(nr + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    LL_HIP(hipMemcpyAsync(rp32.data(), op->csr.row_ptr.get(), (size_t)(nr + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     LL_HIP(hipStreamSynchronize(s));
     for (int64_t i = 0; i <= nr; ++i) rp[(size_t)i] = rp32[(size_t)i];
   }
@@ -742,71 +679,39 @@ template <typename T> void build_csr_split(ll_operator* op) {
     rp_own[(size_t)i + 1] = rp_own[(size_t)i] + cnt[(size_t)i];
     rp_rem[(size_t)i + 1] = rp_rem[(size_t)i] + (rp[(size_t)i + 1] - rp[(size_t)i] - cnt[(size_t)i]);
   }
-  auto upload_rp = [&](const std::vector<int64_t>& v, void** dst) {
-    if (op->rp64) {
-      ctx->dev_malloc(dst, v.size() * sizeof(int64_t), "split row offsets");
-      LL_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  CsrImage own, rem;
+  own.rp64 = rem.rp64 = rp64;
+  auto upload_rp = [&](const std::vector<int64_t>& v, CsrImage& im) {
+    if (rp64) {
+      im.row_ptr = ctx->dev_alloc<int64_t>(v.size(), "split row offsets");
+      LL_HIP(hipMemcpy(im.row_ptr.get(), v.data(), v.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     } else {
       std::vector<int32_t> v32(v.size());
       for (size_t i = 0; i < v.size(); ++i) v32[i] = (int32_t)v[i];
-      ctx->dev_malloc(dst, v32.size() * sizeof(int32_t), "split row offsets");
-      LL_HIP(hipMemcpy(*dst, v32.data(), v32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      im.row_ptr = ctx->dev_alloc<int32_t>(v32.size(), "split row offsets");
+      LL_HIP(hipMemcpy(im.row_ptr.get(), v32.data(), v32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   };
-  auto upload_tiles = [&](const std::vector<int64_t>& v, int32_t** dst, int* ntiles) {
+  auto upload_tiles = [&](const std::vector<int64_t>& v, CsrImage& im) {
     std::vector<int32_t> tiles;
     build_tiles(v.data(), nr, tiles, sizeof(T) >= 16 ? kMaxSpmvGrid : kMaxGrid, ctx->tune.spmv_tile_balance);
-    *ntiles = (int)tiles.size() - 1;
-    ctx->dev_malloc((void**)dst, tiles.size() * sizeof(int32_t), "split SpMV tiles");
-    LL_HIP(hipMemcpy(*dst, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    im.ntiles = (int)tiles.size() - 1;
+    im.tiles = ctx->dev_alloc<int32_t>(tiles.size(), "split SpMV tiles");
+    LL_HIP(hipMemcpy(im.tiles.get(), tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   };
-  upload_rp(rp_own, &op->d_rp_own);
-  upload_rp(rp_rem, &op->d_rp_rem);
-  upload_tiles(rp_own, &op->d_tiles_own, &op->ntiles_own);
-  upload_tiles(rp_rem, &op->d_tiles_rem, &op->ntiles_rem);
+  upload_rp(rp_own, own);
+  upload_rp(rp_rem, rem);
+  upload_tiles(rp_own, own);
+  upload_tiles(rp_rem, rem);
   const size_t n_own = (size_t)rp_own[(size_t)nr], n_rem = (size_t)rp_rem[(size_t)nr];
-  ctx->dev_malloc((void**)&op->d_col_own, std::max<size_t>(n_own, 1) * sizeof(int32_t), "own-column indices");
-  ctx->dev_malloc(&op->d_val_own, std::max<size_t>(n_own, 1) * sizeof(T), "own-column values");
-  ctx->dev_malloc((void**)&op->d_col_rem, std::max<size_t>(n_rem, 1) * sizeof(int32_t), "remote-column indices");
-  ctx->dev_malloc(&op->d_val_rem, std::max<size_t>(n_rem, 1) * sizeof(T), "remote-column values");
-  launch_csr_split<T>(*op, s);
+  own.col = ctx->dev_alloc<int32_t>(std::max<size_t>(n_own, 1), "own-column indices");
+  own.val = ctx->dev_alloc<T>(std::max<size_t>(n_own, 1), "own-column values");
+  rem.col = ctx->dev_alloc<int32_t>(std::max<size_t>(n_rem, 1), "remote-column indices");
+  rem.val = ctx->dev_alloc<T>(std::max<size_t>(n_rem, 1), "remote-column values");
+  launch_csr_split<T>(*op, own, rem, s);
   LL_HIP(hipStreamSynchronize(s));
-  op->csr_split = true;
-}
-
-// Undo a (possibly partial) column split: the operator runs gather-then-multiply on its unsplit image.
-void release_csr_split(ll_operator* op) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  drop(op->d_rp_own);
-  drop(op->d_rp_rem);
-  drop(op->d_col_own);
-  drop(op->d_col_rem);
-  drop(op->d_val_own);
-  drop(op->d_val_rem);
-  drop(op->d_tiles_own);
-  drop(op->d_tiles_rem);
-  op->ntiles_own = op->ntiles_rem = 0;
-  op->csr_split = false;
-}
-// The unsplit CSR arrays of an operator that runs on its column-split image (the row offsets stay: 4 bytes per row, and
-// they mark the operator as one that still has a CSR-stream image).
-void release_unsplit_csr(ll_operator* op) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  if (op->owns_arrays) {
-    drop(op->d_col);
-    drop(op->d_val);
-  } else {
-    op->d_col = nullptr;  // the caller's arrays: just forget them
-    op->d_val = nullptr;
-  }
-  drop(op->d_tile_rows);
-  op->ntiles = 0;
+  op->csr_own = std::move(own);
+  op->csr_rem = std::move(rem);
 }
 
 // Row ranges of a sharded operator must be the ll_partition() ones (equal shard strides).
@@ -825,64 +730,15 @@ void set_partition(ll_context* ctx, ll_operator* op, int64_t n, int64_t row_begi
   }
 }
 
-// Drop the device arrays of the SpMV image that is NOT selected (LL_SPMV_KEEP_BOTH=1 keeps both for A/B timing).
-void release_image(ll_operator* op, int keep_kind);
+// Drop the SpMV images that are NOT selected (LL_SPMV_KEEP_BOTH=1 keeps both for A/B timing).  CSR-stream needs the CSR image;
+// the other kernels need none of it (the caller's borrowed arrays are just forgotten).
 void release_unselected_image(ll_operator* op) {
   if (op->ctx->tune.keep_both) return;
-  release_image(op, op->spmv_kind);
-}
-void release_image(ll_operator* op, int keep_kind) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  if (keep_kind != LL_SPMV_CSR_STREAM) {  // CSR-stream needs row_ptr / col / val / tiles; the other kernels need none of them
-    if (op->owns_arrays) {
-      drop(op->d_col);
-      drop(op->d_val);
-    } else {
-      op->d_col = nullptr;  // the caller's arrays: just forget them
-      op->d_val = nullptr;
-    }
-    drop(op->d_row_ptr);
-    drop(op->d_tile_rows);
-    op->ntiles = 0;
-  }
-  if (keep_kind != LL_SPMV_PB) {
-    drop(op->d_pb_segq);
-    drop(op->d_pb_segdest);
-    drop(op->d_pb_rptr);
-    drop(op->d_pb_xoff);
-    drop(op->d_pb_ncols);
-    drop(op->d_pb_arena);
-    drop(op->d_pb_rexp);
-    drop(op->d_pb_blockmax);
-    drop(op->d_pb_diag);
-    op->d_pb_val = op->d_pb_prod = nullptr;  // interior pointers of the arena
-    op->d_pb_col = op->d_pb_row = nullptr;
-    op->pb_ncb = op->pb_nrb = 0;
-  }
-  if (keep_kind != LL_SPMV_TILED) tl_release(op);
-  if (keep_kind != LL_SPMV_SYM) sym_release(op);
-}
-// the part of the PB image that is allocated so far (a failed or refused build)
-void release_pb_image(ll_operator* op) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  drop(op->d_pb_segq);
-  drop(op->d_pb_segdest);
-  drop(op->d_pb_rptr);
-  drop(op->d_pb_xoff);
-  drop(op->d_pb_ncols);
-  drop(op->d_pb_arena);
-  drop(op->d_pb_rexp);
-  drop(op->d_pb_blockmax);
-  drop(op->d_pb_diag);
-  op->d_pb_val = op->d_pb_prod = nullptr;
-  op->d_pb_col = op->d_pb_row = nullptr;
-  op->pb_ncb = op->pb_nrb = 0;
+  const int keep = op->spmv_kind;
+  if (keep != LL_SPMV_CSR_STREAM) op->csr = CsrImage();
+  if (keep != LL_SPMV_PB) op->pb = PbImage();
+  if (keep != LL_SPMV_TILED) op->tl = TiledImage();
+  if (keep != LL_SPMV_SYM) op->sym = SymImage();
 }
 
 // Placement of the PB image.  The same image at another address runs up to 5-8 % faster or slower (round 2: "position
@@ -894,28 +750,26 @@ void release_pb_image(ll_operator* op) {
 template <typename T> double tune_pb_placement(ll_operator* op) {
   ll_context* ctx = op->ctx;
   hipStream_t s = ctx->stream;
-  if (op->d_pb_arena == nullptr || op->nnz < ((int64_t)1 << 22)) return -1.0;
+  PbImage& pb = op->pb;
+  if (!pb.present() || op->nnz < ((int64_t)1 << 22)) return -1.0;
   const size_t xn = (size_t)std::max<int64_t>(op->n, op->n_shard * std::max(1, ctx->nranks));
-  struct Scratch {
-    T *x = nullptr, *y = nullptr;
+  struct Events {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch() {
-      if (x) (void)hipFree(x);
-      if (y) (void)hipFree(y);
+    ~Events() {
       if (e0) (void)hipEventDestroy(e0);
       if (e1) (void)hipEventDestroy(e1);
     }
   } w;
-  ctx->dev_malloc((void**)&w.x, xn * sizeof(T), "placement timing x");
-  ctx->dev_malloc((void**)&w.y, (size_t)std::max<int64_t>(op->n_local, 1) * sizeof(T), "placement timing y");
-  LL_HIP(hipMemsetAsync(w.x, 0, xn * sizeof(T), s));
+  const DevArray<T> x = ctx->dev_alloc<T>(xn, "placement timing x");
+  const DevArray<T> y = ctx->dev_alloc<T>((size_t)std::max<int64_t>(op->n_local, 1), "placement timing y");
+  LL_HIP(hipMemsetAsync(x.get(), 0, xn * sizeof(T), s));
   LL_HIP(hipEventCreate(&w.e0));
   LL_HIP(hipEventCreate(&w.e1));
   auto time_pb = [&]() {
     double best = 1e30;
     for (int rep = 0; rep < 3; ++rep) {
       LL_HIP(hipEventRecord(w.e0, s));
-      launch_spmv_pb<T>(*op, w.x, w.x + op->row_begin, w.x + op->row_begin, w.y, 0.0, nullptr, s);
+      launch_spmv_pb<T>(*op, x.get(), x.get() + op->row_begin, x.get() + op->row_begin, y.get(), 0.0, nullptr, s);
       LL_HIP(hipEventRecord(w.e1, s));
       LL_HIP(hipEventSynchronize(w.e1));
       float ms = 0.f;
@@ -924,74 +778,63 @@ template <typename T> double tune_pb_placement(ll_operator* op) {
     }
     return best;
   };
-  auto rebase = [&](void* arena) {
-    const ptrdiff_t d = (char*)arena - (char*)op->d_pb_arena;
-    op->d_pb_arena = arena;
-    op->d_pb_val = (char*)op->d_pb_val + d;
-    op->d_pb_col = (uint16_t*)((char*)op->d_pb_col + d);
-    op->d_pb_row = (uint16_t*)((char*)op->d_pb_row + d);
-    op->d_pb_prod = (char*)op->d_pb_prod + d;
-  };
   // Every candidate stays allocated until all have been timed (an allocation freed at once would simply be handed out
-  // again for the next one); then all but the fastest are freed.
+  // again for the next one); then all but the fastest are freed.  cand[0] is the arena the image was built in.
+  std::vector<DevArray<void>> cand;
+  cand.push_back(std::move(pb.arena));
+  size_t best_i = 0;
+  std::vector<size_t> losers;  // in the order they lost
   double best = time_pb();
-  if (op->ctx->tune.pb_placement_trace) std::fprintf(stderr, "[ll placement] draw 0 at %p: %.4f ms\n", op->d_pb_arena, best);
-  void* best_arena = op->d_pb_arena;
-  std::vector<void*> losers;
+  if (ctx->tune.pb_placement_trace) std::fprintf(stderr, "[ll placement] draw 0 at %p: %.4f ms\n", cand[0].get(), best);
   // The candidates that lose are not returned to the device: sized like a Krylov-basis slab of a default run on this operator
   // (when that is at least the arena's size), they go into the context's slab cache and become the first basis slabs.  A process
   // that starts on a GPU another process has just left pays ~120 ms per fresh 4 GiB hipMalloc: config 3's
   // first run() to convergence needs seven slabs — the search has already paid for seven allocations.
   const size_t slab_hint = (size_t)default_slab_bytes(op->n, op->n_local, op->n_shard, op->elem_bytes, ctx->tune);
-  const size_t cand_bytes = slab_hint >= op->pb_arena_bytes && slab_hint <= 2 * op->pb_arena_bytes ? slab_hint : op->pb_arena_bytes;
-  void* const first_arena = op->d_pb_arena;
-  bool finished = false;
-  // Unwinding (a failed copy or launch, thrown through LL_HIP): the operator goes back to the best image found so far and
-  // every other copy is freed exactly once — `losers` never contains the arena the operator is bound to at that point.
-  struct Guard {
-    std::vector<void*>& v;
-    void*& best;
-    decltype(rebase)& rb;
-    ll_context* ctx;
-    void* first;
-    size_t cand_bytes, slab_hint;
-    bool& finished;
-    ~Guard() {
-      rb(best);
-      for (void* p : v) {
-        if (p == best) continue;
-        // (at most eight slabs of that size are kept this way: a context on which many operators are created must not pile up
-        // a placement search's worth of HBM per operator)
-        size_t same = 0;
-        for (auto& c : ctx->slab_cache) same += c.second == cand_bytes;
-        if (finished && p != first && cand_bytes == slab_hint && same < 8) ctx->cache_put(p, cand_bytes);
-        else (void)hipFree(p);
+  const size_t cand_bytes = slab_hint >= pb.arena_bytes && slab_hint <= 2 * pb.arena_bytes ? slab_hint : pb.arena_bytes;
+  // The image goes back to the best arena found so far — also when a copy or launch throws (LL_HIP) — and the other copies
+  // are freed, or, after a completed search, cached.
+  auto settle = [&](bool finished) {
+    pb.rebase(cand[best_i].get());
+    pb.arena = std::move(cand[best_i]);
+    for (size_t i : losers) {
+      // (at most eight slabs of that size are kept this way: a context on which many operators are created must not pile up
+      // a placement search's worth of HBM per operator)
+      size_t same = 0;
+      for (auto& c : ctx->slab_cache) same += c.second == cand_bytes;
+      if (finished && i != 0 && cand_bytes == slab_hint && same < 8) ctx->cache_put(cand[i].release(), cand_bytes);
+    }
+    cand.clear();  // frees the others
+  };
+  try {
+    // candidates come from the context's allocator: under memory pressure it releases the cached Krylov slabs once before
+    // giving up, so a large matrix is not silently left with fewer draws
+    for (int t = 1; t < ctx->tune.pb_placements; ++t) {
+      try {
+        cand.push_back(ctx->dev_alloc<void>(cand_bytes, "PB placement candidate"));
+      } catch (const Failure&) {  // no room for another copy: decide among what we have
+        (void)hipGetLastError();
+        break;
       }
+      LL_HIP(hipMemcpyAsync(cand.back().get(), cand[best_i].get(), pb.arena_static_bytes, hipMemcpyDeviceToDevice, s));
+      pb.rebase(cand.back().get());
+      const double ms = time_pb();
+      if (ctx->tune.pb_placement_trace)
+        std::fprintf(stderr, "[ll placement] draw %d at %p: %.4f ms (best so far %.4f)\n", t, cand.back().get(), ms, best);
+      if (ms < best) {
+        best = ms;
+        losers.push_back(best_i);  // the previous best becomes a loser
+        best_i = cand.size() - 1;
+      } else {
+        losers.push_back(cand.size() - 1);
+      }
+      pb.rebase(cand[best_i].get());
     }
-  } guard{losers, best_arena, rebase, ctx, first_arena, cand_bytes, slab_hint, finished};
-  // candidates come from the context's allocator: under memory pressure it releases the cached Krylov slabs once before
-  // giving up, so a large matrix is not silently left with fewer draws
-  for (int t = 1; t < ctx->tune.pb_placements; ++t) {
-    void* cand = nullptr;
-    try {
-      ctx->dev_malloc(&cand, cand_bytes, "PB placement candidate");
-    } catch (const Failure&) {  // no room for another copy: decide among what we have
-      (void)hipGetLastError();
-      break;
-    }
-    losers.push_back(cand);
-    LL_HIP(hipMemcpyAsync(cand, best_arena, op->pb_arena_static_bytes, hipMemcpyDeviceToDevice, s));
-    rebase(cand);
-    const double ms = time_pb();
-    if (op->ctx->tune.pb_placement_trace) std::fprintf(stderr, "[ll placement] draw %d at %p: %.4f ms (best so far %.4f)\n", t, cand, ms, best);
-    if (ms < best) {
-      best = ms;
-      losers.back() = best_arena;  // the previous best becomes a loser
-      best_arena = cand;
-    }
-    rebase(best_arena);
+  } catch (...) {
+    settle(false);
+    throw;
   }
-  finished = true;
+  settle(true);
   return best;
 }
 
@@ -1002,34 +845,29 @@ template <typename T> void autotune_spmv(ll_operator* op) {
   ll_context* ctx = op->ctx;
   hipStream_t s = ctx->stream;
   const size_t xn = (size_t)std::max<int64_t>(op->n, op->n_shard * std::max(1, ctx->nranks));
-  struct Scratch {
-    T *x = nullptr, *y = nullptr;
-    double* t = nullptr;
+  struct Events {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch() {
-      if (x) (void)hipFree(x);
-      if (y) (void)hipFree(y);
-      if (t) (void)hipFree(t);
+    ~Events() {
       if (e0) (void)hipEventDestroy(e0);
       if (e1) (void)hipEventDestroy(e1);
     }
   } w;
-  ctx->dev_malloc((void**)&w.x, xn * sizeof(T), "autotune x");
-  ctx->dev_malloc((void**)&w.y, (size_t)std::max<int64_t>(op->n_local, 1) * sizeof(T), "autotune y");
-  ctx->dev_malloc((void**)&w.t, 3 * sizeof(double), "autotune scalars");
-  LL_HIP(hipMemsetAsync(w.x, 0, xn * sizeof(T), s));
+  const DevArray<T> x = ctx->dev_alloc<T>(xn, "autotune x");
+  const DevArray<T> y = ctx->dev_alloc<T>((size_t)std::max<int64_t>(op->n_local, 1), "autotune y");
+  const DevArray<double> t = ctx->dev_alloc<double>(3, "autotune scalars");
+  LL_HIP(hipMemsetAsync(x.get(), 0, xn * sizeof(T), s));
   LL_HIP(hipEventCreate(&w.e0));
   LL_HIP(hipEventCreate(&w.e1));
   double t_kind[3] = {1e30, 1e30, 1e30};
   for (int kind : {LL_SPMV_CSR_STREAM, LL_SPMV_PB, LL_SPMV_TILED}) {
-    if (kind == LL_SPMV_PB && op->d_pb_val == nullptr) continue;     // image not built: not a candidate
-    if (kind == LL_SPMV_TILED && op->tl_nrb <= 0) continue;
+    if (kind == LL_SPMV_PB && !op->pb.present()) continue;     // image not built: not a candidate
+    if (kind == LL_SPMV_TILED && !op->tl.present()) continue;
     try {
       for (int rep = 0; rep < 3; ++rep) {
         LL_HIP(hipEventRecord(w.e0, s));
-        if (kind == LL_SPMV_PB) launch_spmv_pb<T>(*op, w.x, w.x + op->row_begin, w.x + op->row_begin, w.y, 0.0, nullptr, s);
-        else if (kind == LL_SPMV_TILED) launch_spmv_tiled<T>(*op, w.x, w.y, 0.0, nullptr, s);
-        else launch_spmv<T>(*op, w.x, w.x + op->row_begin, w.y, 0.0, nullptr, s);
+        if (kind == LL_SPMV_PB) launch_spmv_pb<T>(*op, x.get(), x.get() + op->row_begin, x.get() + op->row_begin, y.get(), 0.0, nullptr, s);
+        else if (kind == LL_SPMV_TILED) launch_spmv_tiled<T>(*op, x.get(), y.get(), 0.0, nullptr, s);
+        else launch_spmv<T>(*op, x.get(), x.get() + op->row_begin, y.get(), 0.0, nullptr, s);
         LL_HIP(hipEventRecord(w.e1, s));
         LL_HIP(hipEventSynchronize(w.e1));
         float ms = 0.f;
@@ -1043,9 +881,9 @@ template <typename T> void autotune_spmv(ll_operator* op) {
   }
   for (int k = 0; k < 3; ++k) op->tune_ms[k] = t_kind[k] < 1e29 ? (float)t_kind[k] : -1.f;
   if (ctx->comm != nullptr) {
-    LL_HIP(hipMemcpyAsync(w.t, t_kind, 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    comm_allreduce_sum(ctx->comm, w.t, 3, s);
-    LL_HIP(hipMemcpyAsync(t_kind, w.t, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    LL_HIP(hipMemcpyAsync(t.get(), t_kind, 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    comm_allreduce_sum(ctx->comm, t.get(), 3, s);
+    LL_HIP(hipMemcpyAsync(t_kind, t.get(), 3 * sizeof(double), hipMemcpyDeviceToHost, s));
     LL_HIP(hipStreamSynchronize(s));
   }
   op->spmv_kind = LL_SPMV_CSR_STREAM;
@@ -1083,15 +921,14 @@ void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, cons
   set_partition(ctx, op.get(), nc, row_begin, nr);
   op->nnz = rp_host[nr];
   const size_t nnz = (size_t)op->nnz;
-  if (on_device) {
-    op->owns_arrays = false;
-    op->d_col = const_cast<int32_t*>(ci);
-    op->d_val = const_cast<void*>(va);
+  if (on_device) {  // the caller's arrays: borrowed, never freed
+    op->csr.col = DevArray<int32_t>::borrow(const_cast<int32_t*>(ci));
+    op->csr.val = DevArray<void>::borrow(const_cast<void*>(va));
   } else {
-    ctx->dev_malloc((void**)&op->d_col, std::max<size_t>(nnz, 1) * sizeof(int32_t), "CSR column indices");
-    ctx->dev_malloc(&op->d_val, std::max<size_t>(nnz, 1) * sizeof(T), "CSR values");
-    LL_HIP(hipMemcpy(op->d_col, ci, nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-    LL_HIP(hipMemcpy(op->d_val, va, nnz * sizeof(T), hipMemcpyHostToDevice));
+    op->csr.col = ctx->dev_alloc<int32_t>(std::max<size_t>(nnz, 1), "CSR column indices");
+    op->csr.val = ctx->dev_alloc<T>(std::max<size_t>(nnz, 1), "CSR values");
+    LL_HIP(hipMemcpy(op->csr.col.get(), ci, nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+    LL_HIP(hipMemcpy(op->csr.val.get(), va, nnz * sizeof(T), hipMemcpyHostToDevice));
   }
   finish_csr<T>(op.get(), rp_host);
   // column range check and max absolute row sum (ll_op_inf_norm; determine_eigenvalue_offset.cpp:12-29), on the device
@@ -1104,20 +941,13 @@ void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, cons
   // out, must not leave the ranks with different kernels: the exchange plan and the collectives issued depend on it).
   auto all_ranks_agree = [&](bool mine) {
     if (ctx->comm == nullptr) return mine;
-    double* d = nullptr;
-    ctx->dev_malloc((void**)&d, sizeof(double), "agreement flag");
+    const DevArray<double> d = ctx->dev_alloc<double>(1, "agreement flag");
     const double v = mine ? 0.0 : 1.0;
     double sum = 0.0;
-    try {
-      LL_HIP(hipMemcpyAsync(d, &v, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      comm_allreduce_sum(ctx->comm, d, 1, ctx->stream);
-      LL_HIP(hipMemcpyAsync(&sum, d, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-      LL_HIP(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-      (void)hipFree(d);
-      throw;
-    }
-    (void)hipFree(d);
+    LL_HIP(hipMemcpyAsync(d.get(), &v, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    comm_allreduce_sum(ctx->comm, d.get(), 1, ctx->stream);
+    LL_HIP(hipMemcpyAsync(&sum, d.get(), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    LL_HIP(hipStreamSynchronize(ctx->stream));
     return sum == 0.0;
   };
   // 0 auto, 1 csr, 2 pb, 3 tiled.
@@ -1138,26 +968,24 @@ void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, cons
       (void)hipGetLastError();
       built = false;
     }
-    if (!built) release_pb_image(op.get());  // whatever part of the image was allocated
     pb_ok = all_ranks_agree(built);
-    if (built && !pb_ok) release_pb_image(op.get());  // some rank could not build it: nobody uses it
+    if (built && !pb_ok) op->pb = PbImage();  // some rank could not build it: nobody uses it
   }
   if ((want == 0 || want == 3) && (nnz > 0 || ctx->comm != nullptr)) {
     // the 2-D tiled image: only for matrices whose row blocks touch few column tiles (tl_build_device decides).  One image serves
     // both accuracy classes: fixed-point sums (norm-wise) or the waves adding in turn in floating point (component-wise).
-    op->tl_ordered = componentwise;
     bool built = false;
     try {
       built = nnz > 0 && tl_build_device<T>(op.get());
     } catch (const Failure& f) {
       if (!(f.code == LL_ERR_ALLOC && (want == 0 || ctx->comm != nullptr))) throw;
       (void)hipGetLastError();
-      tl_release(op.get());
       built = false;
     }
+    op->tl.ordered = componentwise;
     // (sharded contexts: the kernel choice is collective — the exchange in front of the tiled kernel carries the ranks' maxima)
     tl_ok = all_ranks_agree(built);
-    if (built && !tl_ok) tl_release(op.get());
+    if (built && !tl_ok) op->tl = TiledImage();
     LL_REQUIRE(!(want == 3 && !tl_ok), "this matrix is not eligible for the tiled SpMV kernel (its row blocks touch too many column tiles)");
   }
   // Asked for by name, the tiled kernel is an error where no tiled image exists (a matrix without entries) — never a silent
@@ -1172,7 +1000,7 @@ void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, cons
   }
   release_unselected_image(op.get());
   // (every rank takes this branch or none: the kernel choice above is collective, the switch comes from the environment)
-  if (ctx->nranks > 1 && ctx->tune.csr_split && op->d_row_ptr != nullptr) {
+  if (ctx->nranks > 1 && ctx->tune.csr_split && op->csr.row_ptr) {
     // The split image is a second copy of the matrix.  When it does not fit next to the original (a shard that already fell
     // back to CSR-stream because the PB image did not fit), the operator stays usable in the gather-then-multiply form — safe
     // per rank: split and unsplit ranks issue the same single all-gather.
@@ -1181,11 +1009,16 @@ void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, cons
     } catch (const Failure& f) {
       if (f.code != LL_ERR_ALLOC) throw;
       (void)hipGetLastError();
-      release_csr_split(op.get());
     }
     // Once split, the unsplit arrays are never read again on this context: return them (steady-state footprint 1 x the matrix)
-    // unless LL_SPMV_KEEP_BOTH=1 asked for every image to stay.
-    if (op->csr_split && !ctx->tune.keep_both && op->spmv_kind == LL_SPMV_CSR_STREAM) release_unsplit_csr(op.get());
+    // unless LL_SPMV_KEEP_BOTH=1 asked for every image to stay.  The row offsets stay (4 bytes per row): they mark the operator
+    // as one that still has a CSR-stream image.
+    if (op->csr_split() && !ctx->tune.keep_both && op->spmv_kind == LL_SPMV_CSR_STREAM) {
+      op->csr.col.reset();
+      op->csr.val.reset();
+      op->csr.tiles.reset();
+      op->csr.ntiles = 0;
+    }
   }
   *out = op.release();
 }
@@ -1211,8 +1044,8 @@ void create_dense(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, co
   }
   op->inf_norm = mx;
   const size_t bytes = (size_t)nr * (size_t)nc * sizeof(T);
-  ctx->dev_malloc(&op->d_dense, std::max<size_t>(bytes, 16), "dense matrix");
-  if (bytes) LL_HIP(hipMemcpy(op->d_dense, a, bytes, hipMemcpyHostToDevice));
+  op->dense = ctx->dev_alloc<void>(std::max<size_t>(bytes, 16), "dense matrix");
+  if (bytes) LL_HIP(hipMemcpy(op->dense.get(), a, bytes, hipMemcpyHostToDevice));
   *out = op.release();
 }
 
@@ -1261,8 +1094,8 @@ void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin
     typedef typename scalar_traits<T>::real R;
     std::vector<R> tmp((size_t)n_local);
     for (int64_t i = 0; i < n_local; ++i) tmp[(size_t)i] = (R)onsite[i];
-    ctx->dev_malloc(&op->d_onsite, std::max<size_t>((size_t)n_local * sizeof(R), 16), "on-site terms");
-    LL_HIP(hipMemcpy(op->d_onsite, tmp.data(), (size_t)n_local * sizeof(R), hipMemcpyHostToDevice));
+    op->onsite = ctx->dev_alloc<void>(std::max<size_t>((size_t)n_local * sizeof(R), 16), "on-site terms");
+    LL_HIP(hipMemcpy(op->onsite.get(), tmp.data(), (size_t)n_local * sizeof(R), hipMemcpyHostToDevice));
   }
   op->inf_norm = diag_max + hops;  // an upper bound of the max absolute row sum (equal to it for interior sites)
   *out = op.release();
@@ -1453,10 +1286,12 @@ void create_csr_sym(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, con
     op->nnz = fnnz;
     op->inf_norm = mx;
     op->sym_stored = nnz;
-    op->sym_halo = (int)win_halo;
-    op->sym_rb_rows = rb_rows;
-    sym_build<T>(op.get(), rp_h.data(), ci_h, va_h);
-    LL_HIP(hipMemcpy(op->d_sym_rexp, rexp.data(), rexp.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    SymImage im;
+    im.halo = (int)win_halo;
+    im.rb_rows = rb_rows;
+    sym_build<T>(*op, im, rp_h.data(), ci_h, va_h);
+    LL_HIP(hipMemcpy(im.rexp.get(), rexp.data(), rexp.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    op->sym = std::move(im);
     op->spmv_kind = LL_SPMV_SYM;
     *out = op.release();
     return;
@@ -1493,33 +1328,6 @@ void create_csr_sym(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, con
   *out = raw;
 }
 
-// device bytes of every allocation the operator holds (interior pointers of the PB arena are not allocations)
-int64_t op_device_bytes(const ll_operator* op) {
-  int64_t total = 0;
-  auto add = [&](const void* p) {
-    if (p == nullptr) return;
-    size_t b = 0;
-    LL_HIP(hipMemPtrGetInfo(const_cast<void*>(p), &b));
-    total += (int64_t)b;
-  };
-  for (const void* q : std::initializer_list<const void*>{op->d_row_ptr, (const void*)op->d_tile_rows, (const void*)op->d_dense, op->d_onsite, (const void*)op->d_pb_segq,
-                        (const void*)op->d_pb_segdest, (const void*)op->d_pb_rptr, (const void*)op->d_pb_xoff,
-                        (const void*)op->d_pb_ncols, op->d_pb_arena, (const void*)op->d_pb_rexp, op->d_pb_diag,
-                        (const void*)op->d_pb_blockmax, op->d_rp_own, op->d_rp_rem, (const void*)op->d_col_own,
-                        (const void*)op->d_col_rem, op->d_val_own, op->d_val_rem, (const void*)op->d_tiles_own,
-                        (const void*)op->d_tiles_rem, (const void*)op->d_tl_first, (const void*)op->d_tl_col,
-                        (const void*)op->d_tl_quad, op->d_tl_val, (const void*)op->d_tl_idx, (const void*)op->d_tl_rexp,
-                        (const void*)op->d_tl_xmax, (const void*)op->d_tl_rbmap, (const void*)op->d_sym_qptr, op->d_sym_val,
-                        (const void*)op->d_sym_idx, (const void*)op->d_sym_rexp, (const void*)op->d_sym_xmax,
-                        (const void*)op->d_sym_fptr, op->d_sym_fval, (const void*)op->d_sym_fdst, (const void*)op->d_sym_fsrc,
-                        op->d_sym_diag})
-    add(q);
-  if (op->owns_arrays) {
-    add(op->d_col);
-    add(op->d_val);
-  }
-  return total;
-}
 }  // namespace
 }  // extern "C++"
 int ll_op_create_csr_sym_d(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const double* va,
@@ -1542,7 +1350,7 @@ int ll_op_device_bytes(const ll_operator* op, int64_t* bytes) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr && bytes != nullptr, "null argument");
     if (op->ctx) LL_HIP(hipSetDevice(op->ctx->device));
-    *bytes = op_device_bytes(op);
+    *bytes = op->device_bytes();
   });
 }
 int ll_op_create_coo_d(ll_context* ctx, int64_t n, int64_t nnz, const int32_t* rows, const int32_t* cols,
@@ -1613,13 +1421,13 @@ int ll_op_select_spmv(ll_operator* op, int kind) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr && op->kind == ll_operator::CSR, "not a CSR operator");
     LL_REQUIRE(kind == LL_SPMV_CSR_STREAM || kind == LL_SPMV_PB || kind == LL_SPMV_TILED || kind == LL_SPMV_SYM, "unknown SpMV kernel");
-    LL_REQUIRE(kind != LL_SPMV_SYM || op->sym_nrb > 0,
+    LL_REQUIRE(kind != LL_SPMV_SYM || op->sym.present(),
                "operator has no one-triangle image (only ll_op_create_csr_sym_* builds it, when it selects that kernel)");
-    LL_REQUIRE(kind != LL_SPMV_PB || op->d_pb_val != nullptr,
+    LL_REQUIRE(kind != LL_SPMV_PB || op->pb.present(),
                "operator has no propagation-blocked image (not selected at creation; LL_SPMV_KEEP_BOTH=1 keeps every image)");
-    LL_REQUIRE(kind != LL_SPMV_CSR_STREAM || (op->d_row_ptr != nullptr && (op->d_col != nullptr || op->nnz == 0 || op->csr_split)),
+    LL_REQUIRE(kind != LL_SPMV_CSR_STREAM || op->has_csr_stream(),
                "operator has released its CSR image (another kernel was selected at creation; LL_SPMV_KEEP_BOTH=1 keeps every image)");
-    LL_REQUIRE(kind != LL_SPMV_TILED || op->tl_nrb > 0,
+    LL_REQUIRE(kind != LL_SPMV_TILED || op->tl.present(),
                "operator has no tiled image (matrix not eligible, or not selected at creation; LL_SPMV_KEEP_BOTH=1 keeps every image)");
     op->spmv_kind = kind;
   });
@@ -1631,23 +1439,23 @@ int ll_op_set_accuracy(ll_operator* op, int accuracy) {
                "accuracy must be LL_ACCURACY_NORMWISE or LL_ACCURACY_COMPONENTWISE");
     LL_REQUIRE(!(op->spmv_kind == LL_SPMV_SYM && accuracy == LL_ACCURACY_COMPONENTWISE),
                "the one-triangle kernel sums in fixed point only (norm-wise class): it has no component-wise form");
-    if (op->tl_nrb > 0) op->tl_ordered = accuracy == LL_ACCURACY_COMPONENTWISE;  // the tiled image serves both classes
+    if (op->tl.present()) op->tl.ordered = accuracy == LL_ACCURACY_COMPONENTWISE;  // the tiled image serves both classes
     op->accuracy_req = accuracy;
-    if (op->d_pb_val == nullptr) return;  // no PB image: CSR-stream is component-wise whatever is asked, the tiled kernel was set above
+    if (!op->pb.present()) return;  // no PB image: CSR-stream is component-wise whatever is asked, the tiled kernel was set above
     if (accuracy == LL_ACCURACY_COMPONENTWISE) {
-      if (op->pb_phase2 == LL_PB_FIXED) op->pb_phase2 = LL_PB_ORDERED;
+      if (op->pb.phase2 == LL_PB_FIXED) op->pb.phase2 = LL_PB_ORDERED;
     } else {
-      LL_REQUIRE(op->d_pb_rexp != nullptr && op->d_pb_blockmax != nullptr,
+      LL_REQUIRE(op->pb.rexp && op->pb.blockmax,
                  "this image was built without the row exponents of the fixed-point sums (row block too large for them)");
-      op->pb_phase2 = LL_PB_FIXED;
+      op->pb.phase2 = LL_PB_FIXED;
     }
   });
 }
 int ll_op_accuracy(const ll_operator* op, int* accuracy_out) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr && accuracy_out != nullptr, "null argument");
-    const bool fixed = op->kind == ll_operator::CSR && ((op->spmv_kind == LL_SPMV_PB && op->pb_phase2 == LL_PB_FIXED) ||
-                                                        (op->spmv_kind == LL_SPMV_TILED && !op->tl_ordered) ||
+    const bool fixed = op->kind == ll_operator::CSR && ((op->spmv_kind == LL_SPMV_PB && op->pb.phase2 == LL_PB_FIXED) ||
+                                                        (op->spmv_kind == LL_SPMV_TILED && !op->tl.ordered) ||
                                                         op->spmv_kind == LL_SPMV_SYM);
     *accuracy_out = fixed ? LL_ACCURACY_NORMWISE : LL_ACCURACY_COMPONENTWISE;
   });
@@ -1674,8 +1482,8 @@ int ll_op_autotune_ms_of(const ll_operator* op, int kind, double* ms) {
 int ll_op_tiled_layout(const ll_operator* op, int* row_blocks, int* own_column_row_blocks) {
   return guarded([&] {
     LL_REQUIRE(op != nullptr, "null operator");
-    if (row_blocks) *row_blocks = op->tl_nrb;
-    if (own_column_row_blocks) *own_column_row_blocks = op->ctx->nranks > 1 ? op->tl_n_interior : op->tl_nrb;
+    if (row_blocks) *row_blocks = op->tl.nrb;
+    if (own_column_row_blocks) *own_column_row_blocks = op->ctx->nranks > 1 ? op->tl.n_interior : op->tl.nrb;
   });
 }
 int ll_op_info(const ll_operator* op, int64_t* n, int64_t* n_local, int64_t* nnz) {
@@ -1742,15 +1550,13 @@ void orth_impl(ll_context* ctx, int64_t n, int64_t nb, const T* basis, int64_t l
   const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
   double* d_htot = nullptr;
   if (h_out && nb > 0) LL_HIP(hipMalloc((void**)&d_htot, (size_t)R * nb * sizeof(double)));
+  const DevArray<double> htot(d_htot);
   const NormRefs refs = E.orth(w, runs, mode, no_tt, E.S(kScalScratch), d_htot);
   ctx->ensure_pinned(16);
-  launch_publish(ctx->h_pinned + 8, nullptr, refs, ctx->stream);
+  launch_publish(ctx->pinned.get() + 8, nullptr, refs, ctx->stream);
   ctx->sync();
-  if (norm_out) *norm_out = std::sqrt(ctx->h_pinned[9]);
-  if (d_htot) {
-    LL_HIP(hipMemcpy(h_out, d_htot, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToHost));
-    LL_HIP(hipFree(d_htot));
-  }
+  if (norm_out) *norm_out = std::sqrt(ctx->pinned.get()[9]);
+  if (d_htot) LL_HIP(hipMemcpy(h_out, d_htot, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToHost));
 }
 template <typename T>
 void gemv_impl(ll_context* ctx, int64_t n, int64_t m, const T* basis, int64_t ld, int64_t nout, const T* coeff,

@@ -215,8 +215,8 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
     sc = &from_norm;
   }
   hipStream_t s = ctx->stream;
-  ctx->ensure_alpha_partials(std::max<size_t>(kMaxSpmvGrid, (size_t)std::max({op->pb_nrb, op->tl_nrb, op->sym_nrb})));
-  double* const dotp = d_alpha ? ctx->d_alpha_partials : nullptr;
+  ctx->ensure_alpha_partials(std::max<size_t>(kMaxSpmvGrid, (size_t)std::max({op->pb.nrb, op->tl.nrb, op->sym.nrb})));
+  double* const dotp = d_alpha ? ctx->alpha_partials.get() : nullptr;
   int nparts = 0;
   if (op->kind == ll_operator::STENCIL) {
     // exchange step of the lattice operator: one hyperplane from each ring neighbour instead of the all-gather
@@ -228,7 +228,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
     } else {
       const size_t hb = (size_t)H * sizeof(T);
       ctx->ensure_halo(2 * hb);
-      T* rlo = (T*)ctx->d_halo;
+      T* rlo = (T*)ctx->halo.get();
       T* rhi = rlo + H;
       const bool ring = op->st.periodic[0] != 0;
       const int prev = ctx->rank > 0 ? ctx->rank - 1 : (ring ? ctx->nranks - 1 : -1);
@@ -249,7 +249,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
     constexpr int64_t V = (int64_t)(16 / sizeof(T)) > 0 ? (int64_t)(16 / sizeof(T)) : 1;
     const bool dense_split_ok = op->n % V == 0 && op->row_begin % V == 0 && (op->row_begin + op->n_local) % V == 0;
     const bool tiled = op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_TILED;
-    const bool split = ctx->comm != nullptr && ((op->kind == ll_operator::CSR && !pb && !tiled && op->csr_split) ||
+    const bool split = ctx->comm != nullptr && ((op->kind == ll_operator::CSR && !pb && !tiled && op->csr_split()) ||
                                                 (op->kind == ll_operator::DENSE && ctx->tune.csr_split && dense_split_ok));
     const T* x_full = x_local;
     const T* x_own = x_local;  // what the own-column blocks of the PB kernels read
@@ -262,19 +262,19 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
       const int P = ctx->nranks;
       const size_t shard_bytes = (size_t)op->n_shard * sizeof(T);
       ctx->ensure_xfull(shard_bytes * (size_t)(P + 1));
-      T* gathered = (T*)ctx->d_xfull;
+      T* gathered = (T*)ctx->xfull.get();
       const T* send = x_local;
       if (!x_padded && op->n_local < op->n_shard) {
-        T* pad = (T*)((char*)ctx->d_xfull + shard_bytes * (size_t)P);
+        T* pad = (T*)((char*)ctx->xfull.get() + shard_bytes * (size_t)P);
         LL_HIP(hipMemsetAsync(pad, 0, shard_bytes, s));
         LL_HIP(hipMemcpyAsync(pad, x_local, (size_t)op->n_local * sizeof(T), hipMemcpyDeviceToDevice, s));
         send = pad;
       }
       x_own = send;
       x_full = gathered;
-      // PB: the gather is cut into chunks (op->gather) laid out chunk-major; every other kernel needs global order
+      // PB: the gather is cut into chunks (op->pb.gather) laid out chunk-major; every other kernel needs global order
       GatherPlan plan;
-      if (pb) plan = op->gather;
+      if (pb) plan = op->pb.gather;
       else {
         plan.nchunks = 1;
         plan.start[0] = 0;
@@ -284,7 +284,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
       hipStream_t cs = overlap ? ctx->comm_stream : s;
       // tiled, fixed-point class: the grid's scale needs max |x| over the WHOLE vector before the first launch — every rank's own
       // maximum (two small kernels) travels in an 8-byte all-gather in front of the vector's
-      const bool tl_max = tiled && !op->tl_ordered;
+      const bool tl_max = tiled && !op->tl.ordered;
       if (tl_max) launch_tl_xmax_local<T>(*op, send, s);
       comm_timer_begin(cs);
       if (overlap) {
@@ -292,7 +292,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
         LL_HIP(hipStreamWaitEvent(cs, ctx->ev_x_ready, 0));  // gathered buffer done) precedes the gather
       }
       if (tl_max) {
-        comm_allgather(ctx->comm, op->d_tl_xmax + tl_xmax_local_slot(), op->d_tl_xmax, sizeof(double), cs);
+        comm_allgather(ctx->comm, op->tl.xmax.get() + tl_xmax_local_slot(), op->tl.xmax.get(), sizeof(double), cs);
         if (overlap) LL_HIP(hipEventRecord(ctx->ev_chunk[1], cs));
       }
       for (int c = 0; c < plan.nchunks; ++c) {
@@ -324,10 +324,10 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
         remote_done = true;
       } else if (overlap) {
         // own-column blocks run under the gather; every chunk's remote blocks start when that chunk has arrived
-        launch_pb_phase1<T>(*op, 0, op->pb_own_count, x_own, s, xnorm2);
+        launch_pb_phase1<T>(*op, 0, op->pb.own_count, x_own, s, xnorm2);
         for (int c = 0; c < plan.nchunks; ++c) {
           LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[c], 0));
-          launch_pb_phase1<T>(*op, op->pb_chunk_first[c], op->pb_chunk_count[c], gathered, s, xnorm2);
+          launch_pb_phase1<T>(*op, op->pb.chunk_first[c], op->pb.chunk_count[c], gathered, s, xnorm2);
         }
         nparts = launch_pb_phase2<T>(*op, x_local, y, offset, dotp, s, xnorm2);
         remote_done = true;
@@ -343,7 +343,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
     else if (op->spmv_kind == LL_SPMV_TILED)  // single GPU (sharded contexts took the two-launch form above): x_local is the whole x
       nparts = launch_spmv_tiled<T>(*op, x_local, y, offset, dotp, s, xnorm2);
     else {
-      LL_REQUIRE(op->d_col != nullptr || op->nnz == 0,
+      LL_REQUIRE(op->csr.col || op->nnz == 0,
                  "this operator kept only its column-split image (created on a sharded context) and needs that communicator");
       nparts = launch_spmv<T>(*op, x_full, x_local, y, offset, dotp, s, sc);
     }
@@ -405,21 +405,21 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
 
 template <typename T> void Engine<T>::norm2_dev(const T* v, double* d_out) {
   ctx->ensure_partials((size_t)kMaxGrid * R);
-  const int grid = launch_dot<T>(n_local, v, v, ctx->d_partials, ctx->stream);
+  const int grid = launch_dot<T>(n_local, v, v, ctx->partials.get(), ctx->stream);
   ctx->ensure_h(4);
   if (R == 1) {
-    launch_reduce_cols(ctx->d_partials, grid, 1, d_out, nullptr, ctx->stream);
+    launch_reduce_cols(ctx->partials.get(), grid, 1, d_out, nullptr, ctx->stream);
   } else {  // real part is column 0
-    launch_reduce_cols(ctx->d_partials, grid, R, ctx->d_h, nullptr, ctx->stream);
-    launch_copy_scalar(d_out, ctx->d_h, ctx->stream);
+    launch_reduce_cols(ctx->partials.get(), grid, R, ctx->h.get(), nullptr, ctx->stream);
+    launch_copy_scalar(d_out, ctx->h.get(), ctx->stream);
   }
   all_reduce(d_out, 1);
 }
 
 template <typename T> void Engine<T>::dot_dev(const T* a, const T* b, double* d_out) {
   ctx->ensure_partials((size_t)kMaxGrid * R);
-  const int grid = launch_dot<T>(n_local, a, b, ctx->d_partials, ctx->stream);
-  launch_reduce_cols(ctx->d_partials, grid, R, d_out, nullptr, ctx->stream);
+  const int grid = launch_dot<T>(n_local, a, b, ctx->partials.get(), ctx->stream);
+  launch_reduce_cols(ctx->partials.get(), grid, R, d_out, nullptr, ctx->stream);
   all_reduce(d_out, R);
 }
 
@@ -436,22 +436,22 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
   const bool sharded = ctx->comm != nullptr;
   const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
   ctx->ensure_h((size_t)2 * (R * nb + 2));
-  double* h1 = ctx->d_h;
-  double* h2 = ctx->d_h + (R * nb + 2);
+  double* h1 = ctx->h.get();
+  double* h2 = ctx->h.get() + (R * nb + 2);
 
   if (nb == 0) {  // three-term update (if any) + ||w||^2 only
     BasisSegs<T> none;
     none.nseg = 0;
     none.ld = runs.ld;
     ctx->ensure_partials(kMaxGrid);
-    const int grid = launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+    const int grid = launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
     if (publish && !sharded && publish->can_defer) {
-      *publish = Publish{publish->host, publish->alpha, true, true, true, ctx->d_partials, grid, c + 1, nullptr};
+      *publish = Publish{publish->host, publish->alpha, true, true, true, ctx->partials.get(), grid, c + 1, nullptr};
     } else if (publish && !sharded) {
-      launch_reduce_publish(ctx->d_partials, grid, c + 1, publish->alpha, nullptr, publish->host, s);
+      launch_reduce_publish(ctx->partials.get(), grid, c + 1, publish->alpha, nullptr, publish->host, s);
       publish->done = true;
     } else {
-      launch_reduce_cols(ctx->d_partials, grid, 1, c + 1, nullptr, s);
+      launch_reduce_cols(ctx->partials.get(), grid, 1, c + 1, nullptr, s);
       all_reduce(c + 1, 1);
     }
     return plain_norm(c + 1);
@@ -464,7 +464,7 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
       BasisSegs<T> none;
       none.nseg = 0;
       none.ld = runs.ld;
-      launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+      launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
     }
     int j = 0, grid = 0;
     for (auto& r : runs.runs)
@@ -474,12 +474,12 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
         one.ld = runs.ld;
         one.base[0] = r.first + (int64_t)i * runs.ld;
         one.count[0] = 1;
-        grid = launch_mdot<T>(n_local, w, one, no_tt, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
-        launch_reduce_cols(ctx->d_partials, grid, R + 1, h1 + R * j, S(kScalSpare), s);
+        grid = launch_mdot<T>(n_local, w, one, no_tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+        launch_reduce_cols(ctx->partials.get(), grid, R + 1, h1 + R * j, S(kScalSpare), s);
         all_reduce(h1 + R * j, R);
-        grid = launch_maxpy<T>(n_local, w, one, h1 + R * j, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+        grid = launch_maxpy<T>(n_local, w, one, h1 + R * j, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
       }
-    launch_reduce_cols(ctx->d_partials, grid, 1, c + 1, nullptr, s);
+    launch_reduce_cols(ctx->partials.get(), grid, 1, c + 1, nullptr, s);
     all_reduce(c + 1, 1);
     if (h_total) LL_HIP(hipMemcpyAsync(h_total, h1, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, s));
     return plain_norm(c + 1);
@@ -500,21 +500,21 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
   // ---- pass 1: h = U^H w (+ fused three-term update and ||w||^2), then w -= U h (+ fused ||w||^2)
   int off = 0;
   int grid = 0;
-  double* norm_partials = ctx->d_partials;  // where the multi-axpy leaves the partial sums of ||w'||^2
+  double* norm_partials = ctx->partials.get();  // where the multi-axpy leaves the partial sums of ||w'||^2
   bool folded_in_maxpy = false;
   for (size_t g = 0; g < groups.size(); ++g) {
     const int nbg = count_of(groups[g]);
     const bool last = g + 1 == groups.size();
-    const int mgrid = launch_mdot<T>(n_local, w, groups[g], g == 0 ? tt : no_tt, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+    const int mgrid = launch_mdot<T>(n_local, w, groups[g], g == 0 ? tt : no_tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
     if (groups.size() == 1 && !sharded && ctx->tune.fuse_launches) {
       // small vectors, small grids: the multi-axpy folds the coefficients itself (one launch less per iteration)
-      if (!ctx->d_norm_partials) ctx->dev_malloc((void**)&ctx->d_norm_partials, (size_t)kMaxGrid * sizeof(double), "norm partials");
-      folded_in_maxpy = launch_maxpy_folding<T>(n_local, w, groups[0], ctx->d_partials, mgrid, h1, c, ctx->d_norm_partials,
+      if (!ctx->norm_partials) ctx->norm_partials = ctx->dev_alloc<double>((size_t)kMaxGrid, "norm partials");
+      folded_in_maxpy = launch_maxpy_folding<T>(n_local, w, groups[0], ctx->partials.get(), mgrid, h1, c, ctx->norm_partials.get(),
                                                 ctx->tune.blas_small_bytes, &grid, s);
-      if (folded_in_maxpy) norm_partials = ctx->d_norm_partials;
+      if (folded_in_maxpy) norm_partials = ctx->norm_partials.get();
     }
     if (!folded_in_maxpy)
-      launch_reduce_cols(ctx->d_partials, mgrid, R * nbg + 1, h1 + R * off, (last && !sharded) ? c : nullptr, s);
+      launch_reduce_cols(ctx->partials.get(), mgrid, R * nbg + 1, h1 + R * off, (last && !sharded) ? c : nullptr, s);
     off += nbg;
   }
   // Sharded whole-loop passes: the norm after the pass follows from what the one all-reduce below delivers
@@ -529,7 +529,7 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
   }
   off = 0;
   for (size_t g = 0; g < groups.size() && !folded_in_maxpy; ++g) {
-    grid = launch_maxpy<T>(n_local, w, groups[g], h1 + R * off, nullptr, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+    grid = launch_maxpy<T>(n_local, w, groups[g], h1 + R * off, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
     off += count_of(groups[g]);
   }
   if (derive && publish && publish->can_defer) {  // ... inside the caller's normalisation kernel (launch_scale_derive)
@@ -560,17 +560,17 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
   off = 0;
   for (size_t g = 0; g < groups.size(); ++g) {
     const int nbg = count_of(groups[g]);
-    const int g2 = launch_mdot<T>(n_local, w, groups[g], no_tt, pred, ctx->d_partials, ctx->tune.blas_small_bytes, s);
-    launch_reduce_cols(ctx->d_partials, g2, R * nbg + 1, h2 + R * off, S(kScalSpare), s);
+    const int g2 = launch_mdot<T>(n_local, w, groups[g], no_tt, pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    launch_reduce_cols(ctx->partials.get(), g2, R * nbg + 1, h2 + R * off, S(kScalSpare), s);
     off += nbg;
   }
   if (sharded) all_reduce(h2, (size_t)R * nb);
   off = 0;
   for (size_t g = 0; g < groups.size(); ++g) {
-    grid = launch_maxpy<T>(n_local, w, groups[g], h2 + R * off, pred, ctx->d_partials, ctx->tune.blas_small_bytes, s);
+    grid = launch_maxpy<T>(n_local, w, groups[g], h2 + R * off, pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
     off += count_of(groups[g]);
   }
-  launch_reduce_cols(ctx->d_partials, grid, 1, c + 2, nullptr, s);
+  launch_reduce_cols(ctx->partials.get(), grid, 1, c + 2, nullptr, s);
   all_reduce(c + 2, 1);
   if (h_total) {
     LL_HIP(hipMemcpyAsync(h_total, h1, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -593,8 +593,8 @@ void Engine<T>::gemv(const RunList<T>& basis, int64_t m, int nout, const T* coef
   TraceRange trace("ll::gemv_basis (Ritz vectors / exp output)");
   const std::vector<BasisSegs<T>> groups = basis.groups(512);
   ctx->ensure_coeff((size_t)nout * m * sizeof(T));
-  LL_HIP(hipMemcpyAsync(ctx->d_coeff, coeff_host, (size_t)nout * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  launch_gemv_basis<T>(n_local, m, groups.data(), (int)groups.size(), nout, (const T*)ctx->d_coeff, out, ld_out,
+  LL_HIP(hipMemcpyAsync(ctx->coeff.get(), coeff_host, (size_t)nout * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  launch_gemv_basis<T>(n_local, m, groups.data(), (int)groups.size(), nout, (const T*)ctx->coeff.get(), out, ld_out,
                        ctx->stream);
   LL_HIP(hipStreamSynchronize(ctx->stream));  // coeff_host may go away; d_coeff is reused
 }
@@ -735,7 +735,7 @@ template <typename T> struct LoopState {
   DevBuf<T> pwork[2];         // with work[0..1]: the four raw vectors of a pair
   DevBuf<T> psplit;           // hand-over vector of a split sweep (more stored vectors than one launch sums columns for)
   static constexpr size_t kPresizeCols = 4096;  // columns the sweeps' partial sums are sized for at pass start
-  DevBuf<double> pbuf;        // coefficient records, predictions, scalars (its own allocation: ctx->d_h may move)
+  DevBuf<double> pbuf;        // coefficient records, predictions, scalars (its own allocation: ctx->h.get() may move)
   const T *pr1 = nullptr, *pr2 = nullptr;
   int pset = 0;               // which pair of buffers holds pr1 / pr2: 0 = work, 1 = pwork
   const double *g1p = nullptr, *g2p = nullptr, *rho1p = nullptr, *rho2p = nullptr;
@@ -813,18 +813,18 @@ template <typename T> struct LoopState {
       if (!w.p) w.alloc(E.ctx, (size_t)ld_);
     bind_buffers();
   }
-  // Everything up front: growing ctx->d_h in the middle of a pass would free the pending coefficients.  Per parity of k:
+  // Everything up front: growing ctx->h.get() in the middle of a pass would free the pending coefficients.  Per parity of k:
   // g (coefficients) and, t_off further, t (lagged_fold_kernel); then the device copy of alpha / beta and the locked
   // eigenvalues.  Called again at the start of every pass: a two-sweep iteration with more than ~7000 coefficient
-  // columns (Engine::orth) may have grown, i.e. moved, ctx->d_h since.
+  // columns (Engine::orth) may have grown, i.e. moved, ctx->h.get() since.
   void bind_buffers() {
     constexpr size_t R = (size_t)Engine<T>::R;
     t_off = (size_t)kLaggedMaxCols + 8;
     const size_t half = 2 * t_off + 2 * R + 8;
     E.ctx->ensure_h(2 * half + 2 * t_off + (size_t)kLaggedMaxLocked);
-    hbuf[0] = E.ctx->d_h;
-    hbuf[1] = E.ctx->d_h + half;
-    hist_alpha = E.ctx->d_h + 2 * half;
+    hbuf[0] = E.ctx->h.get();
+    hbuf[1] = E.ctx->h.get() + half;
+    hist_alpha = E.ctx->h.get() + 2 * half;
     hist_beta = hist_alpha + t_off;
     d_lambda = hist_beta + t_off;
   }
@@ -884,8 +884,8 @@ template <typename T> struct LoopState {
       T* y = work[0].p;
       E.apply(z, y, offset, measure_theta ? d_lambda + i : nullptr, true);  // (theta_i = Re <z_i, y>: the fused dot of the operator kernel)
       const ThreeTerm<T> tt{nullptr, z, d_lambda + i, NormRefs{nullptr, nullptr, nullptr, 0}};  // y <- y - lambda_i z, ||y||^2
-      const int grid = launch_mdot<T>(nl, y, none, tt, nullptr, E.ctx->d_partials, small_bytes, s);
-      launch_reduce_cols(E.ctx->d_partials, grid, 1, r2_dev + i, nullptr, s);
+      const int grid = launch_mdot<T>(nl, y, none, tt, nullptr, E.ctx->partials.get(), small_bytes, s);
+      launch_reduce_cols(E.ctx->partials.get(), grid, 1, r2_dev + i, nullptr, s);
     }
     E.all_reduce(r2_dev, (size_t)n_lock);  // one collective and one fetch for all locked vectors
     std::vector<double> r2((size_t)n_lock), theta;
@@ -937,7 +937,7 @@ template <typename T> struct LoopState {
     const RunList<T> runs = basis_runs(lag_k);
     int off = 0;
     for (auto& g : runs.groups(max_vecs_per_launch<T>())) {
-      launch_maxpy<T>(nl, dst, g, hbuf[lag_k & 1] + Engine<T>::R * off, nullptr, E.ctx->d_partials, small_bytes, s);
+      launch_maxpy<T>(nl, dst, g, hbuf[lag_k & 1] + Engine<T>::R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
       for (int i = 0; i < g.nseg; ++i) off += g.count[i];
     }
     const NormRefs nr{lag_c1, lag_c1, lag_c1, 0};
@@ -966,7 +966,7 @@ template <typename T> struct LoopState {
       const RunList<T> runs = basis_runs(P + v);
       int off = 0;
       for (auto& g : runs.groups(max_vecs_per_launch<T>())) {
-        launch_maxpy<T>(nl, dst, g, coef[v] + R * off, nullptr, E.ctx->d_partials, small_bytes, s);
+        launch_maxpy<T>(nl, dst, g, coef[v] + R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
         for (int i = 0; i < g.nseg; ++i) off += g.count[i];
       }
       const NormRefs nr{rho[v], rho[v], rho[v], 0};
@@ -1087,10 +1087,10 @@ template <typename T> struct LoopState {
     // no fold launch in between.  The PB / tiled kernels and sharded contexts want the folded scalar (all-reduced).
     const bool fold_in_consumers = fuse_launches && E.can_defer_scale();
     int grid = launch_pair_three_term<T>(nl, r3, r2, r1, e1, da1.nparts > 0 ? da1.partials : nullptr, da1.nparts, rho2sq, rho1sq,
-                                         E.ctx->d_partials, fold_in_consumers, s);
+                                         E.ctx->partials.get(), fold_in_consumers, s);
     const int tt_grid = grid;
     if (!fold_in_consumers) {
-      launch_reduce_cols(E.ctx->d_partials, grid, 1 + R, t3, nullptr, s);
+      launch_reduce_cols(E.ctx->partials.get(), grid, 1 + R, t3, nullptr, s);
       if (E.ctx->comm != nullptr) E.all_reduce(t3, (size_t)(1 + R));  // |r3|^2 and <r1, r3> over the shards
     }
     timer.mark();
@@ -1098,7 +1098,7 @@ template <typename T> struct LoopState {
     timer.mark();
     if (fold_in_consumers) {
       ScaleIn<T> sc;
-      sc.partials = E.ctx->d_partials;  // column 0: |r3|^2 per workgroup
+      sc.partials = E.ctx->partials.get();  // column 0: |r3|^2 per workgroup
       sc.nparts = tt_grid;
       sc.c1_out = t3;                   // the folded |r3|^2, for the predict / sweep / fold kernels
       E.apply(r3, r4, offset, e2, true, &da2, &sc, nullptr);
@@ -1107,7 +1107,7 @@ template <typename T> struct LoopState {
     }
     timer.mark();
     // ---- one sweep for both
-    launch_pair_predict((int)P, (int)Lk, R, g1, g2, rho1sq, rho2sq, gam, t3, fold_in_consumers ? E.ctx->d_partials : nullptr, tt_grid,
+    launch_pair_predict((int)P, (int)Lk, R, g1, g2, rho1sq, rho2sq, gam, t3, fold_in_consumers ? E.ctx->partials.get() : nullptr, tt_grid,
                         e1, e2, da2.nparts > 0 ? da2.partials : nullptr, da2.nparts, hist_alpha, hist_beta, d_lambda, pp3, pp4, s);
     T* const uP = U.vec(P);
     T* const uQ = U.vec(P + 1);  // (may add a slab: the pointer table is brought up to date after it)
@@ -1117,17 +1117,17 @@ template <typename T> struct LoopState {
       none.ld = ld;
       const std::vector<BasisSegs<T>> one = stored.groups(max_vecs_per_launch<T>());  // a single group (checked above)
       LL_REQUIRE(launch_pair_sweep_small<T>(nl, one.empty() ? none : one[0], (int)K, r1, r2, r3, r4, uP, uQ, g1, g2, gam, pp4, rho1sq, rho2sq,
-                                            e2, t3, E.ctx->d_partials, &grid, s),
+                                            e2, t3, E.ctx->partials.get(), &grid, s),
                  "internal: the small-geometry pair sweep refused a launch that was checked to fit");
     } else {
       grid = launch_pair_sweep<T>(nl, groups, (int)K, r1, r2, r3, r4, uP, uQ, psplit.p, g1, g2, gam, pp4, rho1sq, rho2sq, e2, t3,
-                                  E.ctx->d_partials, E.ctx->tune.lagged_pieces, s, vtab_sync(), E.ctx->tune.sweep_pipeline >= 2);
+                                  E.ctx->partials.get(), E.ctx->tune.lagged_pieces, s, vtab_sync(), E.ctx->tune.sweep_pipeline >= 2);
     }
-    launch_reduce_cols(E.ctx->d_partials, grid, ncols, pcols, nullptr, s);
+    launch_reduce_cols(E.ctx->partials.get(), grid, ncols, pcols, nullptr, s);
     // sharded: ONE all-reduce carries both iterations' columns; every rank then folds the same numbers to the same bits
     if (E.ctx->comm != nullptr) E.all_reduce(pcols, (size_t)ncols);
     launch_pair_fold(pcols, (int)P, (int)Lk, R, d_lambda, pp4, g2, gam, rho2sq, t3, e1, e2, rec3, rec4, nxt, hist_alpha, hist_beta, pfold,
-                     E.ctx->h_pinned + 4 * sa, E.ctx->h_pinned + 4 * sb, E.ctx->h_pinned + 16 + sa, E.ctx->h_pinned + 16 + sb, s,
+                     E.ctx->pinned.get() + 4 * sa, E.ctx->pinned.get() + 4 * sb, E.ctx->pinned.get() + 16 + sa, E.ctx->pinned.get() + 16 + sb, s,
                      E.ctx->tune.event_in_launch ? ring.ev[sb] : nullptr);
     // ONE event for both iterations of the pair (their scalars are published by the same fold kernel): every event record is a marker
     // packet between two dependent kernels of a loop that is bound by exactly those gaps at small sizes
@@ -1196,25 +1196,25 @@ template <typename T> struct LoopState {
     int grid;
     if (lag_pending) {
       const Lagged<T> lg{work[(k - 1) & 1].p, U.vec(k - 1), hbuf[(k - 1) & 1], hbuf[(k - 1) & 1] + t_off, lag_c1};
-      grid = launch_lagged<T>(nl, y, groups.empty() ? none : groups[0], lg, tt, E.ctx->d_partials, E.ctx->tune.lagged_pieces,
+      grid = launch_lagged<T>(nl, y, groups.empty() ? none : groups[0], lg, tt, E.ctx->partials.get(), E.ctx->tune.lagged_pieces,
                               stream_bytes, s);
       ++n_lagged;
     } else {
-      grid = launch_mdot<T>(nl, y, groups.empty() ? none : groups[0], tt, nullptr, E.ctx->d_partials, small_bytes, s);
+      grid = launch_mdot<T>(nl, y, groups.empty() ? none : groups[0], tt, nullptr, E.ctx->partials.get(), small_bytes, s);
     }
     double* c = E.S(kScalNorms + 3 * slot);
     double* hb = hbuf[k & 1];
     const double* c0 = c;
     if (E.ctx->comm == nullptr) {
-      launch_reduce_cols(E.ctx->d_partials, grid, ncols, hb, c, s);  // coefficients -> hb, ||w||^2 -> c[0]
+      launch_reduce_cols(E.ctx->partials.get(), grid, ncols, hb, c, s);  // coefficients -> hb, ||w||^2 -> c[0]
     } else {  // one all-reduce for the coefficients and ||w||^2; every rank then folds the same numbers to the same bits
-      launch_reduce_cols(E.ctx->d_partials, grid, ncols, hb, nullptr, s);
+      launch_reduce_cols(E.ctx->partials.get(), grid, ncols, hb, nullptr, s);
       E.all_reduce(hb, (size_t)ncols);
       c0 = hb + R * nb_total;
     }
     const double* pg = lag_pending ? hbuf[(k - 1) & 1] : nullptr;
     launch_lagged_fold(hb, (int)nb_total, (int)n_locked, R, hb + t_off, c0, c, c + 1, E.S(kScalAlpha + slot), pg,
-                       pg ? pg + t_off : nullptr, lag_c1, hist_alpha, hist_beta, d_lambda, E.ctx->h_pinned + 4 * slot, s,
+                       pg ? pg + t_off : nullptr, lag_c1, hist_alpha, hist_beta, d_lambda, E.ctx->pinned.get() + 4 * slot, s,
                        E.ctx->tune.event_in_launch ? ring.ev[slot] : nullptr);
     ev_of_slot[slot] = slot;
     if (!E.ctx->tune.event_in_launch) LL_HIP(hipEventRecord(ring.ev[slot], s));
@@ -1267,7 +1267,7 @@ template <typename T> struct LoopState {
       tt.alpha_nparts = da.nparts;
       tt.alpha_out = E.S(kScalAlpha + slot);
     }
-    typename Engine<T>::Publish pub{E.ctx->h_pinned + 4 * slot, E.S(kScalAlpha + slot), false};
+    typename Engine<T>::Publish pub{E.ctx->pinned.get() + 4 * slot, E.S(kScalAlpha + slot), false};
     pub.can_defer = fuse_launches;
     const NormRefs refs = E.orth(y, runs, mode, tt, E.S(kScalNorms + 3 * slot), nullptr, true, &pub);  // P5-P7
     if (pub.deferred && defer) {  // P8 rides in the next operator kernel
@@ -1558,7 +1558,7 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
       const double tw0 = now_s();
       LL_HIP(hipEventSynchronize(ring.ev[LS.ev_of_slot[slot]]));
       t_wait += now_s() - tw0;
-      const volatile double* hp = ctx->h_pinned + 4 * slot;
+      const volatile double* hp = ctx->pinned.get() + 4 * slot;
       const double alpha_j = hp[0], c0_j = hp[2], c1_j = hp[3];
       double beta2_j = hp[1];
       int verdict = kContinue;
@@ -1592,7 +1592,7 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
         LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
         verdict = kRedone;  // the speculative iteration j+1 took the one-sweep form: it is enqueued again
       }
-      if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->h_pinned[16 + slot] <= pair_gate)) {
+      if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->pinned.get()[16 + slot] <= pair_gate)) {
         // A coefficient of this iteration's raw vector grew beyond what the pair form tracks to first order (beta -> eps: an
         // exhausted Krylov space, breakdown).  The iteration itself stands — its coefficients were MEASURED, its alpha / beta
         // are exact — but whatever took the vector as an operator input (the second iteration of its pair, the next pair) is
@@ -2005,7 +2005,7 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
     const double tw0 = now_s();
     LL_HIP(hipEventSynchronize(ring.ev[LS.ev_of_slot[slot]]));
     t_wait += now_s() - tw0;
-    const volatile double* hp = ctx->h_pinned + 4 * slot;
+    const volatile double* hp = ctx->pinned.get() + 4 * slot;
     const double alpha_j = hp[0], c0_j = hp[2], c1_j = hp[3];
     double beta2_j = hp[1];
     int verdict = kContinue;
@@ -2029,7 +2029,7 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
         beta2_j = 0.0;
       }
     }
-    if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->h_pinned[16 + slot] <= pair_gate)) {  // the pair form's gate (see lanczos_run)
+    if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->pinned.get()[16 + slot] <= pair_gate)) {  // the pair form's gate (see lanczos_run)
       LS.pair_allowed = false;
       ++LS.n_gate_trips;
       LS.make_final(j);

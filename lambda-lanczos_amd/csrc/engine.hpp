@@ -10,7 +10,7 @@
 
 namespace ll {
 
-// Device scalar area (ctx->d_scal, 64 doubles):
+// Device scalar area (ctx->scal, 64 doubles):
 //   [0..4)    alpha ring (slot = k % 4)
 //   [8..20)   norm triples (c0,c1,c2) ring, slot s at 8 + 3*s
 //   [24..27)  scratch triple for one-off orthogonalisations (start vector, primitives)
@@ -61,7 +61,7 @@ template <typename T> struct Engine {
 
   Engine(ll_context* c, ll_operator* o, int64_t n_local_) : ctx(c), op(o), n_local(n_local_) {}
 
-  double* S(int i) const { return ctx->d_scal + i; }
+  double* S(int i) const { return ctx->scal.get() + i; }
   NormRefs plain_norm(double* c1) const { return NormRefs{S(kScalZero), c1, c1, 0}; }
 
   // y = A x + offset x ; Re<x,y> -> *d_alpha (device scalar, all-reduced over ranks); d_alpha nullable.

@@ -154,17 +154,18 @@ template <typename T>
 int launch_spmv(const ll_operator& op, const T* x_full, const T* x_local, T* y, double offset, double* dot_partials,
                 hipStream_t s, const ScaleIn<T>* scp, int part) {
   // part 1 / 2: the two halves of a column-split image (x_full = the local shard for part 1, the gathered vector for part 2)
-  const int ntiles = part == 1 ? op.ntiles_own : (part == 2 ? op.ntiles_rem : op.ntiles);
-  const int32_t* tiles = part == 1 ? op.d_tiles_own : (part == 2 ? op.d_tiles_rem : op.d_tile_rows);
-  const void* rp = part == 1 ? op.d_rp_own : (part == 2 ? op.d_rp_rem : op.d_row_ptr);
-  const int32_t* ci = part == 1 ? op.d_col_own : (part == 2 ? op.d_col_rem : op.d_col);
-  const void* va = part == 1 ? op.d_val_own : (part == 2 ? op.d_val_rem : op.d_val);
+  const CsrImage& im = part == 1 ? op.csr_own : (part == 2 ? op.csr_rem : op.csr);
+  const int ntiles = im.ntiles;
+  const int32_t* tiles = im.tiles.get();
+  const void* rp = im.row_ptr.get();
+  const int32_t* ci = im.col.get();
+  const void* va = im.val.get();
   const int grid = spmv_grid(ntiles, sizeof(T));
   const ScaleIn<T> sc = scp ? *scp : ScaleIn<T>{};
   // (the kernel that publishes an iteration's scalars may complete that iteration's event itself: ll_context::stop_next)
   hipEvent_t stop = part != 1 ? op.ctx->stop_next : nullptr;
   op.ctx->stop_next = stop ? nullptr : op.ctx->stop_next;
-  if (op.rp64)
+  if (im.rp64)
     LL_LAUNCH_STOP(stop, (spmv_stream<T, int64_t>), dim3(grid), dim3(kBlock), 0, s, ntiles, tiles, (const int64_t*)rp, ci,
                    (const T*)va, x_full, x_local, y, offset, part == 1 ? nullptr : dot_partials, sc, part);
   else
@@ -210,31 +211,33 @@ template <typename T>
 void launch_csr_count_own(const ll_operator& op, int32_t* own_cnt, hipStream_t s) {
   const int grid = (int)std::max<long long>(1, std::min<long long>(kMaxGrid, (op.n_local + 255) / 256));
   const long long c0 = op.row_begin, c1 = op.row_begin + op.n_local;
-  if (op.rp64)
+  const CsrImage& a = op.csr;
+  if (a.rp64)
     hipLaunchKernelGGL((csr_count_own_kernel<int64_t>), dim3(grid), dim3(256), 0, s, (long long)op.n_local, c0, c1,
-                       (const int64_t*)op.d_row_ptr, op.d_col, own_cnt);
+                       (const int64_t*)a.row_ptr.get(), a.col.get(), own_cnt);
   else
     hipLaunchKernelGGL((csr_count_own_kernel<int32_t>), dim3(grid), dim3(256), 0, s, (long long)op.n_local, c0, c1,
-                       (const int32_t*)op.d_row_ptr, op.d_col, own_cnt);
+                       (const int32_t*)a.row_ptr.get(), a.col.get(), own_cnt);
   LL_HIP(hipGetLastError());
 }
-template <typename T> void launch_csr_split(const ll_operator& op, hipStream_t s) {
+template <typename T> void launch_csr_split(const ll_operator& op, const CsrImage& own, const CsrImage& rem, hipStream_t s) {
   const int grid = (int)std::max<long long>(1, std::min<long long>(kMaxGrid, (op.n_local + 255) / 256));
   const long long c0 = op.row_begin, c1 = op.row_begin + op.n_local;
-  if (op.rp64)
+  const CsrImage& a = op.csr;
+  if (a.rp64)
     hipLaunchKernelGGL((csr_split_kernel<T, int64_t>), dim3(grid), dim3(256), 0, s, (long long)op.n_local, c0, c1,
-                       (const int64_t*)op.d_row_ptr, op.d_col, (const T*)op.d_val, (const int64_t*)op.d_rp_own,
-                       (const int64_t*)op.d_rp_rem, op.d_col_own, (T*)op.d_val_own, op.d_col_rem, (T*)op.d_val_rem);
+                       (const int64_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), (const int64_t*)own.row_ptr.get(),
+                       (const int64_t*)rem.row_ptr.get(), own.col.get(), (T*)own.val.get(), rem.col.get(), (T*)rem.val.get());
   else
     hipLaunchKernelGGL((csr_split_kernel<T, int32_t>), dim3(grid), dim3(256), 0, s, (long long)op.n_local, c0, c1,
-                       (const int32_t*)op.d_row_ptr, op.d_col, (const T*)op.d_val, (const int32_t*)op.d_rp_own,
-                       (const int32_t*)op.d_rp_rem, op.d_col_own, (T*)op.d_val_own, op.d_col_rem, (T*)op.d_val_rem);
+                       (const int32_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), (const int32_t*)own.row_ptr.get(),
+                       (const int32_t*)rem.row_ptr.get(), own.col.get(), (T*)own.val.get(), rem.col.get(), (T*)rem.val.get());
   LL_HIP(hipGetLastError());
 }
 #define LL_INST_SPMV(T)                                                                                                       \
   template int launch_spmv<T>(const ll_operator&, const T*, const T*, T*, double, double*, hipStream_t, const ScaleIn<T>*, int); \
   template void launch_csr_count_own<T>(const ll_operator&, int32_t*, hipStream_t);                                            \
-  template void launch_csr_split<T>(const ll_operator&, hipStream_t);
+  template void launch_csr_split<T>(const ll_operator&, const CsrImage&, const CsrImage&, hipStream_t);
 LL_INST_SPMV(double) LL_INST_SPMV(zc) LL_INST_SPMV(float) LL_INST_SPMV(cf)
 
 
@@ -2867,7 +2870,7 @@ int launch_dense_mv(const ll_operator& op, const T* x_full, const T* x_local, T*
   const bool aligned = op.n % V == 0 && a0 % V == 0 && a1 % V == 0 && b0 % V == 0 && b1 % V == 0 && xshift % V == 0;
   const int vec = aligned && (reinterpret_cast<uintptr_t>(x_full) & 15) == 0 ? 1 : 0;  // rows then start 16-B aligned
   hipLaunchKernelGGL((dense_mv_kernel<T>), dim3(grid), dim3(kBlock), 0, s, (long long)op.n_local, (long long)op.n,
-                     (const T*)op.d_dense, x_full, x_local, y, offset, part == 1 ? nullptr : dot_partials, vec, sc, a0, a1, b0, b1,
+                     (const T*)op.dense.get(), x_full, x_local, y, offset, part == 1 ? nullptr : dot_partials, vec, sc, a0, a1, b0, b1,
                      xshift, part);
   LL_HIP(hipGetLastError());
   return grid;
@@ -3177,10 +3180,10 @@ int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, co
     const int vgrid = (int)std::max<long long>(1, std::min<long long>(kMaxGrid, (chunks + kBlock - 1) / kBlock));
     if (op.n < ((long long)1 << 31))
       hipLaunchKernelGGL((stencil_vec_kernel<T, unsigned, V>), dim3(vgrid), dim3(kBlock), 0, s, g, x_local, halo_lo,
-                         halo_hi, (const R*)op.d_onsite, y, offset, dot_partials, sc);
+                         halo_hi, (const R*)op.onsite.get(), y, offset, dot_partials, sc);
     else
       hipLaunchKernelGGL((stencil_vec_kernel<T, unsigned long long, V>), dim3(vgrid), dim3(kBlock), 0, s, g, x_local,
-                         halo_lo, halo_hi, (const R*)op.d_onsite, y, offset, dot_partials, sc);
+                         halo_lo, halo_hi, (const R*)op.onsite.get(), y, offset, dot_partials, sc);
     LL_HIP(hipGetLastError());
     return vgrid;
   }
@@ -3188,10 +3191,10 @@ int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, co
   const int grid = (int)std::max<long long>(1, std::min<long long>(kMaxGrid, want));
   if (op.n < ((long long)1 << 31))
     hipLaunchKernelGGL((stencil_kernel<T, unsigned>), dim3(grid), dim3(kBlock), 0, s, g, x_local, halo_lo, halo_hi,
-                       (const R*)op.d_onsite, y, offset, dot_partials, sc);
+                       (const R*)op.onsite.get(), y, offset, dot_partials, sc);
   else
     hipLaunchKernelGGL((stencil_kernel<T, unsigned long long>), dim3(grid), dim3(kBlock), 0, s, g, x_local, halo_lo,
-                       halo_hi, (const R*)op.d_onsite, y, offset, dot_partials, sc);
+                       halo_hi, (const R*)op.onsite.get(), y, offset, dot_partials, sc);
   LL_HIP(hipGetLastError());
   return grid;
 }

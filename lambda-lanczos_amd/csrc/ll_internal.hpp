@@ -12,6 +12,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lanczos_hip.h"
@@ -94,6 +95,67 @@ struct Failure {
       throw ::ll::Failure{LL_ERR_INVALID};                                         \
     }                                                                              \
   } while (0)
+
+// ---------------------------------------------------------------- owned device memory
+// The one owner of a library allocation: freed (Free: hipFree, or hipHostFree for pinned host memory) when reset, replaced or
+// destroyed; moved, never copied.  A BORROWED handle (the caller's arrays of ll_op_create_csr_dev_*) is forgotten instead
+// of freed and holds no bytes of the library's.
+template <typename T, hipError_t (*Free)(void*) = hipFree> class DevArray {
+ public:
+  DevArray() = default;
+  explicit DevArray(T* p, bool owned = true) : p_(p), owned_(owned) {}
+  static DevArray borrow(T* p) { return DevArray(p, false); }
+  DevArray(DevArray&& o) noexcept : p_(o.p_), owned_(o.owned_) { o.p_ = nullptr; }
+  // typed -> untyped, like T* -> void* (images keep their arrays of the storage type T as void)
+  template <typename U, typename V = T, typename = std::enable_if_t<std::is_void_v<V> && !std::is_void_v<U>>>
+  DevArray(DevArray<U, Free>&& o) noexcept : owned_(o.owned()) { p_ = o.release(); }
+  DevArray& operator=(DevArray&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      owned_ = o.owned_;
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  DevArray(const DevArray&) = delete;
+  DevArray& operator=(const DevArray&) = delete;
+  ~DevArray() { reset(); }
+  T* get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  bool owned() const { return owned_; }
+  void reset() noexcept { (void)free_now(); }
+  // reset, with the status of the free (the growth path of the workspace reports it)
+  hipError_t free_now() noexcept {
+    const hipError_t e = p_ != nullptr && owned_ ? Free((void*)p_) : hipSuccess;
+    p_ = nullptr;
+    return e;
+  }
+  T* release() noexcept {  // the caller takes the allocation over
+    T* p = p_;
+    p_ = nullptr;
+    return p;
+  }
+  // size of the owned allocation (0: none, or borrowed)
+  int64_t bytes() const {
+    if (p_ == nullptr || !owned_) return 0;
+    size_t b = 0;
+    LL_HIP(hipMemPtrGetInfo((void*)p_, &b));
+    return (int64_t)b;
+  }
+
+ private:
+  T* p_ = nullptr;
+  bool owned_ = true;
+};
+template <typename T> using HostArray = DevArray<T, hipHostFree>;
+
+// A workspace buffer that only grows (ll_context::ensure_*); cap counts elements of T (bytes for void).
+template <typename T, hipError_t (*Free)(void*) = hipFree> struct Workspace {
+  DevArray<T, Free> buf;
+  size_t cap = 0;
+  T* get() const { return buf.get(); }
+};
 
 // ---------------------------------------------------------------- launch geometry
 constexpr int kBlock = 256;          // threads per workgroup (4 waves of 64)
@@ -237,18 +299,14 @@ struct ll_context {
   hipEvent_t t0 = nullptr, t1 = nullptr;  // ll_timer_*
 
   // workspace, all sized lazily
-  double* d_partials = nullptr;  // [grid][ncols] block partial sums
-  double* d_alpha_partials = nullptr;  // the operator kernels' partial <x, Ax> (kept apart: the multi-dot that follows
-  size_t alpha_partials_cap = 0;       // may fold them itself while it writes its own partials)
-  size_t partials_cap = 0;       // doubles
-  double* d_h = nullptr;         // reduced projection coefficients / small scalars
-  size_t h_cap = 0;              // doubles
-  double* d_scal = nullptr;      // 64 doubles of device scalars (ring slots, flags)
-  double* d_norm_partials = nullptr;  // kMaxGrid norm partials of the folding multi-axpy (must not alias d_partials)
-  double* h_pinned = nullptr;    // pinned host mirror for scalar read-back
-  size_t pinned_cap = 0;         // doubles
-  void* d_coeff = nullptr;       // coefficient upload area for gemv_basis
-  size_t coeff_cap = 0;          // bytes
+  ll::Workspace<double> partials;        // [grid][ncols] block partial sums
+  ll::Workspace<double> alpha_partials;  // the operator kernels' partial <x, Ax> (kept apart: the multi-dot that follows
+                                         // may fold them itself while it writes its own partials)
+  ll::Workspace<double> h;               // reduced projection coefficients / small scalars
+  ll::DevArray<double> scal;             // 64 doubles of device scalars (ring slots, flags)
+  ll::DevArray<double> norm_partials;    // kMaxGrid norm partials of the folding multi-axpy (must not alias partials)
+  ll::Workspace<double, hipHostFree> pinned;  // pinned host mirror for scalar read-back
+  ll::Workspace<void> coeff;             // coefficient upload area for gemv_basis
   std::vector<hipEvent_t> timer_events;  // PhaseTimer's ring of timing events (profiling mode), created once and kept between runs
   std::vector<std::pair<void*, size_t>> slab_cache;  // Krylov-basis slabs kept between runs (ptr, bytes), oldest first
   // Return a buffer to the cache.  The cache is bounded (kSlabCacheMaxEntries): a long-lived context that solves problems
@@ -256,35 +314,143 @@ struct ll_context {
   // it happens only when the bound is hit, never inside a loop).
   static constexpr size_t kSlabCacheMaxEntries = 64;
   void cache_put(void* p, size_t bytes);
-  void* d_xfull = nullptr;       // all-gather target (sharded runs)
-  size_t xfull_cap = 0;          // bytes
-  void* d_halo = nullptr;        // received halos of the lattice operator: [from prev | from next]
-  size_t halo_cap = 0;           // bytes
+  ll::Workspace<void> xfull;      // all-gather target (sharded runs)
+  ll::Workspace<void> halo;       // received halos of the lattice operator: [from prev | from next]
 
   // hipMalloc that makes room first when the device is full: the cached Krylov slabs of earlier runs are returned to
   // the device and the allocation is retried; LL_ERR_ALLOC (with the size in the message) if it still fails.
   void dev_malloc(void** out, size_t bytes, const char* what);
-  void ensure_partials(size_t doubles);
-  void ensure_alpha_partials(size_t doubles);
-  void ensure_h(size_t doubles);
+  // the same, owned: count elements of T (bytes for void)
+  template <typename T> ll::DevArray<T> dev_alloc(size_t count, const char* what) {
+    void* p = nullptr;
+    if constexpr (std::is_void_v<T>) dev_malloc(&p, count, what);
+    else dev_malloc(&p, count * sizeof(T), what);
+    return ll::DevArray<T>((T*)p);
+  }
+  // Grow a device workspace buffer to at least `count` elements: geometrically (1.5 x + 64) or to exactly `count`.
+  template <typename T> T* ensure(ll::Workspace<T>& w, size_t count, bool geometric, const char* what);
+  void ensure_partials(size_t doubles) { ensure(partials, doubles, true, "partial sums"); }
+  void ensure_alpha_partials(size_t doubles) { ensure(alpha_partials, doubles, true, "alpha partial sums"); }
+  void ensure_h(size_t doubles) { ensure(h, doubles, true, "projection coefficients"); }
+  void ensure_coeff(size_t bytes) { ensure(coeff, bytes, true, "Ritz coefficients"); }
+  void ensure_xfull(size_t bytes) { ensure(xfull, bytes, false, "gathered vector"); }
+  void ensure_halo(size_t bytes) { ensure(halo, bytes, false, "halo buffer"); }
   void ensure_pinned(size_t doubles);
-  void ensure_coeff(size_t bytes);
-  void ensure_xfull(size_t bytes);
-  void ensure_halo(size_t bytes);
   // device-time stamps of the exchange steps (only with profiling on): (start, end) pairs on the stream they ran on
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_gather, ev_allreduce;
   void drain_comm_events(double* gather_s, double* allreduce_s);  // adds the elapsed device seconds, frees the events
-  void* h_stage = nullptr;       // pinned host staging buffer for n-sized transfers (start vector, Ritz vectors)
-  size_t stage_cap = 0;          // bytes
+  ll::Workspace<void, hipHostFree> stage;  // pinned host staging buffer for n-sized transfers (start vector, Ritz vectors)
   void* ensure_stage(size_t bytes);
-  void* h_cb = nullptr;          // pinned [in | out] buffers of the host-callback operator
-  size_t cb_cap = 0;
+  ll::Workspace<void, hipHostFree> cb;     // pinned [in | out] buffers of the host-callback operator
   hipEvent_t ev_cb = nullptr;    // recorded after the upload of a callback result
   hipEvent_t stop_next = nullptr;  // set by the loop in front of an operator application whose kernel publishes an iteration's scalars: that
                                    // launch completes the event itself (LL_LAUNCH_STOP) and clears the field; still set afterwards = not taken
   void* ensure_cb_stage(size_t bytes);
   void sync();
 };
+
+// ---------------------------------------------------------------- SpMV images of an operator
+// Every image owns its arrays and knows its own geometry; a builder fills a local image and moves it into the operator
+// only when it succeeds, and dropping an image is resetting it.
+namespace ll {
+// CSR: row offsets (int32, or int64 when rp64), columns, values and the ntiles + 1 row boundaries of the SpMV tiles
+struct CsrImage {
+  DevArray<void> row_ptr;
+  DevArray<int32_t> col;
+  DevArray<void> val;
+  DevArray<int32_t> tiles;
+  int ntiles = 0;
+  bool rp64 = false;
+  int64_t device_bytes() const { return row_ptr.bytes() + col.bytes() + val.bytes() + tiles.bytes(); }
+};
+
+// Propagation-blocked image (spmv_pb.hip).  Column-block table order: the blocks over the rank's OWN columns first (their x
+// slice is the local shard, no exchange needed), then, gather chunk by gather chunk, the blocks over the other ranks' columns
+// (x slice in the gathered buffer).  One phase-1 launch per range, so own-column work runs under the all-gather.
+struct PbImage {
+  int ncb = 0, nrb = 0, cb_cols = 0, rb_rows = 0;  // cb_cols = longest column block (LDS sizing)
+  DevArray<int64_t> segq;        // [ncb][nrb+1] entry offsets of the segments in column-block order
+  DevArray<int64_t> segdest;     // [ncb][nrb]   position of each segment in row-block order
+  DevArray<int64_t> rptr;        // [nrb+1]      entry offsets of the row blocks in row-block order
+  DevArray<int64_t> xoff;        // [ncb]        element offset of the block's x slice in ITS source buffer
+  DevArray<int32_t> ncols;       // [ncb]        columns of the block
+  DevArray<void> arena;          // the one allocation that holds the four big streams below (interior pointers)
+  size_t arena_bytes = 0, arena_static_bytes = 0;  // its size; the part in front of the product buffer
+  void* val = nullptr;           // values, column-block order (the start of the arena)
+  uint16_t* col = nullptr;       // local column, column-block order
+  uint16_t* row = nullptr;       // local row, row-block order
+  void* prod = nullptr;          // product buffer P (nnz elements of T), row-block order
+  DevArray<int16_t> rexp;        // LL_PB_PHASE2=fixed: exponent of every local row's absolute sum
+  DevArray<double> blockmax;     // LL_PB_PHASE2=fixed: max |x| per column block, left by phase 1
+  DevArray<void> diag;           // a_ii of every local row (T): the diagonal is kept outside the streams (spmv_pb.hip pb_diag_kernel)
+  int64_t entries = 0;           // padded entry count of the image
+  int phase2 = 4;                // form of phase 2 (ll::LL_PB_FIXED / _ORDERED / _ATOMIC): set when the image is built,
+                                 // changed by ll_op_set_accuracy (both forms read the same image)
+  int threads1 = 1024;           // lanes per workgroup of phase 1 (1024; 512 for the thin column blocks of a sharded image)
+  bool xpre = true;              // fixed-point phase 2 requests the epilogue's x_i before its stream (LL_PB_XPRE)
+  int own_count = 0;             // table range [0, own_count)
+  int chunk_first[kMaxGatherChunks] = {0};  // remote blocks of gather chunk c: [first, first + count)
+  int chunk_count[kMaxGatherChunks] = {0};
+  GatherPlan gather;             // how a sharded vector is all-gathered when the PB kernels are selected
+  bool present() const { return (bool)arena; }
+  // point the interior pointers at a copy of the arena that starts at `base` (placement search, capi.cpp)
+  void rebase(void* base) {
+    const ptrdiff_t d = (char*)base - (char*)val;
+    val = base;
+    col = (uint16_t*)((char*)col + d);
+    row = (uint16_t*)((char*)row + d);
+    prod = (char*)prod + d;
+  }
+  int64_t device_bytes() const {
+    return segq.bytes() + segdest.bytes() + rptr.bytes() + xoff.bytes() + ncols.bytes() + arena.bytes() + rexp.bytes() +
+           blockmax.bytes() + diag.bytes();
+  }
+};
+
+// 2-D tiled image (spmv_pb.hip, tl_*): row blocks with the y slice in LDS, each walking its non-empty column tiles of 16 KiB of x;
+// entries = value (pre-scaled by the row's exponent) + packed 16-bit local column / row
+struct TiledImage {
+  int nrb = 0, rb_rows = 0, ncb = 0;
+  int n_interior = 0;            // sharded: row blocks whose tiles are all own-column tiles (first in rbmap; they run under the all-gather)
+  DevArray<int32_t> rbmap;       // sharded: [nrb] row blocks in launch order (interior first); null on one GPU
+  int64_t entries = 0, tiles = 0;
+  DevArray<int32_t> first;       // [nrb + 1]     first tile of each row block in the tile list
+  DevArray<int32_t> col;         // [ntiles]      column tile index
+  DevArray<int64_t> quad;        // [ntiles + 1]  first quad (4 entries) of each tile in the entry stream
+  DevArray<void> val;            // values in tile order
+  DevArray<uint32_t> idx;        // local column | local row << 16
+  DevArray<int16_t> rexp;        // exponent of every row's absolute sum (the scale the values were divided by)
+  DevArray<double> xmax;         // maxima of |x| the kernel folds (per workgroup of the pre-pass; sharded: one per rank), then scratch of the own-shard pre-pass
+  bool ordered = false;          // the tiled kernel sums in floating point, the waves in turn (component-wise class) instead of in fixed point
+  bool present() const { return nrb > 0; }
+  int64_t device_bytes() const {
+    return rbmap.bytes() + first.bytes() + col.bytes() + quad.bytes() + val.bytes() + idx.bytes() + rexp.bytes() + xmax.bytes();
+  }
+};
+
+// One-triangle image of a symmetric / Hermitian matrix (spmv_sym.hip): one stream per row block of every stored entry with an
+// end in the block; an entry whose two ends lie in different blocks is in both streams
+struct SymImage {
+  int nrb = 0, rb_rows = 0, halo = 0;  // row blocks, rows per block, half-bandwidth max |i - j| of the triangle
+  DevArray<int64_t> qptr;        // [nrb + 1] first quad (4 entries) of each row block's stream
+  DevArray<void> val;            // values as stored (T)
+  DevArray<uint32_t> idx;        // window index of the entry's row | of its column << 16 (0xffffffff: padding)
+  DevArray<int16_t> rexp;        // exponent of every row's absolute sum over the FULL row of A
+  DevArray<double> xmax;         // kXmaxParts maxima of |x| (pre-pass)
+  DevArray<void> diag;           // [n] the first diagonal entry of every row, kept outside the streams (0: none)
+  // entries whose other end lies outside the row block's x window (the few beyond the halo, e.g. the wrap-around corners of a
+  // periodic band): one product each, x read from memory — destination local row | 1 << 31 for the mirrored product, source row
+  DevArray<int64_t> fptr;        // [nrb + 1] first far entry of each row block
+  DevArray<void> fval;
+  DevArray<uint32_t> fdst;
+  DevArray<int32_t> fsrc;
+  bool present() const { return nrb > 0; }
+  int64_t device_bytes() const {
+    return qptr.bytes() + val.bytes() + idx.bytes() + rexp.bytes() + xmax.bytes() + diag.bytes() + fptr.bytes() + fval.bytes() +
+           fdst.bytes() + fsrc.bytes();
+  }
+};
+}  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
@@ -295,91 +461,32 @@ struct ll_operator {
   int64_t n = 0, n_local = 0, row_begin = 0, nnz = 0;
   int64_t n_shard = 0;  // padded shard length used by the all-gather (= n when not sharded)
   double inf_norm = -1.0;  // max absolute row sum of the local rows (-1: unknown)
-  // CSR
-  void* d_row_ptr = nullptr;  // int32 or int64
-  bool rp64 = false;
-  int32_t* d_col = nullptr;
-  void* d_val = nullptr;
-  bool owns_arrays = true;
-  int32_t* d_tile_rows = nullptr;  // ntiles+1 row boundaries of the SpMV tiles
-  int ntiles = 0;
-  // Sharded contexts, CSR-stream selected: the same rows split by column ownership (capi.cpp build_csr_split) — the
-  // entries over the rank's OWN columns (indices rebased to the local shard; their product needs no exchange and runs
-  // under the all-gather) and the entries over the other ranks' columns (global indices into the gathered vector).
-  bool csr_split = false;
-  void *d_rp_own = nullptr, *d_rp_rem = nullptr;  // row offsets, int32 or int64 like d_row_ptr
-  int32_t *d_col_own = nullptr, *d_col_rem = nullptr;
-  void *d_val_own = nullptr, *d_val_rem = nullptr;
-  int32_t *d_tiles_own = nullptr, *d_tiles_rem = nullptr;
-  int ntiles_own = 0, ntiles_rem = 0;
-  // propagation-blocked image of the same matrix (spmv_pb.hip pb_phase1 / pb_phase2)
+  // CSR-stream image (kernels.hip launch_spmv).  Sharded contexts, CSR-stream selected: the same rows split by column ownership
+  // (capi.cpp build_csr_split) — csr_own holds the entries over the rank's OWN columns (indices rebased to the local shard; their
+  // product needs no exchange and runs under the all-gather), csr_rem the entries over the other ranks' columns (global indices
+  // into the gathered vector).
+  ll::CsrImage csr, csr_own, csr_rem;
+  bool csr_split() const { return (bool)csr_own.row_ptr; }
+  bool has_csr_stream() const { return csr.row_ptr && (csr.col || nnz == 0 || csr_split()); }
   int spmv_kind = 0;                 // LL_SPMV_*
   float tune_ms[3] = {-1.f, -1.f, -1.f};  // what the creation-time autotune measured per LL_SPMV_* kernel (-1: not timed)
-  int pb_ncb = 0, pb_nrb = 0, pb_cb_cols = 0, pb_rb_rows = 0;   // cb_cols = longest column block (LDS sizing)
-  int64_t* d_pb_segq = nullptr;      // [ncb][nrb+1] entry offsets of the segments in column-block order
-  int64_t* d_pb_segdest = nullptr;   // [ncb][nrb]   position of each segment in row-block order
-  int64_t* d_pb_rptr = nullptr;      // [nrb+1]      entry offsets of the row blocks in row-block order
-  int64_t* d_pb_xoff = nullptr;      // [ncb]        element offset of the block's x slice in ITS source buffer
-  int32_t* d_pb_ncols = nullptr;     // [ncb]        columns of the block
-  void* d_pb_arena = nullptr;        // the one allocation that holds the four big streams below (interior pointers)
-  size_t pb_arena_bytes = 0, pb_arena_static_bytes = 0;  // its size; the part in front of the product buffer
-  void* d_pb_val = nullptr;          // values, column-block order
-  uint16_t* d_pb_col = nullptr;      // local column, column-block order
-  uint16_t* d_pb_row = nullptr;      // local row, row-block order
-  void* d_pb_prod = nullptr;         // product buffer P (nnz elements of T), row-block order
-  int16_t* d_pb_rexp = nullptr;      // LL_PB_PHASE2=fixed: exponent of every local row's absolute sum
-  double* d_pb_blockmax = nullptr;   // LL_PB_PHASE2=fixed: max |x| per column block, left by phase 1
-  void* d_pb_diag = nullptr;         // a_ii of every local row (T): the diagonal is kept outside the streams (spmv_pb.hip pb_diag_kernel)
-  int64_t pb_entries = 0;            // padded entry count of the image
-  int pb_phase2 = 4;                 // form of phase 2 (ll::LL_PB_FIXED / _ORDERED / _ATOMIC): set when the image is built,
-                                     // changed by ll_op_set_accuracy (both forms read the same image)
   int accuracy_req = 0;              // LL_ACCURACY_* asked for at creation (ll_csr_options.accuracy); 0 = the environment decides
-  // 2-D tiled image (spmv_pb.hip, tl_*; LL_SPMV_TILED): row blocks with the y slice in LDS, each walking its non-empty
-  // column tiles of 16 KiB of x; entries = value (pre-scaled by the row's exponent) + packed 16-bit local column / row
-  int tl_nrb = 0, tl_rb_rows = 0, tl_ncb = 0;
-  int tl_n_interior = 0;             // sharded: row blocks whose tiles are all own-column tiles (first in d_tl_rbmap; they run under the all-gather)
-  int32_t* d_tl_rbmap = nullptr;     // sharded: [nrb] row blocks in launch order (interior first); nullptr on one GPU
-  int64_t tl_entries = 0, tl_tiles = 0;
-  int32_t* d_tl_first = nullptr;     // [nrb + 1]     first tile of each row block in the tile list
-  int32_t* d_tl_col = nullptr;       // [ntiles]      column tile index
-  int64_t* d_tl_quad = nullptr;      // [ntiles + 1]  first quad (4 entries) of each tile in the entry stream
-  void* d_tl_val = nullptr;          // values in tile order
-  uint32_t* d_tl_idx = nullptr;      // local column | local row << 16
-  int16_t* d_tl_rexp = nullptr;      // exponent of every row's absolute sum (the scale the values were divided by)
-  double* d_tl_xmax = nullptr;       // maxima of |x| the kernel folds (per workgroup of the pre-pass; sharded: one per rank), then scratch of the own-shard pre-pass
-  bool tl_ordered = false;           // the tiled kernel sums in floating point, the waves in turn (component-wise class) instead of in fixed point
-  // Column-block table order: the blocks over the rank's OWN columns first (their x slice is the local shard, no
-  // exchange needed), then, gather chunk by gather chunk, the blocks over the other ranks' columns (x slice in the
-  // gathered buffer).  One phase-1 launch per range, so own-column work runs under the all-gather.
-  int pb_threads1 = 1024;                      // lanes per workgroup of phase 1 (1024; 512 for the thin column blocks of a sharded image)
-  bool pb_xpre = true;                         // fixed-point phase 2 requests the epilogue's x_i before its stream (LL_PB_XPRE)
-  int pb_own_count = 0;                        // table range [0, own_count)
-  int pb_chunk_first[ll::kMaxGatherChunks] = {0};  // remote blocks of gather chunk c: [first, first + count)
-  int pb_chunk_count[ll::kMaxGatherChunks] = {0};
-  ll::GatherPlan gather;             // how a sharded vector is all-gathered when the PB kernels are selected
-  // one-triangle image of a symmetric / Hermitian matrix (spmv_sym.hip; LL_SPMV_SYM, ll_op_create_csr_sym_*): one stream per
-  // row block of every stored entry with an end in the block; an entry whose two ends lie in different blocks is in both streams
+  ll::PbImage pb;                    // propagation-blocked image (spmv_pb.hip pb_phase1 / pb_phase2)
+  ll::TiledImage tl;                 // 2-D tiled image (spmv_pb.hip tl_*; LL_SPMV_TILED)
   int64_t sym_stored = -1;           // entries of the triangle the operator was created from (ll_op_info); -1: full storage
-  int sym_nrb = 0, sym_rb_rows = 0, sym_halo = 0;  // row blocks, rows per block, half-bandwidth max |i - j| of the triangle
-  int64_t* d_sym_qptr = nullptr;     // [nrb + 1] first quad (4 entries) of each row block's stream
-  void* d_sym_val = nullptr;         // values as stored (T)
-  uint32_t* d_sym_idx = nullptr;     // window index of the entry's row | of its column << 16 (0xffffffff: padding)
-  int16_t* d_sym_rexp = nullptr;     // exponent of every row's absolute sum over the FULL row of A
-  double* d_sym_xmax = nullptr;      // kXmaxParts maxima of |x| (pre-pass)
-  void* d_sym_diag = nullptr;        // [n] the first diagonal entry of every row, kept outside the streams (0: none)
-  // entries whose other end lies outside the row block's x window (the few beyond the halo, e.g. the wrap-around corners of a
-  // periodic band): one product each, x read from memory — destination local row | 1 << 31 for the mirrored product, source row
-  int64_t* d_sym_fptr = nullptr;     // [nrb + 1] first far entry of each row block
-  void* d_sym_fval = nullptr;
-  uint32_t* d_sym_fdst = nullptr;
-  int32_t* d_sym_fsrc = nullptr;
+  ll::SymImage sym;                  // one-triangle image (spmv_sym.hip; LL_SPMV_SYM, ll_op_create_csr_sym_*)
   // dense row-major block (kind DENSE): n_local x n values of T
-  void* d_dense = nullptr;
+  ll::DevArray<void> dense;
   // lattice operator (kind STENCIL)
   ll_stencil_desc st = {};
   int64_t st_stride[3] = {0, 0, 0};  // flattened-index stride of each dimension (last index fastest)
   int64_t st_halo = 0;               // sites of one hyperplane = reach of the operator in the flattened index
-  void* d_onsite = nullptr;          // n_local on-site terms in the real type of T (nullable)
+  ll::DevArray<void> onsite;         // n_local on-site terms in the real type of T (nullable)
+  // device bytes the operator holds (the caller's borrowed arrays excluded)
+  int64_t device_bytes() const {
+    return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
+           sym.device_bytes() + dense.bytes() + onsite.bytes();
+  }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
   ll_dev_mv_mul dev_fn = nullptr;
@@ -387,7 +494,7 @@ struct ll_operator {
   ll_operator() = default;
   ll_operator(const ll_operator&) = delete;
   ll_operator& operator=(const ll_operator&) = delete;
-  ~ll_operator();  // frees every device array the operator owns (capi.cpp)
+  ~ll_operator();  // selects the device; the images free their arrays (capi.cpp)
 };
 
 namespace ll {
@@ -413,13 +520,13 @@ template <typename T> struct ScaleIn {
 
 // y = A x_full(cols) + offset * x_local ; dot_partials (nullable): one double per workgroup, Re<x_local, y>.
 // Returns the number of partials written.
-// part: 0 = the whole image; 1 / 2 = the own-column / other-columns half of a column-split image (ll_operator::csr_split).
+// part: 0 = the whole image (op.csr); 1 / 2 = the own-column / other-columns half of a column-split image (op.csr_own / csr_rem).
 template <typename T>
 int launch_spmv(const ll_operator& op, const T* x_full, const T* x_local, T* y, double offset, double* dot_partials,
                 hipStream_t s, const ScaleIn<T>* sc = nullptr, int part = 0);
 // build helpers of the column split (kernels.hip): own-column entries per row; scatter into the two halves
 template <typename T> void launch_csr_count_own(const ll_operator& op, int32_t* own_cnt, hipStream_t s);
-template <typename T> void launch_csr_split(const ll_operator& op, hipStream_t s);
+template <typename T> void launch_csr_split(const ll_operator& op, const CsrImage& own, const CsrImage& rem, hipStream_t s);
 // Same contract, propagation-blocked kernels (op.spmv_kind == LL_SPMV_PB; spmv_pb.hip): phase 1 over the own-column
 // blocks (x slices from x_own: the local shard readable up to the shard stride), then over every gather chunk's remote blocks (x slices from x_gathered, laid out
 // per op.gather), then phase 2.  The pieces are exposed so that the sharded driver can run the own-column part under
@@ -435,14 +542,13 @@ void launch_pb_phase1(const ll_operator& op, int blk_first, int blk_count, const
 template <typename T>
 int launch_pb_phase2(const ll_operator& op, const T* x_local, T* y, double offset, double* dot_partials, hipStream_t s,
                      const double* xnorm2 = nullptr);
-// forms of PB phase 2 (Tuning::pb_phase2, ll_operator::pb_phase2)
+// forms of PB phase 2 (Tuning::pb_phase2, PbImage::phase2)
 constexpr int LL_PB_ATOMIC = 0, LL_PB_ORDERED = 1, LL_PB_FIXED = 4;
 // Build the propagation-blocked image on the device from the operator's CSR arrays (false: shape not supported).
 template <typename T> bool pb_build_device(ll_operator* op);
 // The 2-D tiled kernel for matrices with column locality (spmv_pb.hip): same contract as launch_spmv on a single GPU
 // (x = the whole vector); build returns false when the matrix is not eligible (too many column tiles per row block).
 template <typename T> bool tl_build_device(ll_operator* op);
-void tl_release(ll_operator* op);
 template <typename T>
 int launch_spmv_tiled(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                       const double* xnorm2 = nullptr);
@@ -457,16 +563,15 @@ template <typename T> void csr_check_device(ll_operator* op);
 // maxima of |x| over n elements, one per workgroup, into parts [kXmaxParts]; returns how many were written (tl_xmax_kernel)
 template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hipStream_t s);
 // The one-triangle kernel (spmv_sym.hip).  sym_rows_for: rows per row block for a triangle of that half-bandwidth, 0 when
-// the triangle is not eligible.  sym_build: the image from the HOST triangle (op->n, sym_halo, sym_rb_rows set; the row
+// the triangle is not eligible.  sym_build: the image from the HOST triangle into im (op->n, im.halo, im.rb_rows set; the row
 // exponents are filled by the caller).  launch_spmv_sym: y = A x + offset x on a single GPU, same contract as launch_spmv.
 template <typename T> int sym_rows_for(int64_t n, int64_t halo);
 // the x window's halo for a triangle: the smallest h that leaves at most 1/16 of the entries with |i - j| > h (-1: none <= 32767)
 int64_t sym_halo_for(const int64_t* rp, const int32_t* ci, int64_t n);
-template <typename T> void sym_build(ll_operator* op, const int64_t* rp, const int32_t* ci, const T* va);
+template <typename T> void sym_build(const ll_operator& op, SymImage& im, const int64_t* rp, const int32_t* ci, const T* va);
 template <typename T>
 int launch_spmv_sym(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                     const double* xnorm2);
-void sym_release(ll_operator* op);
 // Same contract for the dense row block (op.kind == DENSE).
 template <typename T>
 int launch_dense_mv(const ll_operator& op, const T* x_full, const T* x_local, T* y, double offset, double* dot_partials,

@@ -592,31 +592,31 @@ template <typename T> void pb_opt_in_lds() {
 
 template <typename T>
 void phase1_launch(const ll_operator& op, int blk_first, int blk_count, const T* xsrc, const double* xnorm2, hipStream_t s) {
-  const size_t lds1 = (((size_t)op.pb_cb_cols * sizeof(T) + 15) & ~(size_t)15) + (size_t)(2 * op.pb_nrb + 1) * sizeof(long long);
-  double* bm = op.pb_phase2 == LL_PB_FIXED ? op.d_pb_blockmax : nullptr;
+  const size_t lds1 = (((size_t)op.pb.cb_cols * sizeof(T) + 15) & ~(size_t)15) + (size_t)(2 * op.pb.nrb + 1) * sizeof(long long);
+  double* bm = op.pb.phase2 == LL_PB_FIXED ? op.pb.blockmax.get() : nullptr;
   // Fewer lanes per workgroup for the thin column blocks of a sharded image: at N = 8 a block holds 16 K entries — four trips of
   // 1024 lanes, two of them requested by the prologue: the ring never reaches its steady state — but 8 trips of 512 lanes
   // (measured on config 4's shards through the stand-in transport, profiles/r05_shard_phase1_lanes.txt: 60.8 -> 41.9 us per
   // launch at N = 8 with the same 68 KB slices; smaller slices with more workgroups per CU lose to their segment count)
-  if (op.pb_threads1 == 256)
-    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, 256>), dim3(blk_count), dim3(256), lds1, s, op.pb_nrb, blk_first, op.d_pb_xoff,
-                       op.d_pb_ncols, op.d_pb_segq, op.d_pb_segdest, (const T*)op.d_pb_val, (const ushort4*)op.d_pb_col, xsrc,
-                       (T*)op.d_pb_prod, op.pb_cb_cols, bm, (long long)op.pb_entries, xnorm2);
-  else if (op.pb_threads1 == 512)
-    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, 512>), dim3(blk_count), dim3(512), lds1, s, op.pb_nrb, blk_first, op.d_pb_xoff,
-                       op.d_pb_ncols, op.d_pb_segq, op.d_pb_segdest, (const T*)op.d_pb_val, (const ushort4*)op.d_pb_col, xsrc,
-                       (T*)op.d_pb_prod, op.pb_cb_cols, bm, (long long)op.pb_entries, xnorm2);
+  if (op.pb.threads1 == 256)
+    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, 256>), dim3(blk_count), dim3(256), lds1, s, op.pb.nrb, blk_first, op.pb.xoff.get(),
+                       op.pb.ncols.get(), op.pb.segq.get(), op.pb.segdest.get(), (const T*)op.pb.val, (const ushort4*)op.pb.col, xsrc,
+                       (T*)op.pb.prod, op.pb.cb_cols, bm, (long long)op.pb.entries, xnorm2);
+  else if (op.pb.threads1 == 512)
+    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, 512>), dim3(blk_count), dim3(512), lds1, s, op.pb.nrb, blk_first, op.pb.xoff.get(),
+                       op.pb.ncols.get(), op.pb.segq.get(), op.pb.segdest.get(), (const T*)op.pb.val, (const ushort4*)op.pb.col, xsrc,
+                       (T*)op.pb.prod, op.pb.cb_cols, bm, (long long)op.pb.entries, xnorm2);
   else
-    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, kPbThreads>), dim3(blk_count), dim3(kPbThreads), lds1, s, op.pb_nrb, blk_first,
-                       op.d_pb_xoff, op.d_pb_ncols, op.d_pb_segq, op.d_pb_segdest, (const T*)op.d_pb_val,
-                       (const ushort4*)op.d_pb_col, xsrc, (T*)op.d_pb_prod, op.pb_cb_cols, bm, (long long)op.pb_entries, xnorm2);
+    hipLaunchKernelGGL((pb_phase1<T, kPbDepth1, kPbThreads>), dim3(blk_count), dim3(kPbThreads), lds1, s, op.pb.nrb, blk_first,
+                       op.pb.xoff.get(), op.pb.ncols.get(), op.pb.segq.get(), op.pb.segdest.get(), (const T*)op.pb.val,
+                       (const ushort4*)op.pb.col, xsrc, (T*)op.pb.prod, op.pb.cb_cols, bm, (long long)op.pb.entries, xnorm2);
   LL_HIP(hipGetLastError());
 }
 }  // namespace
 
 template <typename T>
 void launch_pb_phase1(const ll_operator& op, int blk_first, int blk_count, const T* xsrc, hipStream_t s, const double* xnorm2) {
-  if (blk_count <= 0 || op.pb_nrb <= 0) return;
+  if (blk_count <= 0 || op.pb.nrb <= 0) return;
   pb_opt_in_lds<T>();
   phase1_launch<T>(op, blk_first, blk_count, xsrc, xnorm2, s);
 }
@@ -624,37 +624,37 @@ void launch_pb_phase1(const ll_operator& op, int blk_first, int blk_count, const
 template <typename T>
 int launch_pb_phase2(const ll_operator& op, const T* x_local, T* y, double offset, double* dot_partials,
                      hipStream_t s, const double* xnorm2) {
-  if (op.pb_nrb <= 0) return 0;
+  if (op.pb.nrb <= 0) return 0;
   pb_opt_in_lds<T>();
-  const dim3 grid(op.pb_nrb), block(kPbThreads);
+  const dim3 grid(op.pb.nrb), block(kPbThreads);
   constexpr int D2 = pb_depth2<T>();
-  if (op.pb_phase2 == LL_PB_FIXED) {  // order-independent fixed-point sums, LATE form
-    const size_t ldsf = (size_t)op.pb_rb_rows * (sizeof(acc_t<T>) + sizeof(int16_t)) + 16;
-    hipLaunchKernelGGL((pb_phase2_fixed<T, D2>), grid, block, ldsf, s, op.pb_rb_rows, op.n_local, op.pb_ncb, op.d_pb_rptr,
-                       (const ushort4*)op.d_pb_row, (const T*)op.d_pb_prod, op.d_pb_rexp, op.d_pb_blockmax, x_local, y,
-                       offset, dot_partials, xnorm2, (op.pb_xpre && op.pb_rb_rows <= kPbXPre * kPbThreads) ? 1 : 0,
-                       (const T*)op.d_pb_diag);
+  if (op.pb.phase2 == LL_PB_FIXED) {  // order-independent fixed-point sums, LATE form
+    const size_t ldsf = (size_t)op.pb.rb_rows * (sizeof(acc_t<T>) + sizeof(int16_t)) + 16;
+    hipLaunchKernelGGL((pb_phase2_fixed<T, D2>), grid, block, ldsf, s, op.pb.rb_rows, op.n_local, op.pb.ncb, op.pb.rptr.get(),
+                       (const ushort4*)op.pb.row, (const T*)op.pb.prod, op.pb.rexp.get(), op.pb.blockmax.get(), x_local, y,
+                       offset, dot_partials, xnorm2, (op.pb.xpre && op.pb.rb_rows <= kPbXPre * kPbThreads) ? 1 : 0,
+                       (const T*)op.pb.diag.get());
   } else {
-    const size_t lds2 = (size_t)op.pb_rb_rows * sizeof(acc_t<T>);
-    if (op.pb_phase2 == LL_PB_ORDERED)
-      hipLaunchKernelGGL((pb_phase2<T, true, D2>), grid, block, lds2, s, op.pb_rb_rows, op.n_local, op.d_pb_rptr,
-                         (const ushort4*)op.d_pb_row, (const T*)op.d_pb_prod, x_local, y, offset, dot_partials, xnorm2,
-                         (const T*)op.d_pb_diag);
+    const size_t lds2 = (size_t)op.pb.rb_rows * sizeof(acc_t<T>);
+    if (op.pb.phase2 == LL_PB_ORDERED)
+      hipLaunchKernelGGL((pb_phase2<T, true, D2>), grid, block, lds2, s, op.pb.rb_rows, op.n_local, op.pb.rptr.get(),
+                         (const ushort4*)op.pb.row, (const T*)op.pb.prod, x_local, y, offset, dot_partials, xnorm2,
+                         (const T*)op.pb.diag.get());
     else
-      hipLaunchKernelGGL((pb_phase2<T, false, D2>), grid, block, lds2, s, op.pb_rb_rows, op.n_local, op.d_pb_rptr,
-                         (const ushort4*)op.d_pb_row, (const T*)op.d_pb_prod, x_local, y, offset, dot_partials, xnorm2,
-                         (const T*)op.d_pb_diag);
+      hipLaunchKernelGGL((pb_phase2<T, false, D2>), grid, block, lds2, s, op.pb.rb_rows, op.n_local, op.pb.rptr.get(),
+                         (const ushort4*)op.pb.row, (const T*)op.pb.prod, x_local, y, offset, dot_partials, xnorm2,
+                         (const T*)op.pb.diag.get());
   }
   LL_HIP(hipGetLastError());
-  return op.pb_nrb;
+  return op.pb.nrb;
 }
 
 template <typename T>
 int launch_spmv_pb(const ll_operator& op, const T* x_gathered, const T* x_own, const T* x_local, T* y, double offset,
                    double* dot_partials, hipStream_t s, const double* xnorm2) {
-  launch_pb_phase1<T>(op, 0, op.pb_own_count, x_own, s, xnorm2);
-  for (int c = 0; c < op.gather.nchunks; ++c)
-    launch_pb_phase1<T>(op, op.pb_chunk_first[c], op.pb_chunk_count[c], x_gathered, s, xnorm2);
+  launch_pb_phase1<T>(op, 0, op.pb.own_count, x_own, s, xnorm2);
+  for (int c = 0; c < op.pb.gather.nchunks; ++c)
+    launch_pb_phase1<T>(op, op.pb.chunk_first[c], op.pb.chunk_count[c], x_gathered, s, xnorm2);
   return launch_pb_phase2<T>(op, x_local, y, offset, dot_partials, s, xnorm2);
 }
 
@@ -828,30 +828,22 @@ __global__ __launch_bounds__(256) void csr_check_kernel(long long n_local, long 
 template <typename T> void csr_check_device(ll_operator* op) {
   const long long nr = op->n_local;
   const int grid = (int)std::max<long long>(1, std::min<long long>(kMaxGrid, (nr + 255) / 256));
-  double* d_part = nullptr;
-  unsigned long long* d_bad = nullptr;
-  op->ctx->dev_malloc((void**)&d_part, (size_t)grid * sizeof(double), "row-sum partials");
-  op->ctx->dev_malloc((void**)&d_bad, sizeof(unsigned long long), "column check");
-  struct Guard {
-    void *a, *b;
-    ~Guard() {
-      (void)hipFree(a);
-      (void)hipFree(b);
-    }
-  } guard{d_part, d_bad};
+  const DevArray<double> d_part = op->ctx->dev_alloc<double>((size_t)grid, "row-sum partials");
+  const DevArray<unsigned long long> d_bad = op->ctx->dev_alloc<unsigned long long>(1, "column check");
   hipStream_t s = op->ctx->stream;
-  LL_HIP(hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), s));
-  if (op->rp64)
+  const CsrImage& a = op->csr;
+  LL_HIP(hipMemsetAsync(d_bad.get(), 0, sizeof(unsigned long long), s));
+  if (a.rp64)
     hipLaunchKernelGGL((csr_check_kernel<T, int64_t>), dim3(grid), dim3(256), 0, s, nr, (long long)op->n,
-                       (const int64_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, d_part, d_bad);
+                       (const int64_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), d_part.get(), d_bad.get());
   else
     hipLaunchKernelGGL((csr_check_kernel<T, int32_t>), dim3(grid), dim3(256), 0, s, nr, (long long)op->n,
-                       (const int32_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, d_part, d_bad);
+                       (const int32_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), d_part.get(), d_bad.get());
   LL_HIP(hipGetLastError());
   std::vector<double> part((size_t)grid);
   unsigned long long bad = 0;
-  LL_HIP(hipMemcpyAsync(part.data(), d_part, (size_t)grid * sizeof(double), hipMemcpyDeviceToHost, s));
-  LL_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+  LL_HIP(hipMemcpyAsync(part.data(), d_part.get(), (size_t)grid * sizeof(double), hipMemcpyDeviceToHost, s));
+  LL_HIP(hipMemcpyAsync(&bad, d_bad.get(), sizeof(bad), hipMemcpyDeviceToHost, s));
   LL_HIP(hipStreamSynchronize(s));
   LL_REQUIRE(bad == 0, "column index out of range");
   double mx = 0.0;
@@ -861,9 +853,11 @@ template <typename T> void csr_check_device(ll_operator* op) {
 
 // Block geometry + tables on the host (O(ncb * nrb)), entry placement on the device.  Returns false when the image
 // cannot be built for this shape (segment tables too large, or the LDS budget cannot hold a slice and its tables):
-// the operator then keeps CSR-stream.
+// the operator then keeps CSR-stream.  The image goes to op->pb only when it is complete.
 template <typename T> bool pb_build_device(ll_operator* op) {
   ll_context* ctx = op->ctx;
+  const CsrImage& a = op->csr;
+  PbImage im;
   hipStream_t s = ctx->stream;
   const int64_t nr = op->n_local;
   const int P = std::max(1, ctx->nranks);
@@ -954,8 +948,8 @@ template <typename T> bool pb_build_device(ll_operator* op) {
   int64_t ncb = own_total;
   for (int c = 0; c < gp.nchunks; ++c) {
     m.rem_base[c] = (int)ncb;
-    op->pb_chunk_first[c] = (int)ncb;
-    op->pb_chunk_count[c] = nrem * m.nb[c];
+    im.chunk_first[c] = (int)ncb;
+    im.chunk_count[c] = nrem * m.nb[c];
     ncb += (int64_t)nrem * m.nb[c];
   }
   if (ncb * nrb > (int64_t)24 << 20) return false;  // segment tables would not pay off (n beyond ~6e7): keep CSR
@@ -977,44 +971,33 @@ template <typename T> bool pb_build_device(ll_operator* op) {
   }
 
   // ---- the diagonal leaves the image (pb_diag_kernel): one bit per CSR entry marks what the passes below skip
-  uint32_t* d_skip = nullptr;
-  struct Free0 {
-    uint32_t*& p;
-    ~Free0() {
-      if (p) (void)hipFree(p);
-    }
-  } free_skip{d_skip};
+  DevArray<uint32_t> d_skip;
   if (tune.pb_diag && nr > 0 && op->nnz > 0) {
     const size_t words = ((size_t)op->nnz + 31) / 32 + 1;
-    ctx->dev_malloc((void**)&d_skip, words * sizeof(uint32_t), "diagonal marks");
-    ctx->dev_malloc(&op->d_pb_diag, std::max<size_t>((size_t)nr, 2) * sizeof(T), "diagonal of the PB image");
-    LL_HIP(hipMemsetAsync(d_skip, 0, words * sizeof(uint32_t), s));
+    d_skip = ctx->dev_alloc<uint32_t>(words, "diagonal marks");
+    im.diag = ctx->dev_alloc<T>(std::max<size_t>((size_t)nr, 2), "diagonal of the PB image");
+    LL_HIP(hipMemsetAsync(d_skip.get(), 0, words * sizeof(uint32_t), s));
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, (nr + 255) / 256));
-    if (op->rp64)
+    if (a.rp64)
       hipLaunchKernelGGL((pb_diag_kernel<T, int64_t>), dim3(g), dim3(256), 0, s, (long long)nr, (long long)op->row_begin,
-                         (const int64_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, (T*)op->d_pb_diag, d_skip);
+                         (const int64_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), (T*)im.diag.get(), d_skip.get());
     else
       hipLaunchKernelGGL((pb_diag_kernel<T, int32_t>), dim3(g), dim3(256), 0, s, (long long)nr, (long long)op->row_begin,
-                         (const int32_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, (T*)op->d_pb_diag, d_skip);
+                         (const int32_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), (T*)im.diag.get(), d_skip.get());
     LL_HIP(hipGetLastError());
   }
   // ---- pass 1 on the device: segment sizes
-  int32_t* d_cnt = nullptr;
-  ctx->dev_malloc((void**)&d_cnt, (size_t)ncb * nrb * sizeof(int32_t), "segment counts");
-  struct Free1 {
-    void* p;
-    ~Free1() { (void)hipFree(p); }
-  } free_cnt{d_cnt};
+  const DevArray<int32_t> d_cnt = ctx->dev_alloc<int32_t>((size_t)ncb * nrb, "segment counts");
   const size_t hist_bytes = (size_t)ncb * sizeof(int);
-  if (op->rp64)
+  if (a.rp64)
     hipLaunchKernelGGL((pb_count_kernel<int64_t>), dim3((int)nrb), dim3(256), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int64_t*)op->d_row_ptr, op->d_col, d_cnt, d_skip);
+                       (int)rb_rows, (long long)nr, (const int64_t*)a.row_ptr.get(), a.col.get(), d_cnt.get(), d_skip.get());
   else
     hipLaunchKernelGGL((pb_count_kernel<int32_t>), dim3((int)nrb), dim3(256), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int32_t*)op->d_row_ptr, op->d_col, d_cnt, d_skip);
+                       (int)rb_rows, (long long)nr, (const int32_t*)a.row_ptr.get(), a.col.get(), d_cnt.get(), d_skip.get());
   LL_HIP(hipGetLastError());
   std::vector<int32_t> cnt32((size_t)ncb * nrb);
-  LL_HIP(hipMemcpyAsync(cnt32.data(), d_cnt, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  LL_HIP(hipMemcpyAsync(cnt32.data(), d_cnt.get(), cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   LL_HIP(hipStreamSynchronize(s));
   // every segment is padded to 16 entries: kernels move quads (4 entries per lane, 16-byte accesses) and every run of
   // products written by phase 1 starts and ends on a 128-byte line (measured 3.5 % faster than quad padding)
@@ -1043,33 +1026,34 @@ template <typename T> bool pb_build_device(ll_operator* op) {
     rptr[(size_t)nrb] = d;
   }
   const size_t entries = (size_t)rptr[(size_t)nrb];
-  op->pb_ncb = (int)ncb;
-  op->pb_nrb = (int)nrb;
-  op->pb_cb_cols = cb_cols;
-  op->pb_rb_rows = (int)rb_rows;
-  op->pb_own_count = own_total;
-  op->pb_entries = (int64_t)entries;
-  op->pb_xpre = tune.pb_xpre;
-  op->pb_threads1 = tune.pb_threads1 > 0 ? tune.pb_threads1 : (P > 1 ? 512 : kPbThreads);
-  op->gather = gp;
+  im.ncb = (int)ncb;
+  im.nrb = (int)nrb;
+  im.cb_cols = cb_cols;
+  im.rb_rows = (int)rb_rows;
+  im.own_count = own_total;
+  im.entries = (int64_t)entries;
+  im.xpre = tune.pb_xpre;
+  im.threads1 = tune.pb_threads1 > 0 ? tune.pb_threads1 : (P > 1 ? 512 : kPbThreads);
+  im.gather = gp;
   // Phase 2 form, fixed per operator at creation (LL_PB_PHASE2).  Default "fixed": order-independent fixed-point sums
   // (integer LDS adds, all waves at once) — bit-reproducible for every launch, kernel geometry and partition, and 2-5 %
   // faster than the wave-ordered form (profiles/r02_spmv_variants_run10_fixed_default.jsonl).  "ordered": floating-
   // point adds, the 16 waves in turn (barriers) — reproducible and component-wise accurate; "atomic": floating-point
   // adds in arrival order (not reproducible; A/B timing reference).
   // The caller's choice through ll_csr_options.accuracy / ll_op_set_accuracy (include/lanczos_hip.h) outranks the environment.
-  op->pb_phase2 = op->accuracy_req == LL_ACCURACY_COMPONENTWISE
-                      ? (tune.pb_phase2 == LL_PB_ATOMIC ? LL_PB_ATOMIC : LL_PB_ORDERED)
-                      : (op->accuracy_req == LL_ACCURACY_NORMWISE ? LL_PB_FIXED : tune.pb_phase2);
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    ctx->dev_malloc(dst, bytes, "propagation-blocking tables");
-    LL_HIP(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
+  im.phase2 = op->accuracy_req == LL_ACCURACY_COMPONENTWISE
+                  ? (tune.pb_phase2 == LL_PB_ATOMIC ? LL_PB_ATOMIC : LL_PB_ORDERED)
+                  : (op->accuracy_req == LL_ACCURACY_NORMWISE ? LL_PB_FIXED : tune.pb_phase2);
+  auto up = [&](auto& dst, const auto& v) {
+    using E = typename std::decay_t<decltype(v)>::value_type;
+    dst = ctx->dev_alloc<E>(v.size(), "propagation-blocking tables");
+    LL_HIP(hipMemcpyAsync(dst.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice, s));
   };
-  up((void**)&op->d_pb_segq, segq.data(), segq.size() * sizeof(int64_t));
-  up((void**)&op->d_pb_segdest, segdest.data(), segdest.size() * sizeof(int64_t));
-  up((void**)&op->d_pb_rptr, rptr.data(), rptr.size() * sizeof(int64_t));
-  up((void**)&op->d_pb_xoff, xoff.data(), xoff.size() * sizeof(int64_t));
-  up((void**)&op->d_pb_ncols, ncols.data(), ncols.size() * sizeof(int32_t));
+  up(im.segq, segq);
+  up(im.segdest, segdest);
+  up(im.rptr, rptr);
+  up(im.xoff, xoff);
+  up(im.ncols, ncols);
   // 16 entries behind the image: the dump quad of phase 1 and the clamped reads of an empty last block
   const size_t cap = entries + 16;
   // ONE allocation for the four big streams (values, local columns, local rows, product buffer), starts 2 MiB aligned
@@ -1082,49 +1066,50 @@ template <typename T> bool pb_build_device(ll_operator* op) {
     const size_t o_row = up2m(o_col + cap * sizeof(uint16_t)) + 2 * stagger;
     const size_t o_prod = up2m(o_row + cap * sizeof(uint16_t)) + 3 * stagger;
     const size_t total = o_prod + cap * sizeof(T);
-    ctx->dev_malloc(&op->d_pb_arena, total, "propagation-blocked image (values, indices, product buffer)");
-    op->pb_arena_bytes = total;
-    op->pb_arena_static_bytes = o_prod;  // everything in front of the product buffer is the matrix (copied on re-placement)
-    char* base = (char*)op->d_pb_arena;
-    op->d_pb_val = base + o_val;
-    op->d_pb_col = (uint16_t*)(base + o_col);
-    op->d_pb_row = (uint16_t*)(base + o_row);
-    op->d_pb_prod = base + o_prod;
+    im.arena = ctx->dev_alloc<void>(total, "propagation-blocked image (values, indices, product buffer)");
+    im.arena_bytes = total;
+    im.arena_static_bytes = o_prod;  // everything in front of the product buffer is the matrix (copied on re-placement)
+    char* base = (char*)im.arena.get();
+    im.val = base + o_val;
+    im.col = (uint16_t*)(base + o_col);
+    im.row = (uint16_t*)(base + o_row);
+    im.prod = base + o_prod;
   }
-  LL_HIP(hipMemsetAsync(op->d_pb_val, 0, cap * sizeof(T), s));  // padding entries: value 0, local indices 0
-  LL_HIP(hipMemsetAsync(op->d_pb_col, 0, cap * sizeof(uint16_t), s));
-  LL_HIP(hipMemsetAsync(op->d_pb_row, 0, cap * sizeof(uint16_t), s));
+  LL_HIP(hipMemsetAsync(im.val, 0, cap * sizeof(T), s));  // padding entries: value 0, local indices 0
+  LL_HIP(hipMemsetAsync(im.col, 0, cap * sizeof(uint16_t), s));
+  LL_HIP(hipMemsetAsync(im.row, 0, cap * sizeof(uint16_t), s));
   // ---- pass 2 on the device: place the entries
-  if (op->rp64)
+  if (a.rp64)
     hipLaunchKernelGGL((pb_scatter_kernel<T, int64_t>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int64_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val,
-                       op->d_pb_segq, op->d_pb_segdest, (T*)op->d_pb_val, op->d_pb_col, op->d_pb_row, nullptr, d_skip);
+                       (int)rb_rows, (long long)nr, (const int64_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(),
+                       im.segq.get(), im.segdest.get(), (T*)im.val, im.col, im.row, nullptr, d_skip.get());
   else
     hipLaunchKernelGGL((pb_scatter_kernel<T, int32_t>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int32_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val,
-                       op->d_pb_segq, op->d_pb_segdest, (T*)op->d_pb_val, op->d_pb_col, op->d_pb_row, nullptr, d_skip);
+                       (int)rb_rows, (long long)nr, (const int32_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(),
+                       im.segq.get(), im.segdest.get(), (T*)im.val, im.col, im.row, nullptr, d_skip.get());
   LL_HIP(hipGetLastError());
   // Fixed-point sums need per-row exponents of the absolute row sums and per-block maxima of |x|.  They are built for EVERY
   // image whose row block leaves room for them (2 bytes per row; the CSR arrays they come from may be released after creation),
   // so that ll_op_set_accuracy can move the operator between the two accuracy classes later.
   // the y slice holds 64-bit integers + one 16-bit exponent per row: it must still fit the LDS
   const bool fixed_fits = (size_t)rb_rows * (sizeof(acc_t<T>) + sizeof(int16_t)) + 16 <= (size_t)kPbLdsCap;
-  if (op->pb_phase2 == LL_PB_FIXED)
+  if (im.phase2 == LL_PB_FIXED)
     LL_REQUIRE(fixed_fits, "LL_PB_PHASE2=fixed: row block too large for the LDS (lower LL_PB_ROW_BLOCK)");
   if (fixed_fits) {
-    ctx->dev_malloc((void**)&op->d_pb_rexp, std::max<size_t>((size_t)nr, 8) * sizeof(int16_t), "row exponents");
-    ctx->dev_malloc((void**)&op->d_pb_blockmax, (size_t)ncb * sizeof(double), "x slice maxima");
-    LL_HIP(hipMemsetAsync(op->d_pb_blockmax, 0, (size_t)ncb * sizeof(double), s));
+    im.rexp = ctx->dev_alloc<int16_t>(std::max<size_t>((size_t)nr, 8), "row exponents");
+    im.blockmax = ctx->dev_alloc<double>((size_t)ncb, "x slice maxima");
+    LL_HIP(hipMemsetAsync(im.blockmax.get(), 0, (size_t)ncb * sizeof(double), s));
     const int g = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, (nr + 255) / 256));
-    if (op->rp64)
-      hipLaunchKernelGGL((pb_rowexp_kernel<T, int64_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int64_t*)op->d_row_ptr,
-                         (const T*)op->d_val, op->d_pb_rexp);
+    if (a.rp64)
+      hipLaunchKernelGGL((pb_rowexp_kernel<T, int64_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int64_t*)a.row_ptr.get(),
+                         (const T*)a.val.get(), im.rexp.get());
     else
-      hipLaunchKernelGGL((pb_rowexp_kernel<T, int32_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int32_t*)op->d_row_ptr,
-                         (const T*)op->d_val, op->d_pb_rexp);
+      hipLaunchKernelGGL((pb_rowexp_kernel<T, int32_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int32_t*)a.row_ptr.get(),
+                         (const T*)a.val.get(), im.rexp.get());
     LL_HIP(hipGetLastError());
   }
   LL_HIP(hipStreamSynchronize(s));  // the host tables above go out of scope
+  op->pb = std::move(im);
   return true;
 }
 
@@ -1522,8 +1507,8 @@ template <typename T> void tl_opt_in_lds() {
 }  // namespace
 
 namespace {
-// One launch over the row blocks [rb_first, rb_first + rb_count) of the image's order (op.d_tl_rbmap; identity without a map); x holds the
-// global columns [col0, col_end), x_local the rank's own rows; the fixed-point class reads n_xmax maxima of |x| from op.d_tl_xmax.
+// One launch over the row blocks [rb_first, rb_first + rb_count) of the image's order (op.tl.rbmap; identity without a map); x holds the
+// global columns [col0, col_end), x_local the rank's own rows; the fixed-point class reads n_xmax maxima of |x| from op.tl.xmax.
 template <typename T>
 void tl_launch_rows(const ll_operator& op, int rb_first, int rb_count, const T* x, int64_t col0, int64_t col_end, const T* x_local, T* y,
                     double offset, double* dot_partials, hipStream_t s, const double* xnorm2, int n_xmax) {
@@ -1532,13 +1517,13 @@ void tl_launch_rows(const ll_operator& op, int rb_first, int rb_count, const T* 
   // 16-byte pieces of x: the fast form needs an aligned window of at least one piece that starts on a piece boundary
   const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && col0 % V == 0 && col_end - col0 >= V;
 #define LL_TL_LAUNCH(AL, ORD)                                                                                                         \
-  hipLaunchKernelGGL((tl_spmv_kernel<T, kTlDepth, AL, ORD>), dim3(rb_count), dim3(kPbThreads), tl_lds_bytes<T>(op.tl_rb_rows), s,      \
-                     op.tl_rb_rows, op.n_local, col_end, op.d_tl_first, op.d_tl_col, op.d_tl_quad, (const T*)op.d_tl_val,              \
-                     (const uint4*)op.d_tl_idx, op.d_tl_rexp, op.d_tl_xmax, n_xmax, x, x_local, y, offset, dot_partials, xnorm2,       \
-                     op.ctx->tune.tl_xcd_order ? 1 : 0, (const int32_t*)op.d_tl_rbmap, rb_first, col0)
-  if (aligned && op.tl_ordered) LL_TL_LAUNCH(true, true);
+  hipLaunchKernelGGL((tl_spmv_kernel<T, kTlDepth, AL, ORD>), dim3(rb_count), dim3(kPbThreads), tl_lds_bytes<T>(op.tl.rb_rows), s,      \
+                     op.tl.rb_rows, op.n_local, col_end, op.tl.first.get(), op.tl.col.get(), op.tl.quad.get(), (const T*)op.tl.val.get(),              \
+                     (const uint4*)op.tl.idx.get(), op.tl.rexp.get(), op.tl.xmax.get(), n_xmax, x, x_local, y, offset, dot_partials, xnorm2,       \
+                     op.ctx->tune.tl_xcd_order ? 1 : 0, (const int32_t*)op.tl.rbmap.get(), rb_first, col0)
+  if (aligned && op.tl.ordered) LL_TL_LAUNCH(true, true);
   else if (aligned) LL_TL_LAUNCH(true, false);
-  else if (op.tl_ordered) LL_TL_LAUNCH(false, true);
+  else if (op.tl.ordered) LL_TL_LAUNCH(false, true);
   else LL_TL_LAUNCH(false, false);
 #undef LL_TL_LAUNCH
   LL_HIP(hipGetLastError());
@@ -1549,22 +1534,22 @@ void tl_launch_rows(const ll_operator& op, int rb_first, int rb_count, const T* 
 template <typename T>
 int launch_spmv_tiled(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                       const double* xnorm2) {
-  if (op.tl_nrb <= 0) return 0;
+  if (op.tl.nrb <= 0) return 0;
   tl_opt_in_lds<T>();
   const int xgrid = (int)std::max<int64_t>(1, std::min<int64_t>(kTlXmaxParts, (op.n + 255) / 256));
-  if (!op.tl_ordered)  // (the component-wise form has no fixed-point grid to scale: no max|x| pre-pass)
-    hipLaunchKernelGGL((tl_xmax_kernel<T>), dim3(xgrid), dim3(256), 0, s, (long long)op.n, x, op.d_tl_xmax,
+  if (!op.tl.ordered)  // (the component-wise form has no fixed-point grid to scale: no max|x| pre-pass)
+    hipLaunchKernelGGL((tl_xmax_kernel<T>), dim3(xgrid), dim3(256), 0, s, (long long)op.n, x, op.tl.xmax.get(),
                        (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? 1 : 0);
-  tl_launch_rows<T>(op, 0, op.tl_nrb, x, 0, op.n, x + op.row_begin, y, offset, dot_partials, s, xnorm2, xgrid);
-  return op.tl_nrb;
+  tl_launch_rows<T>(op, 0, op.tl.nrb, x, 0, op.n, x + op.row_begin, y, offset, dot_partials, s, xnorm2, xgrid);
+  return op.tl.nrb;
 }
 
 // Sharded contexts (engine.cpp apply_operator): the maximum of |x| over the rank's own shard, one double at
-// op.d_tl_xmax[tl_xmax_local_slot()] — the ranks' maxima are then all-gathered into op.d_tl_xmax[0, nranks), the table the kernel
+// op.tl.xmax[tl_xmax_local_slot()] — the ranks' maxima are then all-gathered into op.tl.xmax[0, nranks), the table the kernel
 // folds (a maximum does not depend on how the vector is cut, so every partition scales its fixed-point grid exactly like one GPU).
 template <typename T> void launch_tl_xmax_local(const ll_operator& op, const T* x_own, hipStream_t s) {
-  if (op.tl_nrb <= 0 || op.tl_ordered) return;
-  double* parts = op.d_tl_xmax + kTlXmaxParts;
+  if (op.tl.nrb <= 0 || op.tl.ordered) return;
+  double* parts = op.tl.xmax.get() + kTlXmaxParts;
   const int g = (int)std::max<int64_t>(1, std::min<int64_t>(kTlXmaxParts, (op.n_local + 255) / 256));
   hipLaunchKernelGGL((tl_xmax_kernel<T>), dim3(g), dim3(256), 0, s, (long long)op.n_local, x_own, parts,
                      (reinterpret_cast<uintptr_t>(x_own) & 15) == 0 ? 1 : 0);
@@ -1574,23 +1559,25 @@ template <typename T> void launch_tl_xmax_local(const ll_operator& op, const T* 
 int tl_xmax_local_slot() { return 2 * kTlXmaxParts; }
 
 // pass 0: the row blocks whose tiles are all own-column tiles (x = the rank's shard, global columns [col0, col_end));
-// pass 1: the others (x = the gathered vector, col0 = 0).  n_xmax maxima (one per rank) wait in op.d_tl_xmax.
+// pass 1: the others (x = the gathered vector, col0 = 0).  n_xmax maxima (one per rank) wait in op.tl.xmax.
 template <typename T>
 int launch_spmv_tiled_pass(const ll_operator& op, int pass, const T* x, int64_t col0, int64_t col_end, const T* x_local, T* y,
                            double offset, double* dot_partials, hipStream_t s, const double* xnorm2, int n_xmax) {
-  if (op.tl_nrb <= 0) return 0;
+  if (op.tl.nrb <= 0) return 0;
   tl_opt_in_lds<T>();
-  const int first = pass == 0 ? 0 : op.tl_n_interior;
-  const int count = pass == 0 ? op.tl_n_interior : op.tl_nrb - op.tl_n_interior;
+  const int first = pass == 0 ? 0 : op.tl.n_interior;
+  const int count = pass == 0 ? op.tl.n_interior : op.tl.nrb - op.tl.n_interior;
   tl_launch_rows<T>(op, first, count, x, col0, col_end, x_local, y, offset, dot_partials, s, xnorm2, n_xmax);
-  return op.tl_nrb;
+  return op.tl.nrb;
 }
 
 // Build the tiled image on the device from the operator's CSR arrays.  false: the matrix is not eligible — its row
 // blocks touch too many column tiles (re-staging x would cost more than the matrix stream itself: matrices without
-// column locality, which keep PB) or the shape does not fit the tables — and nothing stays allocated.
+// column locality, which keep PB) or the shape does not fit the tables — and nothing stays allocated.  The image goes to op->tl
+// only when it is complete (the caller sets tl.ordered).
 template <typename T> bool tl_build_device(ll_operator* op) {
   ll_context* ctx = op->ctx;
+  const CsrImage& a = op->csr;
   hipStream_t s = ctx->stream;
   const int64_t nr = op->n_local;
   if (nr <= 0 || op->nnz <= 0 || ctx->nranks > kTlXmaxParts) return false;
@@ -1621,24 +1608,17 @@ template <typename T> bool tl_build_device(ll_operator* op) {
   m.own_base[0] = 0;
   m.rem_base[0] = (int)ncb;
   // ---- entries per (column tile, row block)
-  int32_t* d_cnt = nullptr;
-  ctx->dev_malloc((void**)&d_cnt, (size_t)ncb * nrb * sizeof(int32_t), "tile counts");
-  struct Free1 {
-    void* p;
-    ~Free1() {
-      if (p) (void)hipFree(p);
-    }
-  } free_cnt{d_cnt};
+  const DevArray<int32_t> d_cnt = ctx->dev_alloc<int32_t>((size_t)ncb * nrb, "tile counts");
   const size_t hist_bytes = (size_t)ncb * sizeof(int);
-  if (op->rp64)
+  if (a.rp64)
     hipLaunchKernelGGL((pb_count_kernel<int64_t>), dim3((int)nrb), dim3(256), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int64_t*)op->d_row_ptr, op->d_col, d_cnt);
+                       (int)rb_rows, (long long)nr, (const int64_t*)a.row_ptr.get(), a.col.get(), d_cnt.get());
   else
     hipLaunchKernelGGL((pb_count_kernel<int32_t>), dim3((int)nrb), dim3(256), hist_bytes, s, m, (int)ncb, (int)nrb,
-                       (int)rb_rows, (long long)nr, (const int32_t*)op->d_row_ptr, op->d_col, d_cnt);
+                       (int)rb_rows, (long long)nr, (const int32_t*)a.row_ptr.get(), a.col.get(), d_cnt.get());
   LL_HIP(hipGetLastError());
   std::vector<int32_t> cnt32((size_t)ncb * nrb);
-  LL_HIP(hipMemcpyAsync(cnt32.data(), d_cnt, cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  LL_HIP(hipMemcpyAsync(cnt32.data(), d_cnt.get(), cnt32.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   LL_HIP(hipStreamSynchronize(s));
   // ---- tile list (non-empty tiles only), row block by row block; every tile padded to 16 entries (whole quads, the
   //      stream of a tile starts on a 128-byte line of both arrays)
@@ -1701,60 +1681,52 @@ template <typename T> bool tl_build_device(ll_operator* op) {
   const bool eligible = staged <= stream && (double)entries <= 1.25 * (double)op->nnz + 16.0 * (double)nrb;
   if (ntiles == 0 || !(eligible || tune.tl_force)) return false;
   if (ntiles > 0x7ffffff0) return false;
-  op->tl_nrb = (int)nrb;
-  op->tl_rb_rows = (int)rb_rows;
-  op->tl_ncb = (int)ncb;
-  op->tl_entries = entries;
-  op->tl_tiles = ntiles;
-  op->tl_n_interior = n_interior;
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    ctx->dev_malloc(dst, std::max<size_t>(bytes, 16), "tiled-image tables");
-    LL_HIP(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
+  TiledImage im;
+  im.nrb = (int)nrb;
+  im.rb_rows = (int)rb_rows;
+  im.ncb = (int)ncb;
+  im.entries = entries;
+  im.tiles = ntiles;
+  im.n_interior = n_interior;
+  auto up = [&](auto& dst, const auto& v) {
+    using E = typename std::decay_t<decltype(v)>::value_type;
+    dst = ctx->dev_alloc<E>(v.size(), "tiled-image tables");
+    LL_HIP(hipMemcpyAsync(dst.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice, s));
   };
-  int64_t* d_segq = nullptr;
-  struct Free2 {
-    int64_t*& p;
-    ~Free2() {
-      if (p) (void)hipFree(p);
-    }
-  } free_segq{d_segq};
-  try {
-    up((void**)&op->d_tl_first, tfirst.data(), tfirst.size() * sizeof(int32_t));
-    up((void**)&op->d_tl_col, tcol.data(), tcol.size() * sizeof(int32_t));
-    up((void**)&op->d_tl_quad, tquad.data(), tquad.size() * sizeof(int64_t));
-    up((void**)&d_segq, segq.data(), segq.size() * sizeof(int64_t));
-    if (!rbmap.empty()) up((void**)&op->d_tl_rbmap, rbmap.data(), rbmap.size() * sizeof(int32_t));
-    const size_t cap = (size_t)entries + 16;  // one quad behind the image: clamped reads of lanes beyond the end
-    ctx->dev_malloc(&op->d_tl_val, cap * sizeof(T), "tiled image (values)");
-    ctx->dev_malloc((void**)&op->d_tl_idx, cap * sizeof(uint32_t), "tiled image (local indices)");
-    ctx->dev_malloc((void**)&op->d_tl_rexp, std::max<size_t>((size_t)nr, 8) * sizeof(int16_t), "row exponents");
-    // [0, parts): what the kernel folds; [parts, 2 parts): the own shard's partial maxima; [2 parts]: the own shard's maximum
-    ctx->dev_malloc((void**)&op->d_tl_xmax, (size_t)(2 * kTlXmaxParts + 8) * sizeof(double), "x maxima");
-    LL_HIP(hipMemsetAsync(op->d_tl_val, 0, cap * sizeof(T), s));  // padding entries: value 0, local indices 0
-    LL_HIP(hipMemsetAsync(op->d_tl_idx, 0, cap * sizeof(uint32_t), s));
-    LL_HIP(hipMemsetAsync(op->d_tl_xmax, 0, (size_t)(2 * kTlXmaxParts + 8) * sizeof(double), s));
-    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, (nr + 255) / 256));
-    if (op->rp64)
-      hipLaunchKernelGGL((pb_rowexp_kernel<T, int64_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int64_t*)op->d_row_ptr,
-                         (const T*)op->d_val, op->d_tl_rexp);
-    else
-      hipLaunchKernelGGL((pb_rowexp_kernel<T, int32_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int32_t*)op->d_row_ptr,
-                         (const T*)op->d_val, op->d_tl_rexp);
-    LL_HIP(hipGetLastError());
-    if (op->rp64)
-      hipLaunchKernelGGL((pb_scatter_kernel<T, int64_t, true>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
-                         (int)rb_rows, (long long)nr, (const int64_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, d_segq,
-                         nullptr, (T*)op->d_tl_val, reinterpret_cast<uint16_t*>(op->d_tl_idx), nullptr, op->d_tl_rexp);
-    else
-      hipLaunchKernelGGL((pb_scatter_kernel<T, int32_t, true>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
-                         (int)rb_rows, (long long)nr, (const int32_t*)op->d_row_ptr, op->d_col, (const T*)op->d_val, d_segq,
-                         nullptr, (T*)op->d_tl_val, reinterpret_cast<uint16_t*>(op->d_tl_idx), nullptr, op->d_tl_rexp);
-    LL_HIP(hipGetLastError());
-    LL_HIP(hipStreamSynchronize(s));  // the host tables above go out of scope
-  } catch (...) {
-    tl_release(op);
-    throw;
-  }
+  DevArray<int64_t> d_segq;
+  up(im.first, tfirst);
+  up(im.col, tcol);
+  up(im.quad, tquad);
+  up(d_segq, segq);
+  if (!rbmap.empty()) up(im.rbmap, rbmap);
+  const size_t cap = (size_t)entries + 16;  // one quad behind the image: clamped reads of lanes beyond the end
+  im.val = ctx->dev_alloc<T>(cap, "tiled image (values)");
+  im.idx = ctx->dev_alloc<uint32_t>(cap, "tiled image (local indices)");
+  im.rexp = ctx->dev_alloc<int16_t>(std::max<size_t>((size_t)nr, 8), "row exponents");
+  // [0, parts): what the kernel folds; [parts, 2 parts): the own shard's partial maxima; [2 parts]: the own shard's maximum
+  im.xmax = ctx->dev_alloc<double>((size_t)(2 * kTlXmaxParts + 8), "x maxima");
+  LL_HIP(hipMemsetAsync(im.val.get(), 0, cap * sizeof(T), s));  // padding entries: value 0, local indices 0
+  LL_HIP(hipMemsetAsync(im.idx.get(), 0, cap * sizeof(uint32_t), s));
+  LL_HIP(hipMemsetAsync(im.xmax.get(), 0, (size_t)(2 * kTlXmaxParts + 8) * sizeof(double), s));
+  const int g = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxGrid, (nr + 255) / 256));
+  if (a.rp64)
+    hipLaunchKernelGGL((pb_rowexp_kernel<T, int64_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int64_t*)a.row_ptr.get(),
+                       (const T*)a.val.get(), im.rexp.get());
+  else
+    hipLaunchKernelGGL((pb_rowexp_kernel<T, int32_t>), dim3(g), dim3(256), 0, s, (long long)nr, (const int32_t*)a.row_ptr.get(),
+                       (const T*)a.val.get(), im.rexp.get());
+  LL_HIP(hipGetLastError());
+  if (a.rp64)
+    hipLaunchKernelGGL((pb_scatter_kernel<T, int64_t, true>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
+                       (int)rb_rows, (long long)nr, (const int64_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), d_segq.get(),
+                       nullptr, (T*)im.val.get(), reinterpret_cast<uint16_t*>(im.idx.get()), nullptr, im.rexp.get());
+  else
+    hipLaunchKernelGGL((pb_scatter_kernel<T, int32_t, true>), dim3((int)nrb), dim3(64), hist_bytes, s, m, (int)ncb, (int)nrb,
+                       (int)rb_rows, (long long)nr, (const int32_t*)a.row_ptr.get(), a.col.get(), (const T*)a.val.get(), d_segq.get(),
+                       nullptr, (T*)im.val.get(), reinterpret_cast<uint16_t*>(im.idx.get()), nullptr, im.rexp.get());
+  LL_HIP(hipGetLastError());
+  LL_HIP(hipStreamSynchronize(s));  // the host tables above go out of scope
+  op->tl = std::move(im);
   return true;
 }
 
@@ -1764,23 +1736,6 @@ template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hip
                      (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? 1 : 0);
   LL_HIP(hipGetLastError());
   return g;
-}
-
-void tl_release(ll_operator* op) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  drop(op->d_tl_first);
-  drop(op->d_tl_col);
-  drop(op->d_tl_quad);
-  drop(op->d_tl_val);
-  drop(op->d_tl_idx);
-  drop(op->d_tl_rexp);
-  drop(op->d_tl_xmax);
-  drop(op->d_tl_rbmap);
-  op->tl_nrb = 0;
-  op->tl_n_interior = 0;
 }
 
 #define LL_INST_PB(T)                                                                                              \

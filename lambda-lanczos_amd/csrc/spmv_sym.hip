@@ -221,9 +221,9 @@ template <typename T> int sym_rows_for(int64_t n, int64_t halo) {
   return 0;
 }
 
-template <typename T> void sym_build(ll_operator* op, const int64_t* rp, const int32_t* ci, const T* va) {
-  ll_context* ctx = op->ctx;
-  const int64_t n = op->n, R = op->sym_rb_rows, H = op->sym_halo;
+template <typename T> void sym_build(const ll_operator& op, SymImage& im, const int64_t* rp, const int32_t* ci, const T* va) {
+  ll_context* ctx = op.ctx;
+  const int64_t n = op.n, R = im.rb_rows, H = im.halo;
   LL_REQUIRE(R > 0 && R + 2 * H <= kSymMaxWindow, "internal: one-triangle image geometry");
   const int64_t nrb = (n + R - 1) / R;
   LL_REQUIRE(nrb < (int64_t)0x7fffffff, "too many row blocks");
@@ -287,66 +287,45 @@ template <typename T> void sym_build(ll_operator* op, const int64_t* rp, const i
       }
     }
   }
-  ctx->dev_malloc((void**)&op->d_sym_qptr, qptr.size() * sizeof(int64_t), "one-triangle image: row block offsets");
-  ctx->dev_malloc(&op->d_sym_val, hv.size() * sizeof(T), "one-triangle image: values");
-  ctx->dev_malloc((void**)&op->d_sym_idx, hi.size() * sizeof(uint32_t), "one-triangle image: indices");
-  ctx->dev_malloc((void**)&op->d_sym_fptr, fptr.size() * sizeof(int64_t), "one-triangle image: far entry offsets");
-  ctx->dev_malloc(&op->d_sym_fval, fv.size() * sizeof(T), "one-triangle image: far values");
-  ctx->dev_malloc((void**)&op->d_sym_fdst, fd.size() * sizeof(uint32_t), "one-triangle image: far destinations");
-  ctx->dev_malloc((void**)&op->d_sym_fsrc, fs.size() * sizeof(int32_t), "one-triangle image: far sources");
-  ctx->dev_malloc(&op->d_sym_diag, hd.size() * sizeof(T), "one-triangle image: diagonal");
-  LL_HIP(hipMemcpy(op->d_sym_diag, hd.data(), hd.size() * sizeof(T), hipMemcpyHostToDevice));
-  ctx->dev_malloc((void**)&op->d_sym_rexp, (size_t)std::max<int64_t>(n, 8) * sizeof(int16_t), "one-triangle image: row exponents");
-  ctx->dev_malloc((void**)&op->d_sym_xmax, (size_t)kXmaxParts * sizeof(double), "one-triangle image: maxima of |x|");
-  LL_HIP(hipMemcpy(op->d_sym_qptr, qptr.data(), qptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_val, hv.data(), hv.size() * sizeof(T), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_idx, hi.data(), hi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_fptr, fptr.data(), fptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_fval, fv.data(), fv.size() * sizeof(T), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_fdst, fd.data(), fd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  LL_HIP(hipMemcpy(op->d_sym_fsrc, fs.data(), fs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  op->sym_nrb = (int)nrb;
+  auto up = [&](auto& dst, const auto& v, const char* what) {
+    using E = typename std::decay_t<decltype(v)>::value_type;
+    dst = ctx->dev_alloc<E>(v.size(), what);
+    LL_HIP(hipMemcpy(dst.get(), v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice));
+  };
+  up(im.qptr, qptr, "one-triangle image: row block offsets");
+  up(im.val, hv, "one-triangle image: values");
+  up(im.idx, hi, "one-triangle image: indices");
+  up(im.fptr, fptr, "one-triangle image: far entry offsets");
+  up(im.fval, fv, "one-triangle image: far values");
+  up(im.fdst, fd, "one-triangle image: far destinations");
+  up(im.fsrc, fs, "one-triangle image: far sources");
+  up(im.diag, hd, "one-triangle image: diagonal");
+  im.rexp = ctx->dev_alloc<int16_t>((size_t)std::max<int64_t>(n, 8), "one-triangle image: row exponents");
+  im.xmax = ctx->dev_alloc<double>((size_t)kXmaxParts, "one-triangle image: maxima of |x|");
+  im.nrb = (int)nrb;
 }
 
 template <typename T>
 int launch_spmv_sym(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                     const double* xnorm2) {
-  if (op.sym_nrb <= 0) return 0;
+  if (op.sym.nrb <= 0) return 0;
   sym_opt_in_lds<T>();
-  const int nx = launch_x_max<T>(op.n, x, op.d_sym_xmax, s);
+  const int nx = launch_x_max<T>(op.n, x, op.sym.xmax.get(), s);
   // (the kernel that publishes an iteration's scalars may complete that iteration's event itself: ll_context::stop_next)
   hipEvent_t stop = op.ctx->stop_next;
   op.ctx->stop_next = nullptr;
-  LL_LAUNCH_STOP(stop, (sym_spmv_kernel<T>), dim3(op.sym_nrb), dim3(kPbThreads), sym_lds_bytes<T>(op.sym_rb_rows, op.sym_halo), s,
-                 op.sym_rb_rows, op.sym_halo, op.n, (const int64_t*)op.d_sym_qptr, (const T*)op.d_sym_val,
-                 (const uint4*)op.d_sym_idx, (const int16_t*)op.d_sym_rexp, (const double*)op.d_sym_xmax, nx, x, y, offset,
-                 dot_partials, xnorm2, (const int64_t*)op.d_sym_fptr, (const T*)op.d_sym_fval, (const uint32_t*)op.d_sym_fdst,
-                 (const int32_t*)op.d_sym_fsrc, (const T*)op.d_sym_diag);
+  LL_LAUNCH_STOP(stop, (sym_spmv_kernel<T>), dim3(op.sym.nrb), dim3(kPbThreads), sym_lds_bytes<T>(op.sym.rb_rows, op.sym.halo), s,
+                 op.sym.rb_rows, op.sym.halo, op.n, (const int64_t*)op.sym.qptr.get(), (const T*)op.sym.val.get(),
+                 (const uint4*)op.sym.idx.get(), (const int16_t*)op.sym.rexp.get(), (const double*)op.sym.xmax.get(), nx, x, y, offset,
+                 dot_partials, xnorm2, (const int64_t*)op.sym.fptr.get(), (const T*)op.sym.fval.get(), (const uint32_t*)op.sym.fdst.get(),
+                 (const int32_t*)op.sym.fsrc.get(), (const T*)op.sym.diag.get());
   LL_HIP(hipGetLastError());
-  return op.sym_nrb;
-}
-
-void sym_release(ll_operator* op) {
-  auto drop = [](auto*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-  };
-  drop(op->d_sym_qptr);
-  drop(op->d_sym_val);
-  drop(op->d_sym_idx);
-  drop(op->d_sym_rexp);
-  drop(op->d_sym_xmax);
-  drop(op->d_sym_fptr);
-  drop(op->d_sym_fval);
-  drop(op->d_sym_fdst);
-  drop(op->d_sym_fsrc);
-  drop(op->d_sym_diag);
-  op->sym_nrb = 0;
+  return op.sym.nrb;
 }
 
 #define LL_INST_SYM(T)                                                                                               \
   template int sym_rows_for<T>(int64_t, int64_t);                                                                   \
-  template void sym_build<T>(ll_operator*, const int64_t*, const int32_t*, const T*);                                \
+  template void sym_build<T>(const ll_operator&, SymImage&, const int64_t*, const int32_t*, const T*);              \
   template int launch_spmv_sym<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const double*);
 LL_INST_SYM(double) LL_INST_SYM(zc) LL_INST_SYM(float) LL_INST_SYM(cf)
 

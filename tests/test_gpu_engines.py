@@ -528,7 +528,8 @@ def test_context_on_a_torch_stream_with_torch_memory():
 
 def test_no_device_memory_growth_over_many_runs():
     """Operators, engines and contexts give their device memory back: create/run/destroy cycles (CSR with both SpMV
-    images, lattice, dense; eigen solver with restart passes, Exponentiator) leave the free device memory where it was
+    images, lattice, dense, one-triangle, every image of a keep-both operator; eigen solver with restart passes, Exponentiator)
+    leave the free device memory where it was
     (40 cycles here; 150 were run once by hand)."""
     import ctypes as C
 
@@ -544,6 +545,17 @@ def test_no_device_memory_growth_over_many_runs():
     tcsr = G.torus_np(40)
     tin = G.start_vector(1600, 1, np.complex128)
     dense = np.diag(np.arange(1.0, 301.0)) + 0.01
+    band = G.randsym_np(20000, band=500)
+    rows = np.repeat(np.arange(20000, dtype=np.int64), np.diff(band[0]))
+    upper = band[1] >= rows   # the upper triangle of the banded matrix (one-triangle operator)
+    tri = (np.concatenate([[0], np.cumsum(np.bincount(rows[upper], minlength=20000))]).astype(np.int64),
+           np.ascontiguousarray(band[1][upper]), np.ascontiguousarray(band[2][upper]))
+
+    def short_run(op):
+        e = L.LambdaLanczos(op, 20000, True, 1)
+        e.max_iteration = 30
+        e.init_vector = fixed_init(init)
+        e.run()
 
     def cycle():
         c = L.Context(0)
@@ -562,6 +574,16 @@ def test_no_device_memory_growth_over_many_runs():
         dn = L.DenseOperator(c, dense)
         L.LambdaLanczos(dn, 300, True, 1).run()
         dn.close()
+        sym = L.CsrOperator.from_triangle(c, *tri, uplo="U", kernel=L.capi.SPMV_SYM)
+        short_run(sym)
+        sym.close()
+        c.set_tuning("spmv_keep_both", 1)   # LL_SPMV_KEEP_BOTH=1: every image stays (tiled forced on this small matrix)
+        c.set_tuning("tl_force", 1)
+        kb = L.CsrOperator(c, *band)
+        for kind in (L.capi.SPMV_PB, L.capi.SPMV_TILED, L.capi.SPMV_CSR_STREAM):
+            kb.select_spmv(kind)
+            short_run(kb)
+        kb.close()
         c.close()
 
     for _ in range(5):   # warm up allocator pools, code objects, RCCL-free paths
