@@ -9,7 +9,8 @@
  *     _s  = float                   (reference T = float)
  *     _c  = float complex           (reference T = std::complex<float>, interleaved re,im)
  *   (the _s/_c declarations are at the end of this file: same arguments as _d/_z with float data pointers; every
- *   scalar — offsets, eps, alpha, eigenvalues, norms — stays double, and all reductions are accumulated in double,
+ *   scalar — offsets, eps, alpha, eigenvalues, norms — is passed as double (ll_spmv_s/_c apply the offset rounded to float,
+ *   see ACCURACY below), and all reductions are accumulated in double,
  *   which is at least the accuracy of the reference's float arithmetic.  long double has no device counterpart.)
  * and the C++ facade include/lambda_lanczos_hip/{lambda_lanczos,exponentiator}.hpp re-creates
  * lambda_lanczos::LambdaLanczos<T> / Exponentiator<T> on top by tag dispatch.
@@ -221,7 +222,8 @@ int ll_op_create_dense_z(ll_context* ctx, int64_t n_rows_local, int64_t n_cols, 
  *     Sharded contexts: flattened sites [row_begin, row_begin + n_local) per ll_partition; the exchange step is a
  *     HALO exchange of one lattice hyperplane (n / dims[0] sites) with the two neighbouring ranks instead of the
  *     all-gather of x; every shard must hold at least one hyperplane.
- *     hop_im must be 0 for the real types.  onsite_host_local: n_local real values, NULL = none. */
+ *     hop_im must be 0 for the real types.  onsite_host_local: n_local real values, NULL = none; they are kept in the real
+ *     type of T (rounded to float for _s / _c) and added to diag in double. */
 typedef struct ll_stencil_desc {
   int32_t ndim;        /* 1..3 */
   int32_t periodic[3];
@@ -267,8 +269,10 @@ int ll_op_create_stencil_z(ll_context* ctx, const ll_stencil_desc* desc, int64_t
  *     |y_i - (A x)_i| <= ~nnz_i * eps * sum_j |a_ij| |x_j|             (COMPONENT-wise, like a plain fp64 row loop).
  *   LL_SPMV_PB and LL_SPMV_TILED in their default form (LL_PB_PHASE2=fixed) round every product to a per-row fixed-point grid and add
  *   64-bit integers (order-independent: same bits for every launch, block geometry and partition of the matrix):
- *     |y_i - (A x)_i| <= eps * sum_j |a_ij| |x_j|  +  nnz_i * 2^-60 * (sum_j |a_ij|) * max_k |x_k|   (NORM-wise)
- *   where max_k runs over the WHOLE input vector.  For vectors whose entries are of comparable size (Lanczos vectors of
+ *     |y_i - (A x)_i| <= 2 eps * sum_j |a_ij| |x_j|  +  nnz_i * 2^-60 * (sum_j |a_ij|) * max_k |x_k|   (NORM-wise)
+ *   where max_k runs over the WHOLE input vector and |.| of a complex number is |re| + |im|.  The factor 2 counts the roundings
+ *   outside the grid: each product rounded to T (a complex product: up to eps (|ar xr| + |ai xi|) per part), the integer sum
+ *   converted back (eps/2), and the first diagonal entry's product, kept outside the streams and added in floating point (eps/2).  For vectors whose entries are of comparable size (Lanczos vectors of
  *   extended states, random vectors) the second term is 2^7 or more times below the first.  For a vector with a huge dynamic
  *   range (x = e_0, a strongly localised state, an entry of 1e20 next to O(1) entries) rows whose terms are all far
  *   below (sum_j |a_ij|) max|x| lose RELATIVE accuracy: their absolute error stays below nnz_i 2^-60 ||A||_inf ||x||_inf, which
@@ -277,7 +281,15 @@ int ll_op_create_stencil_z(ll_context* ctx, const ll_stencil_desc* desc, int64_t
  *   Callers who need that on such vectors ask for LL_ACCURACY_COMPONENTWISE (ll_csr_options.accuracy / ll_op_set_accuracy below;
  *   3-5 % slower); the environment's LL_PB_PHASE2=ordered or LL_SPMV_KERNEL=csr does the same for every operator of a context.
  *   Rows that meet an Inf / NaN are reported as NaN.  float / complex float storage: the product a_ij x_j is rounded to
- *   the storage type once (exactly what a float multiply gives) before it is summed in fixed point / double. */
+ *   the storage type once (exactly what a float multiply gives; complex float: each of the four real products and their
+ *   difference / sum rounded to float) before it is summed in fixed point / double.  Exceptions, which form every product
+ *   EXACTLY in double (fma of the widened operands): CSR-stream's rows of more than 1024 entries (one workgroup strides over
+ *   the row), the dense operator (4) and the lattice operator (5).  The row sum is then rounded to T once.
+ *   The offset (a2) and alpha (a3) of ll_spmv_*: y_i = fl_T(row sum) + fl_T(offset * x_i), added in T — for float / complex
+ *   float the offset is rounded to float first (an offset such as 0.1 is not exact there) and the product and the addition
+ *   round in float; alpha = Re<x, y> of the RETURNED (already rounded) y, accumulated in double, so that
+ *   |alpha - exact Re<x, y>| <= ~n eps_double sum_i |x_i||y_i| in every type (tests/test_gpu_accuracy_contracts.py checks
+ *   these against an exact host reference, tests/exact_ref.py). */
 enum { LL_SPMV_CSR_STREAM = 0, LL_SPMV_PB = 1, LL_SPMV_TILED = 2, LL_SPMV_SYM = 3 /* ll_op_create_csr_sym_* only, see below */ };
 /* The ACCURACY CLASS above as a per-operator choice of the caller (who knows whether the vectors are localised), not of
  * the environment:
@@ -399,6 +411,7 @@ int ll_orth_block_d(ll_context* ctx, int64_t n_local, int64_t nb, const double* 
 int ll_orth_block_z(ll_context* ctx, int64_t n_local, int64_t nb, const void* basis_dev, int64_t ld, void* w_dev,
                     int mode, double* norm_host, double* h_host);
 /* a9+a10: out_r = sum_{k=m-1..0} coeff[r*m + k] * basis_k for r < nout in ONE pass over the basis
+ * (the sums are carried in double / complex double for every type and rounded to T once; the _s / _c coefficients stay double)
  * (LL:51-57: Ritz vectors, real coefficients; EX:166-170: exp(aA)v, coefficients of type T).
  * coeff_host: nout*m values of type T (re,im pairs for _z).  out_dev: nout vectors, leading dimension ld_out. */
 int ll_gemv_basis_d(ll_context* ctx, int64_t n_local, int64_t m, const double* basis_dev, int64_t ld, int64_t nout,

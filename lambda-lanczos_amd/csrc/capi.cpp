@@ -1558,8 +1558,8 @@ void orth_impl(ll_context* ctx, int64_t n, int64_t nb, const T* basis, int64_t l
   if (norm_out) *norm_out = std::sqrt(ctx->pinned.get()[9]);
   if (d_htot) LL_HIP(hipMemcpy(h_out, d_htot, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToHost));
 }
-template <typename T>
-void gemv_impl(ll_context* ctx, int64_t n, int64_t m, const T* basis, int64_t ld, int64_t nout, const T* coeff,
+template <typename T, typename C>
+void gemv_impl(ll_context* ctx, int64_t n, int64_t m, const T* basis, int64_t ld, int64_t nout, const C* coeff,
                T* out, int64_t ld_out) {
   use(ctx);
   LL_REQUIRE(n >= 0 && m >= 1 && nout >= 1 && basis && coeff && out && ld >= n && ld_out >= n, "bad argument");
@@ -1567,7 +1567,8 @@ void gemv_impl(ll_context* ctx, int64_t n, int64_t m, const T* basis, int64_t ld
   RunList<T> runs;
   runs.ld = ld;
   runs.add(basis, m);
-  E.gemv(runs, m, (int)nout, coeff, out, ld_out);
+  if constexpr (std::is_same<C, T>::value) E.gemv(runs, m, (int)nout, coeff, out, ld_out);
+  else E.gemv_acc(runs, m, (int)nout, coeff, out, ld_out);
 }
 }  // namespace
 }  // extern "C++"
@@ -1904,21 +1905,13 @@ int ll_orth_block_s(ll_context* ctx, int64_t n, int64_t nb, const float* basis, 
 }
 int ll_gemv_basis_c(ll_context* ctx, int64_t n, int64_t m, const void* basis, int64_t ld, int64_t nout,
                     const double* coeff, void* out, int64_t ld_out) {
-  return guarded([&] {  // coefficients arrive as doubles (re,im pairs) like every scalar of the _s/_c API
-    LL_REQUIRE(coeff != nullptr && m >= 1 && nout >= 1, "bad argument");
-    std::vector<cf> cc((size_t)(nout * m));
-    for (size_t i = 0; i < cc.size(); ++i) cc[i] = cf{(float)coeff[2 * i], (float)coeff[2 * i + 1]};
-    gemv_impl<cf>(ctx, n, m, (const cf*)basis, ld, nout, cc.data(), (cf*)out, ld_out);
+  return guarded([&] {  // coefficients arrive as doubles (re,im pairs) like every scalar of the _s/_c API and stay double
+    gemv_impl<cf, zc>(ctx, n, m, (const cf*)basis, ld, nout, (const zc*)coeff, (cf*)out, ld_out);
   });
 }
 int ll_gemv_basis_s(ll_context* ctx, int64_t n, int64_t m, const float* basis, int64_t ld, int64_t nout,
                     const double* coeff, float* out, int64_t ld_out) {
-  return guarded([&] {
-    LL_REQUIRE(coeff != nullptr && m >= 1 && nout >= 1, "bad argument");
-    std::vector<float> cc((size_t)(nout * m));
-    for (size_t i = 0; i < cc.size(); ++i) cc[i] = (float)coeff[i];
-    gemv_impl<float>(ctx, n, m, (const float*)basis, ld, nout, cc.data(), (float*)out, ld_out);
-  });
+  return guarded([&] { gemv_impl<float, double>(ctx, n, m, (const float*)basis, ld, nout, coeff, (float*)out, ld_out); });
 }
 int ll_lanczos_run_c(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigvals, void* eigvecs,
                      int64_t* n_found, int64_t* iter_counts, int64_t iter_cap, double* alpha_out, double* beta_out,

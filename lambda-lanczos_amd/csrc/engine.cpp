@@ -590,13 +590,29 @@ template <typename T> double Engine<T>::second_pass(T* u, const RunList<T>& runs
 
 template <typename T>
 void Engine<T>::gemv(const RunList<T>& basis, int64_t m, int nout, const T* coeff_host, T* out, int64_t ld_out) {
+  typedef acc_t<T> A;
+  std::vector<A> wide((size_t)nout * m);
+  for (size_t i = 0; i < wide.size(); ++i) {  // exact: every T is representable in acc_t<T>
+    if constexpr (std::is_same<A, T>::value) wide[i] = coeff_host[i];
+    else if constexpr (scalar_traits<T>::is_complex) wide[i] = A{(double)coeff_host[i].re, (double)coeff_host[i].im};
+    else wide[i] = (double)coeff_host[i];
+  }
+  gemv_acc(basis, m, nout, wide.data(), out, ld_out);
+}
+template <typename T>
+void Engine<T>::gemv_acc(const RunList<T>& basis, int64_t m, int nout, const acc_t<T>* coeff_host, T* out, int64_t ld_out) {
   TraceRange trace("ll::gemv_basis (Ritz vectors / exp output)");
+  typedef acc_t<T> A;
   const std::vector<BasisSegs<T>> groups = basis.groups(512);
-  ctx->ensure_coeff((size_t)nout * m * sizeof(T));
-  LL_HIP(hipMemcpyAsync(ctx->coeff.get(), coeff_host, (size_t)nout * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  launch_gemv_basis<T>(n_local, m, groups.data(), (int)groups.size(), nout, (const T*)ctx->coeff.get(), out, ld_out,
-                       ctx->stream);
-  LL_HIP(hipStreamSynchronize(ctx->stream));  // coeff_host may go away; d_coeff is reused
+  ctx->ensure_coeff((size_t)nout * m * sizeof(A));
+  LL_HIP(hipMemcpyAsync(ctx->coeff.get(), coeff_host, (size_t)nout * m * sizeof(A), hipMemcpyHostToDevice, ctx->stream));
+  // float types over more than one basis group: the partial sums stay in double between the launches
+  DevArray<double> scratch;
+  if (!std::is_same<A, T>::value && groups.size() > 1)
+    scratch = ctx->dev_alloc<double>((size_t)nout * n_local * scalar_traits<T>::reals, "gemv partial sums");
+  launch_gemv_basis<T>(n_local, m, groups.data(), (int)groups.size(), nout, (const A*)ctx->coeff.get(), out, ld_out,
+                       reinterpret_cast<A*>(scratch.get()), ctx->stream);
+  LL_HIP(hipStreamSynchronize(ctx->stream));  // coeff_host may go away; d_coeff is reused; scratch is released after this
 }
 
 // ================================================================= helpers shared by the loops

@@ -137,6 +137,8 @@ template <typename T> struct Engine {
   void fetch(const double* d, double* host, size_t count);
   // out_r = sum_k coeff[r*m+k] u_k  (coeff host, type T)
   void gemv(const RunList<T>& basis, int64_t m, int nout, const T* coeff_host, T* out, int64_t ld_out);
+  // the same with coefficients in acc_t<T> (the float entry points take them as doubles, like every scalar)
+  void gemv_acc(const RunList<T>& basis, int64_t m, int nout, const acc_t<T>* coeff_host, T* out, int64_t ld_out);
 };
 
 template <typename T> struct host_scalar;

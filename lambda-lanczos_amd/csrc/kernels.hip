@@ -3206,14 +3206,39 @@ LL_INST_STENCIL(double) LL_INST_STENCIL(zc) LL_INST_STENCIL(float) LL_INST_STENC
 // ================================================================= a9/a10: tall-skinny GEMV over the basis
 // out_r = sum_k coeff[r*m + k] u_k for r < NOUT in one pass over the basis: every basis strip is read once and
 // feeds all NOUT accumulators (the reference re-reads the basis per root, LL:51-57).  Vectors are visited in
-// DESCENDING k like the reference (LL:53).  coeff (type T) is staged in LDS.  accumulate: start from out.
+// DESCENDING k like the reference (LL:53).  The coefficients and the accumulators are acc_t<T> (double / complex double
+// for every type: the float sums are carried in double like every reduction of the library), the coefficients staged in
+// LDS.  part (ld_part): the partial sums of the launches over the other basis groups — load_part: start from part;
+// out == nullptr: leave the sum in part for the next launch; otherwise round it to T once into out.
+template <typename T> __device__ __forceinline__ void load_acc_strip(const acc_t<T>* __restrict__ p, int64_t base, int64_t n,
+                                                                     acc_t<T> (&r)[strip<T>::EPT]) {
+  if constexpr (std::is_same<acc_t<T>, T>::value) {
+    load_strip<T>(p, base, n, r);
+  } else {
+    const int64_t i0 = base + (int64_t)threadIdx.x * strip<T>::EPT;
+#pragma unroll
+    for (int e = 0; e < strip<T>::EPT; ++e) r[e] = (i0 + e < n) ? p[i0 + e] : zero<acc_t<T>>();
+  }
+}
+template <typename T> __device__ __forceinline__ void store_acc_strip(acc_t<T>* __restrict__ p, int64_t base, int64_t n,
+                                                                      const acc_t<T> (&r)[strip<T>::EPT]) {
+  if constexpr (std::is_same<acc_t<T>, T>::value) {
+    store_strip<T>(p, base, n, r);
+  } else {
+    const int64_t i0 = base + (int64_t)threadIdx.x * strip<T>::EPT;
+#pragma unroll
+    for (int e = 0; e < strip<T>::EPT; ++e)
+      if (i0 + e < n) p[i0 + e] = r[e];
+  }
+}
 template <typename T, int NOUT>
 __global__ __launch_bounds__(kBlock) void gemv_basis_kernel(int64_t n, BasisSegs<T> segs, int kofs, int m_total,
-                                                            const T* __restrict__ coeff, T* __restrict__ out,
-                                                            int64_t ld_out, int accumulate) {
+                                                            const acc_t<T>* __restrict__ coeff, acc_t<T>* part, int64_t ld_part,
+                                                            int load_part, T* out, int64_t ld_out) {
+  typedef acc_t<T> A;
   constexpr int EPT = strip<T>::EPT;
   extern __shared__ double lds_raw[];
-  T* cs = reinterpret_cast<T*>(lds_raw);  // [NOUT][nb]
+  A* cs = reinterpret_cast<A*>(lds_raw);  // [NOUT][nb]
   int nb = 0;
   for (int i = 0; i < segs.nseg; ++i) nb += segs.count[i];
   for (int i = threadIdx.x; i < NOUT * nb; i += kBlock) {
@@ -3224,13 +3249,13 @@ __global__ __launch_bounds__(kBlock) void gemv_basis_kernel(int64_t n, BasisSegs
   const int64_t nstrips = (n + strip<T>::ELEMS - 1) / strip<T>::ELEMS;
   for (int64_t sidx = blockIdx.x; sidx < nstrips; sidx += gridDim.x) {
     const int64_t base = sidx * strip<T>::ELEMS;
-    T acc[NOUT][EPT];
+    A acc[NOUT][EPT];
 #pragma unroll
     for (int r = 0; r < NOUT; ++r) {
-      if (accumulate) load_strip<T>(out + (int64_t)r * ld_out, base, n, acc[r]);
+      if (load_part) load_acc_strip<T>(part + (int64_t)r * ld_part, base, n, acc[r]);
       else {
 #pragma unroll
-        for (int e = 0; e < EPT; ++e) acc[r][e] = zero<T>();
+        for (int e = 0; e < EPT; ++e) acc[r][e] = zero<A>();
       }
     }
     int col = nb;
@@ -3242,58 +3267,72 @@ __global__ __launch_bounds__(kBlock) void gemv_basis_kernel(int64_t n, BasisSegs
         load_strip<T>(ub + (int64_t)j * segs.ld, base, n, ur);
 #pragma unroll
         for (int r = 0; r < NOUT; ++r) {
-          const T c = cs[r * nb + col];
+          const A c = cs[r * nb + col];
 #pragma unroll
-          for (int e = 0; e < EPT; ++e) fma_acc(acc[r][e], c, ur[e]);
+          for (int e = 0; e < EPT; ++e) fma_acc(acc[r][e], c, to_acc(ur[e]));
         }
       }
     }
 #pragma unroll
-    for (int r = 0; r < NOUT; ++r) store_strip<T>(out + (int64_t)r * ld_out, base, n, acc[r]);
+    for (int r = 0; r < NOUT; ++r) {
+      if (out == nullptr) {
+        store_acc_strip<T>(part + (int64_t)r * ld_part, base, n, acc[r]);
+      } else {
+        T o[EPT];
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) o[e] = narrow<T>(acc[r][e]);
+        store_strip<T>(out + (int64_t)r * ld_out, base, n, o);
+      }
+    }
   }
 }
 
 template <typename T, int NOUT>
-static void gemv_launch_n(int64_t n, const BasisSegs<T>& segs, int kofs, int m_total, const T* coeff, T* out,
-                          int64_t ld_out, int accumulate, hipStream_t s) {
+static void gemv_launch_n(int64_t n, const BasisSegs<T>& segs, int kofs, int m_total, const acc_t<T>* coeff, acc_t<T>* part,
+                          int64_t ld_part, int load_part, T* out, int64_t ld_out, hipStream_t s) {
   int nb = 0;
   for (int i = 0; i < segs.nseg; ++i) nb += segs.count[i];
-  const size_t lds_bytes = (size_t)NOUT * nb * sizeof(T);
+  const size_t lds_bytes = (size_t)NOUT * nb * sizeof(acc_t<T>);
   hipLaunchKernelGGL((gemv_basis_kernel<T, NOUT>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), lds_bytes, s,
-                     n, segs, kofs, m_total, coeff, out, ld_out, accumulate);
+                     n, segs, kofs, m_total, coeff, part, ld_part, load_part, out, ld_out);
   LL_HIP(hipGetLastError());
 }
 
 // segs[0..nlaunch) cover vectors 0..m_total-1 in order; launches run from the last group to the first so that the
-// overall accumulation order is k = m-1 .. 0.
+// overall accumulation order is k = m-1 .. 0.  Between launches the partial sums stay in acc_t<T>: in out itself where that is
+// the same type (double, complex double), in scratch (nout x n values of acc_t<T>, needed when nlaunch > 1) for float types.
 template <typename T>
-void launch_gemv_basis(int64_t n, int64_t m_total, const BasisSegs<T>* segs, int nlaunch, int nout, const T* coeff,
-                       T* out, int64_t ld_out, hipStream_t s) {
+void launch_gemv_basis(int64_t n, int64_t m_total, const BasisSegs<T>* segs, int nlaunch, int nout, const acc_t<T>* coeff,
+                       T* out, int64_t ld_out, acc_t<T>* scratch, hipStream_t s) {
   std::vector<int> kofs(nlaunch);
   int k = 0;
   for (int i = 0; i < nlaunch; ++i) {
     kofs[i] = k;
     for (int g = 0; g < segs[i].nseg; ++g) k += segs[i].count[g];
   }
+  constexpr bool same = std::is_same<acc_t<T>, T>::value;
   for (int r0 = 0; r0 < nout; r0 += 4) {  // up to 4 outputs per pass (register budget: 4*EPT accumulators)
     const int nr = nout - r0 < 4 ? nout - r0 : 4;
     for (int i = nlaunch - 1; i >= 0; --i) {
-      const int acc = (i != nlaunch - 1);
-      const T* c = coeff + (size_t)r0 * m_total;
+      const int load = (i != nlaunch - 1);
+      const acc_t<T>* c = coeff + (size_t)r0 * m_total;
       T* o = out + (int64_t)r0 * ld_out;
+      acc_t<T>* part = same ? reinterpret_cast<acc_t<T>*>(o) : (scratch ? scratch + (int64_t)r0 * n : nullptr);
+      const int64_t ld_part = same ? ld_out : n;
+      T* dst = (same || i == 0) ? o : nullptr;  // float types: the last launch rounds once into out
+      LL_REQUIRE(part != nullptr || nlaunch == 1, "gemv_basis: scratch missing");
       switch (nr) {
-        case 1: gemv_launch_n<T, 1>(n, segs[i], kofs[i], (int)m_total, c, o, ld_out, acc, s); break;
-        case 2: gemv_launch_n<T, 2>(n, segs[i], kofs[i], (int)m_total, c, o, ld_out, acc, s); break;
-        case 3: gemv_launch_n<T, 3>(n, segs[i], kofs[i], (int)m_total, c, o, ld_out, acc, s); break;
-        default: gemv_launch_n<T, 4>(n, segs[i], kofs[i], (int)m_total, c, o, ld_out, acc, s); break;
+        case 1: gemv_launch_n<T, 1>(n, segs[i], kofs[i], (int)m_total, c, part, ld_part, load, dst, ld_out, s); break;
+        case 2: gemv_launch_n<T, 2>(n, segs[i], kofs[i], (int)m_total, c, part, ld_part, load, dst, ld_out, s); break;
+        case 3: gemv_launch_n<T, 3>(n, segs[i], kofs[i], (int)m_total, c, part, ld_part, load, dst, ld_out, s); break;
+        default: gemv_launch_n<T, 4>(n, segs[i], kofs[i], (int)m_total, c, part, ld_part, load, dst, ld_out, s); break;
       }
     }
   }
 }
-template void launch_gemv_basis<double>(int64_t, int64_t, const BasisSegs<double>*, int, int, const double*, double*, int64_t, hipStream_t);
-template void launch_gemv_basis<zc>(int64_t, int64_t, const BasisSegs<zc>*, int, int, const zc*, zc*, int64_t, hipStream_t);
-template void launch_gemv_basis<float>(int64_t, int64_t, const BasisSegs<float>*, int, int, const float*, float*, int64_t, hipStream_t);
-template void launch_gemv_basis<cf>(int64_t, int64_t, const BasisSegs<cf>*, int, int, const cf*, cf*, int64_t, hipStream_t);
+#define LL_INST_GEMV(T) \
+  template void launch_gemv_basis<T>(int64_t, int64_t, const BasisSegs<T>*, int, int, const acc_t<T>*, T*, int64_t, acc_t<T>*, hipStream_t);
+LL_INST_GEMV(double) LL_INST_GEMV(zc) LL_INST_GEMV(float) LL_INST_GEMV(cf)
 
 // ================================================================= tiny scalar kernels
 __global__ void accumulate_h_kernel(double* h_acc, const double* h_add, int count, NormRefs pred, int predicated) {

@@ -718,11 +718,12 @@ template <typename T>
 void launch_three_term(int64_t n, T* w, const T* u_prev, const T* u_cur, double beta, double alpha, hipStream_t s);
 // partials of <a,b> (reals per workgroup). Returns grid.
 template <typename T> int launch_dot(int64_t n, const T* a, const T* b, double* partials, hipStream_t s);
-// out_r = sum_{k=m-1..0} coeff[r*m+k] * u_k, r < nout (<= 8); coeff on device, type T. scale (nullable device
-// scalar) multiplies every output.
+// out_r = sum_{k=m-1..0} coeff[r*m+k] * u_k, r < nout; coeff on device, type acc_t<T>; the sums are carried in acc_t<T> and
+// rounded to T once.  scratch: nout * n values of acc_t<T> for the partial sums between launches (float types with nlaunch > 1;
+// nullable otherwise).
 template <typename T>
-void launch_gemv_basis(int64_t n, int64_t m, const BasisSegs<T>* segs, int nlaunch, int nout, const T* coeff, T* out,
-                       int64_t ld_out, hipStream_t s);
+void launch_gemv_basis(int64_t n, int64_t m, const BasisSegs<T>* segs, int nlaunch, int nout, const acc_t<T>* coeff, T* out,
+                       int64_t ld_out, acc_t<T>* scratch, hipStream_t s);
 // small helpers
 // h_acc += h_add when the second pass ran
 void launch_accumulate_h(double* h_acc, const double* h_add, int count, const NormRefs* pred, hipStream_t s);

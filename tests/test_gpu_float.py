@@ -6,9 +6,10 @@ import numpy as np
 import pytest
 
 import cases
+import exact_ref as E
 import lambda_lanczos_amd as L
 from lambda_lanczos_amd import generators as G
-from util import overlap
+from util import check_orth_h, overlap
 
 pytestmark = pytest.mark.gpu
 F32 = float(np.finfo(np.float32).eps)
@@ -40,7 +41,8 @@ def test_spmv_single_precision(ctx, oracle, name, dtype, kind, llenv):
     y_ref = oracle.spmv(widen(csr), x.astype(REAL[np.dtype(dtype)])) - 1.5 * x
     scale = np.max(np.abs(y_ref)) + 1.0
     assert np.max(np.abs(y - y_ref)) <= 40 * F32 * scale
-    assert abs(alpha - np.vdot(x, y_ref).real) <= 40 * F32 * np.sum(np.abs(x) * np.abs(y_ref))
+    # alpha = Re<x, y> of the RETURNED y summed in double (lanczos_hip.h): a double-level bound against the exact dot product
+    assert abs(alpha - E.dot_exact(x, y).real) <= E.dot_bound(x, y)
     op.close()
 
 
@@ -83,6 +85,8 @@ def test_orth_and_gemv_single_precision(ctx, dtype, mode, n, nb, geometry, llenv
     nrm, h = L.orth_block(ctx, bd, nb, ld, wd, n, mode=mode, want_h=True)
     got = wd.get().astype(wide)
     bw = basis.astype(wide)
+    # h against exact projections at the double-level bound (util.check_orth_h; a float-level term only for a second DGKS pass)
+    check_orth_h(ctx, llenv, bd, basis, ld, w, mode, h)
     want = w.astype(wide) - (bw.conj() @ w.astype(wide)) @ bw
     scale = np.linalg.norm(w)
     assert np.linalg.norm(got - want) <= 20 * F32 * scale
@@ -93,6 +97,13 @@ def test_orth_and_gemv_single_precision(ctx, dtype, mode, n, nb, geometry, llenv
     od = ctx.empty((3, ld), dtype)
     L.gemv_basis(ctx, bd, nb, ld, coeff, od, ld, n)
     assert np.max(np.abs(od.get()[:, :n] - coeff @ bw)) <= 20 * F32 * nb
+    # and element-wise: the exact sum (double coefficients) rounded once to float, plus a double-level sum error
+    absum = E.abs1(coeff) @ E.abs1(bw)
+    de = 2 * (2 * nb + 4) * E.EPS_D * absum
+    ex = coeff @ bw
+    errs = E.part_errors(od.get()[:, :n], ex)
+    bounds = (0.5 * F32 * (1 + F32) * (np.abs(ex.real) + de) + de + 1e-38, 0.5 * F32 * (1 + F32) * (np.abs(ex.imag) + de) + de + 1e-38)
+    assert E.within(errs, bounds)[0]
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.complex64])

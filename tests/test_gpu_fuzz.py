@@ -124,6 +124,19 @@ def test_random_exponentiator_matches_oracle(ctx, oracle, seed):
         # outputs are held to the reference's own criterion.
         ov = abs(np.vdot(out, o_out)) / (np.linalg.norm(out) * np.linalg.norm(o_out))
         assert 1 - ov <= 10 * ex.eps
+        # and the 1e-8 parity at EQUAL iteration counts: the side that ran longer is run again, capped at the other's count
+        if it < o_it:
+            o_same, o_same_it, _ = oracle.expo((rp, ci, va), a_coef, inp, full_orthogonalize=ex.full_orthogonalize,
+                                               max_iteration=it)
+            same, same_it = out, it
+        else:
+            ex2 = L.Exponentiator(op, n)
+            ex2.full_orthogonalize = ex.full_orthogonalize
+            ex2.max_iteration = o_it
+            same, same_it = ex2.run(a_coef, inp)
+            o_same, o_same_it = o_out, o_it
+        assert same_it == o_same_it, (same_it, o_same_it)
+        assert np.linalg.norm(same - o_same) <= 1e-8 * max(np.linalg.norm(o_same), 1e-300)
     wv, v = np.linalg.eigh(a.toarray())
     exact = v @ (np.exp(a_coef * wv) * (v.conj().T @ inp))
     if "max_iteration" not in kw or it < kw["max_iteration"]:   # (a run cut off by the bound of the stress seeds is compared with the oracle only)

@@ -77,3 +77,45 @@ def install_hook_sync():
 
     if sync_hooks not in L.CONTEXT_CREATED_HOOKS:
         L.CONTEXT_CREATED_HOOKS.append(sync_hooks)
+
+
+# ------------------------------------------------------------------ Gram-Schmidt coefficients against exact projections
+def check_orth_h(ctx, llenv, basis_dev, basis, ld, w, mode, h):
+    """h of ll_orth_block_* (returned with the default settings) against EXACT projections at the double-level bound of
+    exact_ref.dot_bound.  MGS: h_j against the exact projection of the w that step j sees — the output of the same call over
+    the first j basis vectors (the steps are strictly sequential, so the first j are the same launches).  DGKS: with
+    LL_DGKS_THRESHOLD=0 (no second pass) h must be the projections of the INPUT w; the default call may add a second pass,
+    whose corrections are float-level (they remove the roundings of w to float): only then a float-level term is allowed.
+    Returns True when the default call ran a second pass."""
+    import exact_ref as E
+    import lambda_lanczos_amd as L
+
+    n, nb = w.shape[0], basis.shape[0]
+    if mode == L.ORTH_MGS:
+        steps = range(nb) if nb <= 64 else sorted({0, 1, 2, nb // 2, nb - 1})
+        for j in steps:
+            wj = w
+            if j > 0:
+                wd = ctx.to_device(w)
+                L.orth_block(ctx, basis_dev, j, ld, wd, n, mode=mode)
+                wj = wd.get()
+                wd.free()
+            assert abs(h[j] - E.dot_exact(basis[j], wj)) <= E.dot_bound(basis[j], wj), ("mgs", j)
+        return False
+    llenv.setenv("LL_DGKS_THRESHOLD", "0")
+    wd = ctx.to_device(w)
+    _, h1 = L.orth_block(ctx, basis_dev, nb, ld, wd, n, mode=mode, want_h=True)
+    wd.free()
+    llenv.delenv("LL_DGKS_THRESHOLD")
+    for j in range(nb):
+        assert abs(h1[j] - E.dot_exact(basis[j], w)) <= E.dot_bound(basis[j], w), ("pass 1", j)
+    if np.array_equal(h, h1):
+        return False   # no second pass: h is the pass-1 h asserted above
+    # a second pass ran: its corrections are the projections of w's roundings to float after pass 1 (nb roundings per element,
+    # fnma_acc) and of the float basis' departure from orthonormality (2 u_f per pair) times sum |h1|
+    hw = np.asarray(h1, dtype=np.complex128)
+    scale = np.abs(w.astype(np.complex128)) + np.abs(hw) @ np.abs(basis.astype(np.complex128))
+    extra = (nb + 2) * E.EPS_F * np.linalg.norm(scale) + 2 * E.EPS_F * np.sum(np.abs(hw))
+    for j in range(nb):
+        assert abs(h[j] - h1[j]) <= extra, ("pass 2", j)
+    return True
