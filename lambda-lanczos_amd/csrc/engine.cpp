@@ -644,8 +644,13 @@ template <typename T> struct DevBuf {
   }
 };
 
+// The host's read-back area (ctx->pinned, pinned and device-mapped): iteration k publishes its four scalars (alpha, beta^2, c0, c1)
+// into ring slot k % kRingSlots; the gate values of the pair form follow the slots, one per slot.
+constexpr int kRingSlots = 4, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
+constexpr size_t kPinnedScalars = 32;  // (kGateAt + kRingSlots used)
+
 struct EventRing {
-  hipEvent_t ev[4];
+  hipEvent_t ev[kRingSlots];
   EventRing() {
     for (auto& e : ev) LL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
@@ -696,6 +701,15 @@ struct PhaseTimer {  // optional per-phase device timing (HIP events on the cont
   }
 };
 
+// ll_context::stop_next for one operator application: set on entry, cleared on every exit — a throwing apply included, so that no later
+// launch on the context is handed an event of a ring that has gone away (~EventRing)
+struct StopNext {
+  ll_context* ctx;
+  StopNext(ll_context* c, hipEvent_t ev) : ctx(c) { ctx->stop_next = ev; }
+  ~StopNext() { ctx->stop_next = nullptr; }
+  bool taken() const { return ctx->stop_next == nullptr; }  // the launcher hung the event on its kernel
+};
+
 // One Lanczos iteration as the device sees it, shared by the eigen-solver and the Exponentiator loops:
 //   y = A u_{k-1} + offset u_{k-1}, alpha (a1-a3)  ->  three-term update + Gram-Schmidt against `runs` + norm (a4-a7)
 //   ->  normalisation + publish of the iteration's four scalars (a8).
@@ -712,13 +726,15 @@ template <typename T> struct LoopState {
   int64_t nl;
   hipStream_t s;
   bool fuse_launches = true, defer = false;
+  bool dgks = false;      // CGS with the DGKS test against the basis (configure): the host takes the second-pass decision (collect)
   DevBuf<T> work[2];      // defer: w_k lives in work[k & 1]
   bool pending = false;   // iteration pend_k ended without its normalisation / publish
   typename Engine<T>::Publish pend{nullptr, nullptr, false};
   int pend_slot = 0;
   int64_t pend_k = 0;
   NormRefs refs_prev{nullptr, nullptr, nullptr, 0};
-  double t_enqueue = 0.0;
+  double t_enqueue = 0.0, t_wait = 0.0;
+  int64_t n_second_passes = 0;  // DGKS second passes taken on the host (collect)
   // Lagged block Gram-Schmidt (kernels.hip, lagged_kernel): ONE sweep over the basis per iteration.  The iteration ends
   // with the raw w_k in work[k & 1], its coefficients g_k = U^H w_k in hbuf[k & 1] and ||w_k||^2 - |g_k|^2 in *lag_c1; the
   // next iteration's operator kernel takes w_k / beta_k as its input and the next sweep writes the corrected u_k.
@@ -743,7 +759,7 @@ template <typename T> struct LoopState {
   // measured coefficients (g1p; g2p followed by <u_P, pr2>) and the squared norms of their orthogonal parts (rho1p, rho2p).
   int64_t max_k_hint = 0;     // the loop's max_iteration (sizes the sweeps' partial sums up front, begin_pass)
   bool pair_enabled = false;
-  bool pair_allowed = true;   // this pass: a coefficient above kPairGate switches the form off for the rest of the pass
+  bool pair_allowed = true;   // this pass: a coefficient above kGate switches the form off for the rest of the pass
   bool pair_pending = false;
   int64_t pair_P = 0;
   int64_t n_pair = 0;         // iterations enqueued in the pair form (statistics; includes speculative ones that were dropped)
@@ -758,10 +774,12 @@ template <typename T> struct LoopState {
   double *prec[4] = {nullptr, nullptr, nullptr, nullptr}, *pzero = nullptr, *pp3 = nullptr, *pp4 = nullptr, *pfold = nullptr,
          *pcols = nullptr, *pscal = nullptr;
   int prec_set = 0;           // records prec[2 * prec_set], prec[2 * prec_set + 1] hold the pending pair's coefficients
-  bool slot_pair[4] = {false, false, false, false};  // the scalars of this ring slot came from a pair fold (its gate is valid)
-  int ev_of_slot[4] = {0, 1, 2, 3};                   // the event that covers a ring slot's scalars (a pair's two slots share one)
+  bool slot_pair[kRingSlots] = {false, false, false, false};  // the scalars of this ring slot came from a pair fold (its gate is valid)
+  int ev_of_slot[kRingSlots] = {0, 1, 2, 3};                  // the event that covers a ring slot's scalars (a pair's two slots share one)
   static constexpr size_t kPairRec = (size_t)kLaggedMaxCols + 32;
-  static constexpr int64_t kPairSmallMinBytes = (int64_t)512 << 10;  // shortest vector of the pair form (small-vector geometry; enqueue_pair)
+  // the gate of the pair form: what is neglected is the SQUARE of a relative coefficient, which must stay below the rounding of the
+  // storage type (float vectors carry coefficients of ~1e-6 by rounding alone)
+  static constexpr double kGate = sizeof(typename scalar_traits<T>::real) == 4 ? 2e-4 : kPairGate;
   // Pointer table of the software-pipelined sweep (kernels.hip, pair_sweep_pipe_kernel): entry c = stored column c of this pass —
   // the locked eigenvectors, then u_0, u_1, ... — written on the device, slab by slab (launch_fill_ptrs), when a pass starts and
   // whenever the basis has grown by a slab.
@@ -785,8 +803,48 @@ template <typename T> struct LoopState {
 
   LoopState(Engine<T>& e, Basis<T>& u, EventRing& r, PhaseTimer& t, int64_t n_local, hipStream_t st)
       : E(e), U(u), ring(r), timer(t), nl(n_local), s(st) {}
-  void enable_pair() {  // after enable_lagged
-    if (!lagged) return;
+  // Which forms this run may take.  orth_dgks: Gram-Schmidt against the basis in the CGS form with the DGKS test, which the one-sweep
+  // forms and the host's second-pass decision (collect) need; defer_ok: the deferred normalisation without it (a loop without
+  // Gram-Schmidt: the Exponentiator without full_orthogonalize).
+  void configure(int64_t ld_, int64_t max_iteration, bool orth_dgks, bool defer_ok) {
+    const Tuning& tune = E.ctx->tune;
+    ld = ld_;
+    max_k_hint = max_iteration;
+    small_bytes = tune.blas_small_bytes;
+    dgks = orth_dgks;
+    // Two launches per iteration less on single-GPU runs: alpha is folded by the multi-dot that needs it, and the fold of
+    // the post-pass norm + the publish step ride in the normalisation kernel.  LL_FUSE_LAUNCHES=0: separate kernels (A/B).
+    fuse_launches = tune.fuse_launches;
+    defer = E.can_defer_scale() && fuse_launches && (orth_dgks || defer_ok);
+    lagged = E.can_scale_input() && fuse_launches && tune.lagged_gs && orth_dgks;
+    if (defer || lagged)
+      for (auto& w : work) w.alloc(E.ctx, (size_t)ld);
+    if (lagged) bind_buffers();
+    // two iterations per sweep (device operators, streaming vectors; enqueue_pair decides per iteration)
+    if (lagged && tune.pair_gs && vec_bytes() >= pair_min_bytes()) enable_pair();
+  }
+  // the vector length the forms are chosen by (sharded: the shard stride, the same on every rank)
+  int64_t vec_bytes() const { return (E.ctx->comm != nullptr ? E.op->n_shard : nl) * (int64_t)sizeof(T); }
+  // from this length on the BLAS kernels take the streaming geometry
+  int64_t stream_bytes() const { return std::min<int64_t>(small_bytes, (int64_t)1 << 20); }
+  // The shortest vector of a one-sweep form: form_min by default, the lagged_min_bytes key if set; the streaming geometry at most.
+  int64_t min_bytes(int64_t form_min) const {
+    const int64_t tuned = E.ctx->tune.lagged_min_bytes;
+    return std::min<int64_t>(stream_bytes(), tuned >= 0 ? tuned : form_min);
+  }
+  // Below the streaming geometry, down to 320 KiB, the one-sweep kernel of the small-vector geometry (lagged_small_kernel): four
+  // launches per iteration against the three of the two small-vector sweeps, but one pass over the basis: Laplacian, window 100:
+  // n = 5.0e4 20.8 -> 25.8 k it/s, 1.0e5 18.3 -> 21.0 k; n = 3.0e4 26.3 -> 25.3 k and n = 1e4 26.4 -> 19.1 k would lose
+  // (profiles/r03_small_vector_kernel_gaps.txt).
+  int64_t lagged_min_bytes() const { return min_bytes((int64_t)320 << 10); }
+  // Below the streaming geometry the pair sweep runs in the small-vector geometry (pair_small_kernel: four waves per 1 KiB strip split
+  // the stored vectors), one launch, as many columns as 64 KiB of LDS hold (Laplacian, window 100, it/s with / without the pair form:
+  // n = 5.0e4 (401 KB) 25.8 k / 26.3 k, n = 1.0e5 (800 KB) 24.3 k / 20.9 k: seven launches per pair against four per iteration, half
+  // the basis traffic — the pair form takes over from 512 KiB).
+  int64_t pair_min_bytes() const { return min_bytes((int64_t)512 << 10); }
+  double* pinned_slot(int slot) const { return E.ctx->pinned.get() + kSlotScalars * slot; }
+  double* pinned_gate(int slot) const { return E.ctx->pinned.get() + kGateAt + slot; }
+  void enable_pair() {
     pair_enabled = true;
     for (auto& w : pwork)
       if (!w.p) w.alloc(E.ctx, (size_t)ld);
@@ -814,20 +872,6 @@ template <typename T> struct LoopState {
       cols = p2;
     }
     E.ctx->ensure_partials((size_t)kMaxGrid * cols);
-  }
-  void enable_defer(int64_t ld_) {
-    defer = true;
-    ld = ld_;
-    for (auto& w : work)
-      if (!w.p) w.alloc(E.ctx, (size_t)ld_);
-  }
-  void enable_lagged(int64_t ld_) {
-    lagged = true;
-    ld = ld_;
-    small_bytes = E.ctx->tune.blas_small_bytes;
-    for (auto& w : work)
-      if (!w.p) w.alloc(E.ctx, (size_t)ld_);
-    bind_buffers();
   }
   // Everything up front: growing ctx->h.get() in the middle of a pass would free the pending coefficients.  Per parity of k:
   // g (coefficients) and, t_off further, t (lagged_fold_kernel); then the device copy of alpha / beta and the locked
@@ -858,8 +902,11 @@ template <typename T> struct LoopState {
   // ||A + offset||_2 restricted to the Krylov space, at most 3 x ||A + offset||_2 — so "3e-8 scale" below means at most
   // 9e-8 ||A + offset||_2 and the neglected term at most ~1e-14 ||A + offset||_2 at a typical beta): the gate is
   // relative to the OPERATOR's size, not to max|lambda + offset|, which collapses when a locked eigenvalue sits near -offset.
-  void begin_pass(const T* locked_vecs, int64_t n_lock, const double* lambda_shifted = nullptr, double offset = 0.0,
-                  double norm_scale = 0.0) {
+  // refs0: the norm of the start vector u_0 (the first three-term update reads it as beta_0^2).
+  void begin_pass(const NormRefs& refs0, const T* locked_vecs, int64_t n_lock, const double* lambda_shifted = nullptr,
+                  double offset = 0.0, double norm_scale = 0.0) {
+    refs_prev = refs0;
+    pending = false;
     locked = locked_vecs;
     n_locked = n_lock;
     lag_pending = false;
@@ -921,21 +968,9 @@ template <typename T> struct LoopState {
       return;
     }
     // c_z ~ ||r|| / beta: the neglected term is <= ||r||^2 / beta; below this beta^2 it would exceed 1e-13 scale and the
-    // loop leaves the one-sweep form for the rest of the pass (lanczos_run, collect)
+    // loop leaves the one-sweep form for the rest of the pass (collect)
     const double bmin = worst * worst / (1e-13 * scale);
     lag_beta2_min = bmin * bmin;
-  }
-  // iteration j ended with a beta too small for the first-order treatment of the locked columns: complete u_j with the
-  // two-sweep kernels (unless the speculative sweep already has) and continue in the two-sweep form
-  void leave_lagged(int64_t j) {
-    make_final(j);
-    lag_pending = false;
-    pair_pending = false;
-    lag_ok = false;
-  }
-  // beta_j changed on the host (second Gram-Schmidt pass on u_{j+1})
-  void set_beta(int64_t j, double value) {
-    if (lag_ok) launch_set_scalar(hist_beta + j, value, s);
   }
   RunList<T> basis_runs(int64_t count) {  // locked vectors, then u_0 .. u_{count-1}
     RunList<T> runs;
@@ -994,7 +1029,7 @@ template <typename T> struct LoopState {
   }
   // End of a pass with a pair pending: the Ritz vectors need u_0 .. u_{count-1}, of which u_P (and u_{P+1}) exist only as raw
   // vectors with their measured coefficients.  Instead of completing them with a sweep of their own (pair_flush: the whole basis
-  // read once per pending vector — 1.4 ms of a 131 ms step on config 3), the caller folds the late update into the COEFFICIENTS of the
+  // read once per pending vector — 1.4 ms of a 131 ms step on config 3), ritz_basis folds the late update into the COEFFICIENTS of the
   // Ritz GEMV:  u_P = (r1 - S g1) / rho1,  u_{P+1} = (r2 - S g2 - gam u_P) / rho2  =>  sum_k s_k u_k is a combination of S, r1, r2.
   struct PairTail {
     bool active = false;
@@ -1021,6 +1056,65 @@ template <typename T> struct LoopState {
     t.rho2[0] = rho1p;
     t.rho2[1] = rho2p;
     return t;
+  }
+  // The GEMV of the Ritz vectors x_w = sum_{k<m} s_wk u_k (coeff: nw rows of m): returns the basis runs the GEMV reads and rewrites
+  // coeff to match them, one row of runs.total() per vector.  Without a tail those are u_0 .. u_{m-1}; with one, the stored columns of
+  // the last sweep (locked vectors first, then u_0 .. u_{P-1}), then r1 (and r2).
+  RunList<T> ritz_basis(const PairTail& tail, int64_t m, int64_t nw, std::vector<T>& coeff) {
+    RunList<T> basis;
+    basis.ld = ld;
+    if (!tail.active) {
+      basis.add_basis(U, m);
+      return basis;
+    }
+    constexpr int R = Engine<T>::R;
+    typedef std::complex<double> Z;
+    const int64_t Pt = tail.P, L = n_locked, K = L + Pt;
+    std::vector<double> g1h((size_t)R * K + 1), g2h((size_t)R * (K + 1) + 1), rho(2, 1.0);
+    if (K > 0) E.fetch(tail.g[0], g1h.data(), (size_t)R * K);
+    E.fetch(tail.g[1], g2h.data(), (size_t)R * (K + 1));
+    E.fetch(tail.rho2[0], &rho[0], 1);
+    E.fetch(tail.rho2[1], &rho[1], 1);
+    const double rho1 = std::sqrt(rho[0]), rho2 = std::sqrt(rho[1]);
+    auto gz = [&](const std::vector<double>& g, int64_t j) { return R == 2 ? Z(g[(size_t)2 * j], g[(size_t)2 * j + 1]) : Z(g[(size_t)j], 0.0); };
+    auto to_t = [&](Z v, T* o) {
+      if constexpr (scalar_traits<T>::is_complex) {
+        o->re = (decltype(o->re))v.real();
+        o->im = (decltype(o->im))v.imag();
+      } else {
+        *o = (T)v.real();
+      }
+    };
+    auto from_t = [&](const T& v) {
+      if constexpr (scalar_traits<T>::is_complex) return Z((double)v.re, (double)v.im);
+      else return Z((double)v, 0.0);
+    };
+    const int64_t mm = K + tail.nvec;
+    std::vector<T> c2((size_t)nw * mm);
+    std::vector<Z> cs((size_t)K);
+    for (int64_t w = 0; w < nw; ++w) {
+      const T* sw = coeff.data() + (size_t)w * m;
+      for (int64_t j = 0; j < K; ++j) cs[(size_t)j] = j < L ? Z(0.0, 0.0) : from_t(sw[j - L]);
+      Z a = from_t(sw[Pt]);                                              // coefficient of u_P
+      Z b = tail.nvec == 2 ? from_t(sw[Pt + 1]) : Z(0.0, 0.0);           // ... of u_{P+1}
+      Z on_r2(0.0, 0.0);
+      if (tail.nvec == 2) {
+        on_r2 = b / rho2;
+        for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r2 * gz(g2h, j);
+        a -= on_r2 * gz(g2h, K);                                         // gam = <u_P, r2>
+      }
+      const Z on_r1 = a / rho1;
+      for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r1 * gz(g1h, j);
+      T* out = c2.data() + (size_t)w * mm;
+      for (int64_t j = 0; j < K; ++j) to_t(cs[(size_t)j], out + j);
+      to_t(on_r1, out + K);
+      if (tail.nvec == 2) to_t(on_r2, out + K + 1);
+    }
+    coeff.swap(c2);
+    basis = basis_runs(Pt);
+    basis.add(tail.src[0], 1);
+    if (tail.nvec == 2) basis.add(tail.src[1], 1);
+    return basis;
   }
   // Iterations k and k + 1 in the pair form.  Entered from the one-sweep state (iteration k - 1 pending with its measured
   // coefficients: u_{k-2} plays the part of an already complete first vector, g1 = 0, rho1 = 1) or continued from a pair.
@@ -1062,18 +1156,11 @@ template <typename T> struct LoopState {
     }
     const int64_t K = Lk + P;  // stored columns of the sweep
     const int ncols = 2 * R * (int)K + 5 * R + 1;
-    const int64_t stream_bytes = std::min<int64_t>(small_bytes, (int64_t)1 << 20);
-    const int64_t len = E.ctx->comm != nullptr ? E.op->n_shard : nl;  // (sharded: decided on the shard stride, the same on every rank)
     // the coefficient records hold reals * (K + 2) (+ reals) numbers, the recorded tridiagonal kLaggedMaxCols + 8 entries; the
-    // sweep's 2 reals K + 5 reals + 1 columns are summed in as many launches as one workgroup's LDS asks for (pair_sweep_max_vecs)
-    // below the streaming geometry, down to the one-sweep form's lower limit (320 KiB by default), the sweep runs in the small-vector
-    // geometry (pair_small_kernel: four waves per 1 KiB strip split the stored vectors), one launch, as many columns as 64 KiB of LDS hold
-    // (Laplacian, window 100, it/s with / without the pair form: n = 5.0e4 (401 KB) 25.8 k / 26.3 k, n = 1.0e5 (800 KB) 24.3 k / 20.9 k:
-    // seven launches per pair against four per iteration, half the basis traffic — the pair form takes over from 512 KiB)
-    const int64_t min_default = std::min<int64_t>(stream_bytes, kPairSmallMinBytes);
-    const int64_t min_bytes = E.ctx->tune.lagged_min_bytes >= 0 ? std::min<int64_t>(E.ctx->tune.lagged_min_bytes, stream_bytes) : min_default;
-    const bool small_geometry = len * (int64_t)sizeof(T) < stream_bytes;
-    if ((int64_t)R * (K + 8) > kLaggedMaxCols || len * (int64_t)sizeof(T) < min_bytes) return false;
+    // sweep's 2 reals K + 5 reals + 1 columns are summed in as many launches as one workgroup's LDS asks for (pair_sweep_max_vecs);
+    // below the streaming geometry, down to pair_min_bytes, in the small-vector geometry
+    const bool small_geometry = vec_bytes() < stream_bytes();
+    if ((int64_t)R * (K + 8) > kLaggedMaxCols || vec_bytes() < pair_min_bytes()) return false;
     if (small_geometry && (!pair_small_fits<T>((int)K) || K > max_vecs_per_launch<T>() || basis_runs(P).runs.size() > (size_t)kMaxSegs)) return false;
     if (E.ctx->tune.pair_max_stored > 0 && K > E.ctx->tune.pair_max_stored) return false;  // (test hook: the hand-over to the one-sweep form)
     const RunList<T> stored = basis_runs(P);
@@ -1089,7 +1176,7 @@ template <typename T> struct LoopState {
     double* nxt = pscal + 8 + 2 * out_rec;
     double* t3 = pscal + 16;  // |r3|^2, <r1, r3>
     const double* gam = g2 + R * K;
-    const int sa = (int)(k % 4), sb = (int)((k + 1) % 4);
+    const int sa = (int)(k % kRingSlots), sb = (int)((k + 1) % kRingSlots);
     double* e1 = E.S(kScalAlpha + sa);
     double* e2 = E.S(kScalAlpha + sb);
     want_partial_cols((size_t)std::max(ncols, 1 + R));
@@ -1143,7 +1230,7 @@ template <typename T> struct LoopState {
     // sharded: ONE all-reduce carries both iterations' columns; every rank then folds the same numbers to the same bits
     if (E.ctx->comm != nullptr) E.all_reduce(pcols, (size_t)ncols);
     launch_pair_fold(pcols, (int)P, (int)Lk, R, d_lambda, pp4, g2, gam, rho2sq, t3, e1, e2, rec3, rec4, nxt, hist_alpha, hist_beta, pfold,
-                     E.ctx->pinned.get() + 4 * sa, E.ctx->pinned.get() + 4 * sb, E.ctx->pinned.get() + 16 + sa, E.ctx->pinned.get() + 16 + sb, s,
+                     pinned_slot(sa), pinned_slot(sb), pinned_gate(sa), pinned_gate(sb), s,
                      E.ctx->tune.event_in_launch ? ring.ev[sb] : nullptr);
     // ONE event for both iterations of the pair (their scalars are published by the same fold kernel): every event record is a marker
     // packet between two dependent kernels of a loop that is bound by exactly those gaps at small sizes
@@ -1172,25 +1259,16 @@ template <typename T> struct LoopState {
     if (!lag_ok) return false;
     const RunList<T> in_memory = basis_runs(lag_pending ? k - 1 : k);  // u_{k-1} is not in memory while its update is pending
     const std::vector<BasisSegs<T>> groups = in_memory.groups(max_vecs_per_launch<T>());
-    // (very short vectors keep the two-sweep form of the small-vector kernels; sharded: decided on the shard stride, the same
-    // on every rank).  The one sweep of the streaming geometry overtakes the two small-vector sweeps from about 1 MiB per
-    // vector, well below the 4 MiB at which the streaming two-sweep kernels do (Laplacian, window 100: n = 2.0e5 14.3 ->
-    // 15.4 k it/s, 3.6e5 10.9 -> 14.0 k, 5.0e5 8.5 -> 12.4 k; n = 1.0e5 would lose 5 %; profiles/r03_small_vector_kernel_gaps.txt)
-    const int64_t len = E.ctx->comm != nullptr ? E.op->n_shard : nl;
-    const int64_t stream_bytes = std::min<int64_t>(small_bytes, (int64_t)1 << 20);  // from here the streaming geometry
-    // ... and below it, down to 320 KiB, the one-sweep kernel of the small-vector geometry (lagged_small_kernel): four
-    // launches per iteration against the three of the two small-vector sweeps, but one pass over the basis: Laplacian,
-    // window 100: n = 5.0e4 20.8 -> 25.8 k it/s, 1.0e5 18.3 -> 21.0 k; n = 3.0e4 26.3 -> 25.3 k and n = 1e4 26.4 -> 19.1 k
-    // would lose (profiles/r03_small_vector_kernel_gaps.txt)
-    const int64_t min_default = std::min<int64_t>(stream_bytes, (int64_t)320 << 10);
-    const int64_t min_bytes = E.ctx->tune.lagged_min_bytes >= 0 ? std::min<int64_t>(E.ctx->tune.lagged_min_bytes, stream_bytes)
-                                                                  : min_default;
-    if (nb_total != k + n_locked || R * nb_total > kLaggedMaxCols || groups.size() > 1 || len * (int64_t)sizeof(T) < min_bytes) {
+    // (very short vectors keep the two-sweep form of the small-vector kernels, lagged_min_bytes).  The one sweep of the streaming
+    // geometry overtakes the two small-vector sweeps from about 1 MiB per vector, well below the 4 MiB at which the streaming
+    // two-sweep kernels do (Laplacian, window 100: n = 2.0e5 14.3 -> 15.4 k it/s, 3.6e5 10.9 -> 14.0 k, 5.0e5 8.5 -> 12.4 k;
+    // n = 1.0e5 would lose 5 %; profiles/r03_small_vector_kernel_gaps.txt)
+    if (nb_total != k + n_locked || R * nb_total > kLaggedMaxCols || groups.size() > 1 || vec_bytes() < lagged_min_bytes()) {
       lag_ok = false;  // for the rest of the pass: the two-sweep iterations do not record T on the device
       return false;
     }
     const double te0 = now_s();
-    const int slot = (int)(k % 4);
+    const int slot = (int)(k % kRingSlots);
     slot_pair[slot] = false;
     T* y = work[k & 1].p;
     const T* x = lag_pending ? work[(k - 1) & 1].p : U.vec(k - 1);
@@ -1213,7 +1291,7 @@ template <typename T> struct LoopState {
     if (lag_pending) {
       const Lagged<T> lg{work[(k - 1) & 1].p, U.vec(k - 1), hbuf[(k - 1) & 1], hbuf[(k - 1) & 1] + t_off, lag_c1};
       grid = launch_lagged<T>(nl, y, groups.empty() ? none : groups[0], lg, tt, E.ctx->partials.get(), E.ctx->tune.lagged_pieces,
-                              stream_bytes, s);
+                              stream_bytes(), s);
       ++n_lagged;
     } else {
       grid = launch_mdot<T>(nl, y, groups.empty() ? none : groups[0], tt, nullptr, E.ctx->partials.get(), small_bytes, s);
@@ -1230,7 +1308,7 @@ template <typename T> struct LoopState {
     }
     const double* pg = lag_pending ? hbuf[(k - 1) & 1] : nullptr;
     launch_lagged_fold(hb, (int)nb_total, (int)n_locked, R, hb + t_off, c0, c, c + 1, E.S(kScalAlpha + slot), pg,
-                       pg ? pg + t_off : nullptr, lag_c1, hist_alpha, hist_beta, d_lambda, E.ctx->pinned.get() + 4 * slot, s,
+                       pg ? pg + t_off : nullptr, lag_c1, hist_alpha, hist_beta, d_lambda, pinned_slot(slot), s,
                        E.ctx->tune.event_in_launch ? ring.ev[slot] : nullptr);
     ev_of_slot[slot] = slot;
     if (!E.ctx->tune.event_in_launch) LL_HIP(hipEventRecord(ring.ev[slot], s));
@@ -1248,7 +1326,7 @@ template <typename T> struct LoopState {
     flush_lag();  // (leaving the lagged form: u_{k-1} must be complete)
     lag_ok = false;
     const double te0 = now_s();
-    const int slot = (int)(k % 4);
+    const int slot = (int)(k % kRingSlots);
     slot_pair[slot] = false;
     const T* x = U.vec(k - 1);
     T* y = defer ? work[k & 1].p : U.vec(k);
@@ -1268,12 +1346,15 @@ template <typename T> struct LoopState {
     // the operator kernel that publishes iteration k-1's scalars completes that iteration's event itself where its launcher can
     // (LL_LAUNCH_STOP: no marker packet between it and the sweep's first kernel); otherwise the event is recorded behind it
     const bool ev_in_launch = pending && E.ctx->tune.event_in_launch;
-    if (ev_in_launch) E.ctx->stop_next = ring.ev[pend_slot];
-    E.apply(x, y, offset, E.S(kScalAlpha + slot), true, fuse_launches ? &da : nullptr, pending ? &sc : nullptr);  // P0-P3
+    bool ev_taken = false;
+    {
+      const StopNext stop(E.ctx, ev_in_launch ? ring.ev[pend_slot] : nullptr);
+      E.apply(x, y, offset, E.S(kScalAlpha + slot), true, fuse_launches ? &da : nullptr, pending ? &sc : nullptr);  // P0-P3
+      ev_taken = ev_in_launch && stop.taken();
+    }
     if (pending) {
       ev_of_slot[pend_slot] = pend_slot;
-      if (!ev_in_launch || E.ctx->stop_next != nullptr) LL_HIP(hipEventRecord(ring.ev[pend_slot], s));  // iteration k-1's scalars are on their way to the host
-      E.ctx->stop_next = nullptr;
+      if (!ev_taken) LL_HIP(hipEventRecord(ring.ev[pend_slot], s));  // iteration k-1's scalars are on their way to the host
       pending = false;
     }
     timer.mark();
@@ -1283,7 +1364,7 @@ template <typename T> struct LoopState {
       tt.alpha_nparts = da.nparts;
       tt.alpha_out = E.S(kScalAlpha + slot);
     }
-    typename Engine<T>::Publish pub{E.ctx->pinned.get() + 4 * slot, E.S(kScalAlpha + slot), false};
+    typename Engine<T>::Publish pub{pinned_slot(slot), E.S(kScalAlpha + slot), false};
     pub.can_defer = fuse_launches;
     const NormRefs refs = E.orth(y, runs, mode, tt, E.S(kScalNorms + 3 * slot), nullptr, true, &pub);  // P5-P7
     if (pub.deferred && defer) {  // P8 rides in the next operator kernel
@@ -1319,7 +1400,195 @@ template <typename T> struct LoopState {
     LL_HIP(hipEventRecord(ring.ev[pend_slot], s));
     pending = false;
   }
+  // Enqueue the next iteration(s) from k on: two at once where the pair form applies (one sweep over the basis for both), else
+  // one, orthogonalised against the locked vectors and u_0 .. u_{k-1} (full) or against nothing.  Returns how many.
+  int64_t enqueue_group(int64_t k, double offset, int mode, bool full) {
+    if (dgks && !pending && enqueue_pair(k, offset)) return 2;
+    RunList<T> runs;
+    runs.ld = ld;
+    if (full) runs = basis_runs(k);
+    enqueue(k, offset, runs, mode);
+    return 1;
+  }
+  // Everything enqueued after iteration j is dropped (u_j is final in its basis slot): the next enqueue is j + 1, and its three-term
+  // update reads beta_j^2 from iteration j's norm triple.
+  void restart_after(int64_t j) {
+    pending = false;
+    lag_pending = false;
+    pair_pending = false;
+    double* cj = E.S(kScalNorms + 3 * (int)(j % kRingSlots));
+    refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
+  }
+  // Host half of iteration j, part 1: wait for its four scalars and take the decisions that may change u_j — the DGKS second pass,
+  // leaving the one-sweep form, the pair form's gate.  redone: u_j changed or the form changed under everything enqueued after it,
+  // which the caller enqueues again from j + 1.
+  struct Scalars {
+    double alpha, beta2, c0, c1;
+    bool redone;
+  };
+  Scalars collect(int64_t j) {
+    const int slot = (int)(j % kRingSlots);
+    const double tw0 = now_s();
+    LL_HIP(hipEventSynchronize(ring.ev[ev_of_slot[slot]]));
+    t_wait += now_s() - tw0;
+    const volatile double* hp = pinned_slot(slot);
+    Scalars r{hp[0], hp[1], hp[2], hp[3], false};
+    double* const beta2_dev = E.S(kScalNorms + 3 * slot) + 1;  // what the next three-term update reads as beta_j^2
+    if (dgks && r.c1 < E.ctx->tune.dgks_threshold * r.c0) {
+      // DGKS "twice is enough", decided here from the published norms: the first pass removed more than half of
+      // ||w||^2, so Gram-Schmidt is repeated on u_j (already scaled to unit norm on the device) and beta_j shrinks
+      // by the norm that survives.  Rare (near breakdown / deflation); costs one pipeline drain.
+      if (r.c1 > 0.0 && std::isfinite(r.c1)) {
+        const RunList<T> again = basis_runs(j);
+        make_final(j);
+        r.beta2 = r.c1 * E.second_pass(U.vec(j), again);
+        ++n_second_passes;
+        launch_set_scalar(beta2_dev, r.beta2, s);
+        if (lag_ok) launch_set_scalar(hist_beta + j - 1, std::sqrt(r.beta2), s);  // the device copy of T
+        restart_after(j);
+        r.redone = true;
+      } else {
+        r.beta2 = 0.0;  // w vanished exactly: breakdown (H3)
+      }
+    }
+    if (!r.redone && lag_ok && n_locked > 0 && r.beta2 < lag_beta2_min) {
+      // beta_j too small for the first-order treatment of the locked columns (begin_pass): u_j is completed with the two-sweep
+      // kernels (unless the speculative sweep already has) and the pass continues in the two-sweep form
+      make_final(j);
+      lag_ok = false;
+      restart_after(j);
+      r.redone = true;
+    }
+    if (!r.redone && slot_pair[slot] && !(*pinned_gate(slot) <= kGate)) {
+      // A coefficient of this iteration's raw vector grew beyond what the pair form tracks to first order (beta -> eps: an
+      // exhausted Krylov space, breakdown).  The iteration itself stands — its coefficients were MEASURED, its alpha / beta
+      // are exact — but whatever took the vector as an operator input (the second iteration of its pair, the next pair) is
+      // second-order inaccurate: u_j is completed with its measured coefficients, everything after it is enqueued again, and
+      // the rest of the pass runs in the one-sweep form (exact for coefficients of any size).
+      pair_allowed = false;
+      ++n_gate_trips;
+      make_final(j);
+      launch_set_scalar(beta2_dev, r.beta2, s);
+      restart_after(j);
+      r.redone = true;
+    }
+    return r;
+  }
 };
+
+// Callback operators run WITHOUT speculation: the user's mv_mul must be called exactly as often as the reference calls it (LL:243:
+// once per executed iteration) and never on the 1/sqrt(~0)-scaled vector that follows a breakdown; a host callback synchronises the
+// stream anyway, so there is nothing to overlap.
+bool speculates(const ll_operator* op) { return !(op->kind == ll_operator::HOST_CB || op->kind == ll_operator::DEV_CB); }
+// Part 2 of the host half (Ritz values, breakdown, convergence; the Exponentiator's exp(a T_j) e_1) runs on a helper thread, in
+// iteration order, wherever the loop speculates; LL_TRIDIAG_THREAD=0 computes the verdicts inline (lag 1, the round-1 behaviour).
+bool threaded_verdicts(const ll_context* ctx, const ll_operator* op) { return speculates(op) && ctx->tune.tridiag_thread; }
+
+// One Lanczos pass of iterations 1 .. max_iteration on the host side, shared by the eigen-solver and the Exponentiator: enqueue,
+// collect the scalars (alpha and beta land in alpha / beta, then on_collect(j, scalars) runs), hand T_j to the worker's tracker and
+// absorb its verdicts into `last`.  Returns whether a stop verdict ended the pass.
+template <typename T, typename Tracker, typename OnCollect>
+bool run_pass(LoopState<T>& LS, StepWorker<Tracker>& worker, int64_t max_iteration, double offset, int mode, bool full,
+              std::vector<double>& alpha, std::vector<double>& beta, typename Tracker::Out& last, double& t_tridiag,
+              OnCollect&& on_collect) {
+  const ll_context* ctx = LS.E.ctx;
+  // This thread keeps enqueuing and looks at the verdicts as they arrive, at most kMaxLag iterations late.  A verdict that arrives
+  // late only means a few speculative iterations more on the device (they write basis slots the results never read).  The lag is
+  // only ever used when the helper is slower than the device — in practice the O(m^2) QR confirmations of LL_TRIDIAG_AUTO near
+  // convergence at large m (190 ms at m = 3300 against 9 ms per device iteration at n = 1e6) — so the bound is generous; while the
+  // helper keeps up the verdicts are one iteration late.
+  const size_t kMaxLag = worker.threaded() ? 24 : 0;
+  const int64_t lockstep_lag = worker.threaded() && ctx->comm != nullptr ? std::max(-1, ctx->tune.tridiag_lag) : -1;  // see StepWorker::consume
+  bool stopped = false;
+  auto absorb = [&](typename Tracker::Out& o) {
+    t_tridiag += o.seconds;
+    last = std::move(o);
+    return last.stop;
+  };
+  auto collect = [&](int64_t j) {
+    const typename LoopState<T>::Scalars sc = LS.collect(j);
+    alpha.push_back(sc.alpha);
+    beta.push_back(std::sqrt(sc.beta2));
+    on_collect(j, sc);
+    worker.submit((int64_t)alpha.size(), alpha.data(), beta.data());
+    return sc.redone;
+  };
+  typename Tracker::Out r;
+  if (speculates(LS.E.op)) {
+    // One group of iterations (one, or the two of a pair) is enqueued ahead of the group whose scalars are collected.
+    int64_t enq = 0, col = 0;  // iterations enqueued / collected so far
+    int64_t ahead_first = 1, ahead_last = 0;  // the group enqueued last, not yet collected (empty: first > last)
+    while (!stopped && col < max_iteration) {
+      const int64_t grp_first = ahead_first, grp_last = ahead_last;
+      if (enq < max_iteration) {
+        ahead_first = enq + 1;
+        enq += LS.enqueue_group(enq + 1, offset, mode, full);
+        ahead_last = enq;
+      } else {
+        LS.flush();  // nothing follows: the last iteration's normalisation / publish step happens now
+        ahead_first = 1;
+        ahead_last = 0;
+      }
+      for (int64_t j = grp_first; j <= std::min(grp_last, max_iteration) && !stopped; ++j) {
+        const bool redo = collect(j);
+        col = j;
+        if (redo) {  // u_j changed under everything enqueued after it: enqueue again from j + 1
+          enq = j;
+          ahead_first = 1;
+          ahead_last = 0;
+        }
+        stopped = worker.consume(j, lockstep_lag, kMaxLag, absorb);
+        if (redo) break;
+      }
+    }
+  } else {
+    for (int64_t k = 1; k <= max_iteration && !stopped; ++k) {
+      // (one iteration at a time: callback operators never take the one-sweep forms, so enqueue_group never enqueues a pair)
+      LS.enqueue_group(k, offset, mode, full);
+      collect(k);  // redone: u_k was repaired in place, nothing ran ahead
+      while (!stopped && worker.wait_pop(r)) stopped = absorb(r);
+    }
+  }
+  while (!stopped && worker.wait_pop(r)) stopped = absorb(r);  // the first stop verdict wins; else the last iteration's values
+  return stopped;
+}
+
+// The argument checks of the whole-loop runs, and their float tolerance: ll_*_params_default() fills in the DOUBLE one
+// (eps_factor * DBL_EPSILON: LL:150, EX:58 with real_t<T> = double); the reference scales it with the epsilon of real_t<T>, so a
+// float run left at that default gets eps_factor * FLT_EPSILON instead of a tolerance float data can never meet (which would run
+// to max_iteration = n).
+template <typename T, typename Params> void check_run(ll_context* ctx, ll_operator* op, Params& P, double eps_factor) {
+  if (sizeof(typename scalar_traits<T>::real) == 4 && P.eps == std::numeric_limits<double>::epsilon() * eps_factor)
+    P.eps = (double)std::numeric_limits<float>::epsilon() * eps_factor;
+  LL_REQUIRE(op && op->ctx == ctx, "operator belongs to another context");
+  LL_REQUIRE(op->is_complex == scalar_traits<T>::is_complex && op->elem_bytes == (int)sizeof(T),
+             "operator scalar type mismatch");
+  LL_REQUIRE(P.matrix_size == op->n, "matrix_size differs from the operator dimension");
+  LL_REQUIRE(P.max_iteration >= 1, "max_iteration must be >= 1");
+}
+
+// The ll_run_stats fields both runs fill (n_passes, seconds_setup and seconds_finish are the eigen-solver's own).
+template <typename T>
+void fill_stats(ll_run_stats* stats, LoopState<T>& loop, int64_t total_iterations, size_t last_alpha_len, double t_tridiag,
+                double t_start) {
+  ll_context* ctx = loop.E.ctx;
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->total_iterations = total_iterations;
+    stats->seconds_host_tridiag = t_tridiag;
+    stats->last_alpha_len = (int64_t)last_alpha_len;
+    stats->seconds_host_enqueue = loop.t_enqueue;
+    stats->seconds_host_wait = loop.t_wait;
+    stats->second_passes = loop.n_second_passes;
+    stats->lagged_iterations = loop.n_lagged;
+    stats->pair_iterations = loop.n_pair;
+    stats->pair_gate_trips = loop.n_gate_trips;
+    loop.timer.collect(stats->seconds_spmv, stats->seconds_orth);
+    ctx->drain_comm_events(&stats->seconds_comm_gather, &stats->seconds_comm_allreduce);
+    stats->seconds_total = now_s() - t_start;
+  }
+  ctx->drain_comm_events(nullptr, nullptr);
+}
 
 template <typename T> void default_init(T* v, int64_t n);
 // LL:70-104: std::random_device-seeded mt19937, uniform [-1,1]; complex: both parts.
@@ -1386,21 +1655,12 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
                  int64_t* n_found, int64_t* iter_counts, int64_t iter_cap, double* alpha_out, double* beta_out,
                  ll_run_stats* stats, const IterationSpec<T>* spec) {
   ll_lanczos_params P = P_in;
-  // ll_lanczos_params_default() fills in the DOUBLE tolerance (LL:150 with real_t<T> = double); the reference scales it
-  // with the epsilon of real_t<T>, so a float run that was left at that default gets 1e3 * FLT_EPSILON instead of a
-  // tolerance float data can never meet (which would run to max_iteration = n).
-  if (sizeof(typename scalar_traits<T>::real) == 4 && P.eps == std::numeric_limits<double>::epsilon() * 1e3)
-    P.eps = (double)std::numeric_limits<float>::epsilon() * 1e3;
-  LL_REQUIRE(op && op->ctx == ctx, "operator belongs to another context");
-  LL_REQUIRE(op->is_complex == scalar_traits<T>::is_complex && op->elem_bytes == (int)sizeof(T),
-             "operator scalar type mismatch");
-  LL_REQUIRE(P.matrix_size == op->n, "matrix_size differs from the operator dimension");
+  check_run<T>(ctx, op, P, 1e3);
   LL_REQUIRE(P.num_eigs >= 1 && P.num_eigs <= P.matrix_size, "num_eigs out of range");
   if (spec) {
     LL_REQUIRE(spec->nroot >= 1 && spec->nroot <= P.matrix_size, "nroot out of range");
     LL_REQUIRE(spec->n_orth >= 0 && (spec->n_orth == 0 || spec->orth_host != nullptr), "bad orthogonalizeTo list");
   }
-  LL_REQUIRE(P.max_iteration >= 1, "max_iteration must be >= 1");
   LL_REQUIRE(P.num_eigs_per_iteration >= 1, "num_eigs_per_iteration must be >= 1");
   LL_HIP(hipSetDevice(ctx->device));
   const double t_start = now_s();
@@ -1408,12 +1668,7 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
   const int64_t n = op->n, nl = op->n_local;
   const int64_t ld = round_up(std::max(nl, op->n_shard), 256);
   const int mode = P.orth_mode;
-  const double dgks_thr = ctx->tune.dgks_threshold;
-  // Two launches per iteration less on single-GPU runs: alpha is folded by the multi-dot that needs it, and the fold of
-  // the post-pass norm + the publish step ride in the normalisation kernel.  LL_FUSE_LAUNCHES=0: separate kernels (A/B).
-  const bool fuse_launches = ctx->tune.fuse_launches;
   Engine<T> E(ctx, op, nl);
-  constexpr int R = scalar_traits<T>::reals;
 
   Basis<T> U;
   U.init(ctx, nl, ld, pick_chunk_vecs(P.initial_vector_size, P.max_iteration, ld * (int64_t)sizeof(T), ctx->tune.slab_bytes));
@@ -1425,7 +1680,7 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
     d_locked.alloc(ctx, (size_t)P.num_eigs * ld);
   }
   const int64_t nroot_max = std::min<int64_t>(P.num_eigs_per_iteration, n);
-  ctx->ensure_pinned(32);  // 4 ring slots of 4 scalars, then the 4 gate values of the pair form
+  ctx->ensure_pinned(kPinnedScalars);
   EventRing ring;
   PhaseTimer timer(ctx, s);
 
@@ -1434,21 +1689,11 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
   if (P.find_maximum) cmp = std::greater<double>(); else cmp = std::less<double>();
   std::multimap<double, std::vector<T>, std::function<bool(double, double)>> kept(cmp);
 
-  int64_t passes = 0, total_iters = 0, second_passes = 0;
+  int64_t passes = 0, total_iters = 0;
   double t_inf_prev = 0.0;  // max over the passes so far of ||T_m||_inf (same numbers on every rank; between 1 and 3 x ||A + offset||_2)
-  double t_tridiag = 0.0, t_wait = 0.0, t_setup = 0.0, t_finish = 0.0;
+  double t_tridiag = 0.0, t_setup = 0.0, t_finish = 0.0;
   LoopState<T> LS(E, U, ring, timer, nl, s);
-  LS.fuse_launches = fuse_launches;
-  if (E.can_defer_scale() && fuse_launches && mode == LL_ORTH_CGS_DGKS) LS.enable_defer(ld);
-  LS.max_k_hint = P.max_iteration;
-  if (E.can_scale_input() && fuse_launches && ctx->tune.lagged_gs && mode == LL_ORTH_CGS_DGKS) LS.enable_lagged(ld);
-  // two iterations per sweep (device operators, streaming vectors, no locked vectors; LoopState::enqueue_pair decides per iteration)
-  {
-    const int64_t stream_bytes = std::min<int64_t>(ctx->tune.blas_small_bytes, (int64_t)1 << 20);
-    const int64_t pair_min = ctx->tune.lagged_min_bytes >= 0 ? std::min<int64_t>(ctx->tune.lagged_min_bytes, stream_bytes)
-                                                             : std::min<int64_t>(stream_bytes, LoopState<T>::kPairSmallMinBytes);
-    if (LS.lagged && ctx->tune.pair_gs && (ctx->comm != nullptr ? op->n_shard : nl) * (int64_t)sizeof(T) >= pair_min) LS.enable_pair();
-  }
+  LS.configure(ld, P.max_iteration, mode == LL_ORTH_CGS_DGKS, false);
   std::vector<double> alpha, beta;
   // Pinned staging buffer owned by the context (reused across runs): the init_vector hook fills it directly and the
   // Ritz vectors land in it, so n-sized host<->device copies run at full PCIe rate and nothing n-sized is zero-filled
@@ -1514,164 +1759,27 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
     std::vector<double> evs, all;
     bool evs_from_qr = true;  // whether `evs` hold the values of the reference's QR arithmetic (else: bisection values)
     int64_t itern = P.max_iteration;
-    bool stopped = false;
-    LS.refs_prev = refs0;
-    LS.pending = false;
     // One-sweep form against locked vectors: they must be eigenvectors (LoopState::begin_pass measures their residuals);
     // a caller's orthogonalizeTo list (run_iteration) is not, and keeps the two-sweep form.
     std::vector<double> locked_lambda;  // of the operator the loop applies (A + eigenvalue_offset)
     if (!spec)
       for (auto& kv : kept) locked_lambda.push_back(kv.first + P.eigenvalue_offset);
-    LS.begin_pass(d_locked.p, L, locked_lambda.empty() ? nullptr : locked_lambda.data(), P.eigenvalue_offset, t_inf_prev);
-    RunList<T> locked_runs;
-    locked_runs.ld = ld;
-    locked_runs.add(d_locked.p, L);  // P5
-    // Enqueue the next iteration(s) from k on: two at once where the pair form applies (one sweep over the basis for both),
-    // else one.  Returns how many.
-    auto enqueue = [&](int64_t k) -> int64_t {
-      if (mode == LL_ORTH_CGS_DGKS && !LS.pending && LS.enqueue_pair(k, P.eigenvalue_offset)) return 2;
-      RunList<T> runs = locked_runs;
-      runs.add_basis(U, k);  // P6
-      LS.enqueue(k, P.eigenvalue_offset, runs, mode);
-      return 1;
-    };
-    // Host half of iteration j, part 1 (this thread): wait for the four scalars, take the DGKS decision, append
-    // alpha_j / beta_j and hand T_j to the Ritz tracker.  kRedone: a second Gram-Schmidt pass changed u_j, the
-    // speculative iteration j+1 must be enqueued again.
-    enum { kContinue = 0, kRedone = 2 };
+    LS.begin_pass(refs0, d_locked.p, L, locked_lambda.empty() ? nullptr : locked_lambda.data(), P.eigenvalue_offset, t_inf_prev);
+    // Host half of iteration j (H1-H4: Ritz values, breakdown, convergence) on the Ritz tracker
     RitzTracker tracker_cfg;
     tracker_cfg.nroot = nroot;
     tracker_cfg.find_maximum = P.find_maximum != 0;
     tracker_cfg.mode = P.tridiag_mode;
     tracker_cfg.eps = P.eps;
     tracker_cfg.breakdown_tol = (double)std::numeric_limits<typename scalar_traits<T>::real>::epsilon() * 1e1;  // H3 LL:279
-    // Callback operators run WITHOUT speculation: the user's mv_mul must be called exactly as often as the reference
-    // calls it (LL:243: once per executed iteration) and never on the 1/sqrt(~0)-scaled vector that follows a
-    // breakdown; a host callback synchronises the stream anyway, so there is nothing to overlap.
-    const bool speculate = !(op->kind == ll_operator::HOST_CB || op->kind == ll_operator::DEV_CB);
-    // Part 2 (H1-H4: Ritz values, breakdown, convergence) runs on a helper thread, in iteration order; this thread
-    // keeps enqueuing and looks at the verdicts as they arrive, at most kMaxLag iterations late.  A verdict that
-    // arrives late only means a few speculative iterations more on the device (they write basis slots the results
-    // never read).  The lag is only ever used when the helper is slower than the device — in practice the O(m^2) QR
-    // confirmations of LL_TRIDIAG_AUTO near convergence at large m (190 ms at m = 3300 against 9 ms per device
-    // iteration at n = 1e6) — so the bound is generous; while the helper keeps up the verdicts are one iteration late
-    // like before.  LL_TRIDIAG_THREAD=0 computes the verdicts inline (lag 1, the round-1 behaviour).
-    const bool threaded = speculate && ctx->tune.tridiag_thread;
-    const size_t kMaxLag = threaded ? 24 : 0;
-    const int64_t lockstep_lag = threaded && ctx->comm != nullptr ? std::max(-1, ctx->tune.tridiag_lag) : -1;  // see StepWorker::consume
-    TridiagWorker worker(tracker_cfg, threaded, ctx->tune.tridiag_test_jitter_us);
+    TridiagWorker worker(tracker_cfg, threaded_verdicts(ctx, op), ctx->tune.tridiag_test_jitter_us);
     RitzTracker::Out last;
-    auto absorb = [&](RitzTracker::Out& r) {
-      t_tridiag += r.seconds;
-      last = std::move(r);
-      return last.stop;
-    };
-    // the gate of the pair form: what is neglected is the SQUARE of a relative coefficient, which must stay below the rounding
-    // of the storage type (float vectors carry coefficients of ~1e-6 by rounding alone)
-    const double pair_gate = sizeof(typename scalar_traits<T>::real) == 4 ? 2e-4 : kPairGate;
-    auto collect = [&](int64_t j) -> int {
-      const int slot = (int)(j % 4);
-      const double tw0 = now_s();
-      LL_HIP(hipEventSynchronize(ring.ev[LS.ev_of_slot[slot]]));
-      t_wait += now_s() - tw0;
-      const volatile double* hp = ctx->pinned.get() + 4 * slot;
-      const double alpha_j = hp[0], c0_j = hp[2], c1_j = hp[3];
-      double beta2_j = hp[1];
-      int verdict = kContinue;
-      if (mode == LL_ORTH_CGS_DGKS && c1_j < dgks_thr * c0_j) {
-        // DGKS "twice is enough", decided here from the published norms: the first pass removed more than half of
-        // ||w||^2, so Gram-Schmidt is repeated on u_j (already scaled to unit norm on the device) and beta_j shrinks
-        // by the norm that survives.  Rare (near breakdown / deflation); costs one pipeline drain.
-        if (c1_j > 0.0 && std::isfinite(c1_j)) {
-          RunList<T> again;
-          again.ld = ld;
-          again.add(d_locked.p, L);
-          again.add_basis(U, j);
-          LS.make_final(j);
-          beta2_j = c1_j * E.second_pass(U.vec(j), again);
-          ++second_passes;
-          double* cj = E.S(kScalNorms + 3 * slot);
-          launch_set_scalar(cj + 1, beta2_j, s);  // what the next three-term update reads as beta_j^2
-          LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
-          LS.pending = false;  // the speculative iteration j+1 was computed from the old u_j: it is enqueued again
-          LS.lag_pending = false;
-          LS.pair_pending = false;
-          LS.set_beta(j - 1, std::sqrt(beta2_j));
-          verdict = kRedone;
-        } else {
-          beta2_j = 0.0;  // w vanished exactly: breakdown (H3)
-        }
-      }
-      if (verdict == kContinue && LS.lag_ok && LS.n_locked > 0 && beta2_j < LS.lag_beta2_min) {
-        LS.leave_lagged(j);
-        double* cj = E.S(kScalNorms + 3 * slot);
-        LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
-        verdict = kRedone;  // the speculative iteration j+1 took the one-sweep form: it is enqueued again
-      }
-      if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->pinned.get()[16 + slot] <= pair_gate)) {
-        // A coefficient of this iteration's raw vector grew beyond what the pair form tracks to first order (beta -> eps: an
-        // exhausted Krylov space, breakdown).  The iteration itself stands — its coefficients were MEASURED, its alpha / beta
-        // are exact — but whatever took the vector as an operator input (the second iteration of its pair, the next pair) is
-        // second-order inaccurate: u_j is completed with its measured coefficients, everything after it is enqueued again, and
-        // the rest of the pass runs in the one-sweep form (exact for coefficients of any size).
-        LS.pair_allowed = false;
-        ++LS.n_gate_trips;
-        LS.make_final(j);
-        LS.pending = false;
-        LS.lag_pending = false;
-        LS.pair_pending = false;
-        double* cj = E.S(kScalNorms + 3 * slot);
-        launch_set_scalar(cj + 1, beta2_j, s);  // what the next three-term update reads as beta_j^2
-        LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
-        verdict = kRedone;
-      }
-      alpha.push_back(alpha_j);
-      beta.push_back(std::sqrt(beta2_j));
-      if (trace_file)
-        std::fprintf(trace_file, "iter %lld %lld %.17g %.17g %.17g %.17g %d\n", (long long)passes, (long long)j, alpha_j, beta2_j,
-                     c0_j, c1_j, verdict);
-      worker.submit((int64_t)alpha.size(), alpha.data(), beta.data());
-      return verdict;
-    };
-
-    RitzTracker::Out r;
-    if (speculate) {
-      // One group of iterations (one, or the two of a pair) is enqueued ahead of the group whose scalars are collected.
-      int64_t enq = 0, col = 0;  // iterations enqueued / collected so far
-      int64_t ahead_first = 1, ahead_last = 0;  // the group enqueued last, not yet collected (empty: first > last)
-      while (!stopped && col < P.max_iteration) {
-        const int64_t grp_first = ahead_first, grp_last = ahead_last;
-        if (enq < P.max_iteration) {
-          ahead_first = enq + 1;
-          enq += enqueue(enq + 1);
-          ahead_last = enq;
-        } else {
-          LS.flush();  // nothing follows: the last iteration's normalisation / publish step happens now
-          ahead_first = 1;
-          ahead_last = 0;
-        }
-        for (int64_t j = grp_first; j <= std::min(grp_last, P.max_iteration) && !stopped; ++j) {
-          const bool redo = collect(j) == kRedone;
-          col = j;
-          if (redo) {  // u_j changed under everything enqueued after it: enqueue again from j + 1
-            enq = j;
-            ahead_first = 1;
-            ahead_last = 0;
-          }
-          stopped = worker.consume(j, lockstep_lag, kMaxLag, absorb);
-          if (redo) break;
-        }
-      }
-    } else {
-      for (int64_t k = 1; k <= P.max_iteration && !stopped; ++k) {
-        RunList<T> runs = locked_runs;
-        runs.add_basis(U, k);
-        LS.enqueue(k, P.eigenvalue_offset, runs, mode);
-        collect(k);  // kRedone: u_k was repaired in place, nothing ran ahead
-        while (!stopped && worker.wait_pop(r)) stopped = absorb(r);
-      }
-    }
-    while (!stopped && worker.wait_pop(r)) stopped = absorb(r);  // the first stop verdict wins; else the last iteration's values
+    const bool stopped = run_pass(LS, worker, P.max_iteration, P.eigenvalue_offset, mode, true, alpha, beta, last, t_tridiag,
+                                  [&](int64_t j, const typename LoopState<T>::Scalars& sc) {
+                                    if (trace_file)  // (verdict 2: redone)
+                                      std::fprintf(trace_file, "iter %lld %lld %.17g %.17g %.17g %.17g %d\n", (long long)passes,
+                                                   (long long)j, sc.alpha, sc.beta2, sc.c0, sc.c1, sc.redone ? 2 : 0);
+                                  });
     itern = last.m;  // == max_iteration without a stop (LL:239,312)
     // (a pending pair: the Ritz vectors below need u_0 .. u_{itern-1}; the pending ones enter the GEMV through their raw vectors)
     if (!ctx->tune.ritz_tail) LS.pair_flush(itern);  // (A/B: complete the pending vectors with a sweep of their own)
@@ -1759,66 +1867,12 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
           for (int64_t k = 0; k < m; ++k) coeff[(size_t)w * m + k] = as_real_coeff(tq[(size_t)it * m + k], (T*)nullptr);
         }
       }
-      RunList<T> basis;
-      basis.ld = ld;
-      int64_t mm = m;
-      if (!tail.active) {
-        basis.add_basis(U, m);
-      } else {
-        // x = sum_{k<m} s_k u_k with the pending vectors expanded (LoopState::PairTail): columns = the stored columns of the last
-        // sweep (locked vectors first, then u_0 .. u_{P-1}), then r1 (and r2)
-        typedef std::complex<double> Z;
-        const int64_t Pt = tail.P, K = L + Pt;
-        std::vector<double> g1h((size_t)R * K + 1), g2h((size_t)R * (K + 1) + 1), rho(2, 1.0);
-        if (K > 0) E.fetch(tail.g[0], g1h.data(), (size_t)R * K);
-        E.fetch(tail.g[1], g2h.data(), (size_t)R * (K + 1));
-        E.fetch(tail.rho2[0], &rho[0], 1);
-        E.fetch(tail.rho2[1], &rho[1], 1);
-        const double rho1 = std::sqrt(rho[0]), rho2 = std::sqrt(rho[1]);
-        auto gz = [&](const std::vector<double>& g, int64_t j) { return R == 2 ? Z(g[(size_t)2 * j], g[(size_t)2 * j + 1]) : Z(g[(size_t)j], 0.0); };
-        auto to_t = [&](Z v, T* o) {
-          if constexpr (scalar_traits<T>::is_complex) {
-            o->re = (decltype(o->re))v.real();
-            o->im = (decltype(o->im))v.imag();
-          } else {
-            *o = (T)v.real();
-          }
-        };
-        auto from_t = [&](const T& v) {
-          if constexpr (scalar_traits<T>::is_complex) return Z((double)v.re, (double)v.im);
-          else return Z((double)v, 0.0);
-        };
-        mm = K + tail.nvec;
-        std::vector<T> c2((size_t)nw * mm);
-        std::vector<Z> cs((size_t)K);
-        for (int64_t w = 0; w < nw; ++w) {
-          const T* sw = coeff.data() + (size_t)w * m;
-          for (int64_t j = 0; j < K; ++j) cs[(size_t)j] = j < L ? Z(0.0, 0.0) : from_t(sw[j - L]);
-          Z a = from_t(sw[Pt]);                                              // coefficient of u_P
-          Z b = tail.nvec == 2 ? from_t(sw[Pt + 1]) : Z(0.0, 0.0);           // ... of u_{P+1}
-          Z on_r2(0.0, 0.0);
-          if (tail.nvec == 2) {
-            on_r2 = b / rho2;
-            for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r2 * gz(g2h, j);
-            a -= on_r2 * gz(g2h, K);                                         // gam = <u_P, r2>
-          }
-          const Z on_r1 = a / rho1;
-          for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r1 * gz(g1h, j);
-          T* out = c2.data() + (size_t)w * mm;
-          for (int64_t j = 0; j < K; ++j) to_t(cs[(size_t)j], out + j);
-          to_t(on_r1, out + K);
-          if (tail.nvec == 2) to_t(on_r2, out + K + 1);
-        }
-        coeff.swap(c2);
-        basis = LS.basis_runs(Pt);
-        basis.add(tail.src[0], 1);
-        if (tail.nvec == 2) basis.add(tail.src[1], 1);
-      }
+      const RunList<T> basis = LS.ritz_basis(tail, m, nw, coeff);
       if (!d_ritz.p || d_ritz_cap < nw) {  // only the surviving vectors are formed; sized by what a pass can return at
         d_ritz_cap = std::max<int64_t>(nw, std::min<int64_t>(nroot_max, spec ? spec->nroot : P.num_eigs));  // most, so that
         d_ritz.alloc(ctx, (size_t)d_ritz_cap * ld);  // repeated runs of one problem reuse ONE cached buffer size
       }
-      E.gemv(basis, mm, (int)nw, coeff.data(), d_ritz.p, ld);
+      E.gemv(basis, basis.total(), (int)nw, coeff.data(), d_ritz.p, ld);
       for (int64_t w = 0; w < nw; ++w) {
         E.norm2_dev(d_ritz.p + w * ld, E.S(kScalScratch) + 1);
         const NormRefs nr = E.plain_norm(E.S(kScalScratch) + 1);
@@ -1884,26 +1938,12 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
   *n_found = cnt;
   if (alpha_out) std::copy(alpha.begin(), alpha.end(), alpha_out);
   if (beta_out) std::copy(beta.begin(), beta.end(), beta_out);
+  fill_stats(stats, LS, total_iters, alpha.size(), t_tridiag, t_start);
   if (stats) {
-    std::memset(stats, 0, sizeof(*stats));
     stats->n_passes = passes;
-    stats->total_iterations = total_iters;
-    stats->seconds_host_tridiag = t_tridiag;
-    stats->last_alpha_len = (int64_t)alpha.size();
-    stats->seconds_host_enqueue = LS.t_enqueue;
-    stats->seconds_host_wait = t_wait;
     stats->seconds_setup = t_setup;
     stats->seconds_finish = t_finish;
-    stats->second_passes = second_passes;
-    stats->lagged_iterations = LS.n_lagged;
-    stats->pair_iterations = LS.n_pair;
-    stats->pair_gate_trips = LS.n_gate_trips;
-    timer.collect(stats->seconds_spmv, stats->seconds_orth);
-    ctx->drain_comm_events(&stats->seconds_comm_gather, &stats->seconds_comm_allreduce);
-    stats->seconds_total = now_s() - t_start;
   }
-  ctx->drain_comm_events(nullptr, nullptr);
-  (void)R;
 }
 
 template void lanczos_run<double>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, double*, int64_t*,
@@ -1928,13 +1968,7 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
               const T* input, T* output, int64_t* itern_out, ll_run_stats* stats) {
   typedef typename host_scalar<T>::type H;
   ll_expo_params P = P_in;
-  if (sizeof(typename scalar_traits<T>::real) == 4 && P.eps == std::numeric_limits<double>::epsilon() * 1e2)
-    P.eps = (double)std::numeric_limits<float>::epsilon() * 1e2;  // EX:58 with real_t<T> = float (see lanczos_run)
-  LL_REQUIRE(op && op->ctx == ctx, "operator belongs to another context");
-  LL_REQUIRE(op->is_complex == scalar_traits<T>::is_complex && op->elem_bytes == (int)sizeof(T),
-             "operator scalar type mismatch");
-  LL_REQUIRE(P.matrix_size == op->n, "matrix_size differs from the operator dimension");
-  LL_REQUIRE(P.max_iteration >= 1, "max_iteration must be >= 1");
+  check_run<T>(ctx, op, P, 1e2);  // EX:58
   LL_HIP(hipSetDevice(ctx->device));
   const double t_start = now_s();
   hipStream_t s = ctx->stream;
@@ -1943,14 +1977,10 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   const int64_t ld = round_up(std::max(nl, op->n_shard), 256);
   Engine<T> E(ctx, op, nl);
   st.at("engine");
-  const double dgks_thr = ctx->tune.dgks_threshold;
-  // Two launches per iteration less on single-GPU runs: alpha is folded by the multi-dot that needs it, and the fold of
-  // the post-pass norm + the publish step ride in the normalisation kernel.  LL_FUSE_LAUNCHES=0: separate kernels (A/B).
-  const bool fuse_launches = ctx->tune.fuse_launches;
   Basis<T> U;
   U.init(ctx, nl, ld, pick_chunk_vecs(P.initial_vector_size, P.max_iteration, ld * (int64_t)sizeof(T), ctx->tune.slab_bytes));
   st.at("basis");
-  ctx->ensure_pinned(32);  // 4 ring slots of 4 scalars, then the 4 gate values of the pair form
+  ctx->ensure_pinned(kPinnedScalars);
   EventRing ring;
   PhaseTimer timer(ctx, s);
   double t_tridiag = 0.0;
@@ -1964,139 +1994,29 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   E.fetch(E.S(kScalScratch) + 1, &in_norm2, 1);
   st.at("input-norm-fetched");
   const double in_norm = std::sqrt(in_norm2);
-  NormRefs refs_prev = E.plain_norm(E.S(kScalScratch) + 1);
-  launch_scale<T>(nl, U.vec(0), 0.0, &refs_prev, s);
+  const NormRefs refs0 = E.plain_norm(E.S(kScalScratch) + 1);
+  launch_scale<T>(nl, U.vec(0), 0.0, &refs0, s);
 
   std::vector<double> alpha, beta;
   std::vector<H> coeff_prev;
-  int64_t second_passes = 0;
   int64_t itern = P.max_iteration;
-  bool stopped = false;
 
-  double t_wait = 0.0;
+  // Gram-Schmidt against the basis with full_orthogonalize (EX:120-122), and with it the one-sweep forms, exactly as in the
+  // eigen-solver loop
+  const bool full = P.full_orthogonalize != 0;
   LoopState<T> LS(E, U, ring, timer, nl, s);
-  LS.fuse_launches = fuse_launches;
-  LS.refs_prev = refs_prev;
-  LS.max_k_hint = P.max_iteration;
-  if (E.can_defer_scale() && fuse_launches && (!P.full_orthogonalize || P.orth_mode == LL_ORTH_CGS_DGKS)) LS.enable_defer(ld);
-  if (E.can_scale_input() && fuse_launches && ctx->tune.lagged_gs && P.full_orthogonalize && P.orth_mode == LL_ORTH_CGS_DGKS)
-    LS.enable_lagged(ld);
-  // two iterations per sweep with full_orthogonalize (EX:120-122), exactly as in the eigen-solver loop (LoopState::enqueue_pair)
-  {
-    const int64_t stream_bytes = std::min<int64_t>(ctx->tune.blas_small_bytes, (int64_t)1 << 20);
-    const int64_t pair_min = ctx->tune.lagged_min_bytes >= 0 ? std::min<int64_t>(ctx->tune.lagged_min_bytes, stream_bytes)
-                                                             : std::min<int64_t>(stream_bytes, LoopState<T>::kPairSmallMinBytes);
-    if (LS.lagged && ctx->tune.pair_gs && (ctx->comm != nullptr ? op->n_shard : nl) * (int64_t)sizeof(T) >= pair_min) LS.enable_pair();
-  }
-  LS.begin_pass(nullptr, 0);
-  auto enqueue = [&](int64_t k) -> int64_t {  // EX:107-118 (+ EX:120-122 with full_orthogonalize), EX:145, EX:160
-    if (P.full_orthogonalize && P.orth_mode == LL_ORTH_CGS_DGKS && !LS.pending && LS.enqueue_pair(k, 0.0)) return 2;
-    RunList<T> runs;
-    runs.ld = ld;
-    if (P.full_orthogonalize) runs.add_basis(U, k);
-    LS.enqueue(k, 0.0, runs, P.orth_mode);
-    return 1;
-  };
-  // Host half of iteration j, part 1 (this thread): the four scalars, the DGKS decision, alpha_j / beta_j; part 2 (EX:124-158:
-  // exp(a T_j) e_1 and the overlap test, O(j^3)) runs on the helper thread like the eigen-solver's Ritz step.
-  enum { kContinue = 0, kRedone = 2 };
+  LS.configure(ld, P.max_iteration, full && P.orth_mode == LL_ORTH_CGS_DGKS, !full);
+  LS.begin_pass(refs0, nullptr, 0);
+  // Host half of iteration j (EX:124-158: exp(a T_j) e_1 and the overlap test, O(j^3)) on the Exponentiator's tracker
   ExpoTracker<H> tracker_cfg;
   tracker_cfg.a = a;
   tracker_cfg.eps = P.eps;
   tracker_cfg.breakdown_tol = (double)std::numeric_limits<typename scalar_traits<T>::real>::epsilon();  // EX:154
-  const bool speculate = !(op->kind == ll_operator::HOST_CB || op->kind == ll_operator::DEV_CB);  // see lanczos_run
-  const bool threaded = speculate && ctx->tune.tridiag_thread;
-  const size_t kMaxLag = threaded ? 24 : 0;
-  const int64_t lockstep_lag = threaded && ctx->comm != nullptr ? std::max(-1, ctx->tune.tridiag_lag) : -1;  // see StepWorker::consume
-  StepWorker<ExpoTracker<H>> worker(tracker_cfg, threaded, ctx->tune.tridiag_test_jitter_us);
-  typename ExpoTracker<H>::Out last, r;
-  auto absorb = [&](typename ExpoTracker<H>::Out& o) {
-    t_tridiag += o.seconds;
-    last = std::move(o);
-    return last.stop;
-  };
-  const double pair_gate = sizeof(typename scalar_traits<T>::real) == 4 ? 2e-4 : kPairGate;
-  auto collect = [&](int64_t j) -> int {
-    const int slot = (int)(j % 4);
-    const double tw0 = now_s();
-    LL_HIP(hipEventSynchronize(ring.ev[LS.ev_of_slot[slot]]));
-    t_wait += now_s() - tw0;
-    const volatile double* hp = ctx->pinned.get() + 4 * slot;
-    const double alpha_j = hp[0], c0_j = hp[2], c1_j = hp[3];
-    double beta2_j = hp[1];
-    int verdict = kContinue;
-    if (P.full_orthogonalize && P.orth_mode == LL_ORTH_CGS_DGKS && c1_j < dgks_thr * c0_j) {  // see lanczos_run
-      if (c1_j > 0.0 && std::isfinite(c1_j)) {
-        RunList<T> again;
-        again.ld = ld;
-        again.add_basis(U, j);
-        LS.make_final(j);
-        beta2_j = c1_j * E.second_pass(U.vec(j), again);
-        ++second_passes;
-        double* cj = E.S(kScalNorms + 3 * slot);
-        launch_set_scalar(cj + 1, beta2_j, s);
-        LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
-        LS.pending = false;  // (see lanczos_run)
-        LS.lag_pending = false;
-        LS.pair_pending = false;
-        LS.set_beta(j - 1, std::sqrt(beta2_j));
-        verdict = kRedone;
-      } else {
-        beta2_j = 0.0;
-      }
-    }
-    if (verdict == kContinue && LS.slot_pair[slot] && !(ctx->pinned.get()[16 + slot] <= pair_gate)) {  // the pair form's gate (see lanczos_run)
-      LS.pair_allowed = false;
-      ++LS.n_gate_trips;
-      LS.make_final(j);
-      LS.pending = false;
-      LS.lag_pending = false;
-      LS.pair_pending = false;
-      double* cj = E.S(kScalNorms + 3 * slot);
-      launch_set_scalar(cj + 1, beta2_j, s);
-      LS.refs_prev = NormRefs{cj, cj + 1, cj + 1, 0};
-      verdict = kRedone;
-    }
-    alpha.push_back(alpha_j);
-    beta.push_back(std::sqrt(beta2_j));  // EX:145
-    worker.submit((int64_t)alpha.size(), alpha.data(), beta.data());
-    return verdict;
-  };
-  if (speculate) {
-    // One group of iterations (one, or the two of a pair) is enqueued ahead of the group whose scalars are collected (lanczos_run).
-    int64_t enq = 0, col = 0;
-    int64_t ahead_first = 1, ahead_last = 0;
-    while (!stopped && col < P.max_iteration) {
-      const int64_t grp_first = ahead_first, grp_last = ahead_last;
-      if (enq < P.max_iteration) {
-        ahead_first = enq + 1;
-        enq += enqueue(enq + 1);
-        ahead_last = enq;
-      } else {
-        LS.flush();
-        ahead_first = 1;
-        ahead_last = 0;
-      }
-      for (int64_t j = grp_first; j <= std::min(grp_last, P.max_iteration) && !stopped; ++j) {
-        const bool redo = collect(j) == kRedone;
-        col = j;
-        if (redo) {
-          enq = j;
-          ahead_first = 1;
-          ahead_last = 0;
-        }
-        stopped = worker.consume(j, lockstep_lag, kMaxLag, absorb);
-        if (redo) break;
-      }
-    }
-  } else {
-    for (int64_t k = 1; k <= P.max_iteration && !stopped; ++k) {
-      enqueue(k);
-      collect(k);
-      while (!stopped && worker.wait_pop(r)) stopped = absorb(r);
-    }
-  }
-  while (!stopped && worker.wait_pop(r)) stopped = absorb(r);
+  StepWorker<ExpoTracker<H>> worker(tracker_cfg, threaded_verdicts(ctx, op), ctx->tune.tridiag_test_jitter_us);
+  typename ExpoTracker<H>::Out last;
+  // EX:107-118 (+ EX:120-122 with full_orthogonalize), EX:145, EX:160
+  run_pass(LS, worker, P.max_iteration, 0.0, P.orth_mode, full, alpha, beta, last, t_tridiag,
+           [](int64_t, const typename LoopState<T>::Scalars&) {});
   itern = last.m;
   coeff_prev = last.coeff;
   LS.pair_flush((int64_t)coeff_prev.size());  // (a pending pair: the output below needs u_0 .. u_{m-1} complete in the basis)
@@ -2122,23 +2042,8 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   LL_HIP(hipStreamSynchronize(s));
   st.at("output-done");
   *itern_out = itern;
-  if (stats) {
-    std::memset(stats, 0, sizeof(*stats));
-    stats->n_passes = 1;
-    stats->total_iterations = itern;
-    stats->seconds_host_tridiag = t_tridiag;
-    stats->last_alpha_len = (int64_t)alpha.size();
-    stats->second_passes = second_passes;
-    stats->lagged_iterations = LS.n_lagged;
-    stats->pair_iterations = LS.n_pair;
-    stats->pair_gate_trips = LS.n_gate_trips;
-    stats->seconds_host_enqueue = LS.t_enqueue;
-    stats->seconds_host_wait = t_wait;
-    timer.collect(stats->seconds_spmv, stats->seconds_orth);
-    ctx->drain_comm_events(&stats->seconds_comm_gather, &stats->seconds_comm_allreduce);
-    stats->seconds_total = now_s() - t_start;
-  }
-  ctx->drain_comm_events(nullptr, nullptr);
+  fill_stats(stats, LS, itern, alpha.size(), t_tridiag, t_start);
+  if (stats) stats->n_passes = 1;
 }
 template void expo_run<double>(ll_context*, ll_operator*, const ll_expo_params&, double, const double*, double*,
                                int64_t*, ll_run_stats*);

@@ -216,6 +216,7 @@ template <typename Tracker> class StepWorker {
   }
   StepWorker(const StepWorker&) = delete;
   StepWorker& operator=(const StepWorker&) = delete;
+  bool threaded() const { return threaded_; }
 
   void submit(int64_t m, const double* alpha, const double* beta) {
     if (!threaded_) {
