@@ -282,6 +282,7 @@ int ll_ctx_destroy(ll_context* ctx) {
     if (ctx->ev_x_ready) (void)hipEventDestroy(ctx->ev_x_ready);
     for (auto e : ctx->ev_chunk)
       if (e) (void)hipEventDestroy(e);
+    if (ctx->ev_xmax) (void)hipEventDestroy(ctx->ev_xmax);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
     if (ctx->ev_cb) (void)hipEventDestroy(ctx->ev_cb);
     for (auto& c : ctx->slab_cache) (void)hipFree(c.first);
@@ -415,6 +416,7 @@ void finish_comm_setup_impl(ll_context* ctx) {
   LL_HIP(hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
   LL_HIP(hipEventCreateWithFlags(&ctx->ev_x_ready, hipEventDisableTiming));
   for (auto& e : ctx->ev_chunk) LL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  LL_HIP(hipEventCreateWithFlags(&ctx->ev_xmax, hipEventDisableTiming));
   const int P = ctx->nranks;
   double* p = nullptr;
   LL_HIP(hipMalloc((void**)&p, (size_t)(P + 2) * sizeof(double)));
@@ -464,6 +466,8 @@ void finish_comm_setup(ll_context* ctx) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
     }
+    if (ctx->ev_xmax) (void)hipEventDestroy(ctx->ev_xmax);
+    ctx->ev_xmax = nullptr;
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
     ctx->comm_stream = nullptr;
     (void)hipGetLastError();

@@ -201,206 +201,204 @@ template <typename T> void Engine<T>::fetch(const double* d, double* host, size_
   LL_HIP(hipStreamSynchronize(ctx->stream));
 }
 
+// Exchange step: every rank needs the whole x for its row block.
+template <typename T>
+typename Engine<T>::Gathered Engine<T>::gather_x(const T* x_local, bool x_padded, bool own_first) {
+  hipStream_t s = ctx->stream;
+  // Every rank sends n_shard elements (equal strides); the last shard can be shorter.  Basis vectors are padded to the
+  // stride (x_padded); a caller-provided shard of exactly n_local elements is copied into a padded send buffer first (the
+  // tail of the gathered buffer beyond n is never referenced by a matrix entry).
+  const int P = ctx->nranks;
+  const size_t shard_bytes = (size_t)op->n_shard * sizeof(T);
+  ctx->ensure_xfull(shard_bytes * (size_t)(P + 1));
+  T* gathered = (T*)ctx->xfull.get();
+  const T* send = x_local;
+  if (!x_padded && op->n_local < op->n_shard) {
+    T* pad = (T*)((char*)ctx->xfull.get() + shard_bytes * (size_t)P);
+    LL_HIP(hipMemsetAsync(pad, 0, shard_bytes, s));
+    LL_HIP(hipMemcpyAsync(pad, x_local, (size_t)op->n_local * sizeof(T), hipMemcpyDeviceToDevice, s));
+    send = pad;
+  }
+  // PB: the gather is cut into chunks (op->pb.gather) laid out chunk-major; every other kernel needs global order
+  const bool pb = op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_PB;
+  GatherPlan plan = pb ? op->pb.gather : GatherPlan();
+  if (!pb) plan.len[0] = op->n_shard;
+  const bool overlap = own_first && ctx->tune.comm_overlap && ctx->comm_stream != nullptr;
+  hipStream_t cs = overlap ? ctx->comm_stream : s;
+  // tiled, fixed-point class: the grid's scale needs max |x| over the WHOLE vector before the first launch — every rank's own
+  // maximum (two small kernels) travels in an 8-byte all-gather in front of the vector's
+  const bool tl_max = op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_TILED && !op->tl.ordered;
+  if (tl_max) launch_tl_xmax_local<T>(*op, send, s);
+  comm_timer_begin(cs);
+  if (overlap) {
+    LL_HIP(hipEventRecord(ctx->ev_x_ready, s));  // everything enqueued so far (x final, previous readers of the
+    LL_HIP(hipStreamWaitEvent(cs, ctx->ev_x_ready, 0));  // gathered buffer done) precedes the gather
+  }
+  if (tl_max) {
+    comm_allgather(ctx->comm, op->tl.xmax.get() + tl_xmax_local_slot(), op->tl.xmax.get(), sizeof(double), cs);
+    if (overlap) LL_HIP(hipEventRecord(ctx->ev_xmax, cs));
+  }
+  for (int c = 0; c < plan.nchunks; ++c) {
+    comm_allgather(ctx->comm, send + plan.start[c], gathered + (int64_t)P * plan.start[c], (size_t)plan.len[c] * sizeof(T), cs);
+    if (overlap) LL_HIP(hipEventRecord(ctx->ev_chunk[c], cs));
+  }
+  comm_timer_end(cs);
+  return Gathered{send, gathered, overlap, overlap && tl_max ? ctx->ev_xmax : nullptr, ctx->ev_chunk, plan.nchunks};
+}
+
 template <typename T>
 void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bool x_padded, DeferredAlpha* defer,
                       const ScaleIn<T>* sc, const double* xnorm2) {
   TraceRange trace("ll::apply (mv_mul + offset + alpha)");
-  LL_REQUIRE(sc == nullptr || can_defer_scale(), "internal: this operator cannot normalise its input on the fly");
-  LL_REQUIRE(xnorm2 == nullptr || (can_scale_input() && sc == nullptr), "internal: this operator cannot scale its input");
-  ScaleIn<T> from_norm;  // the non-PB kernels take the norm as a one-element list of "partials" (nothing published)
-  if (xnorm2 && !(op->kind == ll_operator::CSR && (op->spmv_kind == LL_SPMV_PB || op->spmv_kind == LL_SPMV_TILED ||
-                                                    op->spmv_kind == LL_SPMV_SYM))) {
-    from_norm.partials = xnorm2;
-    from_norm.nparts = 1;
-    sc = &from_norm;
-  }
-  hipStream_t s = ctx->stream;
+  const InputCaps caps = input_caps();
+  LL_REQUIRE(sc == nullptr || caps.defer, "internal: this operator cannot normalise its input on the fly");
+  LL_REQUIRE(xnorm2 == nullptr || ((caps.norm2 || caps.scale_in) && sc == nullptr), "internal: this operator cannot scale its input");
+  const ScaleIn<T> from_norm{xnorm2, 1};  // the norm as a one-element list of "partials" (nothing published)
+  if (xnorm2 && caps.scale_in) sc = &from_norm;
   ctx->ensure_alpha_partials(std::max<size_t>(kMaxSpmvGrid, (size_t)std::max({op->pb.nrb, op->tl.nrb, op->sym.nrb})));
   double* const dotp = d_alpha ? ctx->alpha_partials.get() : nullptr;
-  int nparts = 0;
-  if (op->kind == ll_operator::STENCIL) {
-    // exchange step of the lattice operator: one hyperplane from each ring neighbour instead of the all-gather
-    const int64_t H = op->st_halo;
-    const T *lo, *hi;
-    if (ctx->comm == nullptr) {  // the shard is the whole lattice: the ring neighbours are its own ends
-      lo = x_local + (n_local - H);
-      hi = x_local;
-    } else {
-      const size_t hb = (size_t)H * sizeof(T);
-      ctx->ensure_halo(2 * hb);
-      T* rlo = (T*)ctx->halo.get();
-      T* rhi = rlo + H;
-      const bool ring = op->st.periodic[0] != 0;
-      const int prev = ctx->rank > 0 ? ctx->rank - 1 : (ring ? ctx->nranks - 1 : -1);
-      const int next = ctx->rank + 1 < ctx->nranks ? ctx->rank + 1 : (ring ? 0 : -1);
-      comm_timer_begin(s);
-      comm_halo_exchange(ctx->comm, x_local, rlo, prev, x_local + (n_local - H), rhi, next, hb, s);
-      comm_timer_end(s);
-      lo = rlo;
-      hi = rhi;
-    }
-    nparts = launch_stencil<T>(*op, x_local, lo, hi, y, offset, dotp, s, sc);
-  } else if (op->kind == ll_operator::CSR || op->kind == ll_operator::DENSE) {
-    const bool pb = op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_PB;
-    // CSR-stream on a sharded context: the image is split by column ownership (capi.cpp build_csr_split); the dense row
-    // block splits by column range without a second image
-    // (dense: only when the shard's column range starts and ends on 16-byte pieces of the rows — with an unaligned boundary both
-    // parts would take the scalar path of dense_mv_kernel, and gather-then-multiply, which vectorises whole rows, is faster)
-    constexpr int64_t V = (int64_t)(16 / sizeof(T)) > 0 ? (int64_t)(16 / sizeof(T)) : 1;
-    const bool dense_split_ok = op->n % V == 0 && op->row_begin % V == 0 && (op->row_begin + op->n_local) % V == 0;
-    const bool tiled = op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_TILED;
-    const bool split = ctx->comm != nullptr && ((op->kind == ll_operator::CSR && !pb && !tiled && op->csr_split()) ||
-                                                (op->kind == ll_operator::DENSE && ctx->tune.csr_split && dense_split_ok));
-    const T* x_full = x_local;
-    const T* x_own = x_local;  // what the own-column blocks of the PB kernels read
-    bool remote_done = false;
-    if (ctx->comm != nullptr) {
-      // exchange step: every rank needs the whole x for its row block.
-      // Every rank sends n_shard elements (equal strides); the last shard can be shorter.  Basis vectors are padded to
-      // the stride (x_padded); a caller-provided shard of exactly n_local elements is copied into a padded send
-      // buffer first (the tail of the gathered buffer beyond n is never referenced by a matrix entry).
-      const int P = ctx->nranks;
-      const size_t shard_bytes = (size_t)op->n_shard * sizeof(T);
-      ctx->ensure_xfull(shard_bytes * (size_t)(P + 1));
-      T* gathered = (T*)ctx->xfull.get();
-      const T* send = x_local;
-      if (!x_padded && op->n_local < op->n_shard) {
-        T* pad = (T*)((char*)ctx->xfull.get() + shard_bytes * (size_t)P);
-        LL_HIP(hipMemsetAsync(pad, 0, shard_bytes, s));
-        LL_HIP(hipMemcpyAsync(pad, x_local, (size_t)op->n_local * sizeof(T), hipMemcpyDeviceToDevice, s));
-        send = pad;
-      }
-      x_own = send;
-      x_full = gathered;
-      // PB: the gather is cut into chunks (op->pb.gather) laid out chunk-major; every other kernel needs global order
-      GatherPlan plan;
-      if (pb) plan = op->pb.gather;
-      else {
-        plan.nchunks = 1;
-        plan.start[0] = 0;
-        plan.len[0] = op->n_shard;
-      }
-      const bool overlap = (pb || split || tiled) && ctx->tune.comm_overlap && ctx->comm_stream != nullptr;
-      hipStream_t cs = overlap ? ctx->comm_stream : s;
-      // tiled, fixed-point class: the grid's scale needs max |x| over the WHOLE vector before the first launch — every rank's own
-      // maximum (two small kernels) travels in an 8-byte all-gather in front of the vector's
-      const bool tl_max = tiled && !op->tl.ordered;
-      if (tl_max) launch_tl_xmax_local<T>(*op, send, s);
-      comm_timer_begin(cs);
-      if (overlap) {
-        LL_HIP(hipEventRecord(ctx->ev_x_ready, s));  // everything enqueued so far (x final, previous readers of the
-        LL_HIP(hipStreamWaitEvent(cs, ctx->ev_x_ready, 0));  // gathered buffer done) precedes the gather
-      }
-      if (tl_max) {
-        comm_allgather(ctx->comm, op->tl.xmax.get() + tl_xmax_local_slot(), op->tl.xmax.get(), sizeof(double), cs);
-        if (overlap) LL_HIP(hipEventRecord(ctx->ev_chunk[1], cs));
-      }
-      for (int c = 0; c < plan.nchunks; ++c) {
-        comm_allgather(ctx->comm, send + plan.start[c], gathered + (int64_t)P * plan.start[c],
-                       (size_t)plan.len[c] * sizeof(T), cs);
-        if (overlap) LL_HIP(hipEventRecord(ctx->ev_chunk[c], cs));
-      }
-      comm_timer_end(cs);
-      if (split) {
-        // the own-column product (no exchange needed) runs under the gather, the other ranks' columns are added when the
-        // gathered vector has arrived; LL_COMM_OVERLAP=0 issues the same two kernels behind the gather on one stream
-        if (op->kind == ll_operator::DENSE) {
-          launch_dense_mv<T>(*op, x_local, x_local, y, offset, nullptr, s, sc, 1);
-          if (overlap) LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[0], 0));
-          nparts = launch_dense_mv<T>(*op, gathered, x_local, y, offset, dotp, s, sc, 2);
-        } else {
-          launch_spmv<T>(*op, x_local, x_local, y, offset, nullptr, s, sc, 1);
-          if (overlap) LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[0], 0));
-          nparts = launch_spmv<T>(*op, gathered, x_local, y, offset, dotp, s, sc, 2);
-        }
-        remote_done = true;
-      } else if (tiled) {
-        // the row blocks whose tiles are all own-column tiles run under the gather (x = the own shard), the others when the
-        // vector has arrived; LL_COMM_OVERLAP=0 issues the same two launches behind the gather on one stream
-        if (overlap && tl_max) LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[1], 0));
-        launch_spmv_tiled_pass<T>(*op, 0, send, op->row_begin, op->row_begin + op->n_shard, x_local, y, offset, dotp, s, xnorm2, P);
-        if (overlap) LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[0], 0));
-        nparts = launch_spmv_tiled_pass<T>(*op, 1, gathered, 0, op->n, x_local, y, offset, dotp, s, xnorm2, P);
-        remote_done = true;
-      } else if (overlap) {
-        // own-column blocks run under the gather; every chunk's remote blocks start when that chunk has arrived
-        launch_pb_phase1<T>(*op, 0, op->pb.own_count, x_own, s, xnorm2);
-        for (int c = 0; c < plan.nchunks; ++c) {
-          LL_HIP(hipStreamWaitEvent(s, ctx->ev_chunk[c], 0));
-          launch_pb_phase1<T>(*op, op->pb.chunk_first[c], op->pb.chunk_count[c], gathered, s, xnorm2);
-        }
-        nparts = launch_pb_phase2<T>(*op, x_local, y, offset, dotp, s, xnorm2);
-        remote_done = true;
-      }
-    }
-    if (remote_done) {
-    } else if (op->kind == ll_operator::DENSE)
-      nparts = launch_dense_mv<T>(*op, x_full, x_local, y, offset, dotp, s, sc);
-    else if (pb)
-      nparts = launch_spmv_pb<T>(*op, x_full, x_own, x_local, y, offset, dotp, s, xnorm2);
-    else if (op->spmv_kind == LL_SPMV_SYM)  // one-triangle image: single GPU only (creation refuses sharded contexts)
-      nparts = launch_spmv_sym<T>(*op, x_local, y, offset, dotp, s, xnorm2);
-    else if (op->spmv_kind == LL_SPMV_TILED)  // single GPU (sharded contexts took the two-launch form above): x_local is the whole x
-      nparts = launch_spmv_tiled<T>(*op, x_local, y, offset, dotp, s, xnorm2);
-    else {
-      LL_REQUIRE(op->csr.col || op->nnz == 0,
-                 "this operator kept only its column-split image (created on a sharded context) and needs that communicator");
-      nparts = launch_spmv<T>(*op, x_full, x_local, y, offset, dotp, s, sc);
-    }
-  } else {
-    LL_REQUIRE(!(ctx->comm != nullptr), "callback operators are not supported on sharded contexts");
-    const size_t bytes = (size_t)n_local * sizeof(T);
-    if (op->kind == ll_operator::HOST_CB) {
-      // unmodified user code (LL:120-126): one D2H + one H2D of an n-vector per call
-      // through the context's pinned callback buffers [in | out]: full-rate DMA, no pageable bounce copies
-      char* h_in = (char*)ctx->ensure_cb_stage(2 * bytes);
-      char* h_out = h_in + bytes;
-      if (ctx->ev_cb) LL_HIP(hipEventSynchronize(ctx->ev_cb));  // the previous call's upload out of h_out has finished
-      LL_HIP(hipMemcpyAsync(h_in, x_local, bytes, hipMemcpyDeviceToHost, s));
-      std::memset(h_out, 0, bytes);  // "out" is zero-filled on entry (LL:242, EX:107); overlaps the copy above
-      LL_HIP(hipStreamSynchronize(s));
-      int rc = op->host_fn(h_in, h_out, n_local, op->user);
-      if (rc != 0) {
-        set_error("mv_mul host callback returned " + std::to_string(rc));
-        throw Failure{LL_ERR_CALLBACK};
-      }
-      if (!ctx->tune.iter_trace.empty()) {  // LL_ITER_TRACE: what the user's code saw and returned (a stale or torn buffer shows here)
-        if (FILE* f = std::fopen(ctx->tune.iter_trace.c_str(), "a")) {
-          double sin2 = 0.0, sout2 = 0.0, dot = 0.0;
-          const typename scalar_traits<T>::real* a = (const typename scalar_traits<T>::real*)h_in;
-          const typename scalar_traits<T>::real* b = (const typename scalar_traits<T>::real*)h_out;
-          for (int64_t i = 0; i < n_local * R; ++i) {
-            sin2 += (double)a[i] * a[i];
-            sout2 += (double)b[i] * b[i];
-            dot += (double)a[i] * b[i];
-          }
-          std::fprintf(f, "cb x=%p |in|^2=%.17g |out|^2=%.17g <in,out>=%.17g\n", (const void*)x_local, sin2, sout2, dot);
-          std::fclose(f);
-        }
-      }
-      // no second synchronisation: the next callback waits for this upload (ev_cb) before it reuses the buffer
-      LL_HIP(hipMemcpyAsync(y, h_out, bytes, hipMemcpyHostToDevice, s));
-      if (!ctx->ev_cb) LL_HIP(hipEventCreateWithFlags(&ctx->ev_cb, hipEventDisableTiming));
-      LL_HIP(hipEventRecord(ctx->ev_cb, s));
-    } else {
-      LL_HIP(hipMemsetAsync(y, 0, bytes, s));
-      int rc = op->dev_fn(x_local, y, n_local, (void*)s, op->user);
-      if (rc != 0) {
-        set_error("mv_mul device callback returned " + std::to_string(rc));
-        throw Failure{LL_ERR_CALLBACK};
-      }
-    }
-    nparts = launch_offset_dot<T>(n_local, x_local, y, offset, dotp, s);
+  // dense row block: split by column range without a second image, but only when the shard's column range starts and
+  // ends on 16-byte pieces of the rows (with an unaligned boundary both parts would take the scalar path of
+  // dense_mv_kernel, and gather-then-multiply, which vectorises whole rows, is faster)
+  constexpr int64_t V = (int64_t)(16 / sizeof(T)) > 0 ? (int64_t)(16 / sizeof(T)) : 1;
+  const bool dense_split_ok = op->n % V == 0 && op->row_begin % V == 0 && (op->row_begin + op->n_local) % V == 0;
+  int nparts;
+  if (op->kind == ll_operator::STENCIL) nparts = apply_lattice(x_local, y, offset, dotp, sc);
+  else if (op->kind == ll_operator::DENSE)
+    nparts = apply_rows(&launch_dense_mv<T>, ctx->tune.csr_split && dense_split_ok, x_local, x_padded, y, offset, dotp, sc);
+  else if (op->kind != ll_operator::CSR) nparts = apply_callback(x_local, y, offset, dotp);
+  else if (op->spmv_kind == LL_SPMV_PB) nparts = apply_pb(x_local, x_padded, y, offset, dotp, xnorm2);
+  else if (op->spmv_kind == LL_SPMV_TILED) nparts = apply_tiled(x_local, x_padded, y, offset, dotp, xnorm2);
+  else if (op->spmv_kind == LL_SPMV_SYM)  // one-triangle image: single GPU only (creation refuses sharded contexts)
+    nparts = launch_spmv_sym<T>(*op, x_local, y, offset, dotp, ctx->stream, xnorm2);
+  else {  // CSR-stream: the column-split image (capi.cpp build_csr_split) on sharded contexts
+    LL_REQUIRE((ctx->comm != nullptr && op->csr_split()) || op->csr.col || op->nnz == 0,
+               "this operator kept only its column-split image (created on a sharded context) and needs that communicator");
+    nparts = apply_rows(&launch_spmv<T>, op->csr_split(), x_local, x_padded, y, offset, dotp, sc);
   }
   if (d_alpha) {
     if (defer && ctx->comm == nullptr) {  // the caller's multi-dot folds them
       defer->partials = dotp;
       defer->nparts = nparts;
     } else {
-      launch_reduce_cols(dotp, nparts, 1, d_alpha, nullptr, s);
+      launch_reduce_cols(dotp, nparts, 1, d_alpha, nullptr, ctx->stream);
       all_reduce(d_alpha, 1);
     }
   }
+}
+
+// CSR-stream and dense: the whole image, on the gathered vector when sharded.  split: the own-column product (no exchange
+// needed) runs under the gather, the other ranks' columns are added when the gathered vector has arrived;
+// LL_COMM_OVERLAP=0 issues the same two kernels behind the gather on one stream.
+template <typename T>
+int Engine<T>::apply_rows(RowLauncher launch, bool split, const T* x, bool x_padded, T* y, double offset, double* dotp,
+                          const ScaleIn<T>* sc) {
+  hipStream_t s = ctx->stream;
+  if (ctx->comm == nullptr) return launch(*op, x, x, y, offset, dotp, s, sc, 0);
+  const Gathered g = gather_x(x, x_padded, split);
+  if (!split) return launch(*op, g.x_full, x, y, offset, dotp, s, sc, 0);
+  launch(*op, x, x, y, offset, nullptr, s, sc, 1);
+  wait(g.whole());
+  return launch(*op, g.x_full, x, y, offset, dotp, s, sc, 2);
+}
+
+// Lattice: no all-gather — one hyperplane from each ring neighbour
+template <typename T> int Engine<T>::apply_lattice(const T* x, T* y, double offset, double* dotp, const ScaleIn<T>* sc) {
+  hipStream_t s = ctx->stream;
+  const int64_t H = op->st_halo;
+  if (ctx->comm == nullptr)  // the shard is the whole lattice: the ring neighbours are its own ends
+    return launch_stencil<T>(*op, x, x + (n_local - H), x, y, offset, dotp, s, sc);
+  const size_t hb = (size_t)H * sizeof(T);
+  ctx->ensure_halo(2 * hb);
+  T* rlo = (T*)ctx->halo.get();
+  T* rhi = rlo + H;
+  const bool ring = op->st.periodic[0] != 0;
+  const int prev = ctx->rank > 0 ? ctx->rank - 1 : (ring ? ctx->nranks - 1 : -1);
+  const int next = ctx->rank + 1 < ctx->nranks ? ctx->rank + 1 : (ring ? 0 : -1);
+  comm_timer_begin(s);
+  comm_halo_exchange(ctx->comm, x, rlo, prev, x + (n_local - H), rhi, next, hb, s);
+  comm_timer_end(s);
+  return launch_stencil<T>(*op, x, rlo, rhi, y, offset, dotp, s, sc);
+}
+
+// PB: one call, or the own-column blocks under the gather and every chunk's remote blocks when that chunk has arrived
+template <typename T>
+int Engine<T>::apply_pb(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2) {
+  hipStream_t s = ctx->stream;
+  if (ctx->comm == nullptr) return launch_spmv_pb<T>(*op, x, x, x, y, offset, dotp, s, xnorm2);
+  const Gathered g = gather_x(x, x_padded, true);
+  launch_pb_phase1<T>(*op, 0, op->pb.own_count, g.x_own, s, xnorm2);
+  for (int c = 0; c < op->pb.gather.nchunks; ++c) {
+    wait(g.chunk(c));
+    launch_pb_phase1<T>(*op, op->pb.chunk_first[c], op->pb.chunk_count[c], g.x_full, s, xnorm2);
+  }
+  return launch_pb_phase2<T>(*op, x, y, offset, dotp, s, xnorm2);
+}
+
+// Tiled: one launch on the whole x, or two passes — the row blocks whose tiles are all own-column tiles run under the
+// gather (x = the own shard), the others when the vector has arrived; LL_COMM_OVERLAP=0 issues the same two launches
+// behind the gather on one stream
+template <typename T>
+int Engine<T>::apply_tiled(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2) {
+  hipStream_t s = ctx->stream;
+  if (ctx->comm == nullptr) return launch_spmv_tiled<T>(*op, x, y, offset, dotp, s, xnorm2);
+  const Gathered g = gather_x(x, x_padded, true);
+  const int P = ctx->nranks;
+  wait(g.xmax);  // (fixed-point class: the scale of the grid)
+  launch_spmv_tiled_pass<T>(*op, 0, g.x_own, op->row_begin, op->row_begin + op->n_shard, x, y, offset, dotp, s, xnorm2, P);
+  wait(g.whole());
+  return launch_spmv_tiled_pass<T>(*op, 1, g.x_full, 0, op->n, x, y, offset, dotp, s, xnorm2, P);
+}
+
+// LL_ITER_TRACE: what the user's code saw and returned (a stale or torn buffer shows here)
+template <typename T> static void trace_callback(const std::string& path, const T* x, const void* h_in, const void* h_out, int64_t n) {
+  FILE* f = std::fopen(path.c_str(), "a");
+  if (!f) return;
+  double sin2 = 0.0, sout2 = 0.0, dot = 0.0;
+  const typename scalar_traits<T>::real* a = (const typename scalar_traits<T>::real*)h_in;
+  const typename scalar_traits<T>::real* b = (const typename scalar_traits<T>::real*)h_out;
+  for (int64_t i = 0; i < n * scalar_traits<T>::reals; ++i) {
+    sin2 += (double)a[i] * a[i];
+    sout2 += (double)b[i] * b[i];
+    dot += (double)a[i] * b[i];
+  }
+  std::fprintf(f, "cb x=%p |in|^2=%.17g |out|^2=%.17g <in,out>=%.17g\n", (const void*)x, sin2, sout2, dot);
+  std::fclose(f);
+}
+
+// Host and device callbacks, then offset and alpha partials in a kernel of their own
+template <typename T> int Engine<T>::apply_callback(const T* x, T* y, double offset, double* dotp) {
+  LL_REQUIRE(ctx->comm == nullptr, "callback operators are not supported on sharded contexts");
+  hipStream_t s = ctx->stream;
+  const size_t bytes = (size_t)n_local * sizeof(T);
+  if (op->kind == ll_operator::HOST_CB) {
+    // unmodified user code (LL:120-126): one D2H + one H2D of an n-vector per call
+    // through the context's pinned callback buffers [in | out]: full-rate DMA, no pageable bounce copies
+    char* h_in = (char*)ctx->ensure_cb_stage(2 * bytes);
+    char* h_out = h_in + bytes;
+    if (ctx->ev_cb) LL_HIP(hipEventSynchronize(ctx->ev_cb));  // the previous call's upload out of h_out has finished
+    LL_HIP(hipMemcpyAsync(h_in, x, bytes, hipMemcpyDeviceToHost, s));
+    std::memset(h_out, 0, bytes);  // "out" is zero-filled on entry (LL:242, EX:107); overlaps the copy above
+    LL_HIP(hipStreamSynchronize(s));
+    int rc = op->host_fn(h_in, h_out, n_local, op->user);
+    if (rc != 0) {
+      set_error("mv_mul host callback returned " + std::to_string(rc));
+      throw Failure{LL_ERR_CALLBACK};
+    }
+    if (!ctx->tune.iter_trace.empty()) trace_callback(ctx->tune.iter_trace, x, h_in, h_out, n_local);
+    // no second synchronisation: the next callback waits for this upload (ev_cb) before it reuses the buffer
+    LL_HIP(hipMemcpyAsync(y, h_out, bytes, hipMemcpyHostToDevice, s));
+    if (!ctx->ev_cb) LL_HIP(hipEventCreateWithFlags(&ctx->ev_cb, hipEventDisableTiming));
+    LL_HIP(hipEventRecord(ctx->ev_cb, s));
+  } else {
+    LL_HIP(hipMemsetAsync(y, 0, bytes, s));
+    int rc = op->dev_fn(x, y, n_local, (void*)s, op->user);
+    if (rc != 0) {
+      set_error("mv_mul device callback returned " + std::to_string(rc));
+      throw Failure{LL_ERR_CALLBACK};
+    }
+  }
+  return launch_offset_dot<T>(n_local, x, y, offset, dotp, s);
 }
 
 template <typename T> void Engine<T>::norm2_dev(const T* v, double* d_out) {

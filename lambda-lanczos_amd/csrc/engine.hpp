@@ -53,6 +53,24 @@ template <typename T> struct RunList {
   std::vector<BasisSegs<T>> groups(int max_vecs) const;
 };
 
+// What an operator image takes as its input x besides a normalised vector: the one statement that Engine::apply and the
+// loops' choice of form (can_scale_input, can_defer_scale) read.  Every device operator can take its input unnormalised
+// (sharded contexts gather / exchange the unnormalised shards): the PB, tiled and one-triangle kernels take ||w||^2
+// themselves (norm2), the others scale the finished row sum through a ScaleIn, to which apply hands ||w||^2 as a
+// one-element list of partials (scale_in).  Only the ScaleIn kernels can normalise their input on the fly with all that
+// goes with it (defer: write u_k, publish), and only on a single GPU: sharded contexts gather the normalised vector.  The
+// PB kernels keep the separate normalisation (they want max|u_k| from it); callbacks hand x to user code.
+struct InputCaps {
+  bool norm2 = false, scale_in = false, defer = false;
+};
+inline InputCaps input_caps(int kind, int spmv_kind, bool sharded) {
+  InputCaps c;
+  if (kind == ll_operator::CSR && spmv_kind != LL_SPMV_CSR_STREAM) c.norm2 = true;
+  else if (kind == ll_operator::CSR || kind == ll_operator::STENCIL || kind == ll_operator::DENSE) c.scale_in = true;
+  c.defer = c.scale_in && !sharded;
+  return c;
+}
+
 template <typename T> struct Engine {
   ll_context* ctx;
   ll_operator* op;  // may be null for pure BLAS-1 use
@@ -60,6 +78,7 @@ template <typename T> struct Engine {
   static constexpr int R = scalar_traits<T>::reals;
 
   Engine(ll_context* c, ll_operator* o, int64_t n_local_) : ctx(c), op(o), n_local(n_local_) {}
+  InputCaps input_caps() const { return op ? ll::input_caps(op->kind, op->spmv_kind, ctx->comm != nullptr) : InputCaps{}; }
 
   double* S(int i) const { return ctx->scal.get() + i; }
   NormRefs plain_norm(double* c1) const { return NormRefs{S(kScalZero), c1, c1, 0}; }
@@ -79,20 +98,32 @@ template <typename T> struct Engine {
   // ||w||^2 = *xnorm2 and the operator works with w / ||w|| (lagged Gram-Schmidt, LoopState).
   void apply(const T* x_local, T* y, double offset, double* d_alpha, bool x_padded = false, DeferredAlpha* defer = nullptr,
              const ScaleIn<T>* sc = nullptr, const double* xnorm2 = nullptr);
-  // any device operator can take its input unnormalised (the PB kernels scale the x slice while they stage it, the
-  // others scale the finished row sum through ScaleIn); sharded contexts gather / exchange the unnormalised shards
-  bool can_scale_input() const {
-    if (op == nullptr) return false;
-    return op->kind == ll_operator::CSR || op->kind == ll_operator::STENCIL || op->kind == ll_operator::DENSE;
+  bool can_scale_input() const { return input_caps().norm2 || input_caps().scale_in; }  // xnorm2 is accepted
+  bool can_defer_scale() const { return input_caps().defer; }                           // sc is accepted
+  // The exchange step of a sharded context: x_local's shard all-gathered (chunk by chunk for PB).  own_first: the image has
+  // work on its own columns to run under the gather (only then is the gather issued on the communication stream).
+  struct Gathered {
+    const T* x_own;   // the rank's shard, readable up to the shard stride n_shard
+    const T* x_full;  // the gathered vector: chunk-major by op->pb.gather for PB, in global order otherwise
+    bool overlap;     // issued on comm_stream: consumers wait on the events below (otherwise they are in stream order)
+    hipEvent_t xmax;  // the tiled kernel's max|x| has arrived (null: not gathered, or no overlap)
+    const hipEvent_t* chunk_ev;
+    int nchunks;
+    hipEvent_t chunk(int c) const { return overlap ? chunk_ev[c] : nullptr; }  // chunk c has arrived
+    hipEvent_t whole() const { return chunk(nchunks - 1); }                     // the whole vector has arrived
+  };
+  Gathered gather_x(const T* x_local, bool x_padded, bool own_first);
+  void wait(hipEvent_t e) {  // the compute stream waits for e (null: nothing to wait for)
+    if (e) LL_HIP(hipStreamWaitEvent(ctx->stream, e, 0));
   }
-  // The operator kernel can normalise its input on the fly: single GPU, and a kernel that reads x itself (CSR-stream,
-  // lattice, dense).  The PB kernels keep the separate normalisation (they want max|u_k| from it), callbacks hand x to
-  // user code, sharded contexts gather the normalised vector.
-  bool can_defer_scale() const {
-    if (ctx->comm != nullptr || op == nullptr) return false;
-    if (op->kind == ll_operator::STENCIL || op->kind == ll_operator::DENSE) return true;
-    return op->kind == ll_operator::CSR && op->spmv_kind == LL_SPMV_CSR_STREAM;
-  }
+  // the operator images (apply); each returns the number of alpha partials it left in dotp
+  typedef int (*RowLauncher)(const ll_operator&, const T*, const T*, T*, double, double*, hipStream_t, const ScaleIn<T>*, int);
+  int apply_rows(RowLauncher launch, bool split, const T* x, bool x_padded, T* y, double offset, double* dotp,
+                 const ScaleIn<T>* sc);
+  int apply_lattice(const T* x, T* y, double offset, double* dotp, const ScaleIn<T>* sc);
+  int apply_pb(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2);
+  int apply_tiled(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2);
+  int apply_callback(const T* x, T* y, double offset, double* dotp);
   // Orthogonalise w against the runs with an optional fused three-term update; c = device triple for the norms.
   // Returns the NormRefs every consumer must use for ||w|| afterwards.  h_total (device, nullable): R*nb doubles.
   // first_pass_only (whole-loop drivers, LL_ORTH_CGS_DGKS): enqueue pass 1 only and return refs whose final norm is

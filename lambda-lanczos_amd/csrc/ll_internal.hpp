@@ -295,6 +295,7 @@ struct ll_context {
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_x_ready = nullptr;
   hipEvent_t ev_chunk[ll::kMaxGatherChunks] = {};
+  hipEvent_t ev_xmax = nullptr;  // the tiled kernel's max|x| all-gather, in front of the vector's chunks
   bool profiling = false;
   hipEvent_t t0 = nullptr, t1 = nullptr;  // ll_timer_*
 
