@@ -271,7 +271,7 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
   else if (op->spmv_kind == LL_SPMV_TILED) nparts = apply_tiled(x_local, x_padded, y, offset, dotp, xnorm2);
   else if (op->spmv_kind == LL_SPMV_SYM)  // one-triangle image: single GPU only (creation refuses sharded contexts)
     nparts = launch_spmv_sym<T>(*op, x_local, y, offset, dotp, ctx->stream, xnorm2);
-  else {  // CSR-stream: the column-split image (capi.cpp build_csr_split) on sharded contexts
+  else {  // CSR-stream: the column-split image (operators.cpp build_csr_split) on sharded contexts
     LL_REQUIRE((ctx->comm != nullptr && op->csr_split()) || op->csr.col || op->nnz == 0,
                "this operator kept only its column-split image (created on a sharded context) and needs that communicator");
     nparts = apply_rows(&launch_spmv<T>, op->csr_split(), x_local, x_padded, y, offset, dotp, sc);
@@ -1640,7 +1640,7 @@ int64_t pick_chunk_vecs(int64_t initial_vector_size, int64_t max_iteration, int6
 }  // namespace
 
 // Bytes of one Krylov-basis slab of a run with default parameters on this operator (initial_vector_size = 200, max_iteration = n):
-// what operator creation sizes its spare placement candidates to, so that they can serve as the first basis slabs (capi.cpp).
+// what operator creation sizes its spare placement candidates to, so that they can serve as the first basis slabs (operators.cpp).
 int64_t default_slab_bytes(int64_t n, int64_t n_local, int64_t n_shard, int elem_bytes, const Tuning& tune) {
   const int64_t ld = round_up(std::max(n_local, n_shard), 256);
   const int64_t vec_bytes = ld * (int64_t)elem_bytes;

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void spmv_stream(int ntiles, const int32_t*
                                                       const T* __restrict__ va, const T* __restrict__ xf,
                                                       const T* __restrict__ xl, T* __restrict__ y, double offset,
                                                       double* __restrict__ dot_partials, ScaleIn<T> sc, int part) {
-  // part (sharded operators whose image is split by column ownership, capi.cpp build_csr_split): 0 = the whole matrix in
+  // part (sharded operators whose image is split by column ownership, operators.cpp build_csr_split): 0 = the whole matrix in
   // one pass; 1 = the own-column part, y = A_own x + offset x (runs under the all-gather, no dot product yet);
   // 2 = the other ranks' columns, y += A_rem x, then Re<x, y> of the finished rows.
   __shared__ T prod[kSpmvTileNnz];

@@ -228,9 +228,9 @@ struct GatherPlan {
 namespace ll {
 struct Tuning {
   // --- operator creation
-  int spmv_kernel = 0;             // LL_SPMV_KERNEL = auto (0, time both and keep the faster) | csr (1) | pb (2)
+  int spmv_kernel = -1;            // LL_SPMV_KERNEL = csr | pb | tiled: that LL_SPMV_* kernel; anything else -1 (auto: time the candidates, keep the fastest)
   bool keep_both = false;          // LL_SPMV_KEEP_BOTH=1: keep the image that lost the timing (ll_op_select_spmv A/B)
-  int pb_phase2 = 4;               // LL_PB_PHASE2 = fixed (4, default) | ordered (1) | atomic (0); see spmv_pb.hip
+  int pb_phase2 = 4;               // LL_PB_PHASE2 = fixed (4, default) | ordered (1) | atomic (0); with the accuracy request: operators.cpp image_forms
   int pb_block = 0;                // LL_PB_BLOCK: rows AND columns per block (0: automatic); tests force ragged blocks
   int pb_row_block = 0;            // LL_PB_ROW_BLOCK / LL_PB_COL_BLOCK: one of the two only
   int pb_col_block = 0;
@@ -238,11 +238,11 @@ struct Tuning {
   int pair_split_vecs = 0;         // key pair_split = n: at most n stored vectors per launch of the pair sweep (test hook: split sweeps on small problems)
   int pb_threads1 = 0;             // LL_PB_THREADS1 = 256 | 512 | 1024: lanes per workgroup of PB phase 1 (0: automatic — 512 for the thin column blocks of a sharded image, 1024 on one GPU); read at creation
   int pb_pad = 0;                  // LL_PB_PAD = 4 | 16: entries every segment of the PB image is padded to (0: automatic — 4 sharded, 16 on one GPU); read at creation
-  int pb_placements = 8;           // LL_PB_PLACEMENTS: arena placements timed at creation (1: keep the first; LL_PB_PLACEMENT_TRACE=1 prints every draw); capi.cpp
+  int pb_placements = 8;           // LL_PB_PLACEMENTS: arena placements timed at creation (1: keep the first; LL_PB_PLACEMENT_TRACE=1 prints every draw); operators.cpp
   bool pb_xpre = true;             // LL_PB_XPRE=0: phase 2 of the PB SpMV loads x_i in its epilogue (A/B of the early request)
   bool pb_diag = true;             // LL_PB_DIAG=0: the diagonal entries travel through the PB streams like every other entry (A/B)
   int gather_chunks = 0;           // LL_GATHER_CHUNKS: pieces of the all-gather (0: 4 on two ranks, 2 on more)
-  bool spmv_tile_balance = true;   // LL_SPMV_TILE_BALANCE=0: CSR-stream tiles always hold up to 1024 nonzeros (capi.cpp build_tiles)
+  bool spmv_tile_balance = true;   // LL_SPMV_TILE_BALANCE=0: CSR-stream tiles always hold up to 1024 nonzeros (operators.cpp build_tiles)
   bool csr_split = true;           // LL_CSR_SPLIT=0: sharded CSR-stream / dense operators gather first, then multiply (round-3 form)
   bool comm_overlap = true;        // LL_COMM_OVERLAP=0: exchange and compute on one stream (serial A/B reference)
   // --- the loops
@@ -271,7 +271,7 @@ struct Tuning {
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
   std::string iter_trace;          // LL_ITER_TRACE=path: the eigen-solver loop appends one line per collected iteration
                                    // (pass k alpha beta^2 c0 c1 second-pass) and one per stop verdict — for parity hunts
-  bool pb_placement_trace = false; // LL_PB_PLACEMENT_TRACE=1: print every placement draw of the PB image (capi.cpp)
+  bool pb_placement_trace = false; // LL_PB_PLACEMENT_TRACE=1: print every placement draw of the PB image (operators.cpp)
 };
 // capi.cpp: defaults <- the user-facing environment switches <- the context's overrides (ll_ctx_set_tuning), in that order
 Tuning read_tuning(const std::map<std::string, std::string>* overrides);
@@ -394,7 +394,7 @@ struct PbImage {
   int chunk_count[kMaxGatherChunks] = {0};
   GatherPlan gather;             // how a sharded vector is all-gathered when the PB kernels are selected
   bool present() const { return (bool)arena; }
-  // point the interior pointers at a copy of the arena that starts at `base` (placement search, capi.cpp)
+  // point the interior pointers at a copy of the arena that starts at `base` (placement search, operators.cpp)
   void rebase(void* base) {
     const ptrdiff_t d = (char*)base - (char*)val;
     val = base;
@@ -463,7 +463,7 @@ struct ll_operator {
   int64_t n_shard = 0;  // padded shard length used by the all-gather (= n when not sharded)
   double inf_norm = -1.0;  // max absolute row sum of the local rows (-1: unknown)
   // CSR-stream image (kernels.hip launch_spmv).  Sharded contexts, CSR-stream selected: the same rows split by column ownership
-  // (capi.cpp build_csr_split) — csr_own holds the entries over the rank's OWN columns (indices rebased to the local shard; their
+  // (operators.cpp build_csr_split) — csr_own holds the entries over the rank's OWN columns (indices rebased to the local shard; their
   // product needs no exchange and runs under the all-gather), csr_rem the entries over the other ranks' columns (global indices
   // into the gathered vector).
   ll::CsrImage csr, csr_own, csr_rem;
@@ -471,7 +471,6 @@ struct ll_operator {
   bool has_csr_stream() const { return csr.row_ptr && (csr.col || nnz == 0 || csr_split()); }
   int spmv_kind = 0;                 // LL_SPMV_*
   float tune_ms[3] = {-1.f, -1.f, -1.f};  // what the creation-time autotune measured per LL_SPMV_* kernel (-1: not timed)
-  int accuracy_req = 0;              // LL_ACCURACY_* asked for at creation (ll_csr_options.accuracy); 0 = the environment decides
   ll::PbImage pb;                    // propagation-blocked image (spmv_pb.hip pb_phase1 / pb_phase2)
   ll::TiledImage tl;                 // 2-D tiled image (spmv_pb.hip tl_*; LL_SPMV_TILED)
   int64_t sym_stored = -1;           // entries of the triangle the operator was created from (ll_op_info); -1: full storage
@@ -499,6 +498,32 @@ struct ll_operator {
 };
 
 namespace ll {
+
+// ---------------------------------------------------------------- operator construction (operators.cpp)
+// What the extern "C" entry points (capi.cpp) call.  create_csr takes resolved options: csr_options_default(false) for the plain
+// entry points, csr_options_default(true) for the _dev_ ones, the caller's for the _opt_ ones.
+void use(ll_context* ctx);  // null check, then the context's device (capi.cpp)
+ll_csr_options csr_options_default(bool arrays_on_device);
+template <typename T>
+void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, const int64_t* rp, const int32_t* ci, const void* va,
+                const ll_csr_options& opt, ll_operator** out);
+template <typename T>
+void create_coo(ll_context* ctx, int64_t n, int64_t nnz, const int32_t* rows, const int32_t* cols, const void* vals,
+                ll_operator** out);
+template <typename T>  // opt nullable: the defaults
+void create_csr_sym(ll_context* ctx, int64_t n, int uplo, const int64_t* rp, const int32_t* ci, const void* va,
+                    const ll_csr_options* opt, ll_operator** out);
+template <typename T> void create_dense(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, const void* a, ll_operator** out);
+template <typename T>
+void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin, int64_t n_local, const double* onsite,
+                    ll_operator** out);
+// a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
+template <typename T>
+void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
+// ll_op_set_accuracy: the images of a CSR operator take the forms of the accuracy class; op_accuracy: the class of the kernel
+// selected now (LL_ACCURACY_NORMWISE / _COMPONENTWISE).  Both follow operators.cpp image_forms.
+void set_op_accuracy(ll_operator* op, int accuracy);
+int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers (kernels.hip)
 // All launchers enqueue on `s` and return immediately.
@@ -545,8 +570,9 @@ int launch_pb_phase2(const ll_operator& op, const T* x_local, T* y, double offse
                      const double* xnorm2 = nullptr);
 // forms of PB phase 2 (Tuning::pb_phase2, PbImage::phase2)
 constexpr int LL_PB_ATOMIC = 0, LL_PB_ORDERED = 1, LL_PB_FIXED = 4;
-// Build the propagation-blocked image on the device from the operator's CSR arrays (false: shape not supported).
-template <typename T> bool pb_build_device(ll_operator* op);
+// Build the propagation-blocked image on the device from the operator's CSR arrays, phase 2 in the form `phase2` (LL_PB_*,
+// resolved by operators.cpp image_forms); false: shape not supported.
+template <typename T> bool pb_build_device(ll_operator* op, int phase2);
 // The 2-D tiled kernel for matrices with column locality (spmv_pb.hip): same contract as launch_spmv on a single GPU
 // (x = the whole vector); build returns false when the matrix is not eligible (too many column tiles per row block).
 template <typename T> bool tl_build_device(ll_operator* op);

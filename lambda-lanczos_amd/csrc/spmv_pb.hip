@@ -854,7 +854,7 @@ template <typename T> void csr_check_device(ll_operator* op) {
 // Block geometry + tables on the host (O(ncb * nrb)), entry placement on the device.  Returns false when the image
 // cannot be built for this shape (segment tables too large, or the LDS budget cannot hold a slice and its tables):
 // the operator then keeps CSR-stream.  The image goes to op->pb only when it is complete.
-template <typename T> bool pb_build_device(ll_operator* op) {
+template <typename T> bool pb_build_device(ll_operator* op, int phase2) {
   ll_context* ctx = op->ctx;
   const CsrImage& a = op->csr;
   PbImage im;
@@ -1040,10 +1040,8 @@ template <typename T> bool pb_build_device(ll_operator* op) {
   // faster than the wave-ordered form (profiles/r02_spmv_variants_run10_fixed_default.jsonl).  "ordered": floating-
   // point adds, the 16 waves in turn (barriers) — reproducible and component-wise accurate; "atomic": floating-point
   // adds in arrival order (not reproducible; A/B timing reference).
-  // The caller's choice through ll_csr_options.accuracy / ll_op_set_accuracy (include/lanczos_hip.h) outranks the environment.
-  im.phase2 = op->accuracy_req == LL_ACCURACY_COMPONENTWISE
-                  ? (tune.pb_phase2 == LL_PB_ATOMIC ? LL_PB_ATOMIC : LL_PB_ORDERED)
-                  : (op->accuracy_req == LL_ACCURACY_NORMWISE ? LL_PB_FIXED : tune.pb_phase2);
+  // The caller resolves it from the accuracy request and the environment (operators.cpp image_forms).
+  im.phase2 = phase2;
   auto up = [&](auto& dst, const auto& v) {
     using E = typename std::decay_t<decltype(v)>::value_type;
     dst = ctx->dev_alloc<E>(v.size(), "propagation-blocking tables");
@@ -1743,7 +1741,7 @@ template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hip
   template int launch_pb_phase2<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const double*);  \
   template int launch_spmv_pb<T>(const ll_operator&, const T*, const T*, const T*, T*, double, double*, hipStream_t, \
                                  const double*);                                                                    \
-  template bool pb_build_device<T>(ll_operator*);                                                                   \
+  template bool pb_build_device<T>(ll_operator*, int);                                                              \
   template bool tl_build_device<T>(ll_operator*);                                                                   \
   template int launch_spmv_tiled<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const double*);  \
   template void launch_tl_xmax_local<T>(const ll_operator&, const T*, hipStream_t);                                 \

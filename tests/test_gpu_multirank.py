@@ -55,7 +55,7 @@ def test_overlapped_exchange_is_bit_identical_to_the_serial_issue_order(tmp_path
 
 
 # The CSR-stream and dense operators of a sharded context multiply the rank's OWN columns under the all-gather and add the
-# other ranks' columns when the vector has arrived (column-split image, capi.cpp build_csr_split; every case below runs it);
+# other ranks' columns when the vector has arrived (column-split image, operators.cpp build_csr_split; every case below runs it);
 # "csr-gather-then-multiply" (LL_CSR_SPLIT=0) is the round-3 form: gather first, then one kernel over whole rows.
 # forced second pass: every iteration takes the host-decided second Gram-Schmidt pass (drain, repeat, re-enqueue): the
 # replicated decision must keep the ranks' collective sequences aligned, results unchanged up to rounding.

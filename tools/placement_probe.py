@@ -1,4 +1,4 @@
-"""Placement draws of config 3's PB image (capi.cpp tune_pb_placement) in one process: LL_PB_PLACEMENTS draws, each timed with the
+"""Placement draws of config 3's PB image (operators.cpp tune_pb_placement) in one process: LL_PB_PLACEMENTS draws, each timed with the
 real kernels; LL_PB_PLACEMENT_TRACE=1 prints every draw.  Run several processes on one box to separate what varies per
 allocation from what varies per process."""
 import os
