@@ -57,6 +57,9 @@ template <typename T> struct abi;
                               ll_operator** o) {                                                                         \
       return ll_op_create_stencil_##SFX(c, d, rb, nl, onsite, o);                                                        \
     }                                                                                                                    \
+    static int create_pauli(ll_context* c, int32_t ns, int64_t nt, const ll_pauli_term* t, ll_operator** o) {            \
+      return ll_op_create_pauli_##SFX(c, ns, nt, t, o);                                                                  \
+    }                                                                                                                    \
     static int create_host(ll_context* c, int64_t n, int (*fn)(const void*, void*, int64_t, void*), void* user,          \
                            ll_operator** o) {                                                                            \
       return ll_op_create_host_##SFX(c, n, reinterpret_cast<HOSTFN>(fn), user, o);                                       \
@@ -269,6 +272,28 @@ template <typename T> class LatticeOperator : public DeviceOperator<T> {
     ll_operator* op = nullptr;
     check(abi<T>::create_stencil(ctx.get(), &d, row_begin, n_local, onsite.empty() ? nullptr : onsite.data(), &op));
     this->adopt(op, n, n_local);
+  }
+};
+
+// Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t on n_sites spins (n = 2^n_sites): what a many-body user writes as an
+// mv_mul plugin, applied on the device from its list of Pauli strings.  Bit j of a basis state is site j; a term's site j
+// carries X (x_mask bit only), Z (z_mask bit only), Y (both).  A Heisenberg bond J S_j.S_k is {m, 0, J/4}, {m, m, J/4},
+// {0, m, J/4} with m = 2^j | 2^k.  Real T: an even number of Y per term.  Single-rank contexts only (ll_op_create_pauli_*).
+using PauliTerm = ll_pauli_term;
+template <typename T> class PauliOperator : public DeviceOperator<T> {
+ public:
+  PauliOperator(int n_sites, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : DeviceOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli(ctx.get(), (int32_t)n_sites, (int64_t)terms.size(), terms.data(), &op));
+    const int64_t n = (int64_t)1 << n_sites;
+    this->adopt(op, n, n);
+  }
+  // sum_t |coef_t|: an upper bound of every absolute row sum (DeviceOperator::inf_norm() returns it)
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
   }
 };
 

@@ -242,6 +242,39 @@ int ll_op_create_stencil_d(ll_context* ctx, const ll_stencil_desc* desc, int64_t
 int ll_op_create_stencil_z(ll_context* ctx, const ll_stencil_desc* desc, int64_t row_begin, int64_t n_local,
                            const double* onsite_host_local, ll_operator** out);
 
+/* (6) matrix-free spin-1/2 Hamiltonian, a sum of Pauli strings: H = sum_t coef_t P_t on n_sites spins, n = 2^n_sites — what the
+ *     README's many-body user ("low-energy excitation of a quantum system", exp(-iH dt)) writes as an mv_mul plugin (LL:120-126),
+ *     applied on the device from the list of terms instead of from a stored matrix.
+ *     Basis state s, 0 <= s < 2^n_sites: BIT j OF s IS SITE j, bit = 0 is sigma_z = +1 (in a Kronecker product site 0 is the LAST
+ *     factor).  A term (x_mask, z_mask, coef): site j carries X if only its x bit is set, Z if only its z bit, Y if both, the
+ *     identity if none.  With nY = popcount(x_mask & z_mask):  P|s> = i^nY (-1)^popcount(s & z_mask) |s ^ x_mask>, so
+ *         (H v)(s) = sum_t coef_t i^nY_t (-1)^popcount((s ^ x_t) & z_t) v(s ^ x_t).
+ *     Every Pauli string is Hermitian and coef is real: H is Hermitian by construction.  The real types (_d, _s) take terms with an
+ *     EVEN nY only (the matrix is then real symmetric); an odd nY there is LL_ERR_INVALID.  coef is a double for every T.
+ *     Examples: a Heisenberg bond J S_j.S_k = (m, 0, J/4), (m, m, J/4), (0, m, J/4) with m = 2^j | 2^k; the transverse-field Ising
+ *     chain -J sum Z_j Z_j+1 - h sum X_j = (0, 2^j | 2^(j+1), -J) and (2^j, 0, -h).
+ *     n_terms == 0 is the zero operator; duplicate terms add; a term with both masks 0 is a multiple of the identity.
+ *     LIMITS: 1 <= n_sites <= 30 (the library's local indices are signed 32-bit: n_local < 2^31 - 1); every mask bit below n_sites;
+ *     finite coefficients; a SINGLE-GPU context (more than one rank is refused: the high bits of s would be the rank and flips of
+ *     high bits pairwise exchanges — not built).
+ *     One apply moves between 2 sizeof(T) n bytes (every partner tile found in cache) and (G + 2) sizeof(T) n, G = the distinct
+ *     x masks that touch a site at or above the tile (2^12 states in fp64); the CSR image of the same matrix
+ *     moves 12 nnz + 20 n.  The image is the term tables: ll_op_device_bytes is a few hundred bytes.
+ *     ACCURACY: component-wise, like the dense and lattice operators — per state the signed coefficients of the terms that share an
+ *     x mask are summed in double (masks ascending, a mask's terms in list order), each sum multiplies its partner value in a double
+ *     fma (float inputs widened), one rounding to T.  The order is fixed: the same bits run to run and for every tile size.
+ *     Queries: ll_op_info reports n = n_local = 2^n_sites and the number of TERMS as nnz_local; ll_op_inf_norm returns
+ *     sum_t |coef_t|, an upper BOUND of every absolute row sum (a safe eigenvalue_offset magnitude), not the maximum itself;
+ *     ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID (not a CSR operator), ll_op_accuracy the component-wise class. */
+typedef struct ll_pauli_term {
+  uint64_t x_mask, z_mask;
+  double coef;
+} ll_pauli_term;
+int ll_op_create_pauli_d(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_z(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_s(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_c(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):
  *   LL_SPMV_CSR_STREAM  plain CSR, products staged in LDS; best when the x gathers hit L1/L2 (stencils, narrow bands).
@@ -369,7 +402,7 @@ int ll_op_autotune_ms_of(const ll_operator* op, int kind /* LL_SPMV_* */, double
 /* The tiled image's row blocks (0: no tiled image) and how many of them need no column of another rank (all of them on one GPU). */
 int ll_op_tiled_layout(const ll_operator* op, int* row_blocks, int* own_column_row_blocks);
 int ll_op_destroy(ll_operator* op);
-/* Global dimension n, local rows, nnz held locally (0 for callbacks). */
+/* Global dimension n, local rows, nnz held locally (0 for callbacks; the number of terms for a sum of Pauli strings). */
 int ll_op_info(const ll_operator* op, int64_t* n, int64_t* n_local, int64_t* nnz_local);
 
 /* ------------------------------------------------------------------ hot-path primitives

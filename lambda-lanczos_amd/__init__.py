@@ -23,6 +23,7 @@ from .engine import (  # noqa: F401
     DeviceArray,
     Exponentiator,
     HostOperator,
+    PauliOperator,
     StencilOperator,
     LambdaLanczos,
     default_context,

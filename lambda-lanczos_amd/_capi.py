@@ -83,6 +83,12 @@ class StencilDesc(C.Structure):
     ]
 
 
+class PauliTerm(C.Structure):
+    """ll_pauli_term"""
+
+    _fields_ = [("x_mask", C.c_uint64), ("z_mask", C.c_uint64), ("coef", C.c_double)]
+
+
 class RunStats(C.Structure):
     _fields_ = [
         ("n_passes", i64),
@@ -158,6 +164,8 @@ PROTOTYPES = {
     "ll_op_create_dense_z": (C.c_int, [vp, i64, i64, i64, vp, P(vp)]),
     "ll_op_create_stencil_d": (C.c_int, [vp, P(StencilDesc), i64, i64, vp, P(vp)]),
     "ll_op_create_stencil_z": (C.c_int, [vp, P(StencilDesc), i64, i64, vp, P(vp)]),
+    "ll_op_create_pauli_d": (C.c_int, [vp, C.c_int32, i64, P(PauliTerm), P(vp)]),
+    "ll_op_create_pauli_z": (C.c_int, [vp, C.c_int32, i64, P(PauliTerm), P(vp)]),
     "ll_op_create_host_d": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_host_z": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_device_d": (C.c_int, [vp, i64, DEV_MV_FN, vp, P(vp)]),

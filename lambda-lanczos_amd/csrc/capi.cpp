@@ -65,6 +65,7 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "pb_test_all_remote") t.pb_test_all_remote = e ? false : to_flag(v);
   else if (key == "force_rp64") t.force_rp64 = e ? false : to_flag(v);
   else if (key == "spmv_tile_balance") t.spmv_tile_balance = e ? d.spmv_tile_balance : to_flag(v);
+  else if (key == "pauli_tile_bits") t.pauli_tile_bits = e ? d.pauli_tile_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "stencil_vec") t.stencil_vec = e ? d.stencil_vec : to_flag(v);
   else if (key == "tl_force") t.tl_force = e ? false : to_flag(v);
   else if (key == "tl_xcd") t.tl_xcd_order = e ? d.tl_xcd_order : to_flag(v);
@@ -663,6 +664,18 @@ int ll_op_create_dense_z(ll_context* ctx, int64_t nr, int64_t nc, int64_t rb, co
 int ll_op_create_stencil_z(ll_context* ctx, const ll_stencil_desc* desc, int64_t rb, int64_t nl, const double* onsite,
                            ll_operator** out) {
   return guarded([&] { create_stencil<zc>(ctx, desc, rb, nl, onsite, out); });
+}
+int ll_op_create_pauli_d(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli<double>(ctx, n_sites, n_terms, terms, out); });
+}
+int ll_op_create_pauli_z(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli<zc>(ctx, n_sites, n_terms, terms, out); });
+}
+int ll_op_create_pauli_s(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli<float>(ctx, n_sites, n_terms, terms, out); });
+}
+int ll_op_create_pauli_c(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli<cf>(ctx, n_sites, n_terms, terms, out); });
 }
 int ll_op_create_host_d(ll_context* ctx, int64_t n, ll_host_mv_mul_d fn, void* user, ll_operator** out) {
   return guarded([&] { create_cb<double>(ctx, n, reinterpret_cast<ll_host_mv_mul_z>(fn), nullptr, user, out); });

@@ -134,6 +134,66 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
   return v;
 }
 
+// Sum of `nparts` workgroup partials, formed by EVERY workgroup in the same fixed order (the order of
+// reduce_one_kernel), returned to all lanes.  scratch: 5 doubles of LDS.  kBlock threads.
+__device__ __forceinline__ double fold_partials_all(const double* __restrict__ p, int nparts, double* scratch) {
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < nparts; b += kBlock) acc += p[b];
+  const double tot = block_sum(acc, scratch);
+  if (threadIdx.x == 0) scratch[4] = tot;
+  __syncthreads();
+  return scratch[4];
+}
+// Deferred normalisation (ScaleIn, ll_internal.hpp): 1 / ||w|| for this launch (1 when x is already normalised); workgroup
+// 0 stores ||w||^2 and publishes the previous iteration's scalars.  scratch: 5 doubles of LDS.
+template <typename T> __device__ __forceinline__ double scale_in_factor(const ScaleIn<T>& sc, double* scratch) {
+  if (sc.partials == nullptr) return 1.0;
+  const double tot = fold_partials_all(sc.partials, sc.nparts, scratch);  // the order of scale_publish_kernel
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (sc.c1_out) *sc.c1_out = tot;
+    if (sc.host) {
+      sc.host[0] = sc.alpha ? *sc.alpha : 0.0;
+      sc.host[1] = tot;
+      sc.host[2] = sc.c0 ? *sc.c0 : 0.0;
+      sc.host[3] = tot;
+    }
+  }
+  return 1.0 / sqrt(tot);  // T(1)/norm, LA:77-80
+}
+__device__ __forceinline__ double scale_acc(double s, double a) { return s * a; }
+__device__ __forceinline__ zc scale_acc(double s, zc a) { return zc{s * a.re, s * a.im}; }
+
+// acc += r * x with a real factor kept in double (the matrix-free operators: lattice, Pauli strings)
+__device__ __forceinline__ void fma_real(double& acc, double r, double x) { acc = fma(r, x, acc); }
+__device__ __forceinline__ void fma_real(double& acc, double r, float x) { acc = fma(r, (double)x, acc); }
+__device__ __forceinline__ void fma_real(zc& acc, double r, zc x) {
+  acc.re = fma(r, x.re, acc.re);
+  acc.im = fma(r, x.im, acc.im);
+}
+__device__ __forceinline__ void fma_real(zc& acc, double r, cf x) {
+  acc.re = fma(r, (double)x.re, acc.re);
+  acc.im = fma(r, (double)x.im, acc.im);
+}
+
+
+// V consecutive elements (V * sizeof(T) a multiple of 16 bytes) as 16-byte pieces; p must be 16-byte aligned.
+template <typename T, int V> __device__ __forceinline__ void load_chunk(const T* __restrict__ p, T (&r)[V]) {
+  constexpr int NCH = (int)(V * sizeof(T) / 16);
+  const uint4* src = reinterpret_cast<const uint4*>(p);
+  uint4 c[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) c[i] = src[i];
+  __builtin_memcpy(&r[0], c, sizeof(c));
+}
+template <typename T, int V> __device__ __forceinline__ void store_chunk(T* __restrict__ p, const T (&r)[V]) {
+  constexpr int NCH = (int)(V * sizeof(T) / 16);
+  uint4 c[NCH];
+  __builtin_memcpy(c, &r[0], sizeof(c));
+  uint4* dst = reinterpret_cast<uint4*>(p);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) dst[i] = c[i];
+}
+
 // DGKS selection (see NormRefs in ll_internal.hpp).
 __device__ __forceinline__ bool second_pass_due(const NormRefs& r) { return r.force2 || *r.c1 < r.thr * *r.c0; }
 __device__ __forceinline__ double final_norm2(const NormRefs& r) { return second_pass_due(r) ? *r.c2 : *r.c1; }

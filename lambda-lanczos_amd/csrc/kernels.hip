@@ -21,35 +21,6 @@
 namespace ll {
 
 
-// Sum of `nparts` workgroup partials, formed by EVERY workgroup in the same fixed order (the order of
-// reduce_one_kernel), returned to all lanes.  scratch: 5 doubles of LDS.  kBlock threads.
-__device__ __forceinline__ double fold_partials_all(const double* __restrict__ p, int nparts, double* scratch) {
-  double acc = 0.0;
-  for (int b = threadIdx.x; b < nparts; b += kBlock) acc += p[b];
-  const double tot = block_sum(acc, scratch);
-  if (threadIdx.x == 0) scratch[4] = tot;
-  __syncthreads();
-  return scratch[4];
-}
-// Deferred normalisation (ScaleIn, ll_internal.hpp): 1 / ||w|| for this launch (1 when x is already normalised); workgroup
-// 0 stores ||w||^2 and publishes the previous iteration's scalars.  scratch: 5 doubles of LDS.
-template <typename T> __device__ __forceinline__ double scale_in_factor(const ScaleIn<T>& sc, double* scratch) {
-  if (sc.partials == nullptr) return 1.0;
-  const double tot = fold_partials_all(sc.partials, sc.nparts, scratch);  // the order of scale_publish_kernel
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (sc.c1_out) *sc.c1_out = tot;
-    if (sc.host) {
-      sc.host[0] = sc.alpha ? *sc.alpha : 0.0;
-      sc.host[1] = tot;
-      sc.host[2] = sc.c0 ? *sc.c0 : 0.0;
-      sc.host[3] = tot;
-    }
-  }
-  return 1.0 / sqrt(tot);  // T(1)/norm, LA:77-80
-}
-__device__ __forceinline__ double scale_acc(double s, double a) { return s * a; }
-__device__ __forceinline__ zc scale_acc(double s, zc a) { return zc{s * a.re, s * a.im}; }
-
 // ================================================================= a1/a2/a3: CSR SpMV ("CSR-stream")
 // One tile = a run of whole rows holding <= kSpmvTileNnz nonzeros (built at upload time).  The workgroup streams
 // the tile's (val, col) pairs with perfectly coalesced loads regardless of the row lengths, multiplies by the
@@ -2780,24 +2751,6 @@ template int launch_offset_dot<zc>(int64_t, const zc*, zc*, double, double*, hip
 template int launch_offset_dot<float>(int64_t, const float*, float*, double, double*, hipStream_t);
 template int launch_offset_dot<cf>(int64_t, const cf*, cf*, double, double*, hipStream_t);
 
-// V consecutive elements (V * sizeof(T) a multiple of 16 bytes) as 16-byte pieces; p must be 16-byte aligned.
-template <typename T, int V> __device__ __forceinline__ void load_chunk(const T* __restrict__ p, T (&r)[V]) {
-  constexpr int NCH = (int)(V * sizeof(T) / 16);
-  const uint4* src = reinterpret_cast<const uint4*>(p);
-  uint4 c[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) c[i] = src[i];
-  __builtin_memcpy(&r[0], c, sizeof(c));
-}
-template <typename T, int V> __device__ __forceinline__ void store_chunk(T* __restrict__ p, const T (&r)[V]) {
-  constexpr int NCH = (int)(V * sizeof(T) / 16);
-  uint4 c[NCH];
-  __builtin_memcpy(c, &r[0], sizeof(c));
-  uint4* dst = reinterpret_cast<uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) dst[i] = c[i];
-}
-
 // ================================================================= a1/a2/a3: dense row block (sample1's operator)
 // One wavefront per row: the row streams in with coalesced loads, x comes from L2, the 64 partial sums fold with
 // shuffles; offset, y write and the alpha partial are fused like in the CSR kernels.  Bound by the matrix stream
@@ -2924,16 +2877,6 @@ __device__ __forceinline__ cf hop_value(const StencilGeom& g, int d, bool conj, 
 // phase of the bond whose lower site has the coordinates c
 __device__ __forceinline__ double bond_phase(const StencilGeom& g, int d, const long long (&c)[3]) {
   return g.grad[d][0] * (double)c[0] + g.grad[d][1] * (double)c[1] + g.grad[d][2] * (double)c[2];
-}
-__device__ __forceinline__ void fma_real(double& acc, double r, double x) { acc = fma(r, x, acc); }
-__device__ __forceinline__ void fma_real(double& acc, double r, float x) { acc = fma(r, (double)x, acc); }
-__device__ __forceinline__ void fma_real(zc& acc, double r, zc x) {
-  acc.re = fma(r, x.re, acc.re);
-  acc.im = fma(r, x.im, acc.im);
-}
-__device__ __forceinline__ void fma_real(zc& acc, double r, cf x) {
-  acc.re = fma(r, (double)x.re, acc.re);
-  acc.im = fma(r, (double)x.im, acc.im);
 }
 
 template <typename T, typename IDX>

@@ -267,6 +267,7 @@ struct Tuning {
   bool tl_force = false;           // LL_TL_FORCE=1: build the tiled image even for matrices that are not eligible (parity tests on small cases)
   bool pb_test_all_remote = false; // LL_PB_TEST_ALL_REMOTE=1: own columns are read from the gathered buffer too
   int tridiag_test_jitter_us = 0;  // LL_TRIDIAG_TEST_JITTER_US: random delay of every helper-thread verdict
+  int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
   bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
   std::string iter_trace;          // LL_ITER_TRACE=path: the eigen-solver loop appends one line per collected iteration
@@ -451,11 +452,26 @@ struct SymImage {
            fdst.bytes() + fsrc.bytes();
   }
 };
+
+// Sum of Pauli strings (pauli.hip): the terms grouped by x mask — groups by ascending mask, the terms of a group in the
+// caller's order; that order is the kernel's order of summation
+constexpr int kPauliMaxSites = 30;               // 2^30 states: the local indices of the library are signed 32-bit (n_local < 2^31 - 1)
+constexpr int kPauliTileBytes = 32 << 10;        // LDS tile of one workgroup (four workgroups per CU beside their reduction scratch)
+constexpr int kPauliMaxTileBytes = 64 << 10;     // largest tile pauli_tile_bits may ask for
+struct PauliImage {
+  int n_sites = 0, ngroups = 0;
+  int64_t nterms = 0;
+  DevArray<uint32_t> gx;         // [ngroups]      x mask of the group
+  DevArray<int32_t> gptr;        // [ngroups + 1]  first term of each group
+  DevArray<uint32_t> tz;         // [nterms]       z mask
+  DevArray<double> tc;           // [nterms] (real types) / [nterms][2] (complex: re, im): c_t i^nY_t
+  int64_t device_bytes() const { return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes(); }
+};
 }  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -482,10 +498,11 @@ struct ll_operator {
   int64_t st_stride[3] = {0, 0, 0};  // flattened-index stride of each dimension (last index fastest)
   int64_t st_halo = 0;               // sites of one hyperplane = reach of the operator in the flattened index
   ll::DevArray<void> onsite;         // n_local on-site terms in the real type of T (nullable)
+  ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
-           sym.device_bytes() + dense.bytes() + onsite.bytes();
+           sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -517,6 +534,9 @@ template <typename T> void create_dense(ll_context* ctx, int64_t nr, int64_t nc,
 template <typename T>
 void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin, int64_t n_local, const double* onsite,
                     ll_operator** out);
+// n = 2^n_sites, single GPU; real types take terms with an even number of Y only
+template <typename T>
+void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -608,6 +628,10 @@ int launch_dense_mv(const ll_operator& op, const T* x_full, const T* x_local, T*
 template <typename T>
 int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, const T* halo_hi, T* y, double offset,
                    double* dot_partials, hipStream_t s, const ScaleIn<T>* sc = nullptr);
+// Sum of Pauli strings (op.kind == PAULI; pauli.hip): x = the whole vector, same contract as launch_stencil on one GPU.
+template <typename T>
+int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                 const ScaleIn<T>* sc = nullptr);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

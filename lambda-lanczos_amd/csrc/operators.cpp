@@ -1,5 +1,5 @@
 // Operator construction: the images of a CSR matrix (upload, SpMV tiles, the column split, the PB and tiled builds, their
-// creation-time timing and the kernel choice), the one-triangle and COO forms, the dense, lattice and callback operators, and the
+// creation-time timing and the kernel choice), the one-triangle and COO forms, the dense, lattice, Pauli-string and callback operators, and the
 // accuracy policy that gives every image its form.  The extern "C" entry points (capi.cpp, documented in include/lanczos_hip.h)
 // call in here.
 #include <algorithm>
@@ -725,6 +725,75 @@ void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin
   *out = op.release();
 }
 
+// Sum of Pauli strings (pauli.hip): validate, fold i^nY into the coefficient (a sign for the real types, one of {1, i, -1, -i}
+// for the complex ones), group the terms by x mask — groups by ascending mask, the terms of a group in the caller's order.
+template <typename T>
+void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  use(ctx);
+  LL_REQUIRE(out != nullptr, "null argument (out)");
+  LL_REQUIRE(n_terms >= 0, "n_terms is negative");
+  LL_REQUIRE(terms != nullptr || n_terms == 0, "null argument (terms)");
+  LL_REQUIRE(n_sites >= 1 && n_sites <= kPauliMaxSites,
+             "n_sites must lie in [1, " + std::to_string(kPauliMaxSites) + "] (2^n_sites states, 32-bit local indices)");
+  LL_REQUIRE(ctx->nranks == 1,
+             "a sum of Pauli strings cannot be created on a sharded context (flips of the sites that would number the ranks are "
+             "exchanges between them, which are not built): use a single-GPU context");
+  LL_REQUIRE(n_terms < (int64_t)0x7fffffff, "too many terms");
+  constexpr bool cplx = scalar_traits<T>::is_complex;
+  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
+  std::vector<int64_t> order((size_t)n_terms);
+  double norm = 0.0;
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const ll_pauli_term& q = terms[t];
+    LL_REQUIRE(((q.x_mask | q.z_mask) & ~site_mask) == 0, "term " + std::to_string(t) + ": a mask bit at or above n_sites");
+    LL_REQUIRE(std::isfinite(q.coef), "term " + std::to_string(t) + ": the coefficient is not finite");
+    LL_REQUIRE(cplx || (__builtin_popcountll(q.x_mask & q.z_mask) & 1) == 0,
+               "term " + std::to_string(t) + ": an odd number of Y factors makes the matrix complex; use a complex storage type");
+    order[(size_t)t] = t;
+    norm += std::fabs(q.coef);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return terms[a].x_mask < terms[b].x_mask; });
+  std::vector<uint32_t> gx, tz((size_t)n_terms);
+  std::vector<int32_t> gptr;
+  std::vector<double> tc((size_t)n_terms * (cplx ? 2 : 1));
+  for (int64_t k = 0; k < n_terms; ++k) {
+    const ll_pauli_term& q = terms[order[(size_t)k]];
+    if (gx.empty() || gx.back() != (uint32_t)q.x_mask) {
+      gx.push_back((uint32_t)q.x_mask);
+      gptr.push_back((int32_t)k);
+    }
+    tz[(size_t)k] = (uint32_t)q.z_mask;
+    const int ny = __builtin_popcountll(q.x_mask & q.z_mask) & 3;  // i^nY: 1, i, -1, -i
+    const double c = ny >= 2 ? -q.coef : q.coef;
+    if (cplx) {
+      tc[2 * (size_t)k] = (ny & 1) ? 0.0 : c;
+      tc[2 * (size_t)k + 1] = (ny & 1) ? c : 0.0;
+    } else {
+      tc[(size_t)k] = c;
+    }
+  }
+  gptr.push_back((int32_t)n_terms);
+  const int64_t n = (int64_t)1 << n_sites;
+  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI, n, 0, n);
+  op->nnz = n_terms;
+  op->inf_norm = norm;  // sum_t |c_t|: a bound of every absolute row sum
+  PauliImage im;
+  im.n_sites = n_sites;
+  im.ngroups = (int)gx.size();
+  im.nterms = n_terms;
+  auto upload = [&](auto& dst, const auto& src, const char* what) {
+    typedef typename std::decay_t<decltype(src)>::value_type V;
+    dst = ctx->dev_alloc<V>(std::max<size_t>(src.size(), 1), what);
+    if (!src.empty()) LL_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
+  };
+  upload(im.gx, gx, "Pauli x masks");
+  upload(im.gptr, gptr, "Pauli group offsets");
+  upload(im.tz, tz, "Pauli z masks");
+  upload(im.tc, tc, "Pauli coefficients");
+  op->pauli = std::move(im);
+  *out = op.release();
+}
+
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out) {
   LL_REQUIRE(host_fn != nullptr || dev_fn != nullptr, "null callback");
@@ -746,6 +815,7 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
                                   ll_operator**);                                                                               \
   template void create_dense<T>(ll_context*, int64_t, int64_t, int64_t, const void*, ll_operator**);                            \
   template void create_stencil<T>(ll_context*, const ll_stencil_desc*, int64_t, int64_t, const double*, ll_operator**);        \
+  template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_INST_OPERATORS(double) LL_INST_OPERATORS(zc) LL_INST_OPERATORS(float) LL_INST_OPERATORS(cf)
 

@@ -394,6 +394,30 @@ class StencilOperator(_Operator):
     inf_norm = CsrOperator.inf_norm
 
 
+class PauliOperator(_Operator):
+    """Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t (ll_op_create_pauli_*): `terms` is a sequence of
+    (x_mask, z_mask, coef); bit j of a basis state is site j, a site carries X (x bit only), Z (z bit only) or Y (both).
+    n = 2^n_sites; single-GPU contexts; the real dtypes take terms with an even number of Y only."""
+
+    def __init__(self, ctx, n_sites, terms, dtype=np.float64):
+        terms = list(terms)
+        arr = (capi.PauliTerm * max(len(terms), 1))()
+        for k, (xm, zm, c) in enumerate(terms):
+            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+        self.ctx, self.dtype = ctx, np.dtype(dtype)
+        self.n_sites = int(n_sites)
+        self.n = self.n_local = 1 << self.n_sites if 0 <= self.n_sites < 63 else 0
+        self.row_begin, self.nnz = 0, len(terms)
+        h = C.c_void_p()
+        fn = getattr(lib(), "ll_op_create_pauli_" + _suffix(self.dtype))
+        check(fn(ctx.handle, self.n_sites, len(terms), arr, C.byref(h)))
+        self.handle = h
+
+    def inf_norm(self):
+        """sum_t |coef_t|: an upper bound of every absolute row sum (a safe |eigenvalue_offset|)."""
+        return CsrOperator.inf_norm(self)
+
+
 class HostOperator(_Operator):
     """Unmodified user code: mv_mul(in, out) on numpy arrays, `out` zero-filled on entry (LL:120-126)."""
 

@@ -194,6 +194,79 @@ def lattice_csr(dims, diag=0.0, hop=-1.0, periodic=False, onsite=None, dtype=np.
     return rp, cols[have].astype(np.int32), np.ascontiguousarray(va.astype(dtype))
 
 
+# ------------------------------------------------------------------ spin-1/2 Hamiltonians as sums of Pauli strings
+# A term is (x_mask, z_mask, coef): site j carries X (x bit only), Z (z bit only), Y (both); bit j of a basis state is site j
+# (include/lanczos_hip.h, ll_op_create_pauli_*).
+def heisenberg_terms(L, J=1.0, delta=1.0, periodic=True):
+    """XXZ chain J sum_j (Sx Sx + Sy Sy + delta Sz Sz)_{j, j+1} on L spins 1/2 (S = sigma / 2): three terms per bond."""
+    terms = []
+    for j in range(L if periodic and L > 2 else L - 1):
+        m = (1 << j) | (1 << ((j + 1) % L))
+        terms += [(m, 0, 0.25 * J), (m, m, 0.25 * J), (0, m, 0.25 * J * delta)]
+    return terms
+
+
+def tfim_terms(L, J, h, periodic=False):
+    """Transverse-field Ising chain -J sum_j Z_j Z_{j+1} - h sum_j X_j (Pauli matrices)."""
+    terms = [(0, (1 << j) | (1 << ((j + 1) % L)), -float(J)) for j in range(L if periodic and L > 2 else L - 1)]
+    return terms + [(1 << j, 0, -float(h)) for j in range(L)]
+
+
+def tfim_ground_energy(L, J, h):
+    """Exact ground-state energy of the OPEN transverse-field Ising chain: minus the sum of the singular values of the
+    L x L matrix with h on the diagonal and J on the superdiagonal (free fermions)."""
+    return -float(np.sum(np.linalg.svd(np.diag(np.full(L, float(h))) + np.diag(np.full(L - 1, float(J)), 1), compute_uv=False)))
+
+
+def _parity(v):
+    """popcount(v) mod 2, element-wise (uint64 arrays)."""
+    v = v.copy()
+    for sh in (32, 16, 8, 4, 2, 1):
+        v ^= v >> np.uint64(sh)
+    return (v & np.uint64(1)).astype(np.int64)
+
+
+def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
+    """The matrix of H = sum_t coef_t P_t as CSR, by the definition: row s holds coef_t i^nY_t (-1)^popcount((s ^ x_t) & z_t) in
+    column s ^ x_t.  merge=True: one entry per row and distinct x mask (masks ascending; the coefficients summed in list
+    order, exact zeros dropped).  merge=False: one entry per term and state, in list order, duplicate columns allowed — every
+    term's own magnitude stays visible to an error bound."""
+    n = 1 << int(n_sites)
+    dtype = np.dtype(dtype)
+    cplx = dtype.kind == "c"
+    terms = [(int(x), int(z), float(c)) for x, z, c in terms]
+    s = np.arange(n, dtype=np.uint64)
+    phase = (1.0, 1j, -1.0, -1j)
+
+    def column(x, z, c):
+        ny = bin(x & z).count("1")
+        if not cplx and ny & 1:
+            raise ValueError("a term with an odd number of Y needs a complex dtype")
+        p = phase[ny & 3] * c
+        sign = 1.0 - 2.0 * _parity((s ^ np.uint64(x)) & np.uint64(z))
+        return (sign * p if cplx else sign * p.real).astype(dtype)
+
+    if merge:
+        groups = {}
+        for x, z, c in terms:
+            groups.setdefault(x, []).append((z, c))
+        masks = sorted(groups)
+        vals = np.zeros((n, len(masks)), dtype=np.complex128 if cplx else np.float64)
+        for k, x in enumerate(masks):
+            for z, c in groups[x]:
+                vals[:, k] += column(x, z, c)
+        vals = vals.astype(dtype)
+        cols = np.stack([(s ^ np.uint64(x)).astype(np.int32) for x in masks], 1) if masks else np.zeros((n, 0), np.int32)
+        keep = vals != 0
+        rp = np.concatenate([[0], np.cumsum(keep.sum(1))]).astype(np.int64)
+        return rp, np.ascontiguousarray(cols[keep]), np.ascontiguousarray(vals[keep])
+    T = len(terms)
+    vals = np.stack([column(*t) for t in terms], 1) if T else np.zeros((n, 0), dtype)
+    cols = np.stack([(s ^ np.uint64(x)).astype(np.int32) for x, _, _ in terms], 1) if T else np.zeros((n, 0), np.int32)
+    rp = (np.arange(n + 1, dtype=np.int64) * T)
+    return rp, np.ascontiguousarray(cols.reshape(-1)), np.ascontiguousarray(vals.reshape(-1))
+
+
 # ------------------------------------------------------------------ C++ versions (BASELINE sizes)
 _gen = None
 
