@@ -1,4 +1,4 @@
-// Device-side scalar helpers shared by the HIP translation units (kernels.hip, spmv_pb.hip).
+// Device-side scalar helpers shared by every HIP translation unit (the *.hip files of this directory).
 #pragma once
 
 #include "ll_internal.hpp"

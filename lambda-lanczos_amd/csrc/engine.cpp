@@ -735,7 +735,7 @@ template <typename T> struct LoopState {
   NormRefs refs_prev{nullptr, nullptr, nullptr, 0};
   double t_enqueue = 0.0, t_wait = 0.0;
   int64_t n_second_passes = 0;  // DGKS second passes taken on the host (collect)
-  // Lagged block Gram-Schmidt (kernels.hip, lagged_kernel): ONE sweep over the basis per iteration.  The iteration ends
+  // Lagged block Gram-Schmidt (kernels.hip, lagged_kernel; gs_small.hip on short vectors): ONE sweep over the basis per iteration.  The iteration ends
   // with the raw w_k in work[k & 1], its coefficients g_k = U^H w_k in hbuf[k & 1] and ||w_k||^2 - |g_k|^2 in *lag_c1; the
   // next iteration's operator kernel takes w_k / beta_k as its input and the next sweep writes the corrected u_k.
   bool lagged = false;
@@ -754,7 +754,7 @@ template <typename T> struct LoopState {
   int64_t ld = 0;
   int64_t small_bytes = 0;
 
-  // Pair form (kernels.hip, "pair" section; tools/pair_gs_model.py): TWO iterations per sweep over the basis.  State between
+  // Pair form (gs_pair.hip, gs_small.hip; tools/pair_gs_model.py): TWO iterations per sweep over the basis.  State between
   // sweeps: u_0 .. u_{pair_P-1} complete in the basis; two raw vectors pending, pr1 -> u_P and pr2 -> u_{P+1}, with their
   // measured coefficients (g1p; g2p followed by <u_P, pr2>) and the squared norms of their orthogonal parts (rho1p, rho2p).
   int64_t max_k_hint = 0;     // the loop's max_iteration (sizes the sweeps' partial sums up front, begin_pass)
@@ -780,7 +780,7 @@ template <typename T> struct LoopState {
   // the gate of the pair form: what is neglected is the SQUARE of a relative coefficient, which must stay below the rounding of the
   // storage type (float vectors carry coefficients of ~1e-6 by rounding alone)
   static constexpr double kGate = sizeof(typename scalar_traits<T>::real) == 4 ? 2e-4 : kPairGate;
-  // Pointer table of the software-pipelined sweep (kernels.hip, pair_sweep_pipe_kernel): entry c = stored column c of this pass —
+  // Pointer table of the software-pipelined sweep (gs_pair.hip, pair_sweep_pipe_kernel): entry c = stored column c of this pass —
   // the locked eigenvectors, then u_0, u_1, ... — written on the device, slab by slab (launch_fill_ptrs), when a pass starts and
   // whenever the basis has grown by a slab.
   DevBuf<const T*> vtab;
@@ -1946,14 +1946,10 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
   }
 }
 
-template void lanczos_run<double>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, double*, int64_t*,
-                                  int64_t*, int64_t, double*, double*, ll_run_stats*, const IterationSpec<double>*);
-template void lanczos_run<zc>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, zc*, int64_t*, int64_t*,
-                              int64_t, double*, double*, ll_run_stats*, const IterationSpec<zc>*);
-template void lanczos_run<float>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, float*, int64_t*,
-                                 int64_t*, int64_t, double*, double*, ll_run_stats*, const IterationSpec<float>*);
-template void lanczos_run<cf>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, cf*, int64_t*, int64_t*,
-                              int64_t, double*, double*, ll_run_stats*, const IterationSpec<cf>*);
+#define LL_INST_LANCZOS_RUN(T)                                                                                         \
+  template void lanczos_run<T>(ll_context*, ll_operator*, const ll_lanczos_params&, double*, T*, int64_t*, int64_t*, int64_t, \
+                               double*, double*, ll_run_stats*, const IterationSpec<T>*);
+LL_FOR_EACH_SCALAR(LL_INST_LANCZOS_RUN)
 
 // ================================================================= Exponentiator<T>::run
 namespace {
@@ -2045,14 +2041,10 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   fill_stats(stats, LS, itern, alpha.size(), t_tridiag, t_start);
   if (stats) stats->n_passes = 1;
 }
-template void expo_run<double>(ll_context*, ll_operator*, const ll_expo_params&, double, const double*, double*,
-                               int64_t*, ll_run_stats*);
-template void expo_run<zc>(ll_context*, ll_operator*, const ll_expo_params&, std::complex<double>, const zc*, zc*,
-                           int64_t*, ll_run_stats*);
-template void expo_run<float>(ll_context*, ll_operator*, const ll_expo_params&, double, const float*, float*, int64_t*,
-                              ll_run_stats*);
-template void expo_run<cf>(ll_context*, ll_operator*, const ll_expo_params&, std::complex<double>, const cf*, cf*,
-                           int64_t*, ll_run_stats*);
+#define LL_INST_EXPO_RUN(T)                                                                                            \
+  template void expo_run<T>(ll_context*, ll_operator*, const ll_expo_params&, typename host_scalar<T>::type, const T*, T*, \
+                            int64_t*, ll_run_stats*);
+LL_FOR_EACH_SCALAR(LL_INST_EXPO_RUN)
 
 // ================================================================= Exponentiator<T>::taylor_run (EX:175-210)
 template <typename T>
@@ -2105,26 +2097,12 @@ void taylor_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P, typen
   LL_HIP(hipStreamSynchronize(s));
   *nterms_out = terms;
 }
-template void taylor_run<double>(ll_context*, ll_operator*, const ll_expo_params&, double, const double*, double*,
-                                 int64_t*);
-template void taylor_run<zc>(ll_context*, ll_operator*, const ll_expo_params&, std::complex<double>, const zc*, zc*,
-                             int64_t*);
-template void taylor_run<float>(ll_context*, ll_operator*, const ll_expo_params&, double, const float*, float*,
-                                int64_t*);
-template void taylor_run<cf>(ll_context*, ll_operator*, const ll_expo_params&, std::complex<double>, const cf*, cf*,
-                             int64_t*);
-
-template struct Basis<double>;
-template struct Basis<zc>;
-template struct Basis<float>;
-template struct Basis<cf>;
-template struct RunList<double>;
-template struct RunList<zc>;
-template struct RunList<float>;
-template struct RunList<cf>;
-template struct Engine<double>;
-template struct Engine<zc>;
-template struct Engine<float>;
-template struct Engine<cf>;
+#define LL_INST_ENGINE(T)                                                                                              \
+  template void taylor_run<T>(ll_context*, ll_operator*, const ll_expo_params&, typename host_scalar<T>::type, const T*, T*, \
+                              int64_t*);                                                                                   \
+  template struct Basis<T>;                                                                                                \
+  template struct RunList<T>;                                                                                              \
+  template struct Engine<T>;
+LL_FOR_EACH_SCALAR(LL_INST_ENGINE)
 
 }  // namespace ll

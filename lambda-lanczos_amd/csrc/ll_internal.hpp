@@ -71,6 +71,9 @@ template <> struct scalar_traits<cf> {
   typedef float real;
 };
 template <typename T> using acc_t = typename scalar_traits<T>::acc;
+// Explicit instantiation for the four storage types: every translation unit lists the templates it defines ONCE, in a macro
+// M(T) per file section, and instantiates them with LL_FOR_EACH_SCALAR(M).
+#define LL_FOR_EACH_SCALAR(M) M(double) M(zc) M(float) M(cf)
 
 // ---------------------------------------------------------------- errors
 void set_error(const std::string& msg);
@@ -350,6 +353,14 @@ struct ll_context {
   void* ensure_cb_stage(size_t bytes);
   void sync();
 };
+namespace ll {
+// The launcher of a publishing kernel takes the event over (and hangs it on its launch: LL_LAUNCH_STOP); null: none pending.
+inline hipEvent_t take_stop(ll_context* ctx) {
+  hipEvent_t stop = ctx->stop_next;
+  ctx->stop_next = nullptr;
+  return stop;
+}
+}  // namespace ll
 
 // ---------------------------------------------------------------- SpMV images of an operator
 // Every image owns its arrays and knows its own geometry; a builder fills a local image and moves it into the operator
@@ -365,6 +376,11 @@ struct CsrImage {
   bool rp64 = false;
   int64_t device_bytes() const { return row_ptr.bytes() + col.bytes() + val.bytes() + tiles.bytes(); }
 };
+// f(RP{}) with RP = the type of an image's row offsets: the one place that turns CsrImage::rp64 into a template argument
+template <typename F> void for_row_ptr_type(bool rp64, F&& f) {
+  if (rp64) f(int64_t{});
+  else f(int32_t{});
+}
 
 // Propagation-blocked image (spmv_pb.hip).  Column-block table order: the blocks over the rank's OWN columns first (their x
 // slice is the local shard, no exchange needed), then, gather chunk by gather chunk, the blocks over the other ranks' columns
@@ -478,7 +494,7 @@ struct ll_operator {
   int64_t n = 0, n_local = 0, row_begin = 0, nnz = 0;
   int64_t n_shard = 0;  // padded shard length used by the all-gather (= n when not sharded)
   double inf_norm = -1.0;  // max absolute row sum of the local rows (-1: unknown)
-  // CSR-stream image (kernels.hip launch_spmv).  Sharded contexts, CSR-stream selected: the same rows split by column ownership
+  // CSR-stream image (op_kernels.hip launch_spmv).  Sharded contexts, CSR-stream selected: the same rows split by column ownership
   // (operators.cpp build_csr_split) — csr_own holds the entries over the rank's OWN columns (indices rebased to the local shard; their
   // product needs no exchange and runs under the all-gather), csr_rem the entries over the other ranks' columns (global indices
   // into the gathered vector).
@@ -545,7 +561,10 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
 void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
-// ---------------------------------------------------------------- kernel launchers (kernels.hip)
+// ---------------------------------------------------------------- kernel launchers
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip; everything
+// from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
+// launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
 
 // Deferred normalisation (a8 folded into the next a1; single-GPU whole-loop drivers, operators that gather x themselves):
@@ -570,7 +589,7 @@ template <typename T> struct ScaleIn {
 template <typename T>
 int launch_spmv(const ll_operator& op, const T* x_full, const T* x_local, T* y, double offset, double* dot_partials,
                 hipStream_t s, const ScaleIn<T>* sc = nullptr, int part = 0);
-// build helpers of the column split (kernels.hip): own-column entries per row; scatter into the two halves
+// build helpers of the column split (op_kernels.hip): own-column entries per row; scatter into the two halves
 template <typename T> void launch_csr_count_own(const ll_operator& op, int32_t* own_cnt, hipStream_t s);
 template <typename T> void launch_csr_split(const ll_operator& op, const CsrImage& own, const CsrImage& rem, hipStream_t s);
 // Same contract, propagation-blocked kernels (op.spmv_kind == LL_SPMV_PB; spmv_pb.hip): phase 1 over the own-column
@@ -578,7 +597,7 @@ template <typename T> void launch_csr_split(const ll_operator& op, const CsrImag
 // per op.gather), then phase 2.  The pieces are exposed so that the sharded driver can run the own-column part under
 // the all-gather and each chunk's part as soon as that chunk has arrived.
 // xnorm2 (nullable device scalar): x is an UNNORMALISED vector w with ||w||^2 = *xnorm2; the kernels work with w / ||w||
-// (lagged Gram-Schmidt, kernels.hip).
+// (lagged Gram-Schmidt, kernels.hip / gs_pair.hip).
 template <typename T>
 int launch_spmv_pb(const ll_operator& op, const T* x_gathered, const T* x_own, const T* x_local, T* y, double offset,
                    double* dot_partials, hipStream_t s, const double* xnorm2 = nullptr);
@@ -691,7 +710,7 @@ constexpr int kLaggedFullStrips = 200;
 template <typename T>
 int launch_lagged(int64_t n, T* w, const BasisSegs<T>& segs, const Lagged<T>& lg, const ThreeTerm<T>& tt, double* partials,
                   int pieces, int64_t small_limit, hipStream_t s);  // vectors below small_limit bytes: lagged_small_kernel
-// The pair form (two iterations per sweep; kernels.hip, "pair" section; tools/pair_gs_model.py is the executable specification).
+// The pair form (two iterations per sweep; gs_pair.hip; tools/pair_gs_model.py is the executable specification).
 // Streaming geometry only; 2 * reals * K + 5 * reals + 1 <= kLaggedMaxCols columns per workgroup (K stored columns).
 constexpr double kPairGate = 1e-8;  // largest relative coefficient the pair form accepts in double precision (second-order terms
                                     // stay below 1e-16; float storage: 2e-4, engine.cpp)
@@ -708,7 +727,7 @@ void launch_pair_predict(int P, int L, int reals, const double* g1, const double
                          const double* lambda, double* p3, double* p4, hipStream_t s);
 // r4 holds y2 = A (r3 / |r3|) on entry; the sweep forms r4 = y2 - (e2 / |r3|) r3 - (|r3| / rho2) r2 on the fly
 // One workgroup keeps 4 x (2 reals Pl + 5 reals + 1) columns in LDS: a sweep over more stored vectors than that is split into
-// launches over consecutive groups of them (same results bit for bit, kernels.hip); part4: scratch n-vector for the hand-over
+// launches over consecutive groups of them (same results bit for bit, gs_pair.hip); part4: scratch n-vector for the hand-over
 // (touched only when there is more than one group).
 constexpr int kPairFirst = 1, kPairLast = 2;
 template <typename T> constexpr int pair_sweep_max_vecs() {

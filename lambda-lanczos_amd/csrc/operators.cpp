@@ -817,6 +817,6 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
   template void create_stencil<T>(ll_context*, const ll_stencil_desc*, int64_t, int64_t, const double*, ll_operator**);        \
   template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
-LL_INST_OPERATORS(double) LL_INST_OPERATORS(zc) LL_INST_OPERATORS(float) LL_INST_OPERATORS(cf)
+LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 
 }  // namespace ll

@@ -197,6 +197,6 @@ int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double*
 }
 #define LL_INST_PAULI(T) \
   template int launch_pauli<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const ScaleIn<T>*);
-LL_INST_PAULI(double) LL_INST_PAULI(zc) LL_INST_PAULI(float) LL_INST_PAULI(cf)
+LL_FOR_EACH_SCALAR(LL_INST_PAULI)
 
 }  // namespace ll

@@ -208,7 +208,7 @@ __global__ __launch_bounds__(TH) void pb_phase1(int nrb, int blk_first, const in
                                                         double* __restrict__ blockmax, long long p_dump,
                                                         const double* __restrict__ xnorm2) {
   extern __shared__ double lds[];
-  // xnorm2 (nullable): the input is an UNNORMALISED vector w with ||w||^2 = *xnorm2 (lagged Gram-Schmidt, kernels.hip): the
+  // xnorm2 (nullable): the input is an UNNORMALISED vector w with ||w||^2 = *xnorm2 (lagged Gram-Schmidt, kernels.hip / gs_pair.hip): the
   // slice is scaled by 1 / ||w|| while it is staged
   const double xs_fac = xnorm2 ? 1.0 / sqrt(*xnorm2) : 1.0;
   __shared__ double bm_red[TH / 64 + 1];
@@ -1749,6 +1749,6 @@ template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hip
                                          double*, hipStream_t, const double*, int);                                 \
   template void csr_check_device<T>(ll_operator*);                                                                 \
   template int launch_x_max<T>(int64_t, const T*, double*, hipStream_t);
-LL_INST_PB(double) LL_INST_PB(zc) LL_INST_PB(float) LL_INST_PB(cf)
+LL_FOR_EACH_SCALAR(LL_INST_PB)
 
 }  // namespace ll

@@ -312,8 +312,7 @@ int launch_spmv_sym(const ll_operator& op, const T* x, T* y, double offset, doub
   sym_opt_in_lds<T>();
   const int nx = launch_x_max<T>(op.n, x, op.sym.xmax.get(), s);
   // (the kernel that publishes an iteration's scalars may complete that iteration's event itself: ll_context::stop_next)
-  hipEvent_t stop = op.ctx->stop_next;
-  op.ctx->stop_next = nullptr;
+  hipEvent_t stop = take_stop(op.ctx);
   LL_LAUNCH_STOP(stop, (sym_spmv_kernel<T>), dim3(op.sym.nrb), dim3(kPbThreads), sym_lds_bytes<T>(op.sym.rb_rows, op.sym.halo), s,
                  op.sym.rb_rows, op.sym.halo, op.n, (const int64_t*)op.sym.qptr.get(), (const T*)op.sym.val.get(),
                  (const uint4*)op.sym.idx.get(), (const int16_t*)op.sym.rexp.get(), (const double*)op.sym.xmax.get(), nx, x, y, offset,
@@ -327,6 +326,6 @@ int launch_spmv_sym(const ll_operator& op, const T* x, T* y, double offset, doub
   template int sym_rows_for<T>(int64_t, int64_t);                                                                   \
   template void sym_build<T>(const ll_operator&, SymImage&, const int64_t*, const int32_t*, const T*);              \
   template int launch_spmv_sym<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const double*);
-LL_INST_SYM(double) LL_INST_SYM(zc) LL_INST_SYM(float) LL_INST_SYM(cf)
+LL_FOR_EACH_SCALAR(LL_INST_SYM)
 
 }  // namespace ll

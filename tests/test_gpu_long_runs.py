@@ -279,7 +279,7 @@ def test_streaming_one_sweep_kernel_over_a_whole_run_matches_the_reference(ctx, 
 def test_run_beyond_the_column_capacity_of_one_sweep_launch_matches_the_reference(ctx, llenv, form):
     """800 x 800 Laplacian, smallest pair, offset -8 (5.12 MB vectors): the REAL reference needs 2 557 iterations (85 minutes on one core) — more
     stored vectors than one workgroup of the pair sweep holds coefficient columns for (2 497), so from there on every sweep of the
-    default form is two launches (kernels.hip pair_sweep_kernel; bit-identical to an unsplit sweep by construction,
+    default form is two launches (gs_pair.hip pair_sweep_kernel; bit-identical to an unsplit sweep by construction,
     test_split_sweeps_change_no_bit) — nothing forced, nothing hooked.  Every alpha / beta of the run, count, eigenvalue, sampled
     eigenvector entries and the residual against the fixture; `one_sweep` (LL_PAIR_GS=0) runs the same length in the form the
     pair form hands over to at 4 992 stored vectors."""

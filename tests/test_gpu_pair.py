@@ -1,4 +1,4 @@
-"""The pair form of the Gram-Schmidt step — TWO Lanczos iterations per sweep over the basis (kernels.hip "pair" section,
+"""The pair form of the Gram-Schmidt step — TWO Lanczos iterations per sweep over the basis (gs_pair.hip, gs_small.hip,
 LoopState::enqueue_pair; tools/pair_gs_model.py is the executable specification) — against the reference's sequential
 modified Gram-Schmidt (LL:260 -> LA:132-144) through the oracle, and against the two forms it replaces on the same operator:
     LL_FUSE_LAUNCHES=1   two sweeps per iteration (multi-dot, multi-axpy)
@@ -231,7 +231,7 @@ def test_pair_form_in_restart_passes_with_locked_eigenvectors(ctx, oracle, llenv
 def test_split_sweeps_change_no_bit(ctx, llenv, name, split):
     """One workgroup of the pair sweep keeps 4 x (2 R K + 5 R + 1) partial columns in LDS: beyond K = 2 497 stored vectors (1 247
     complex) the sweep is split into launches over consecutive groups of the stored vectors, the three running strips handed over
-    through memory (kernels.hip pair_sweep_kernel).  Every coefficient column is summed in exactly one launch over the same strips
+    through memory (gs_pair.hip pair_sweep_kernel).  Every coefficient column is summed in exactly one launch over the same strips
     by the same waves, a strip written and read back is the same bits: with the group size forced down (LL_TEST_PAIR_SPLIT: ragged
     groups, one vector per launch) whole runs — restart passes behind locked vectors included — reproduce the unsplit run bit for
     bit: alpha, beta, counts, eigenvalues, eigenvectors."""

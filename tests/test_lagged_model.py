@@ -1,4 +1,4 @@
-"""The algebra of the one-sweep (lagged, compensated) Gram-Schmidt form (kernels.hip: lagged_kernel,
+"""The algebra of the one-sweep (lagged, compensated) Gram-Schmidt form (kernels.hip / gs_small.hip: lagged_kernel,
 lagged_fold_kernel) in numpy, at a size the CPU suite runs in seconds: the statements the design rests on.  The GPU
 kernels are checked against the two-sweep form and the oracle in tests/test_gpu_round3.py; this file pins the scheme
 itself (tools/lagged_gs_model.py is the same model at the size quoted in DESIGN.md)."""

@@ -1,5 +1,5 @@
 """The algebra of the pair form of the Gram-Schmidt step — two Lanczos iterations per sweep over the basis (DESIGN.md 3.2;
-kernels.hip "pair" section, LoopState::enqueue_pair) — in numpy, at a size the CPU suite runs in seconds.  tools/pair_gs_model.py
+gs_pair.hip, LoopState::enqueue_pair) — in numpy, at a size the CPU suite runs in seconds.  tools/pair_gs_model.py
 is the executable specification the device kernels were written from (same launches, same formulas, real and complex); the GPU
 kernels themselves are checked against the oracle and the real reference in tests/test_gpu_pair.py / test_gpu_long_runs.py."""
 import importlib.util

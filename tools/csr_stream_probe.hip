@@ -1,4 +1,4 @@
-// Kernel-quality probe for the CSR-stream SpMV (csrc/kernels.hip: spmv_stream) on matrices whose gathers are LOCAL
+// Kernel-quality probe for the CSR-stream SpMV (csrc/op_kernels.hip: spmv_stream) on matrices whose gathers are LOCAL
 // (banded random, 5-point Laplacian) next to the uniformly random pattern of config 3: how much of the gap to the HBM
 // roofline is the gather and how much is the kernel's own latency chain (tile_rows -> row offsets -> columns -> x ->
 // LDS -> barrier -> row offsets again -> fold)?

@@ -1,4 +1,4 @@
-"""numpy model of the one-sweep (lagged) block Gram-Schmidt form of DESIGN.md section 3.2 (kernels.hip: lagged_kernel,
+"""numpy model of the one-sweep (lagged) block Gram-Schmidt form of DESIGN.md section 3.2 (kernels.hip / gs_small.hip: lagged_kernel,
 lagged_fold_kernel), against Lanczos with full re-orthogonalisation on the same matrix and start vector.
 
     python tools/lagged_gs_model.py            -> profiles/r03_lagged_gs_model.txt
