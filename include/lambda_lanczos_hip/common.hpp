@@ -60,6 +60,10 @@ template <typename T> struct abi;
     static int create_pauli(ll_context* c, int32_t ns, int64_t nt, const ll_pauli_term* t, ll_operator** o) {            \
       return ll_op_create_pauli_##SFX(c, ns, nt, t, o);                                                                  \
     }                                                                                                                    \
+    static int create_pauli_sector(ll_context* c, int32_t ns, int32_t nd, int64_t nt, const ll_pauli_term* t,            \
+                                   ll_operator** o) {                                                                    \
+      return ll_op_create_pauli_sector_##SFX(c, ns, nd, nt, t, o);                                                       \
+    }                                                                                                                    \
     static int create_host(ll_context* c, int64_t n, int (*fn)(const void*, void*, int64_t, void*), void* user,          \
                            ll_operator** o) {                                                                            \
       return ll_op_create_host_##SFX(c, n, reinterpret_cast<HOSTFN>(fn), user, o);                                       \
@@ -290,6 +294,29 @@ template <typename T> class PauliOperator : public DeviceOperator<T> {
     this->adopt(op, n, n);
   }
   // sum_t |coef_t|: an upper bound of every absolute row sum (DeviceOperator::inf_norm() returns it)
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
+  }
+};
+
+// The same Hamiltonian on one magnetisation sector: vectors hold the C(n_sites, n_down) amplitudes of the states with n_down set
+// bits (a set bit is sigma_z = -1), in ascending integer order; size() returns that number.  H must conserve total S_z
+// (Heisenberg, XXZ, J1-J2, Dzyaloshinskii-Moriya, z fields): one that does not is refused with an Error that names the x mask
+// at fault (ll_op_create_pauli_sector_*).
+template <typename T> class PauliSectorOperator : public DeviceOperator<T> {
+ public:
+  PauliSectorOperator(int n_sites, int n_down, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : DeviceOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
+    int64_t n = 0, n_local = 0, n_terms = 0;
+    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
+    if (rc != LL_OK) (void)ll_op_destroy(op);
+    check(rc);
+    this->adopt(op, n, n_local);
+  }
   int64_t device_bytes() const {
     int64_t b = 0;
     check(ll_op_device_bytes(this->get(), &b));

@@ -53,7 +53,9 @@ extern "C" {
                              * 5: additive — ll_ctx_set_tuning (the test hooks and geometry overrides left the environment),
                              *    ll_comm_transport, ll_bandwidth_probe, ll_op_tiled_layout; no struct changed;
                              *    also additive under minor 5 — ll_op_create_csr_sym_* (one stored triangle), the one-triangle
-                             *    SpMV kernel id, ll_op_device_bytes; no struct changed */
+                             *    SpMV kernel id, ll_op_device_bytes; no struct changed;
+                             *    also additive under minor 5 — ll_op_create_pauli_sector_* (one S_z sector; the minor stays 5:
+                             *    no struct changed, and callers that need these entry points find them by name) */
 
 enum {
   LL_OK = 0,
@@ -274,6 +276,38 @@ int ll_op_create_pauli_d(ll_context* ctx, int32_t n_sites, int64_t n_terms, cons
 int ll_op_create_pauli_z(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
 int ll_op_create_pauli_s(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
 int ll_op_create_pauli_c(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+
+/* (7) the same sum of Pauli strings on ONE MAGNETISATION SECTOR, for an H that conserves total S_z (Heisenberg, XXZ, J1-J2,
+ *     Dzyaloshinskii-Moriya, each with or without a z field) — the space an exact-diagonalisation code works in.
+ *     Conventions of (6): bit j of s is site j, a SET bit is sigma_z = -1.  The sector (n_sites, n_down) is the set of states with
+ *     popcount(s) = n_down in ASCENDING integer order: state number i is s_i, 0 <= i < D = C(n_sites, n_down), and the operator
+ *     acts on vectors of length D,
+ *         y(i) = sum_g w_g(s_i) v(rank(s_i ^ X_g)),   over the groups g (distinct x masks X_g) whose s_i ^ X_g lies in the sector,
+ *     with the groups, the term order, the folded i^nY and the weights w_g of (6).  rank() is the inverse of i -> s_i.
+ *     LIMITS: those of (6) — 1 <= n_sites <= 30, every mask bit below n_sites, finite coefficients, an even nY for the real types,
+ *     a single-GPU context — and 0 <= n_down <= n_sites.
+ *     CONSERVATION: an H that does not commute with total S_z is refused with LL_ERR_INVALID; the message names the x mask of the
+ *     first offending group.  The rule, per group with X_g != 0: over every assignment of the sites the group touches (X_g and
+ *     its z masks) for which flipping X_g changes the number of set bits, the weight w_g — summed in the kernel's order, in double —
+ *     must be exactly 0.0.  That is exact for the models above (a Heisenberg bond gives c + (-c) on aligned spins) and refuses the
+ *     transverse-field Ising chain, a lone XX term, J_x != J_y and every x mask with an odd number of bits that carries weight.  A
+ *     group that touches more than 20 sites is refused too: the check visits 2^sites assignments and cannot be made.
+ *     The image is the term tables, the D states (4 D bytes) and two rank tables of at most 2^15 entries each
+ *     (rank(s) = lo_rank[low bits of s] + hi_rank[the other bits]); ll_op_device_bytes counts them.  One apply moves between
+ *     (2 sizeof(T) + 4) D bytes (every gathered partner found in cache) and ((G + 2) sizeof(T) + 4) D, G = the x masks != 0.
+ *     ACCURACY: as (6), and more: per state the same fma chain as (6) forms, without the groups that leave the sector (their weight
+ *     is exactly 0) — applied to a vector embedded in 2^n_sites zeros, (6) gives the same bits.  The same bits run to run and
+ *     for every block size.
+ *     Queries: ll_op_info reports n = n_local = D and the number of TERMS as nnz_local; ll_op_inf_norm returns sum_t |coef_t|;
+ *     ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID (not a CSR operator), ll_op_accuracy the component-wise class. */
+int ll_op_create_pauli_sector_d(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms_host,
+                                ll_operator** out);
+int ll_op_create_pauli_sector_z(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms_host,
+                                ll_operator** out);
+int ll_op_create_pauli_sector_s(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms_host,
+                                ll_operator** out);
+int ll_op_create_pauli_sector_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms_host,
+                                ll_operator** out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

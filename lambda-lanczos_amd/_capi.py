@@ -166,6 +166,8 @@ PROTOTYPES = {
     "ll_op_create_stencil_z": (C.c_int, [vp, P(StencilDesc), i64, i64, vp, P(vp)]),
     "ll_op_create_pauli_d": (C.c_int, [vp, C.c_int32, i64, P(PauliTerm), P(vp)]),
     "ll_op_create_pauli_z": (C.c_int, [vp, C.c_int32, i64, P(PauliTerm), P(vp)]),
+    "ll_op_create_pauli_sector_d": (C.c_int, [vp, C.c_int32, C.c_int32, i64, P(PauliTerm), P(vp)]),
+    "ll_op_create_pauli_sector_z": (C.c_int, [vp, C.c_int32, C.c_int32, i64, P(PauliTerm), P(vp)]),
     "ll_op_create_host_d": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_host_z": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_device_d": (C.c_int, [vp, i64, DEV_MV_FN, vp, P(vp)]),

@@ -271,6 +271,7 @@ struct Tuning {
   bool pb_test_all_remote = false; // LL_PB_TEST_ALL_REMOTE=1: own columns are read from the gathered buffer too
   int tridiag_test_jitter_us = 0;  // LL_TRIDIAG_TEST_JITTER_US: random delay of every helper-thread verdict
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
+  int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
   std::string iter_trace;          // LL_ITER_TRACE=path: the eigen-solver loop appends one line per collected iteration
@@ -483,11 +484,31 @@ struct PauliImage {
   DevArray<double> tc;           // [nterms] (real types) / [nterms][2] (complex: re, im): c_t i^nY_t
   int64_t device_bytes() const { return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes(); }
 };
+// The same sum on one S_z sector (pauli_sector.hip): the term tables above, the sector's states in ascending order, and the
+// two tables that give a state's index back: rank(s) = lo_rank[s & (2^h - 1)] + hi_rank[s >> h].  With the set bits of s at
+// p_1 < ... < p_m the index is sum_k C(p_k, k); the low bits' share depends on them alone, the others' on them alone too,
+// since popcount(low bits) = n_down - popcount(the others).
+constexpr int kPauliSectorBlockBits = 10;        // indices of a workgroup's block: one pass of kBlock lanes with four states each
+constexpr int kPauliSectorMaxSupport = 20;       // creation's conservation check enumerates 2^|support| assignments per group
+struct PauliSectorImage {
+  int n_sites = 0, n_down = 0, ngroups = 0, h = 0;
+  int64_t nterms = 0, dim = 0;   // dim = C(n_sites, n_down)
+  DevArray<uint32_t> gx;
+  DevArray<int32_t> gptr;
+  DevArray<uint32_t> tz;
+  DevArray<double> tc;
+  DevArray<uint32_t> states;     // [dim]                 the states of the sector, ascending
+  DevArray<uint32_t> lo_rank;    // [2^h]
+  DevArray<uint32_t> hi_rank;    // [2^(n_sites - h)]
+  int64_t device_bytes() const {
+    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + states.bytes() + lo_rank.bytes() + hi_rank.bytes();
+  }
+};
 }  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -515,10 +536,12 @@ struct ll_operator {
   int64_t st_halo = 0;               // sites of one hyperplane = reach of the operator in the flattened index
   ll::DevArray<void> onsite;         // n_local on-site terms in the real type of T (nullable)
   ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
+  ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
-           sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes();
+           sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes() +
+           pauli_sector.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -553,6 +576,10 @@ void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin
 // n = 2^n_sites, single GPU; real types take terms with an even number of Y only
 template <typename T>
 void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out);
+// n = C(n_sites, n_down): the same terms on the states with n_down set bits; refuses an H that does not conserve S_z
+template <typename T>
+void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms,
+                         ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -562,7 +589,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -651,6 +678,10 @@ int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, co
 template <typename T>
 int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                  const ScaleIn<T>* sc = nullptr);
+// The same on one S_z sector (op.kind == PAULI_SECTOR; pauli_sector.hip): x, y hold C(n_sites, n_down) elements.
+template <typename T>
+int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                        const ScaleIn<T>* sc = nullptr);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

@@ -725,10 +725,18 @@ void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin
   *out = op.release();
 }
 
-// Sum of Pauli strings (pauli.hip): validate, fold i^nY into the coefficient (a sign for the real types, one of {1, i, -1, -i}
-// for the complex ones), group the terms by x mask — groups by ascending mask, the terms of a group in the caller's order.
+// Sum of Pauli strings (pauli.hip, pauli_sector.hip): validate, fold i^nY into the coefficient (a sign for the real types, one
+// of {1, i, -1, -i} for the complex ones), group the terms by x mask — groups by ascending mask, the terms of a group in the
+// caller's order.
+namespace {
+struct PauliTables {
+  std::vector<uint32_t> gx, tz;   // x mask per group, z mask per term
+  std::vector<int32_t> gptr;      // [groups + 1] first term of each group
+  std::vector<double> tc;         // per term: c i^nY (real types), (re, im) of it (complex types)
+  double norm = 0.0;              // sum_t |c_t|
+};
 template <typename T>
-void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+PauliTables pauli_tables(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
   use(ctx);
   LL_REQUIRE(out != nullptr, "null argument (out)");
   LL_REQUIRE(n_terms >= 0, "n_terms is negative");
@@ -742,7 +750,7 @@ void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pa
   constexpr bool cplx = scalar_traits<T>::is_complex;
   const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
   std::vector<int64_t> order((size_t)n_terms);
-  double norm = 0.0;
+  PauliTables pt;
   for (int64_t t = 0; t < n_terms; ++t) {
     const ll_pauli_term& q = terms[t];
     LL_REQUIRE(((q.x_mask | q.z_mask) & ~site_mask) == 0, "term " + std::to_string(t) + ": a mask bit at or above n_sites");
@@ -750,47 +758,151 @@ void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pa
     LL_REQUIRE(cplx || (__builtin_popcountll(q.x_mask & q.z_mask) & 1) == 0,
                "term " + std::to_string(t) + ": an odd number of Y factors makes the matrix complex; use a complex storage type");
     order[(size_t)t] = t;
-    norm += std::fabs(q.coef);
+    pt.norm += std::fabs(q.coef);
   }
   std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return terms[a].x_mask < terms[b].x_mask; });
-  std::vector<uint32_t> gx, tz((size_t)n_terms);
-  std::vector<int32_t> gptr;
-  std::vector<double> tc((size_t)n_terms * (cplx ? 2 : 1));
+  pt.tz.resize((size_t)n_terms);
+  pt.tc.resize((size_t)n_terms * (cplx ? 2 : 1));
   for (int64_t k = 0; k < n_terms; ++k) {
     const ll_pauli_term& q = terms[order[(size_t)k]];
-    if (gx.empty() || gx.back() != (uint32_t)q.x_mask) {
-      gx.push_back((uint32_t)q.x_mask);
-      gptr.push_back((int32_t)k);
+    if (pt.gx.empty() || pt.gx.back() != (uint32_t)q.x_mask) {
+      pt.gx.push_back((uint32_t)q.x_mask);
+      pt.gptr.push_back((int32_t)k);
     }
-    tz[(size_t)k] = (uint32_t)q.z_mask;
+    pt.tz[(size_t)k] = (uint32_t)q.z_mask;
     const int ny = __builtin_popcountll(q.x_mask & q.z_mask) & 3;  // i^nY: 1, i, -1, -i
     const double c = ny >= 2 ? -q.coef : q.coef;
     if (cplx) {
-      tc[2 * (size_t)k] = (ny & 1) ? 0.0 : c;
-      tc[2 * (size_t)k + 1] = (ny & 1) ? c : 0.0;
+      pt.tc[2 * (size_t)k] = (ny & 1) ? 0.0 : c;
+      pt.tc[2 * (size_t)k + 1] = (ny & 1) ? c : 0.0;
     } else {
-      tc[(size_t)k] = c;
+      pt.tc[(size_t)k] = c;
     }
   }
-  gptr.push_back((int32_t)n_terms);
+  pt.gptr.push_back((int32_t)n_terms);
+  return pt;
+}
+// the four term tables of an image (PauliImage, PauliSectorImage) on the device
+template <typename V> void pauli_upload(ll_context* ctx, DevArray<V>& dst, const std::vector<V>& src, const char* what) {
+  dst = ctx->dev_alloc<V>(std::max<size_t>(src.size(), 1), what);
+  if (!src.empty()) LL_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
+}
+template <typename Image> void pauli_upload_tables(ll_context* ctx, Image& im, const PauliTables& pt) {
+  im.ngroups = (int)pt.gx.size();
+  im.nterms = (int64_t)pt.tz.size();
+  pauli_upload(ctx, im.gx, pt.gx, "Pauli x masks");
+  pauli_upload(ctx, im.gptr, pt.gptr, "Pauli group offsets");
+  pauli_upload(ctx, im.tz, pt.tz, "Pauli z masks");
+  pauli_upload(ctx, im.tc, pt.tc, "Pauli coefficients");
+}
+
+// S_z conservation, group by group: over every assignment of the bits the group touches (its x mask and its z masks) for which
+// flipping the x mask changes the number of set bits, the group's weight — summed as the kernel sums it, in double, terms in
+// order — must be exactly 0.  R = doubles per coefficient (2: re, im, summed separately as the kernel does).
+void pauli_require_sz_conserving(const PauliTables& pt, int R) {
+  for (size_t g = 0; g < pt.gx.size(); ++g) {
+    const uint32_t X = pt.gx[g];
+    if (X == 0) continue;
+    char hex[16];
+    std::snprintf(hex, sizeof hex, "0x%x", (unsigned)X);
+    const std::string who = "the terms with x mask " + std::string(hex);
+    uint32_t U = X;
+    for (int32_t k = pt.gptr[g]; k < pt.gptr[g + 1]; ++k) U |= pt.tz[(size_t)k];
+    LL_REQUIRE(__builtin_popcount(U) <= kPauliSectorMaxSupport,
+               who + " act on " + std::to_string(__builtin_popcount(U)) + " sites: the S_z conservation check cannot be made for more than " +
+                   std::to_string(kPauliSectorMaxSupport) + " (it visits every assignment of them)");
+    const int px = __builtin_popcount(X);
+    uint32_t s = 0;
+    do {  // every subset s of U
+      if (2 * __builtin_popcount(s & X) != px) {
+        for (int r = 0; r < R; ++r) {
+          double w = 0.0;
+          for (int32_t k = pt.gptr[g]; k < pt.gptr[g + 1]; ++k) {
+            const double c = pt.tc[(size_t)k * R + r];
+            w += (__builtin_popcount((s ^ X) & pt.tz[(size_t)k]) & 1) ? -c : c;
+          }
+          LL_REQUIRE(w == 0.0, who + " do not conserve S_z (they change the number of flipped spins with a weight that is not "
+                                     "zero): a magnetisation sector needs an H that commutes with total S_z");
+        }
+      }
+      s = (s - U) & U;
+    } while (s != 0);
+  }
+}
+}  // namespace
+
+template <typename T>
+void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
   const int64_t n = (int64_t)1 << n_sites;
   std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI, n, 0, n);
   op->nnz = n_terms;
-  op->inf_norm = norm;  // sum_t |c_t|: a bound of every absolute row sum
+  op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
   PauliImage im;
   im.n_sites = n_sites;
-  im.ngroups = (int)gx.size();
-  im.nterms = n_terms;
-  auto upload = [&](auto& dst, const auto& src, const char* what) {
-    typedef typename std::decay_t<decltype(src)>::value_type V;
-    dst = ctx->dev_alloc<V>(std::max<size_t>(src.size(), 1), what);
-    if (!src.empty()) LL_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
-  };
-  upload(im.gx, gx, "Pauli x masks");
-  upload(im.gptr, gptr, "Pauli group offsets");
-  upload(im.tz, tz, "Pauli z masks");
-  upload(im.tc, tc, "Pauli coefficients");
+  pauli_upload_tables(ctx, im, pt);
   op->pauli = std::move(im);
+  *out = op.release();
+}
+
+// The same terms on the sector of n_down set bits (pauli_sector.hip).  The states and the two rank tables are built here, on the
+// host: one pass over the C(n_sites, n_down) states in ascending order.
+template <typename T>
+void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms,
+                         ll_operator** out) {
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
+  LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
+  pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
+  // binom[p][k] = C(p, k), p <= n_sites <= 30: below 2^32
+  std::vector<std::vector<uint64_t>> binom((size_t)n_sites + 1, std::vector<uint64_t>((size_t)n_sites + 2, 0));
+  for (int p = 0; p <= n_sites; ++p) {
+    binom[(size_t)p][0] = 1;
+    for (int k = 1; k <= p; ++k) binom[(size_t)p][(size_t)k] = binom[(size_t)p - 1][(size_t)k - 1] + binom[(size_t)p - 1][(size_t)k];
+  }
+  const int64_t dim = (int64_t)binom[(size_t)n_sites][(size_t)n_down];
+  const int h = (n_sites + 1) / 2, hb = n_sites - h;  // low / other bits: both tables at most 2^15 entries
+  // rank(s) = sum_k C(p_k, k) over the set bits p_1 < p_2 < ...: the low bits count k from 1, the others from
+  // n_down - popcount(others) + 1 (entries no state of the sector reaches stay 0)
+  std::vector<uint32_t> lo_rank((size_t)1 << h, 0), hi_rank((size_t)1 << hb, 0);
+  for (uint32_t lo = 0; lo < ((uint32_t)1 << h); ++lo) {
+    if (__builtin_popcount(lo) > n_down) continue;
+    uint64_t r = 0;
+    int k = 0;
+    for (int p = 0; p < h; ++p)
+      if (lo >> p & 1u) r += binom[(size_t)p][(size_t)++k];
+    lo_rank[lo] = (uint32_t)r;
+  }
+  for (uint32_t hi = 0; hi < ((uint32_t)1 << hb); ++hi) {
+    int k = n_down - __builtin_popcount(hi);
+    if (k < 0 || k > h) continue;
+    uint64_t r = 0;
+    for (int p = 0; p < hb; ++p)
+      if (hi >> p & 1u) r += binom[(size_t)(p + h)][(size_t)++k];
+    hi_rank[hi] = (uint32_t)r;
+  }
+  std::vector<uint32_t> states((size_t)dim);
+  {
+    uint64_t s = ((uint64_t)1 << n_down) - 1;  // the smallest state; the next one with as many set bits follows (Gosper)
+    for (int64_t i = 0; i < dim; ++i) {
+      states[(size_t)i] = (uint32_t)s;
+      if (s == 0) break;
+      const uint64_t c = s & (0 - s), r = s + c;
+      s = (((r ^ s) >> 2) >> __builtin_ctzll(s)) | r;
+    }
+  }
+  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_SECTOR, dim, 0, dim);
+  op->nnz = n_terms;
+  op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
+  PauliSectorImage im;
+  im.n_sites = n_sites;
+  im.n_down = n_down;
+  im.h = h;
+  im.dim = dim;
+  pauli_upload_tables(ctx, im, pt);
+  pauli_upload(ctx, im.states, states, "S_z sector states");
+  pauli_upload(ctx, im.lo_rank, lo_rank, "S_z sector rank table (low bits)");
+  pauli_upload(ctx, im.hi_rank, hi_rank, "S_z sector rank table (high bits)");
+  op->pauli_sector = std::move(im);
   *out = op.release();
 }
 
@@ -816,6 +928,7 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
   template void create_dense<T>(ll_context*, int64_t, int64_t, int64_t, const void*, ll_operator**);                            \
   template void create_stencil<T>(ll_context*, const ll_stencil_desc*, int64_t, int64_t, const double*, ll_operator**);        \
   template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
+  template void create_pauli_sector<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);             \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 

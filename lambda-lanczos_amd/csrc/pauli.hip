@@ -22,44 +22,11 @@
 
 #include "dev_helpers.hpp"
 #include "ll_internal.hpp"
+#include "pauli_shared.hpp"
 
 namespace ll {
 
 namespace {
-constexpr int kPauliLaneStates = 4;  // states a lane carries through the term loop at a time (accumulators in registers)
-
-// coefficient of a term as the accumulator's weight type: one double (real types), (re, im) of c i^nY (complex types)
-template <typename A> struct PauliWeight;
-template <> struct PauliWeight<double> {
-  static __device__ __forceinline__ double load(const double* __restrict__ tc, int t, unsigned flip) {
-    return __hiloint2double(__double2hiint(tc[t]) ^ (int)(flip << 31), __double2loint(tc[t]));
-  }
-  static __device__ __forceinline__ void add(double& w, double c, unsigned par) {
-    w += __hiloint2double(__double2hiint(c) ^ (int)(par << 31), __double2loint(c));
-  }
-};
-template <> struct PauliWeight<zc> {
-  static __device__ __forceinline__ zc load(const double* __restrict__ tc, int t, unsigned flip) {
-    return zc{PauliWeight<double>::load(tc, 2 * t, flip), PauliWeight<double>::load(tc, 2 * t + 1, flip)};
-  }
-  static __device__ __forceinline__ void add(zc& w, zc c, unsigned par) {
-    PauliWeight<double>::add(w.re, c.re, par);
-    PauliWeight<double>::add(w.im, c.im, par);
-  }
-};
-__device__ __forceinline__ void pauli_fma(double& acc, double w, double x) { acc = fma(w, x, acc); }
-__device__ __forceinline__ void pauli_fma(double& acc, double w, float x) { acc = fma(w, (double)x, acc); }
-__device__ __forceinline__ void pauli_fma(zc& acc, zc w, zc x) { fma_acc(acc, w, x); }
-__device__ __forceinline__ void pauli_fma(zc& acc, zc w, cf x) { fma_acc(acc, w, to_acc(x)); }
-
-template <typename T, int V> __device__ __forceinline__ void pauli_load(const T* __restrict__ p, T (&r)[V]) {
-  if constexpr (V == 1) r[0] = p[0];
-  else load_chunk<T, V>(p, r);
-}
-template <typename T, int V> __device__ __forceinline__ void pauli_store(T* __restrict__ p, const T (&r)[V]) {
-  if constexpr (V == 1) p[0] = r[0];
-  else store_chunk<T, V>(p, r);
-}
 // r[v] <- r[v ^ m] for a wave-uniform m < V, one butterfly per bit of m (a register array indexed at run time would go to
 // scratch memory)
 template <typename T, int V> __device__ __forceinline__ void pauli_xor_permute(T (&r)[V], unsigned m) {

@@ -6,6 +6,7 @@ tests read like the reference's own tests; the C++ twin of this file is include/
 All numerics run in liblanczos_hip.so on the GPU — there is no CPU path in this package.
 """
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -416,6 +417,29 @@ class PauliOperator(_Operator):
     def inf_norm(self):
         """sum_t |coef_t|: an upper bound of every absolute row sum (a safe |eigenvalue_offset|)."""
         return CsrOperator.inf_norm(self)
+
+
+class PauliSectorOperator(_Operator):
+    """The same Hamiltonian on one magnetisation sector (ll_op_create_pauli_sector_*): the basis is the comb(n_sites, n_down)
+    states with n_down set bits (a set bit is sigma_z = -1) in ascending integer order (generators.sector_states), and H must
+    conserve total S_z — creation refuses one that does not, naming the x mask at fault.  Terms, dtypes and limits as
+    PauliOperator; 0 <= n_down <= n_sites."""
+
+    def __init__(self, ctx, n_sites, n_down, terms, dtype=np.float64):
+        terms = list(terms)
+        arr = (capi.PauliTerm * max(len(terms), 1))()
+        for k, (xm, zm, c) in enumerate(terms):
+            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+        self.ctx, self.dtype = ctx, np.dtype(dtype)
+        self.n_sites, self.n_down = int(n_sites), int(n_down)
+        self.n = self.n_local = math.comb(self.n_sites, self.n_down) if 0 <= self.n_down <= self.n_sites else 0
+        self.row_begin, self.nnz = 0, len(terms)
+        h = C.c_void_p()
+        fn = getattr(lib(), "ll_op_create_pauli_sector_" + _suffix(self.dtype))
+        check(fn(ctx.handle, self.n_sites, self.n_down, len(terms), arr, C.byref(h)))
+        self.handle = h
+
+    inf_norm = PauliOperator.inf_norm
 
 
 class HostOperator(_Operator):

@@ -226,16 +226,29 @@ def _parity(v):
     return (v & np.uint64(1)).astype(np.int64)
 
 
+def _popcount(v):
+    """popcount(v), element-wise (uint64 arrays below 2^32)."""
+    v = v - ((v >> np.uint64(1)) & np.uint64(0x55555555))
+    v = (v & np.uint64(0x33333333)) + ((v >> np.uint64(2)) & np.uint64(0x33333333))
+    v = (v + (v >> np.uint64(4))) & np.uint64(0x0F0F0F0F)
+    return ((v * np.uint64(0x01010101)) >> np.uint64(24)) & np.uint64(0xFF)
+
+
 def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
     """The matrix of H = sum_t coef_t P_t as CSR, by the definition: row s holds coef_t i^nY_t (-1)^popcount((s ^ x_t) & z_t) in
     column s ^ x_t.  merge=True: one entry per row and distinct x mask (masks ascending; the coefficients summed in list
     order, exact zeros dropped).  merge=False: one entry per term and state, in list order, duplicate columns allowed — every
     term's own magnitude stays visible to an error bound."""
-    n = 1 << int(n_sites)
+    return _pauli_rows(np.arange(1 << int(n_sites), dtype=np.uint64), terms, dtype, merge, None)
+
+
+def _pauli_rows(s, terms, dtype, merge, column_of):
+    """pauli_csr for the rows of the states s (uint64).  column_of (None: the partner state itself) maps an array of partner
+    states to (column numbers, entries to keep)."""
+    n = s.shape[0]
     dtype = np.dtype(dtype)
     cplx = dtype.kind == "c"
     terms = [(int(x), int(z), float(c)) for x, z, c in terms]
-    s = np.arange(n, dtype=np.uint64)
     phase = (1.0, 1j, -1.0, -1j)
 
     def column(x, z, c):
@@ -245,6 +258,14 @@ def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
         p = phase[ny & 3] * c
         sign = 1.0 - 2.0 * _parity((s ^ np.uint64(x)) & np.uint64(z))
         return (sign * p if cplx else sign * p.real).astype(dtype)
+
+    def partners(masks):
+        if not masks:
+            return np.zeros((n, 0), np.int32), np.ones((n, 0), bool)
+        if column_of is None:
+            return np.stack([(s ^ np.uint64(x)).astype(np.int32) for x in masks], 1), np.ones((n, len(masks)), bool)
+        both = [column_of(s ^ np.uint64(x)) for x in masks]
+        return np.stack([c.astype(np.int32) for c, _ in both], 1), np.stack([k for _, k in both], 1)
 
     if merge:
         groups = {}
@@ -256,16 +277,95 @@ def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
             for z, c in groups[x]:
                 vals[:, k] += column(x, z, c)
         vals = vals.astype(dtype)
-        cols = np.stack([(s ^ np.uint64(x)).astype(np.int32) for x in masks], 1) if masks else np.zeros((n, 0), np.int32)
-        keep = vals != 0
+        cols, inside = partners(masks)
+        keep = (vals != 0) & inside
         rp = np.concatenate([[0], np.cumsum(keep.sum(1))]).astype(np.int64)
         return rp, np.ascontiguousarray(cols[keep]), np.ascontiguousarray(vals[keep])
     T = len(terms)
     vals = np.stack([column(*t) for t in terms], 1) if T else np.zeros((n, 0), dtype)
-    cols = np.stack([(s ^ np.uint64(x)).astype(np.int32) for x, _, _ in terms], 1) if T else np.zeros((n, 0), np.int32)
-    rp = (np.arange(n + 1, dtype=np.int64) * T)
-    return rp, np.ascontiguousarray(cols.reshape(-1)), np.ascontiguousarray(vals.reshape(-1))
+    cols, inside = partners([x for x, _, _ in terms])
+    if column_of is None:
+        rp = (np.arange(n + 1, dtype=np.int64) * T)
+        return rp, np.ascontiguousarray(cols.reshape(-1)), np.ascontiguousarray(vals.reshape(-1))
+    rp = np.concatenate([[0], np.cumsum(inside.sum(1))]).astype(np.int64)
+    return rp, np.ascontiguousarray(cols[inside]), np.ascontiguousarray(vals[inside])
 
+
+def dm_terms(L, D=1.0, periodic=True):
+    """Dzyaloshinskii-Moriya chain D sum_j (X_j Y_{j+1} - Y_j X_{j+1}) (Pauli matrices): complex Hermitian, conserves S_z."""
+    terms = []
+    for j in range(L if periodic and L > 2 else L - 1):
+        a, b = 1 << j, 1 << ((j + 1) % L)
+        terms += [(a | b, b, float(D)), (a | b, a, -float(D))]
+    return terms
+
+
+def zfield_terms(L, h):
+    """Uniform field along z, -h sum_j Z_j (Pauli matrices): diagonal, shifts a sector by -h (L - 2 n_down)."""
+    return [(0, 1 << j, -float(h)) for j in range(L)]
+
+
+# ------------------------------------------------------------------ one magnetisation (S_z) sector
+# The states with n_down set bits (a set bit is sigma_z = -1) in ascending integer order (ll_op_create_pauli_sector_*).
+def sector_states(n_sites, n_down):
+    """The comb(n_sites, n_down) states with n_down set bits, ascending, as uint32."""
+    n_sites, n_down = int(n_sites), int(n_down)
+    if not 0 <= n_down <= n_sites <= 32:
+        raise ValueError("need 0 <= n_down <= n_sites <= 32")
+    out = np.zeros(1, dtype=np.uint32)   # the states on the first p sites, by number of set bits
+    by_count = [out] + [np.zeros(0, np.uint32)] * n_down
+    for p in range(n_sites):
+        bit = np.uint32(1 << p)
+        for m in range(min(p + 1, n_down), 0, -1):   # states on p + 1 sites with m set bits: bit p clear first, then set
+            keep = by_count[m] if n_sites - (p + 1) >= n_down - m else by_count[m][:0]
+            by_count[m] = np.concatenate([keep, by_count[m - 1] | bit])
+        if n_sites - (p + 1) < n_down:   # too few sites left to reach n_down from here
+            by_count[0] = by_count[0][:0]
+    return by_count[n_down]
+
+
+def sector_rank_tables(n_sites, n_down, h):
+    """(lo_rank, hi_rank), uint32 of 2^h and 2^(n_sites - h) entries: the index of a state s of the sector in sector_states is
+    lo_rank[s & (2^h - 1)] + hi_rank[s >> h].  With the set bits of s at p_1 < ... < p_m the index is sum_k comb(p_k, k): the
+    low bits count k from 1, the others from n_down - popcount(others) + 1.  Entries no state of the sector reaches are 0."""
+    n_sites, n_down, h = int(n_sites), int(n_down), int(h)
+    if not 0 <= h <= n_sites:
+        raise ValueError("need 0 <= h <= n_sites")
+    binom = np.array([[math.comb(p, k) for k in range(n_sites + 2)] for p in range(n_sites + 1)], dtype=np.uint64)
+
+    def share(width, first_site, below):
+        """sum over the set bits p of v < 2^width of comb(first_site + p, k), k counting on from below(popcount(v)); 0 where
+        below is negative (no such state in the sector)."""
+        v = np.arange(1 << width, dtype=np.int64)
+        bits = [(v >> p) & 1 for p in range(width)]
+        k = below(sum(bits) if bits else np.zeros_like(v))
+        ok = (k >= 0) & (k <= n_down)
+        k, r = np.where(ok, k, 0), np.zeros(1 << width, dtype=np.uint64)
+        for p in range(width):
+            k = k + bits[p]
+            r += np.where((bits[p] == 1) & ok & (k <= n_down), binom[first_site + p, np.minimum(k, n_sites + 1)], np.uint64(0))
+        return r.astype(np.uint32)
+
+    lo = share(h, 0, lambda pc: np.where(pc <= n_down, 0, -1))
+    hi = share(n_sites - h, h, lambda pc: np.where(n_down - pc <= h, n_down - pc, -1))
+    return lo, hi
+
+
+def pauli_sector_csr(n_sites, n_down, terms, dtype=np.float64, merge=True):
+    """The block of pauli_csr(n_sites, terms, dtype, merge) on the rows and columns of the sector (n_sites, n_down), columns
+    renumbered by position in sector_states; entries whose column leaves the sector are dropped (exact zeros for an H that
+    conserves S_z once merged; with merge=False the single terms that cancel there).  Only the sector's rows are formed."""
+    n_sites, n_down = int(n_sites), int(n_down)
+    states = sector_states(n_sites, n_down).astype(np.uint64)
+    h = (n_sites + 1) // 2
+    lo, hi = sector_rank_tables(n_sites, n_down, h)
+
+    def column_of(p):
+        inside = _popcount(p) == n_down
+        q = np.where(inside, p, states[0])
+        return lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)], inside
+
+    return _pauli_rows(states, terms, dtype, merge, column_of)
 
 # ------------------------------------------------------------------ C++ versions (BASELINE sizes)
 _gen = None
