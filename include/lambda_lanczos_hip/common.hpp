@@ -64,6 +64,10 @@ template <typename T> struct abi;
                                    ll_operator** o) {                                                                    \
       return ll_op_create_pauli_sector_##SFX(c, ns, nd, nt, t, o);                                                       \
     }                                                                                                                    \
+    static int create_pauli_momentum(ll_context* c, int32_t ns, int32_t nd, int32_t m, int64_t nt, const ll_pauli_term* t,\
+                                     ll_operator** o) {                                                                  \
+      return ll_op_create_pauli_momentum_##SFX(c, ns, nd, m, nt, t, o);                                                  \
+    }                                                                                                                    \
     static int create_host(ll_context* c, int64_t n, int (*fn)(const void*, void*, int64_t, void*), void* user,          \
                            ll_operator** o) {                                                                            \
       return ll_op_create_host_##SFX(c, n, reinterpret_cast<HOSTFN>(fn), user, o);                                       \
@@ -311,6 +315,32 @@ template <typename T> class PauliSectorOperator : public DeviceOperator<T> {
       : DeviceOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
+    int64_t n = 0, n_local = 0, n_terms = 0;
+    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
+    if (rc != LL_OK) (void)ll_op_destroy(op);
+    check(rc);
+    this->adopt(op, n, n_local);
+  }
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
+  }
+};
+
+// One momentum block of that sector on a ring: H must also commute with the one-site translation T (site j -> j + 1 mod n_sites).
+// Vectors hold the D_m amplitudes of the basis |r; m> = N_r^(-1/2) sum_j e^(-2 pi i m j / n_sites) T^j |r>, r running over the
+// orbit representatives (smallest member) whose orbit length R satisfies m R = 0 (mod n_sites), ascending; size() returns D_m.
+// 0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image holds 4 C(n_sites, n_down) bytes of look-up
+// table (device_bytes()); inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue| (ll_op_create_pauli_momentum_*).
+template <typename T> class PauliMomentumOperator : public DeviceOperator<T> {
+ public:
+  PauliMomentumOperator(int n_sites, int n_down, int momentum, const std::vector<PauliTerm>& terms,
+                        Context ctx = Context::default_context())
+      : DeviceOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli_momentum(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int64_t)terms.size(),
+                                        terms.data(), &op));
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
     if (rc != LL_OK) (void)ll_op_destroy(op);

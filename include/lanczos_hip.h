@@ -55,7 +55,9 @@ extern "C" {
                              *    also additive under minor 5 — ll_op_create_csr_sym_* (one stored triangle), the one-triangle
                              *    SpMV kernel id, ll_op_device_bytes; no struct changed;
                              *    also additive under minor 5 — ll_op_create_pauli_sector_* (one S_z sector; the minor stays 5:
-                             *    no struct changed, and callers that need these entry points find them by name) */
+                             *    no struct changed, and callers that need these entry points find them by name);
+                             *    also additive under minor 5, with the same note — ll_op_create_pauli_momentum_* (one momentum block
+                             *    of an S_z sector of a ring) */
 
 enum {
   LL_OK = 0,
@@ -308,6 +310,52 @@ int ll_op_create_pauli_sector_s(ll_context* ctx, int32_t n_sites, int32_t n_down
                                 ll_operator** out);
 int ll_op_create_pauli_sector_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms_host,
                                 ll_operator** out);
+
+/* (8) the same sum on ONE MOMENTUM BLOCK of one magnetisation sector of a RING, for an H that conserves total S_z and commutes with
+ *     the one-site translation T — the next step of an exact-diagonalisation code: each sector splits into n_sites blocks of about
+ *     D / n_sites states.  Conventions of (6) and (7).  L = n_sites, momentum = m with 0 <= m < L, that is k = 2 pi m / L.
+ *     T rotates a basis state LEFT by one bit: site j goes to site (j + 1) mod L.  The orbit of s is {T^j s}; its length R_s divides
+ *     L; its REPRESENTATIVE is its smallest integer.  The basis of block m is the set of representatives r of the sector with
+ *     (m R_r) mod L = 0, in ASCENDING integer order, D_m of them, each standing for
+ *         |r; m> = N_r^(-1/2) sum_{j=0}^{L-1} e^(-2 pi i m j / L) T^j |r>,     N_r = L^2 / R_r.
+ *     With B the D x D_m matrix of these vectors in the basis of (7) — an isometry — THE OPERATOR IS B^H H_sector B, H_sector the
+ *     operator of (7).  The sum over m of D_m is D and the union of the blocks' spectra is the sector's.  Equivalent gather form,
+ *     which the kernel evaluates: for representative a (number i) and group g let p = a ^ X_g; if p stays in the sector write
+ *     p = T^l b with b its representative; if b is in the block,
+ *         y(i) += w_g(a) sqrt(R_a / R_b) e^(-2 pi i m l / L) v(number of b),
+ *     with w_g the weight of (6) / (7), groups in ascending mask order.
+ *     LIMITS: those of (7), and 0 <= momentum < n_sites.  The block is real symmetric only for a real H at 2 m = 0 (mod L): the
+ *     real types (_d, _s) take m = 0 and, for even L, m = L / 2 (besides the even-nY rule); _z / _c take every m.
+ *     REFUSALS (LL_ERR_INVALID, each naming its cause): momentum outside [0, L); a real type with 2 m mod L != 0; an H that leaves
+ *     the sector (the message of (7)); an H that does not commute with T — after merging the coefficients of equal (x_mask, z_mask),
+ *     rotating every term's masks by one site must map the term set onto itself with EXACTLY equal coefficients; the message names
+ *     the (x_mask, z_mask) of the first term at fault (an open chain is refused this way); an empty block (D_m = 0: n = 0 is not an
+ *     operator here); a context of more than one rank.
+ *     The image is the term tables, the D_m representatives (4 D_m bytes) and their orbit lengths (D_m bytes), the two rank tables
+ *     of (7), two small tables (sqrt(R_a / R_b): 8 KiB; the L phases) and orbit[D]: for EVERY state of the sector 4 bytes that pack
+ *     (number of its representative << 5 | l), all ones where the block excludes the orbit — 4 D bytes, e.g. 10.8 MB at L = 24,
+ *     n_down = 12 and 620 MB at L = 30, n_down = 15, for a block whose vectors are L times shorter.  ll_op_device_bytes counts all
+ *     of it.  One apply moves between (2 sizeof(T) + 5) D_m bytes (every gather found in cache) and
+ *     (2 sizeof(T) + 5 + G (sizeof(T) + 4)) D_m, G = the x masks != 0 (per group one orbit entry and one vector element).
+ *     ACCURACY: component-wise, as (6): per state and group the weight w_g is summed in double as in (6), multiplied by
+ *     sqrt(R_a / R_b) where the two orbit lengths differ (a table entry rounded once) and by the phase where m != 0 (a table entry,
+ *     exact on the axes; a complex product in double), and enters the row by one double fma against the partner value (float
+ *     inputs widened); one rounding to T.  An entry of the block therefore carries a few double roundings and is in general NOT a
+ *     number of the storage type: the single-type contract "products rounded once to T" of the CSR kernels is not claimed here,
+ *     only the component-wise class against the exact block.  The order is fixed: the same bits run to run and for every block
+ *     size, grid and buffer alignment.
+ *     Queries: ll_op_info reports n = n_local = D_m and the number of TERMS as nnz_local; ll_op_inf_norm returns sum_t |coef_t|,
+ *     which bounds the 2-norm of H and so EVERY |EIGENVALUE| of the block (B is an isometry) — a safe eigenvalue_offset magnitude;
+ *     it is not claimed as a bound of the block's absolute row sums.  ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID
+ *     (not a CSR operator), ll_op_accuracy the component-wise class. */
+int ll_op_create_pauli_momentum_d(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                                  const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_z(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                                  const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_s(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                                  const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                                  const ll_pauli_term* terms_host, ll_operator** out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

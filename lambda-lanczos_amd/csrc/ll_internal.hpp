@@ -271,6 +271,7 @@ struct Tuning {
   bool pb_test_all_remote = false; // LL_PB_TEST_ALL_REMOTE=1: own columns are read from the gathered buffer too
   int tridiag_test_jitter_us = 0;  // LL_TRIDIAG_TEST_JITTER_US: random delay of every helper-thread verdict
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
+  int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
@@ -504,11 +505,39 @@ struct PauliSectorImage {
     return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + states.bytes() + lo_rank.bytes() + hi_rank.bytes();
   }
 };
+// One momentum block of an S_z sector of a ring (pauli_momentum.hip): the basis is the representatives (smallest member of an orbit
+// under the one-site shift T) whose period R satisfies m R = 0 (mod n_sites), ascending.  orbit[rank(s)] packs, for every state s
+// of the sector, (index of its representative in the block << 5 | l) with s = T^l representative; kPauliOrbitExcluded marks a
+// state whose orbit the block excludes.  ratio[Ra * 32 + Rb] = sqrt(Ra / Rb); phase[l] = e^(-2 pi i m l / n_sites) as (re, im).
+constexpr uint32_t kPauliOrbitExcluded = 0xffffffffu;
+constexpr int kPauliMomentumBlockBits = 8;       // indices of a workgroup's block: one state per lane (blocks are L times fewer than the sector's: 2^8 fills the device sooner)
+constexpr int kPauliOrbitShiftBits = 5;          // l < n_sites <= 30 < 2^5; index of the representative < 2^27
+struct PauliMomentumImage {
+  int n_sites = 0, n_down = 0, momentum = 0, ngroups = 0, h = 0;
+  int nshort = 0;                // distinct primes q of n_sites: a state s has a short orbit iff T^(n_sites / q) s = s for one of them;
+  int short_shift[3] = {0, 0, 0};  // the shifts n_sites / q (0 entries when the block holds no short orbit: nothing to test)
+  int64_t nterms = 0, dim = 0, sector_dim = 0;   // dim = D_m, sector_dim = C(n_sites, n_down)
+  DevArray<uint32_t> gx;
+  DevArray<int32_t> gptr;
+  DevArray<uint32_t> tz;
+  DevArray<double> tc;
+  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
+  DevArray<uint8_t> period;      // [dim]                 their orbit lengths R
+  DevArray<uint32_t> orbit;      // [sector_dim]          see above
+  DevArray<uint32_t> lo_rank;    // [2^h]
+  DevArray<uint32_t> hi_rank;    // [2^(n_sites - h)]
+  DevArray<double> ratio;        // [32 * 32]
+  DevArray<double> phase;        // [n_sites][2]
+  int64_t device_bytes() const {
+    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + period.bytes() + orbit.bytes() + lo_rank.bytes() +
+           hi_rank.bytes() + ratio.bytes() + phase.bytes();
+  }
+};
 }  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -537,11 +566,12 @@ struct ll_operator {
   ll::DevArray<void> onsite;         // n_local on-site terms in the real type of T (nullable)
   ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
   ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
+  ll::PauliMomentumImage pauli_momentum;  // one momentum block of an S_z sector of a ring (kind PAULI_MOMENTUM)
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
            sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes() +
-           pauli_sector.device_bytes();
+           pauli_sector.device_bytes() + pauli_momentum.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -580,6 +610,11 @@ void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pa
 template <typename T>
 void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms,
                          ll_operator** out);
+// n = D_m: the block of momentum 2 pi m / n_sites of that sector, for an H that also commutes with the one-site shift of the ring;
+// real types take m = 0 and m = n_sites / 2 only
+template <typename T>
+void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                           const ll_pauli_term* terms, ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -589,7 +624,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -682,6 +717,10 @@ int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double*
 template <typename T>
 int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                         const ScaleIn<T>* sc = nullptr);
+// One momentum block of that sector (op.kind == PAULI_MOMENTUM; pauli_momentum.hip): x, y hold D_m elements.
+template <typename T>
+int launch_pauli_momentum(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                          const ScaleIn<T>* sc = nullptr);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

@@ -4,8 +4,11 @@
 // call in here.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine.hpp"
@@ -829,6 +832,61 @@ void pauli_require_sz_conserving(const PauliTables& pt, int R) {
     } while (s != 0);
   }
 }
+
+// The states of the sector of n_down set bits in ascending order and the two tables that give a state's index back
+// (ll_internal.hpp PauliSectorImage): one pass over the C(n_sites, n_down) states, on the host.
+struct SectorTables {
+  int h = 0;
+  int64_t dim = 0;
+  std::vector<uint32_t> states, lo_rank, hi_rank;
+  uint32_t rank(uint32_t s) const { return lo_rank[s & (((uint32_t)1 << h) - 1)] + hi_rank[s >> h]; }
+};
+SectorTables sector_tables(int32_t n_sites, int32_t n_down) {
+  // binom[p][k] = C(p, k), p <= n_sites <= 30: below 2^32
+  std::vector<std::vector<uint64_t>> binom((size_t)n_sites + 1, std::vector<uint64_t>((size_t)n_sites + 2, 0));
+  for (int p = 0; p <= n_sites; ++p) {
+    binom[(size_t)p][0] = 1;
+    for (int k = 1; k <= p; ++k) binom[(size_t)p][(size_t)k] = binom[(size_t)p - 1][(size_t)k - 1] + binom[(size_t)p - 1][(size_t)k];
+  }
+  SectorTables st;
+  st.dim = (int64_t)binom[(size_t)n_sites][(size_t)n_down];
+  const int h = st.h = (n_sites + 1) / 2, hb = n_sites - h;  // low / other bits: both tables at most 2^15 entries
+  // rank(s) = sum_k C(p_k, k) over the set bits p_1 < p_2 < ...: the low bits count k from 1, the others from
+  // n_down - popcount(others) + 1 (entries no state of the sector reaches stay 0)
+  std::vector<uint32_t>& lo_rank = st.lo_rank;
+  std::vector<uint32_t>& hi_rank = st.hi_rank;
+  lo_rank.assign((size_t)1 << h, 0);
+  hi_rank.assign((size_t)1 << hb, 0);
+  for (uint32_t lo = 0; lo < ((uint32_t)1 << h); ++lo) {
+    if (__builtin_popcount(lo) > n_down) continue;
+    uint64_t r = 0;
+    int k = 0;
+    for (int p = 0; p < h; ++p)
+      if (lo >> p & 1u) r += binom[(size_t)p][(size_t)++k];
+    lo_rank[lo] = (uint32_t)r;
+  }
+  for (uint32_t hi = 0; hi < ((uint32_t)1 << hb); ++hi) {
+    int k = n_down - __builtin_popcount(hi);
+    if (k < 0 || k > h) continue;
+    uint64_t r = 0;
+    for (int p = 0; p < hb; ++p)
+      if (hi >> p & 1u) r += binom[(size_t)(p + h)][(size_t)++k];
+    hi_rank[hi] = (uint32_t)r;
+  }
+  const int64_t dim = st.dim;
+  std::vector<uint32_t>& states = st.states;
+  states.resize((size_t)dim);
+  {
+    uint64_t s = ((uint64_t)1 << n_down) - 1;  // the smallest state; the next one with as many set bits follows (Gosper)
+    for (int64_t i = 0; i < dim; ++i) {
+      states[(size_t)i] = (uint32_t)s;
+      if (s == 0) break;
+      const uint64_t c = s & (0 - s), r = s + c;
+      s = (((r ^ s) >> 2) >> __builtin_ctzll(s)) | r;
+    }
+  }
+  return st;
+}
 }  // namespace
 
 template <typename T>
@@ -853,56 +911,131 @@ void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64
   const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
   LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
   pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
-  // binom[p][k] = C(p, k), p <= n_sites <= 30: below 2^32
-  std::vector<std::vector<uint64_t>> binom((size_t)n_sites + 1, std::vector<uint64_t>((size_t)n_sites + 2, 0));
-  for (int p = 0; p <= n_sites; ++p) {
-    binom[(size_t)p][0] = 1;
-    for (int k = 1; k <= p; ++k) binom[(size_t)p][(size_t)k] = binom[(size_t)p - 1][(size_t)k - 1] + binom[(size_t)p - 1][(size_t)k];
-  }
-  const int64_t dim = (int64_t)binom[(size_t)n_sites][(size_t)n_down];
-  const int h = (n_sites + 1) / 2, hb = n_sites - h;  // low / other bits: both tables at most 2^15 entries
-  // rank(s) = sum_k C(p_k, k) over the set bits p_1 < p_2 < ...: the low bits count k from 1, the others from
-  // n_down - popcount(others) + 1 (entries no state of the sector reaches stay 0)
-  std::vector<uint32_t> lo_rank((size_t)1 << h, 0), hi_rank((size_t)1 << hb, 0);
-  for (uint32_t lo = 0; lo < ((uint32_t)1 << h); ++lo) {
-    if (__builtin_popcount(lo) > n_down) continue;
-    uint64_t r = 0;
-    int k = 0;
-    for (int p = 0; p < h; ++p)
-      if (lo >> p & 1u) r += binom[(size_t)p][(size_t)++k];
-    lo_rank[lo] = (uint32_t)r;
-  }
-  for (uint32_t hi = 0; hi < ((uint32_t)1 << hb); ++hi) {
-    int k = n_down - __builtin_popcount(hi);
-    if (k < 0 || k > h) continue;
-    uint64_t r = 0;
-    for (int p = 0; p < hb; ++p)
-      if (hi >> p & 1u) r += binom[(size_t)(p + h)][(size_t)++k];
-    hi_rank[hi] = (uint32_t)r;
-  }
-  std::vector<uint32_t> states((size_t)dim);
-  {
-    uint64_t s = ((uint64_t)1 << n_down) - 1;  // the smallest state; the next one with as many set bits follows (Gosper)
-    for (int64_t i = 0; i < dim; ++i) {
-      states[(size_t)i] = (uint32_t)s;
-      if (s == 0) break;
-      const uint64_t c = s & (0 - s), r = s + c;
-      s = (((r ^ s) >> 2) >> __builtin_ctzll(s)) | r;
-    }
-  }
+  const SectorTables st = sector_tables(n_sites, n_down);
+  const int64_t dim = st.dim;
   std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_SECTOR, dim, 0, dim);
   op->nnz = n_terms;
   op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
   PauliSectorImage im;
   im.n_sites = n_sites;
   im.n_down = n_down;
-  im.h = h;
+  im.h = st.h;
   im.dim = dim;
   pauli_upload_tables(ctx, im, pt);
-  pauli_upload(ctx, im.states, states, "S_z sector states");
-  pauli_upload(ctx, im.lo_rank, lo_rank, "S_z sector rank table (low bits)");
-  pauli_upload(ctx, im.hi_rank, hi_rank, "S_z sector rank table (high bits)");
+  pauli_upload(ctx, im.states, st.states, "S_z sector states");
+  pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
+  pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
   op->pauli_sector = std::move(im);
+  *out = op.release();
+}
+
+namespace {
+// Translation invariance on the ring: with the coefficients of equal (x_mask, z_mask) merged (summed in the caller's order),
+// rotating every term's masks by one site must map the term set onto itself with exactly equal coefficients (a missing term
+// counts as coefficient 0).  i^nY does not change under the rotation, so the caller's coefficients are compared.
+void pauli_require_translation_invariant(int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms) {
+  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
+  auto rot = [&](uint64_t v) { return ((v << 1) | (v >> (n_sites - 1))) & site_mask; };
+  std::map<std::pair<uint64_t, uint64_t>, double> merged;
+  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask}, moved{rot(key.first), rot(key.second)};
+    const auto it = merged.find(moved);
+    const double there = it == merged.end() ? 0.0 : it->second;
+    if (there == merged[key]) continue;
+    char hex[64];
+    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
+    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the one-site translation of the ring: "
+                      "shifted by one site it meets a different coefficient (an open chain, or bonds that differ); a momentum "
+                      "sector needs a translation-invariant H");
+  }
+}
+}  // namespace
+
+// One momentum block of that sector (pauli_momentum.hip).  One pass over the sector's states in ascending order, on the host: the
+// first state of an orbit not seen before is its representative; walking the orbit gives its period R and, for the blocks's
+// orbits (m R = 0 mod n_sites), the entries orbit[rank(T^j r)] = (index of r << 5 | j).
+template <typename T>
+void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
+                           const ll_pauli_term* terms, ll_operator** out) {
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
+  LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
+  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
+  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
+             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
+             "storage type");
+  pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
+  pauli_require_translation_invariant(n_sites, n_terms, terms);
+  const SectorTables st = sector_tables(n_sites, n_down);
+  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << n_sites) - 1);
+  auto rot = [&](uint32_t v) { return ((v << 1) | (v >> (n_sites - 1))) & site_mask; };
+  std::vector<uint32_t> orbit((size_t)st.dim, kPauliOrbitExcluded), reps;
+  std::vector<uint8_t> period;
+  std::vector<bool> seen((size_t)st.dim, false);
+  bool any_short = false;
+  for (int64_t i = 0; i < st.dim; ++i) {
+    if (seen[(size_t)i]) continue;
+    const uint32_t r = st.states[(size_t)i];  // ascending order: the smallest state of a new orbit
+    int R = 0;
+    for (uint32_t t = r;;) {
+      seen[(size_t)st.rank(t)] = true;
+      ++R;
+      if ((t = rot(t)) == r) break;
+    }
+    if (((int64_t)momentum * R) % n_sites != 0) continue;  // the orbit's states keep kPauliOrbitExcluded
+    const uint64_t idx = reps.size();
+    LL_REQUIRE(idx < ((uint64_t)1 << (32 - kPauliOrbitShiftBits)) - 1, "internal: a momentum block of 2^27 states or more");
+    uint32_t t = r;
+    for (int j = 0; j < R; ++j, t = rot(t)) orbit[(size_t)st.rank(t)] = (uint32_t)(idx << kPauliOrbitShiftBits) | (uint32_t)j;
+    reps.push_back(r);
+    period.push_back((uint8_t)R);
+    any_short = any_short || R != n_sites;
+  }
+  static_assert(kPauliMaxSites < (1 << kPauliOrbitShiftBits), "the shift l of an orbit entry needs n_sites < 2^5");
+  const int64_t dim = (int64_t)reps.size();
+  LL_REQUIRE(dim >= 1, "the momentum block is empty: no orbit of the sector (n_sites " + std::to_string(n_sites) + ", n_down " +
+                           std::to_string(n_down) + ") has a length R with momentum * R = 0 (mod n_sites)");
+  std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
+  for (int a = 1; a < 32; ++a)
+    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
+  for (int l = 0; l < n_sites; ++l) {  // e^(-2 pi i m l / n_sites), exact on the axes
+    const int k = (int)(((int64_t)momentum * l) % n_sites);
+    const double th = 2.0 * M_PI * (double)k / (double)n_sites;
+    double c = std::cos(th), sn = -std::sin(th);
+    if (4 * k % n_sites == 0) {
+      const int quarter = 4 * k / n_sites;  // 0 .. 3
+      c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
+      sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
+    }
+    phase[2 * (size_t)l] = c;
+    phase[2 * (size_t)l + 1] = sn;
+  }
+  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM, dim, 0, dim);
+  op->nnz = n_terms;
+  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
+  PauliMomentumImage im;
+  im.n_sites = n_sites;
+  im.n_down = n_down;
+  im.momentum = momentum;
+  im.h = st.h;
+  im.dim = dim;
+  im.sector_dim = st.dim;
+  if (any_short)  // the primes q of n_sites: a state has a short orbit iff rotating it by n_sites / q gives it back for one of them
+    for (int q = 2, rest = n_sites; rest > 1; ++q)
+      if (rest % q == 0) {
+        LL_REQUIRE(im.nshort < 3, "internal: more than three primes in n_sites");
+        im.short_shift[im.nshort++] = n_sites / q;
+        while (rest % q == 0) rest /= q;
+      }
+  pauli_upload_tables(ctx, im, pt);
+  pauli_upload(ctx, im.reps, reps, "momentum block representatives");
+  pauli_upload(ctx, im.period, period, "momentum block orbit lengths");
+  pauli_upload(ctx, im.orbit, orbit, "momentum block orbit table");
+  pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
+  pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
+  pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
+  pauli_upload(ctx, im.phase, phase, "momentum block phases");
+  op->pauli_momentum = std::move(im);
   *out = op.release();
 }
 
@@ -929,6 +1062,7 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
   template void create_stencil<T>(ll_context*, const ll_stencil_desc*, int64_t, int64_t, const double*, ll_operator**);        \
   template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
   template void create_pauli_sector<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);             \
+  template void create_pauli_momentum<T>(ll_context*, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);  \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 

@@ -442,6 +442,33 @@ class PauliSectorOperator(_Operator):
     inf_norm = PauliOperator.inf_norm
 
 
+class PauliMomentumOperator(_Operator):
+    """One momentum block of one magnetisation sector of a ring (ll_op_create_pauli_momentum_*): the operator B^H H_sector B with
+    B = generators.momentum_embedding(n_sites, n_down, momentum); the basis is the orbit representatives of
+    generators.momentum_basis, ascending.  H must conserve total S_z and commute with the one-site translation — creation
+    refuses one that does not, naming the term at fault.  0 <= momentum < n_sites; the real dtypes take momentum 0 and
+    n_sites / 2 only.  Holds 4 comb(n_sites, n_down) bytes of look-up table on the device (device_bytes)."""
+
+    def __init__(self, ctx, n_sites, n_down, momentum, terms, dtype=np.float64):
+        terms = list(terms)
+        arr = (capi.PauliTerm * max(len(terms), 1))()
+        for k, (xm, zm, c) in enumerate(terms):
+            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+        self.ctx, self.dtype = ctx, np.dtype(dtype)
+        self.n_sites, self.n_down, self.momentum = int(n_sites), int(n_down), int(momentum)
+        self.n = self.n_local = 0
+        self.row_begin, self.nnz = 0, len(terms)
+        h = C.c_void_p()
+        fn = getattr(lib(), "ll_op_create_pauli_momentum_" + _suffix(self.dtype))
+        check(fn(ctx.handle, self.n_sites, self.n_down, self.momentum, len(terms), arr, C.byref(h)))
+        self.handle = h
+        self.n = self.n_local = self.info()[0]   # D_m: counted at creation
+
+    def inf_norm(self):
+        """sum_t |coef_t|: an upper bound of every |eigenvalue| of the block (a safe |eigenvalue_offset|)."""
+        return CsrOperator.inf_norm(self)
+
+
 class HostOperator(_Operator):
     """Unmodified user code: mv_mul(in, out) on numpy arrays, `out` zero-filled on entry (LL:120-126)."""
 

@@ -244,7 +244,7 @@ def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
 
 def _pauli_rows(s, terms, dtype, merge, column_of):
     """pauli_csr for the rows of the states s (uint64).  column_of (None: the partner state itself) maps an array of partner
-    states to (column numbers, entries to keep)."""
+    states to (column numbers, entries to keep) or to (column numbers, entries to keep, a factor of each entry in double)."""
     n = s.shape[0]
     dtype = np.dtype(dtype)
     cplx = dtype.kind == "c"
@@ -261,11 +261,17 @@ def _pauli_rows(s, terms, dtype, merge, column_of):
 
     def partners(masks):
         if not masks:
-            return np.zeros((n, 0), np.int32), np.ones((n, 0), bool)
+            return np.zeros((n, 0), np.int32), np.ones((n, 0), bool), None
         if column_of is None:
-            return np.stack([(s ^ np.uint64(x)).astype(np.int32) for x in masks], 1), np.ones((n, len(masks)), bool)
+            return np.stack([(s ^ np.uint64(x)).astype(np.int32) for x in masks], 1), np.ones((n, len(masks)), bool), None
         both = [column_of(s ^ np.uint64(x)) for x in masks]
-        return np.stack([c.astype(np.int32) for c, _ in both], 1), np.stack([k for _, k in both], 1)
+        factor = np.stack([b[2] for b in both], 1) if len(both[0]) > 2 else None
+        return np.stack([b[0].astype(np.int32) for b in both], 1), np.stack([b[1] for b in both], 1), factor
+
+    def scaled(vals, factor):
+        if factor is None:
+            return vals
+        return vals * (factor if cplx else factor.real)
 
     if merge:
         groups = {}
@@ -276,14 +282,15 @@ def _pauli_rows(s, terms, dtype, merge, column_of):
         for k, x in enumerate(masks):
             for z, c in groups[x]:
                 vals[:, k] += column(x, z, c)
-        vals = vals.astype(dtype)
-        cols, inside = partners(masks)
+        cols, inside, factor = partners(masks)
+        vals = scaled(vals, factor).astype(dtype)
         keep = (vals != 0) & inside
         rp = np.concatenate([[0], np.cumsum(keep.sum(1))]).astype(np.int64)
         return rp, np.ascontiguousarray(cols[keep]), np.ascontiguousarray(vals[keep])
     T = len(terms)
     vals = np.stack([column(*t) for t in terms], 1) if T else np.zeros((n, 0), dtype)
-    cols, inside = partners([x for x, _, _ in terms])
+    cols, inside, factor = partners([x for x, _, _ in terms])
+    vals = scaled(vals, factor).astype(dtype)
     if column_of is None:
         rp = (np.arange(n + 1, dtype=np.int64) * T)
         return rp, np.ascontiguousarray(cols.reshape(-1)), np.ascontiguousarray(vals.reshape(-1))
@@ -366,6 +373,119 @@ def pauli_sector_csr(n_sites, n_down, terms, dtype=np.float64, merge=True):
         return lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)], inside
 
     return _pauli_rows(states, terms, dtype, merge, column_of)
+
+
+# ------------------------------------------------------------------ one momentum block of an S_z sector of a ring
+# T rotates a state left by one bit (site j -> j + 1 mod L); the representative of an orbit {T^j s} is its smallest integer; block
+# m holds the representatives whose orbit length R satisfies m R = 0 (mod L), ascending (ll_op_create_pauli_momentum_*).
+def _orbits(n_sites, n_down):
+    """For every state s of sector_states(n_sites, n_down): (states, its representative b, l with s = T^l b and 0 <= l < R, R)."""
+    L = int(n_sites)
+    states = sector_states(L, n_down).astype(np.uint64)
+    mask = np.uint64((1 << L) - 1)
+    rep, first = states.copy(), np.zeros(states.shape[0], np.int64)    # min over the rotations, the first j with T^j s = min
+    period = np.full(states.shape[0], L, np.int64)
+    cur = states.copy()
+    for j in range(1, L):
+        cur = ((cur << np.uint64(1)) | (cur >> np.uint64(L - 1))) & mask
+        period = np.where((cur == states) & (period == L), j, period)
+        less = cur < rep
+        rep, first = np.where(less, cur, rep), np.where(less, j, first)
+    return states, rep, (period - first) % period, period
+
+
+def _momentum_phases(n_sites, m):
+    """e^(-2 pi i m l / n_sites) for l = 0 .. n_sites - 1 in double, exact where it lies on an axis."""
+    L = int(n_sites)
+    k = (int(m) * np.arange(L, dtype=np.int64)) % L
+    ph = np.exp(-2j * np.pi * k / L)
+    axis = (4 * k) % L == 0
+    ph[axis] = np.array([1.0, -1j, -1.0, 1j])[(4 * k[axis]) // L]
+    return ph
+
+
+def _check_momentum(n_sites, n_down, m):
+    n_sites, n_down, m = int(n_sites), int(n_down), int(m)
+    if not (1 <= n_sites <= 30 and 0 <= n_down <= n_sites and 0 <= m < n_sites):
+        raise ValueError("need 1 <= n_sites <= 30, 0 <= n_down <= n_sites, 0 <= m < n_sites")
+    return n_sites, n_down, m
+
+
+def momentum_basis(n_sites, n_down, m):
+    """(representatives, periods) of block m of the sector: the representatives r (uint32, ascending) with m R_r = 0 (mod n_sites)
+    and their orbit lengths R_r (int64)."""
+    n_sites, n_down, m = _check_momentum(n_sites, n_down, m)
+    states, rep, _, period = _orbits(n_sites, n_down)
+    inb = (states == rep) & ((m * period) % n_sites == 0)
+    return states[inb].astype(np.uint32), period[inb]
+
+
+def momentum_embedding(n_sites, n_down, m, dense=True):
+    """B: the basis vectors |r; m> = N_r^(-1/2) sum_j e^(-2 pi i m j / L) T^j |r>, N_r = L^2 / R_r, as the columns of a
+    comb(n_sites, n_down) x D_m matrix in the sector_states basis (an isometry).  A row holds at most one entry,
+    e^(-2 pi i m l / L) / sqrt(R) for the state T^l r: dense=False returns (column of each row or -1, its value)."""
+    n_sites, n_down, m = _check_momentum(n_sites, n_down, m)
+    states, rep, l, period = _orbits(n_sites, n_down)
+    inb = (m * period) % n_sites == 0
+    reps = states[(states == rep) & inb]
+    col = np.where(inb, np.searchsorted(reps, rep), -1).astype(np.int64)
+    val = np.where(inb, _momentum_phases(n_sites, m)[l] / np.sqrt(period.astype(np.float64)), 0.0)
+    if not dense:
+        return col, val
+    B = np.zeros((states.shape[0], reps.shape[0]), np.complex128)
+    B[np.flatnonzero(inb), col[inb]] = val[inb]
+    return B
+
+
+def translation_fault(n_sites, terms):
+    """None when H = sum of `terms` commutes with the one-site translation of the ring by the rule of
+    ll_op_create_pauli_momentum_* (coefficients of equal masks merged in list order; the masks rotated by one site meet exactly
+    the same coefficient, a missing term counting as 0); else the number of the first term at fault."""
+    L = int(n_sites)
+    full = (1 << L) - 1
+
+    def rot(v):
+        return ((v << 1) | (v >> (L - 1))) & full
+
+    merged = {}
+    for x, z, c in terms:
+        merged[(int(x), int(z))] = merged.get((int(x), int(z)), 0.0) + float(c)
+    for t, (x, z, _) in enumerate(terms):
+        if merged.get((rot(int(x)), rot(int(z))), 0.0) != merged[(int(x), int(z))]:
+            return t
+    return None
+
+
+def pauli_momentum_csr(n_sites, n_down, m, terms, dtype=np.float64, merge=True):
+    """The block B^H H_sector B (B = momentum_embedding, H_sector = pauli_sector_csr) as CSR over momentum_basis, from the gather
+    form, in double: row a holds, per x mask X whose partner a ^ X = T^l b stays in the sector with b in the block,
+    w(a) sqrt(R_a / R_b) e^(-2 pi i m l / L) in the column of b, w as in pauli_csr.  merge as in pauli_sector_csr (merge=False:
+    one entry per term and state).  A real dtype needs 2 m = 0 (mod n_sites); H must commute with the translation."""
+    n_sites, n_down, m = _check_momentum(n_sites, n_down, m)
+    terms = list(terms)
+    if np.dtype(dtype).kind != "c" and (2 * m) % n_sites:
+        raise ValueError("a real dtype takes m = 0 and m = n_sites / 2 only")
+    t = translation_fault(n_sites, terms)
+    if t is not None:
+        raise ValueError("term %d (x_mask 0x%x, z_mask 0x%x) does not commute with the one-site translation"
+                         % (t, terms[t][0], terms[t][1]))
+    states, rep, l, period = _orbits(n_sites, n_down)
+    inb = (m * period) % n_sites == 0
+    isrep = (states == rep) & inb
+    reps = states[isrep]
+    col = np.where(inb, np.searchsorted(reps, rep), 0).astype(np.int64)
+    phases = _momentum_phases(n_sites, m)
+    h = (n_sites + 1) // 2
+    lo, hi = sector_rank_tables(n_sites, n_down, h)
+    ra = period[isrep].astype(np.float64)
+
+    def column_of(p):
+        inside = _popcount(p) == n_down
+        q = np.where(inside, p, states[0])
+        k = lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)]
+        return col[k], inside & inb[k], np.sqrt(ra / period[k]) * phases[l[k]]
+
+    return _pauli_rows(reps, terms, dtype, merge, column_of)
 
 # ------------------------------------------------------------------ C++ versions (BASELINE sizes)
 _gen = None
