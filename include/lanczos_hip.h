@@ -400,6 +400,18 @@ int ll_op_create_pauli_momentum_c(ll_context* ctx, int32_t n_sites, int32_t n_do
  *   difference / sum rounded to float) before it is summed in fixed point / double.  Exceptions, which form every product
  *   EXACTLY in double (fma of the widened operands): CSR-stream's rows of more than 1024 entries (one workgroup strides over
  *   the row), the dense operator (4) and the lattice operator (5).  The row sum is then rounded to T once.
+ *   COLUMN-SPLIT FORMS — the one exception to "rounded once".  On a sharded context the CSR-stream operator, and the dense
+ *   operator on a rank whose column range starts and ends on 16-byte pieces of the rows, multiply the rank's OWN columns under
+ *   the all-gather and add the other ranks' columns in a second kernel (LL_CSR_SPLIT=0: gather first, one kernel, the rule
+ *   above).  A row is then TWO partial sums, S_own over the own columns and S_rem over the others, each accumulated in double,
+ *   each rounded to T once, and added in T:  y_i = fl_T( fl_T( fl_T(S_own) + fl_T(offset * x_i) ) + fl_T(S_rem) )
+ *   — one narrowing and one addition in T more than the unsplit form.  The component-wise class bound above holds unchanged
+ *   in every type; for float / complex float the result differs from the unsplit one by up to an ulp of T of the partial
+ *   sums (the two forms agree within the class bound, not bit for bit).  CSR-stream's "more than 1024 entries" rule goes by
+ *   the row's length in EACH part: a row of 3000 entries with 900 of them over own columns forms those 900 products in the
+ *   storage type and the 2100 others exactly.  PB, tiled and lattice operators have no such form: sharded, they round a row
+ *   once, and the fixed-point forms stitch to the bits of the single-GPU product (tests/test_gpu_sharded_contracts.py checks
+ *   all of this against tests/exact_ref.py, split_storage_bound).
  *   The offset (a2) and alpha (a3) of ll_spmv_*: y_i = fl_T(row sum) + fl_T(offset * x_i), added in T — for float / complex
  *   float the offset is rounded to float first (an offset such as 0.1 is not exact there) and the product and the addition
  *   round in float; alpha = Re<x, y> of the RETURNED (already rounded) y, accumulated in double, so that

@@ -1,5 +1,6 @@
 """Inputs of the accuracy-contract tests (numpy only): matrices built where SpMV kernels go wrong, shared by the host checks of the
-bound helpers (test_exact_ref.py) and the GPU tests (test_gpu_accuracy_contracts.py), so that both see the same rows."""
+bound helpers (test_exact_ref.py) and the GPU tests (test_gpu_accuracy_contracts.py; test_gpu_sharded_contracts.py and its rank
+processes for sharded contexts), so that all see the same rows."""
 import numpy as np
 
 # |x_j| in [1/2, 1] with random signs: the designed rows below rely on it
@@ -90,6 +91,60 @@ def edge_matrix(n, dtype, seed=0, band=300, long_rows=(1500, 3000), small_terms=
     return _finish(rows, n, dtype), x
 
 
+def shard_rows(csr, row_begin, n_local):
+    """Rows [row_begin, row_begin + n_local) of a CSR matrix, as a CSR row block with GLOBAL column indices (what a rank of a
+    sharded context passes to its operator)."""
+    rp, ci, va = csr
+    rp = np.asarray(rp, dtype=np.int64)
+    lo, hi = int(rp[row_begin]), int(rp[row_begin + n_local])
+    return rp[row_begin: row_begin + n_local + 1] - lo, ci[lo:hi].copy(), va[lo:hi].copy()
+
+
+def shard_cuts(n, worlds):
+    """First rows of the second, third, ... shard for every number of ranks in `worlds`: k * ceil(n / P), 0 < k < P, below n."""
+    cuts = set()
+    for p in worlds:
+        stride = -(-n // p)
+        cuts |= {k * stride for k in range(1, p) if 0 < k * stride < n}
+    return sorted(cuts)
+
+
+def sharded_edge_matrix(n, dtype, worlds=(2, 3)):
+    """edge_matrix(n, dtype) with two ordinary rows per shard cut replaced by rows that sit on the cut: for every cut c (the
+    first row of a shard, shard_cuts) the row just below and the row at the cut hold exactly the columns
+    {c - 1, c, 0, n - 1, the row's own index}, unsorted, the column c twice — the last column of one rank and the first of the
+    next, the first and the last column of the whole vector, and a duplicate whose two copies a column split must send the same
+    way.  The rows are c - 1 and c; where one of them is a designed row of edge_matrix (n = 5003: the long rows lie on the
+    2-rank cut, the small-terms and the cancellation row on the first 3-rank cut) the designed row stays and the nearest
+    ordinary row outward (c - 2, c + 1) takes the columns instead.  Everything else of edge_matrix stays: empty rows, the long
+    rows (1500 and 3000 random columns: on 3 ranks their own parts hold fewer, the second one's remote part more than 1024
+    entries), the small-terms row, the cancellation row.  n <= 3: edge_matrix itself.
+    Returns (csr, x, designed row indices — those of designed_rows plus "cuts": the cuts, "cut_rows": the replaced rows)."""
+    csr, x = edge_matrix(n, dtype)
+    special = dict(designed_rows(n))
+    special["cuts"], special["cut_rows"] = shard_cuts(n, worlds) if n >= 64 else [], []
+    if n < 64:
+        return csr, x, special
+    rp, ci, va = csr
+    rows = [(ci[rp[i]:rp[i + 1]], va[rp[i]:rp[i + 1]]) for i in range(n)]
+    taken = set(special["empty"]) | {special[k] for k in ("two_diag", "long1", "long2", "small_terms", "cancel")}
+    rng = np.random.default_rng(1000 + n)
+    for c in special["cuts"]:
+        for i, step in ((c - 1, -1), (c, 1)):
+            while i in taken:
+                i += step
+            assert 0 < i < n - 1, "no ordinary row next to the cut"
+            taken.add(i)
+            # c first and last; between them n - 1, the row's own index, c - 1 and 0, each once (the row may itself be c - 1 or c)
+            cols = [c] + [j for j in dict.fromkeys([n - 1, i, c - 1, 0]) if j != c] + [c]
+            v = rng.uniform(0.25, 1.0, len(cols)) * rng.choice([-1.0, 1.0], len(cols))   # no explicit zero on a cut
+            if np.dtype(dtype).kind == "c":
+                v = v + 1j * rng.uniform(-1, 1, len(cols))
+            rows[i] = (np.asarray(cols), v)
+            special["cut_rows"].append(i)
+    return _finish(rows, n, dtype), x, special
+
+
 def dense_of(csr, n):
     rp, ci, va = csr
     a = np.zeros((rp.shape[0] - 1, n), dtype=va.dtype)
@@ -141,6 +196,25 @@ def stencil_csr(dims, hop, diag, onsite, dtype):
     rp[1:] = np.cumsum([len(c) for c in cols])
     wide = np.complex128 if np.dtype(dtype).kind == "c" else np.float64
     return rp, np.concatenate(cols).astype(np.int32), np.concatenate(vals).astype(wide)
+
+
+def open_boundaries(csr, dims, periodic):
+    """stencil_csr's matrix (rows: the diagonal, then per dimension the upper and the lower neighbour) without the bonds that wrap
+    around a dimension that is not periodic."""
+    dims = list(dims)
+    if all(periodic):
+        return csr
+    rp, ci, va = csr
+    n = int(np.prod(dims))
+    coords = np.stack(np.unravel_index(np.arange(n), dims), axis=1)
+    keep = np.ones(ci.shape[0], dtype=bool)
+    for d, per in enumerate(periodic):
+        if not per:
+            keep[rp[:-1] + 1 + 2 * d] = coords[:, d] + 1 < dims[d]   # the upper neighbour
+            keep[rp[:-1] + 2 + 2 * d] = coords[:, d] > 0             # the lower neighbour
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    cnt = np.bincount(rows[keep], minlength=n)
+    return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), ci[keep], va[keep]
 
 
 def sym_triangle(n, dtype, seed=0, band=200, long_row=1500):

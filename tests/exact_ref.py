@@ -6,7 +6,9 @@ magnitudes leave the range where that is exact (denormal or near-overflow terms)
 
 The bound helpers state, one function per accuracy class of include/lanczos_hip.h, the largest error a kernel of that class may
 make; tests/test_exact_ref.py shows that each of them rejects the outputs of plausibly wrong kernels (float accumulation, a
-product rounded to a narrower type or in another sequence, a skipped row, y rounded to the wrong type, a fused dot product accumulated in float)."""
+product rounded to a narrower type or in another sequence, a skipped row, y rounded to the wrong type, a fused dot product accumulated in float;
+for the column-split forms of a sharded context: the remote part accumulated in float, a boundary column read from the wrong
+rank, the offset added by both parts, the padded tail of a short last shard read as data)."""
 import math
 from fractions import Fraction
 
@@ -259,6 +261,109 @@ def storage_bound(y, x, offset, dtype, sum_err):
     if np.iscomplexobj(y):
         return part(y.real, t.real, sum_err, oe[0]), part(y.imag, t.imag, sum_err, oe[1])
     return part(y, t, sum_err, oe[0]), None
+
+
+def class_bound(rows, x, y, offset, eps, fixed_point):
+    """The bound of the operator's accuracy class on |y_i - ((A x)_i + offset x_i)| per part, as the GPU contract tests assert it:
+    normwise_bound (max |x| over the WHOLE vector) for the fixed-point forms, componentwise_bound otherwise, plus
+    eps (|offset x_i| + |y_i|) for the offset product and the addition in T."""
+    x = np.asarray(x)
+    xw = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+    xmax = float(np.max(abs1(x))) if x.size else 0.0
+    cls = normwise_bound(rows, xmax, eps) if fixed_point else componentwise_bound(rows, eps)
+    return cls + eps * (np.abs(offset) * abs1(xw) + abs1(y)) + 1e-300
+
+
+# ------------------------------------------------------------------ column-split operators of a sharded context
+# A rank of a sharded context owns the rows AND the columns [cut_r, cut_{r+1}) (cut_r = min(n, r ceil(n / P))).  The CSR-stream and
+# the dense operator multiply the own columns first (under the all-gather) and add the other ranks' columns in a second kernel
+# (lanczos_hip.h, ACCURACY, "column-split forms").
+
+def owner_ranges(n, world):
+    """(col0, col1) per row: the column range the row's rank owns."""
+    stride = -(-n // world)
+    r = np.arange(n) // max(stride, 1)
+    return np.minimum(n, r * stride), np.minimum(n, (r + 1) * stride)
+
+
+def split_csr(csr, col0, col1):
+    """(own, rem): the entries of every row inside / outside [col0_i, col1_i), the order inside a row kept, column indices
+    global in both (the host twin of csr_split_kernel, which rebases the own part)."""
+    rp, ci, va = csr
+    rp = np.asarray(rp, dtype=np.int64)
+    n = rp.shape[0] - 1
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    ci64 = np.asarray(ci, dtype=np.int64)
+    own = (ci64 >= np.asarray(col0)[rows]) & (ci64 < np.asarray(col1)[rows])
+    out = []
+    for keep in (own, ~own):
+        cnt = np.bincount(rows[keep], minlength=n)
+        out.append((np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64), np.asarray(ci)[keep], np.asarray(va)[keep]))
+    return out[0], out[1]
+
+
+def formed_products_rows(csr, x, dtype, exact_above):
+    """Rows of the exact sums of the products a float / complex-float kernel FORMS: rounded to the storage type once
+    (rows_storage_products) in rows of at most `exact_above` entries, exact (rows_exact) in longer rows — CSR-stream:
+    exact_above = 1024, counted in the image the kernel walks; dense: exact_above = -1, every product exact."""
+    ex = rows_exact(csr, x)
+    if exact_above < 0:
+        return ex
+    sp = rows_storage_products(csr, x, dtype)
+    return Rows(np.where(ex.nnz > exact_above, ex.y, sp.y), ex.absrow, ex.rowsum, ex.nnz)
+
+
+def split_rows(csr, x, dtype, world, exact_above):
+    """(own, rem): formed_products_rows of the two halves of the column split on `world` ranks.  The > 1024 rule of CSR-stream
+    goes by the length of the row's PART: a row of 3000 entries whose own part holds 900 forms those 900 products in the storage
+    type."""
+    n = np.asarray(csr[0]).shape[0] - 1
+    own, rem = split_csr(csr, *owner_ranges(n, world))
+    return formed_products_rows(own, x, dtype, exact_above), formed_products_rows(rem, x, dtype, exact_above)
+
+
+def split_chain(s_own, s_rem, x, offset, dtype, offset_twice=False):
+    """What a right column-split kernel returns when its two accumulators are exact: fl_T(fl_T(fl_T(S_own) + t) + fl_T(S_rem)),
+    t = offset_term (numpy rounds every operation of the storage type once, like the device)."""
+    dtype = np.dtype(dtype)
+    t = offset_term(x, offset, dtype)
+    w = np.asarray(s_own).astype(dtype) + t
+    v = np.asarray(s_rem).astype(dtype)
+    if offset_twice:   # a wrong kernel: the offset term added by both parts
+        v = v + t
+    return (w + v).astype(dtype)
+
+
+def split_storage_bound(y, x, offset, dtype, own, rem, se_own, se_rem):
+    """Bound on |y_i - (S_own,i + S_rem,i + offset x_i)| per part for a float / complex-float column-split kernel (own, rem:
+    split_rows; se_*: double_sum_error of each part).  Part 1 leaves w_i = fl_f(v_o + t_i), v_o = fl_f(acc_o), t_i = offset_term;
+    part 2 returns y_i = fl_f(w_i + v_r), v_r = fl_f(acc_r); acc_* are double accumulators with |acc_* - S_*| <= se_*:
+        |y - (S_o + S_r + offset x)| <= |acc_o - S_o| + |acc_r - S_r|      the two sums                  se_own + se_rem
+                                      + |v_o - acc_o| + |v_r - acc_r|      TWO narrowings to T           u_f (|S_o| + se_own) + u_f (|S_r| + se_rem)
+                                      + |w - (v_o + t)|                     the addition of part 1        u_f |w|
+                                      + |y - (w + v_r)|                     the addition of part 2        u_f |y|
+                                      + |t - offset x|                      offset_error
+    with |w| <= (|v_o| + |t|)(1 + u_f), |v_o| <= (|S_o| + se_own)(1 + u_f).  storage_bound has one narrowing and one addition.
+    With offset == 0 part 1 adds a zero (w = v_o: no u_f |w|); in a row without remote entries part 2 adds a zero (y = w: no
+    u_f |y|).  Returns (bound of the real part, bound of the imaginary part or None)."""
+    u = 0.5 * EPS_F
+    t = offset_term(x, offset, dtype)
+    oe = offset_error(x, offset, dtype)
+    has_rem = rem.nnz > 0
+
+    def part(yp, tp, so, sr, op_err):
+        yp, tp = np.abs(yp.astype(np.float64)), np.abs(tp.astype(np.float64))
+        vo = (np.abs(so) + se_own) * (1 + u)
+        b = se_own + se_rem + u * (np.abs(so) + se_own) + u * (np.abs(sr) + se_rem) + op_err
+        if offset != 0.0:
+            b = b + u * (vo + tp) * (1 + u)
+        b = b + np.where(has_rem, u * yp, 0.0)
+        return b * (1 + 4 * u) + 1e-300   # (1 + 4 u_f): the second-order terms left out above
+
+    so, sr = np.asarray(own.y), np.asarray(rem.y)
+    if np.iscomplexobj(y):
+        return part(y.real, t.real, so.real, sr.real, oe[0]), part(y.imag, t.imag, so.imag, sr.imag, oe[1])
+    return part(y, t, np.real(so), np.real(sr), oe[0]), None
 
 
 def dot_bound(x, y, n=None):

@@ -184,3 +184,115 @@ def test_dot_bound_rejects_a_float_accumulated_alpha(dtype):
     terms = (np.real(x).astype(single) * np.real(y).astype(single) + np.imag(x).astype(single) * np.imag(y).astype(single))
     alpha_f = float(_seq_sum(terms, single))
     assert abs(alpha_f - d) > E.dot_bound(x, y)
+
+
+# ------------------------------------------------------------------ the column-split forms of a sharded context
+def _split_bound_ok(csr, x, dtype, world, y, offset, exact_above=1024):
+    """The storage contract of the column-split CSR-stream operator exactly as tests/test_gpu_sharded_contracts.py asserts it."""
+    own, rem = E.split_rows(csr, x, dtype, world, exact_above)
+    se_o, se_r = E.double_sum_error(own), E.double_sum_error(rem)
+    xw = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+    b = E.split_storage_bound(y, x, offset, dtype, own, rem, se_o, se_r)
+    return E.within(E.part_errors(y, own.y + rem.y + offset * xw), b)[0]
+
+
+def _class_ok(csr, x, y, offset, eps):
+    ex = E.rows_exact(csr, x)
+    xw = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+    b = E.class_bound(ex, x, y, offset, eps, False)
+    return E.within(E.part_errors(y, ex.y + offset * xw), (b, b))[0]
+
+
+def _emulate_split(csr, x, dtype, world, offset, how):
+    """Host emulation of a column-split CSR-stream kernel on `world` ranks, stitched over the ranks: "right", or one of the
+    plausibly wrong ones."""
+    n = x.shape[0]
+    col0, col1 = E.owner_ranges(n, world)
+    own_csr, rem_csr = E.split_csr(csr, col0, col1)
+    xo = xr = x
+    if how == "boundary_to_wrong_rank":
+        # ownership test off by one (col <= col1): the next rank's first column counts as own and is read one past the local
+        # shard, where the padded send buffer holds a zero
+        rp, ci, va = csr
+        rows = np.repeat(np.arange(n), np.diff(rp))
+        va = np.where(ci == col1[rows], 0, va).astype(va.dtype)
+        own_csr, rem_csr = E.split_csr((rp, ci, va), col0, col1)
+    if how == "padded_tail_as_data":
+        # the gathered vector has the stride ceil(n / P) per rank, the last shard is shorter and its tail is padding; a kernel
+        # that places the last shard at the END of the buffer reads the padding (zeros) as data and every column of that shard shifted
+        stride = -(-n // world)
+        pad = world * stride - n
+        assert pad > 0
+        rp, ci, va = rem_csr
+        xr = np.concatenate([x, np.zeros(pad, x.dtype)])
+        last = (world - 1) * stride
+        xr[last + pad:] = x[last:]
+        xr[last:last + pad] = 0
+    so = E.formed_products_rows(own_csr, xo, dtype, 1024)
+    sr = E.formed_products_rows(rem_csr, xr, dtype, 1024)
+    if how == "remote_part_in_float":
+        rp, ci, va = rem_csr
+        p = E.storage_products(va, x[ci], dtype)
+        v = np.array([_seq_sum(p[rp[i]:rp[i + 1]], dtype) for i in range(n)], dtype=dtype)
+        w = (so.y.astype(dtype) + E.offset_term(x, offset, dtype)).astype(dtype)
+        return (w + v).astype(dtype)
+    return E.split_chain(so.y, sr.y, x, offset, dtype, offset_twice=(how == "offset_in_both_parts"))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.complex64], ids=["s", "c"])
+@pytest.mark.parametrize("world", [2, 3])
+def test_split_storage_bound_rejects_wrong_split_kernels(dtype, world):
+    csr, x, special = K.sharded_edge_matrix(5003, dtype)
+    for offset in (0.0, -2.5, 0.1):
+        assert _split_bound_ok(csr, x, dtype, world, _emulate_split(csr, x, dtype, world, offset, "right"), offset), offset
+    for how in ("remote_part_in_float", "boundary_to_wrong_rank", "offset_in_both_parts", "padded_tail_as_data"):
+        assert 5003 % world != 0   # the last shard is short: there is a padded tail to misread
+        offset = 0.0 if how != "offset_in_both_parts" else 0.1
+        assert not _split_bound_ok(csr, x, dtype, world, _emulate_split(csr, x, dtype, world, offset, how), offset), how
+    # the split form is not the unsplit contract: two narrowings and two additions in T leave the one-rounding bound
+    assert not _storage_ok(csr, x, dtype, _emulate_split(csr, x, dtype, world, 0.0, "right"), offset=0.0)
+    # the > 1024 rule goes by the length of each part: on 3 ranks the own parts of both long rows stay below it
+    own, rem = E.split_rows(csr, x, dtype, world, 1024)
+    whole = E.formed_products_rows(csr, x, dtype, 1024)
+    long2 = special["long2"]
+    assert whole.nnz[long2] > 1024
+    if world == 3:
+        assert own.nnz[long2] <= 1024 < rem.nnz[long2] and own.nnz[special["long1"]] <= 1024 and rem.nnz[special["long1"]] <= 1024
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["d", "s"])
+@pytest.mark.parametrize("world", [2, 3])
+def test_class_bound_rejects_a_misplaced_boundary_column_and_a_padded_tail(dtype, world):
+    csr, x, special = K.sharded_edge_matrix(5003, dtype)
+    eps = E.EPS_D if dtype == np.float64 else E.EPS_F
+    for offset in (0.0, -2.5):
+        assert _class_ok(csr, x, _emulate_split(csr, x, dtype, world, offset, "right"), offset, eps)
+    assert not _class_ok(csr, x, _emulate_split(csr, x, dtype, world, 0.0, "boundary_to_wrong_rank"), 0.0, eps)
+    assert not _class_ok(csr, x, _emulate_split(csr, x, dtype, world, 0.0, "padded_tail_as_data"), 0.0, eps)
+    assert not _class_ok(csr, x, _emulate_split(csr, x, dtype, world, -2.5, "offset_in_both_parts"), -2.5, eps)
+
+
+def test_sharded_edge_matrix_puts_rows_on_every_cut():
+    n = 5003
+    csr, x, special = K.sharded_edge_matrix(n, np.float32)
+    base, _ = K.edge_matrix(n, np.float32)
+    assert special["cuts"] == [1668, 2502, 3336] and special["cut_rows"] == [1666, 1669, 2500, 2503, 3335, 3336]
+    rp, ci, va = csr
+    for c, (lo, hi) in zip(special["cuts"], zip(special["cut_rows"][0::2], special["cut_rows"][1::2])):
+        for i in (lo, hi):
+            cols = list(ci[rp[i]:rp[i + 1]])
+            assert set(cols) == {c - 1, c, 0, n - 1, i} and cols.count(c) == 2 and len(cols) == len(set(cols)) + 1
+            assert cols != sorted(cols)
+    # every other row is edge_matrix's
+    changed = set(special["cut_rows"])
+    for i in range(n):
+        if i not in changed:
+            a, b = slice(rp[i], rp[i + 1]), slice(base[0][i], base[0][i + 1])
+            assert np.array_equal(ci[a], base[1][b]) and np.array_equal(va[a], base[2][b])
+    # shard_rows: the row blocks of the ranks stitch back to the matrix, column indices global
+    for world in (2, 3):
+        stride = -(-n // world)
+        parts = [K.shard_rows(csr, min(n, r * stride), min(n, (r + 1) * stride) - min(n, r * stride)) for r in range(world)]
+        assert np.array_equal(np.concatenate([p[1] for p in parts]), ci)
+        assert np.array_equal(np.concatenate([p[0][1:] + rp[min(n, r * stride)] for r, p in enumerate(parts)]), rp[1:])
+        assert all(p[0][0] == 0 for p in parts)
