@@ -68,6 +68,10 @@ template <typename T> struct abi;
                                      ll_operator** o) {                                                                  \
       return ll_op_create_pauli_momentum_##SFX(c, ns, nd, m, nt, t, o);                                                  \
     }                                                                                                                    \
+    static int create_pauli_momentum_full(ll_context* c, int32_t ns, int32_t m, int64_t nt, const ll_pauli_term* t,      \
+                                          ll_operator** o) {                                                             \
+      return ll_op_create_pauli_momentum_full_##SFX(c, ns, m, nt, t, o);                                                 \
+    }                                                                                                                    \
     static int create_host(ll_context* c, int64_t n, int (*fn)(const void*, void*, int64_t, void*), void* user,          \
                            ll_operator** o) {                                                                            \
       return ll_op_create_host_##SFX(c, n, reinterpret_cast<HOSTFN>(fn), user, o);                                       \
@@ -341,6 +345,32 @@ template <typename T> class PauliMomentumOperator : public DeviceOperator<T> {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int64_t)terms.size(),
                                         terms.data(), &op));
+    int64_t n = 0, n_local = 0, n_terms = 0;
+    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
+    if (rc != LL_OK) (void)ll_op_destroy(op);
+    check(rc);
+    this->adopt(op, n, n_local);
+  }
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
+  }
+};
+
+// One momentum block of the FULL 2^n_sites space of a ring: H must commute with the one-site translation and need not conserve
+// S_z (transverse-field Ising, XYZ rings, transverse fields).  Vectors hold the D_m amplitudes of |r; m>, r running over the
+// orbit representatives of ALL states whose orbit length R satisfies m R = 0 (mod n_sites), ascending; size() returns D_m (about
+// 2^n_sites / n_sites).  0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image is O(D_m) — no table
+// over the 2^n_sites states: device_bytes() <= 8 D_m + 64 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
+// (ll_op_create_pauli_momentum_full_*).
+template <typename T> class PauliMomentumFullOperator : public DeviceOperator<T> {
+ public:
+  PauliMomentumFullOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : DeviceOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli_momentum_full(ctx.get(), (int32_t)n_sites, (int32_t)momentum, (int64_t)terms.size(), terms.data(),
+                                             &op));
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
     if (rc != LL_OK) (void)ll_op_destroy(op);

@@ -57,7 +57,8 @@ extern "C" {
                              *    also additive under minor 5 — ll_op_create_pauli_sector_* (one S_z sector; the minor stays 5:
                              *    no struct changed, and callers that need these entry points find them by name);
                              *    also additive under minor 5, with the same note — ll_op_create_pauli_momentum_* (one momentum block
-                             *    of an S_z sector of a ring) */
+                             *    of an S_z sector of a ring) and ll_op_create_pauli_momentum_full_* (one momentum block of the full
+                             *    2^n_sites space of a ring: no S_z conservation asked) */
 
 enum {
   LL_OK = 0,
@@ -356,6 +357,48 @@ int ll_op_create_pauli_momentum_s(ll_context* ctx, int32_t n_sites, int32_t n_do
                                   const ll_pauli_term* terms_host, ll_operator** out);
 int ll_op_create_pauli_momentum_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
                                   const ll_pauli_term* terms_host, ll_operator** out);
+
+/* (9) the same sum on ONE MOMENTUM BLOCK OF THE FULL 2^n_sites SPACE of a RING, for an H that commutes with the one-site
+ *     translation T and need NOT conserve total S_z: the transverse-field Ising ring (the second example of (6), which (7) and (8)
+ *     refuse), XYZ rings (J_x != J_y), transverse or tilted fields.  An H that does conserve S_z is accepted too; its block here is
+ *     the direct sum over n_down of the blocks of (8).  Conventions of (6) and (8): bit j is site j, T rotates a state LEFT by one
+ *     bit, the representative of an orbit is its smallest integer, L = n_sites, k = 2 pi m / L.  The basis of block m is the set of
+ *     representatives r of ALL 2^L states with (m R_r) mod L = 0, in ASCENDING integer order, D_m of them (about 2^L / L), each
+ *     standing for |r; m> = N_r^(-1/2) sum_{j=0}^{L-1} e^(-2 pi i m j / L) T^j |r>, N_r = L^2 / R_r.  With B the 2^L x D_m matrix of
+ *     these vectors — an isometry — THE OPERATOR IS B^H H B, H the operator of (6).  The sum over m of D_m is 2^L and the union of
+ *     the blocks' spectra is the spectrum of H.  Equivalent gather form, which the kernel evaluates: for representative a (number i)
+ *     and EVERY group g (there is no sector to leave) write a ^ X_g = T^l b with b the representative; if b is in the block,
+ *         y(i) += w_g(a) sqrt(R_a / R_b) e^(-2 pi i m l / L) v(number of b),
+ *     with w_g the weight of (6), groups in ascending mask order.
+ *     LIMITS: those of (6), and 0 <= momentum < n_sites.  The real types (_d, _s) take m = 0 and, for even L, m = L / 2 (besides
+ *     the even-nY rule); _z / _c take every m.  D_m < 2^27 - 1 (D_m is about 3.6e7 at L = 30).
+ *     REFUSALS (LL_ERR_INVALID, each naming its cause): those of (6); momentum outside [0, L); a real type with 2 m mod L != 0; a
+ *     real type with an odd nY; an H that does not commute with T (the rule and the message of (8): the (x_mask, z_mask) of the
+ *     first term at fault; an open chain is refused this way); a context of more than one rank.  There is no S_z check, and a block
+ *     is never empty: the state 0..01 has R = L, which every m admits (L = 1 has m = 0 only).
+ *     The image is O(D_m), with NO table over the 2^L states (the look-up table of (8) would be 4 * 2^L bytes: 4 GiB at L = 30 for
+ *     vectors of 3.6e7 elements): the term tables, the D_m representatives (4 D_m bytes) and their orbit lengths (D_m bytes), the
+ *     two small tables of (8), and a bucket table over the top bits of a representative — the number of representatives below each
+ *     prefix, about D_m / 8 prefixes, at most D_m / 2 bytes.  ll_op_device_bytes counts all of it and stays below
+ *     8 D_m + 64 KiB.  The kernel rotates a partner to its representative in registers (L - 1 rotate / compare steps, about 5 L
+ *     integer operations per partner) and finds its number by a binary search inside the partner's bucket, whose length is fixed
+ *     at creation from the LARGEST bucket (representatives crowd at small integers).  One apply moves between
+ *     (2 sizeof(T) + 5) D_m bytes (every gather found in cache) and (2 sizeof(T) + 5 + G (sizeof(T) + 8 + 4 t)) D_m, G = the x
+ *     masks != 0 and t the halvings of the search (per group one vector element, two bucket bounds, at most t representatives).
+ *     ACCURACY: that of (8), word for word — component-wise against the exact block; w_g summed in double as in (6), times
+ *     sqrt(R_a / R_b) where the orbit lengths differ, times the phase where m != 0 (exact on the axes), one double fma per group,
+ *     one rounding to T; the same bits run to run and for every block size, grid and buffer alignment.
+ *     Queries: ll_op_info reports n = n_local = D_m and the number of TERMS as nnz_local; ll_op_inf_norm returns sum_t |coef_t|, a
+ *     bound of EVERY |EIGENVALUE| of the block (B is an isometry), not claimed as a bound of its absolute row sums;
+ *     ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID (not a CSR operator), ll_op_accuracy the component-wise class. */
+int ll_op_create_pauli_momentum_full_d(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
+                                       const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_full_z(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
+                                       const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_full_s(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
+                                       const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_momentum_full_c(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
+                                       const ll_pauli_term* terms_host, ll_operator** out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

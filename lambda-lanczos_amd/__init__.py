@@ -24,6 +24,7 @@ from .engine import (  # noqa: F401
     Exponentiator,
     HostOperator,
     PauliOperator,
+    PauliMomentumFullOperator,
     PauliMomentumOperator,
     PauliSectorOperator,
     StencilOperator,

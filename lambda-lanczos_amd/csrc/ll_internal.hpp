@@ -272,6 +272,7 @@ struct Tuning {
   int tridiag_test_jitter_us = 0;  // LL_TRIDIAG_TEST_JITTER_US: random delay of every helper-thread verdict
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
   int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
+  int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
@@ -533,11 +534,35 @@ struct PauliMomentumImage {
            hi_rank.bytes() + ratio.bytes() + phase.bytes();
   }
 };
+// One momentum block of the FULL 2^n_sites space of a ring (pauli_momentum_full.hip): no S_z sector and no table over the states.
+// The basis is every representative whose period R satisfies m R = 0 (mod n_sites), ascending.  The kernel rotates a partner to
+// its representative b in registers and finds b's number by a bounded binary search in reps[] inside one bucket of the top bits:
+// start[q] = the number of representatives below q << prefix_shift, 2^(n_sites - prefix_shift) + 1 entries (about dim / 8 buckets:
+// at most dim / 2 bytes); search_trips = the halvings the LARGEST bucket needs (measured at creation: representatives crowd at
+// small integers), the uniform length of the kernel's search loop.  ratio[], phase[] as PauliMomentumImage.
+constexpr int kPauliMomentumFullBlockBits = 8;   // indices of a workgroup's block: one state per lane, as kPauliMomentumBlockBits
+struct PauliMomentumFullImage {
+  int n_sites = 0, momentum = 0, ngroups = 0, prefix_shift = 0, search_trips = 0;
+  int64_t nterms = 0, dim = 0, max_bucket = 0;   // dim = D_m; max_bucket = the most representatives under one prefix
+  DevArray<uint32_t> gx;
+  DevArray<int32_t> gptr;
+  DevArray<uint32_t> tz;
+  DevArray<double> tc;
+  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
+  DevArray<uint8_t> period;      // [dim]                 their orbit lengths R
+  DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
+  DevArray<double> ratio;        // [32 * 32]
+  DevArray<double> phase;        // [n_sites][2]
+  int64_t device_bytes() const {
+    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + period.bytes() + start.bytes() + ratio.bytes() +
+           phase.bytes();
+  }
+};
 }  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM, PAULI_MOMENTUM_FULL } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -567,11 +592,12 @@ struct ll_operator {
   ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
   ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
   ll::PauliMomentumImage pauli_momentum;  // one momentum block of an S_z sector of a ring (kind PAULI_MOMENTUM)
+  ll::PauliMomentumFullImage pauli_momentum_full;  // one momentum block of the full space of a ring (kind PAULI_MOMENTUM_FULL)
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
            sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes() +
-           pauli_sector.device_bytes() + pauli_momentum.device_bytes();
+           pauli_sector.device_bytes() + pauli_momentum.device_bytes() + pauli_momentum_full.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -615,6 +641,11 @@ void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64
 template <typename T>
 void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
                            const ll_pauli_term* terms, ll_operator** out);
+// n = D_m: the block of momentum 2 pi m / n_sites of ALL 2^n_sites states of a ring, for an H that commutes with the one-site shift
+// (no S_z conservation asked: the transverse-field Ising ring, XYZ rings); real types take m = 0 and m = n_sites / 2 only
+template <typename T>
+void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
+                                ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -624,7 +655,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -721,6 +752,10 @@ int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, 
 template <typename T>
 int launch_pauli_momentum(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                           const ScaleIn<T>* sc = nullptr);
+// One momentum block of the full space (op.kind == PAULI_MOMENTUM_FULL; pauli_momentum_full.hip): x, y hold D_m elements.
+template <typename T>
+int launch_pauli_momentum_full(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                               const ScaleIn<T>* sc = nullptr);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

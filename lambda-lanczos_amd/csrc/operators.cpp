@@ -950,6 +950,21 @@ void pauli_require_translation_invariant(int32_t n_sites, int64_t n_terms, const
                       "sector needs a translation-invariant H");
   }
 }
+// phase[l] = e^(-2 pi i m l / n_sites) as (re, im), l < n_sites, exact on the axes: the table of both momentum-block operators
+void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>& phase) {
+  for (int l = 0; l < n_sites; ++l) {
+    const int k = (int)(((int64_t)momentum * l) % n_sites);
+    const double th = 2.0 * M_PI * (double)k / (double)n_sites;
+    double c = std::cos(th), sn = -std::sin(th);
+    if (4 * k % n_sites == 0) {
+      const int quarter = 4 * k / n_sites;  // 0 .. 3
+      c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
+      sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
+    }
+    phase[2 * (size_t)l] = c;
+    phase[2 * (size_t)l + 1] = sn;
+  }
+}
 }  // namespace
 
 // One momentum block of that sector (pauli_momentum.hip).  One pass over the sector's states in ascending order, on the host: the
@@ -998,18 +1013,7 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
   std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
   for (int a = 1; a < 32; ++a)
     for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
-  for (int l = 0; l < n_sites; ++l) {  // e^(-2 pi i m l / n_sites), exact on the axes
-    const int k = (int)(((int64_t)momentum * l) % n_sites);
-    const double th = 2.0 * M_PI * (double)k / (double)n_sites;
-    double c = std::cos(th), sn = -std::sin(th);
-    if (4 * k % n_sites == 0) {
-      const int quarter = 4 * k / n_sites;  // 0 .. 3
-      c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
-      sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
-    }
-    phase[2 * (size_t)l] = c;
-    phase[2 * (size_t)l + 1] = sn;
-  }
+  momentum_phase_table(n_sites, momentum, phase);
   std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM, dim, 0, dim);
   op->nnz = n_terms;
   op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
@@ -1039,6 +1043,86 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
   *out = op.release();
 }
 
+// One momentum block of the full 2^n_sites space (pauli_momentum_full.hip).  The representatives and their periods come from the
+// Fredricksen-Kessler-Maiorana enumeration of binary necklaces: a string read from site n_sites - 1 down to site 0 that is the
+// lexicographically smallest of its rotations is the smallest integer of its orbit, and the enumeration yields these strings in
+// ascending order with their period (the length of the Lyndon word they repeat) — one step per pre-necklace, about two steps per
+// representative, no pass over the 2^n_sites states.  A step: raise the lowest 0 bit (position i from the top), drop what lies
+// below it and repeat the top i bits downwards; the result is a necklace iff i divides n_sites, and then its period is i.
+template <typename T>
+void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
+                                ll_operator** out) {
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
+  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
+  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
+             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
+             "storage type");
+  pauli_require_translation_invariant(n_sites, n_terms, terms);
+  const int L = n_sites;
+  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
+  std::vector<uint32_t> reps;
+  std::vector<uint8_t> period;
+  {
+    // a lower bound of D_m that saves most of the re-allocations: the orbits of full length alone, when the block takes them
+    reps.reserve((size_t)(((uint64_t)1 << L) / (uint64_t)L) + 64);
+    period.reserve(reps.capacity());
+    if (momentum == 0) {  // the first necklace, the string of zeros: period 1, in block 0 only
+      reps.push_back(0);
+      period.push_back(1);
+    }
+    uint32_t a = 0;
+    while (a != site_mask) {
+      const int low0 = __builtin_ctz(~a);  // the lowest 0 bit of a (a != all ones): string position i = L - low0 from the top
+      const int i = L - low0;
+      a = ((a >> low0) | 1u) << low0;      // raise it, clear what lies below
+      for (int sft = i; sft < L; sft *= 2) a |= a >> sft;  // repeat the top i bits downwards (bits shifted out fall off the end)
+      if (L % i != 0) continue;            // a pre-necklace only
+      if (((int64_t)momentum * i) % L != 0) continue;
+      LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "internal: a momentum block of 2^27 states or more");
+      reps.push_back(a);
+      period.push_back((uint8_t)i);
+    }
+  }
+  const int64_t dim = (int64_t)reps.size();
+  // never empty: the state 0..01 has the full period n_sites, which every m admits (n_sites = 1: m = 0, and both states have R = 1)
+  LL_REQUIRE(dim >= 1, "internal: an empty momentum block of the full space");
+  // buckets over the top bits: the largest power of two not above dim / 8 of them (the table stays below dim / 2 bytes)
+  int pb = 0;
+  while (pb < L && ((int64_t)2 << pb) <= dim / 8) ++pb;
+  const int shift = L - pb;
+  std::vector<uint32_t> start(((size_t)1 << pb) + 1, 0);
+  for (int64_t k = 0; k < dim; ++k) ++start[(size_t)(reps[(size_t)k] >> shift) + 1];
+  int64_t max_bucket = 0;
+  for (size_t q = 1; q < start.size(); ++q) {
+    max_bucket = std::max<int64_t>(max_bucket, start[q]);
+    start[q] += start[q - 1];
+  }
+  int trips = 0;  // halvings that bring the largest bucket down to one candidate (n -> n - n / 2)
+  for (int64_t n = max_bucket; n > 1; n -= n / 2) ++trips;
+  std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
+  for (int a = 1; a < 32; ++a)
+    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
+  momentum_phase_table(n_sites, momentum, phase);
+  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM_FULL, dim, 0, dim);
+  op->nnz = n_terms;
+  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
+  PauliMomentumFullImage im;
+  im.n_sites = n_sites;
+  im.momentum = momentum;
+  im.dim = dim;
+  im.prefix_shift = shift;
+  im.search_trips = trips;
+  im.max_bucket = max_bucket;
+  pauli_upload_tables(ctx, im, pt);
+  pauli_upload(ctx, im.reps, reps, "momentum block representatives");
+  pauli_upload(ctx, im.period, period, "momentum block orbit lengths");
+  pauli_upload(ctx, im.start, start, "momentum block bucket table");
+  pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
+  pauli_upload(ctx, im.phase, phase, "momentum block phases");
+  op->pauli_momentum_full = std::move(im);
+  *out = op.release();
+}
+
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out) {
   LL_REQUIRE(host_fn != nullptr || dev_fn != nullptr, "null callback");
@@ -1063,6 +1147,7 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
   template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
   template void create_pauli_sector<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);             \
   template void create_pauli_momentum<T>(ll_context*, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);  \
+  template void create_pauli_momentum_full<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);    \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 

@@ -32,12 +32,6 @@
 namespace ll {
 
 namespace {
-// w * f * (c + i s): a real weight takes real factors only (creation admits m = 0 and n_sites / 2 for the real types: s = 0)
-__device__ __forceinline__ double momentum_scale(double w, double f) { return w * f; }
-__device__ __forceinline__ zc momentum_scale(zc w, double f) { return zc{w.re * f, w.im * f}; }
-__device__ __forceinline__ double momentum_phase(double w, double c, double) { return w * c; }
-__device__ __forceinline__ zc momentum_phase(zc w, double c, double s) { return zc{w.re * c - w.im * s, w.re * s + w.im * c}; }
-
 struct MomentumTables {
   const uint32_t* __restrict__ reps;
   const uint8_t* __restrict__ period;

@@ -469,6 +469,32 @@ class PauliMomentumOperator(_Operator):
         return CsrOperator.inf_norm(self)
 
 
+class PauliMomentumFullOperator(_Operator):
+    """One momentum block of the full 2^n_sites space of a ring (ll_op_create_pauli_momentum_full_*): the operator B^H H B with
+    B = generators.full_momentum_embedding(n_sites, momentum) and H the PauliOperator of the same terms; the basis is the orbit
+    representatives of generators.full_momentum_basis, ascending.  H must commute with the one-site translation — creation
+    refuses one that does not, naming the term at fault — and need not conserve S_z (transverse-field Ising, XYZ rings).
+    0 <= momentum < n_sites; the real dtypes take momentum 0 and n_sites / 2 only.  The image is O(n): no table over the
+    2^n_sites states (device_bytes <= 8 n + 64 KiB)."""
+
+    def __init__(self, ctx, n_sites, momentum, terms, dtype=np.float64):
+        terms = list(terms)
+        arr = (capi.PauliTerm * max(len(terms), 1))()
+        for k, (xm, zm, c) in enumerate(terms):
+            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+        self.ctx, self.dtype = ctx, np.dtype(dtype)
+        self.n_sites, self.momentum = int(n_sites), int(momentum)
+        self.n = self.n_local = 0
+        self.row_begin, self.nnz = 0, len(terms)
+        h = C.c_void_p()
+        fn = getattr(lib(), "ll_op_create_pauli_momentum_full_" + _suffix(self.dtype))
+        check(fn(ctx.handle, self.n_sites, self.momentum, len(terms), arr, C.byref(h)))
+        self.handle = h
+        self.n = self.n_local = self.info()[0]   # D_m: counted at creation
+
+    inf_norm = PauliMomentumOperator.inf_norm
+
+
 class HostOperator(_Operator):
     """Unmodified user code: mv_mul(in, out) on numpy arrays, `out` zero-filled on entry (LL:120-126)."""
 

@@ -212,6 +212,16 @@ def tfim_terms(L, J, h, periodic=False):
     return terms + [(1 << j, 0, -float(h)) for j in range(L)]
 
 
+def xyz_terms(L, jx, jy, jz, periodic=True):
+    """XYZ chain sum_j (jx X_j X_{j+1} + jy Y_j Y_{j+1} + jz Z_j Z_{j+1}) (Pauli matrices): three terms per bond; real symmetric;
+    conserves S_z only where jx = jy."""
+    terms = []
+    for j in range(L if periodic and L > 2 else L - 1):
+        a = (1 << j) | (1 << ((j + 1) % L))
+        terms += [(a, 0, float(jx)), (a, a, float(jy)), (0, a, float(jz))]
+    return terms
+
+
 def tfim_ground_energy(L, J, h):
     """Exact ground-state energy of the OPEN transverse-field Ising chain: minus the sum of the singular values of the
     L x L matrix with h on the diagonal and J on the superdiagonal (free fermions)."""
@@ -380,8 +390,11 @@ def pauli_sector_csr(n_sites, n_down, terms, dtype=np.float64, merge=True):
 # m holds the representatives whose orbit length R satisfies m R = 0 (mod L), ascending (ll_op_create_pauli_momentum_*).
 def _orbits(n_sites, n_down):
     """For every state s of sector_states(n_sites, n_down): (states, its representative b, l with s = T^l b and 0 <= l < R, R)."""
-    L = int(n_sites)
-    states = sector_states(L, n_down).astype(np.uint64)
+    return _orbits_of(int(n_sites), sector_states(int(n_sites), n_down).astype(np.uint64))
+
+
+def _orbits_of(L, states):
+    """_orbits for any array of states (uint64) that is closed under the rotation: L - 1 rotations of the whole array."""
     mask = np.uint64((1 << L) - 1)
     rep, first = states.copy(), np.zeros(states.shape[0], np.int64)    # min over the rotations, the first j with T^j s = min
     period = np.full(states.shape[0], L, np.int64)
@@ -484,6 +497,74 @@ def pauli_momentum_csr(n_sites, n_down, m, terms, dtype=np.float64, merge=True):
         q = np.where(inside, p, states[0])
         k = lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)]
         return col[k], inside & inb[k], np.sqrt(ra / period[k]) * phases[l[k]]
+
+    return _pauli_rows(reps, terms, dtype, merge, column_of)
+
+
+# ------------------------------------------------------------------ one momentum block of the full 2^n_sites space of a ring
+# The conventions above without the sector: block m holds the representatives of ALL states whose orbit length R satisfies
+# m R = 0 (mod L), ascending (ll_op_create_pauli_momentum_full_*); H need not conserve S_z.
+def _check_full_momentum(n_sites, m):
+    n_sites, m = int(n_sites), int(m)
+    if not (1 <= n_sites <= 30 and 0 <= m < n_sites):
+        raise ValueError("need 1 <= n_sites <= 30, 0 <= m < n_sites")
+    return n_sites, m
+
+
+def _orbits_full(n_sites):
+    return _orbits_of(n_sites, np.arange(1 << n_sites, dtype=np.uint64))
+
+
+def full_momentum_basis(n_sites, m):
+    """(representatives, periods) of block m of the full space: the representatives r (uint32, ascending) of all 2^n_sites states
+    with m R_r = 0 (mod n_sites) and their orbit lengths R_r (int64)."""
+    n_sites, m = _check_full_momentum(n_sites, m)
+    states, rep, _, period = _orbits_full(n_sites)
+    inb = (states == rep) & ((m * period) % n_sites == 0)
+    return states[inb].astype(np.uint32), period[inb]
+
+
+def full_momentum_embedding(n_sites, m, dense=True):
+    """B: the basis vectors |r; m> = N_r^(-1/2) sum_j e^(-2 pi i m j / L) T^j |r>, N_r = L^2 / R_r, as the columns of a
+    2^n_sites x D_m matrix (an isometry).  A row holds at most one entry, e^(-2 pi i m l / L) / sqrt(R) for the state T^l r:
+    dense=False returns (column of each row or -1, its value)."""
+    n_sites, m = _check_full_momentum(n_sites, m)
+    states, rep, l, period = _orbits_full(n_sites)
+    inb = (m * period) % n_sites == 0
+    reps = states[(states == rep) & inb]
+    col = np.where(inb, np.searchsorted(reps, rep), -1).astype(np.int64)
+    val = np.where(inb, _momentum_phases(n_sites, m)[l] / np.sqrt(period.astype(np.float64)), 0.0)
+    if not dense:
+        return col, val
+    B = np.zeros((states.shape[0], reps.shape[0]), np.complex128)
+    B[np.flatnonzero(inb), col[inb]] = val[inb]
+    return B
+
+
+def pauli_momentum_full_csr(n_sites, m, terms, dtype=np.float64, merge=True):
+    """The block B^H H B (B = full_momentum_embedding, H = pauli_csr) as CSR over full_momentum_basis, from the gather form, in
+    double: row a holds, per x mask X whose partner a ^ X = T^l b has b in the block, w(a) sqrt(R_a / R_b) e^(-2 pi i m l / L) in
+    the column of b, w as in pauli_csr.  merge as in pauli_csr (merge=False: one entry per term and state).  A real dtype needs
+    2 m = 0 (mod n_sites); H must commute with the translation (it need not conserve S_z)."""
+    n_sites, m = _check_full_momentum(n_sites, m)
+    terms = list(terms)
+    if np.dtype(dtype).kind != "c" and (2 * m) % n_sites:
+        raise ValueError("a real dtype takes m = 0 and m = n_sites / 2 only")
+    t = translation_fault(n_sites, terms)
+    if t is not None:
+        raise ValueError("term %d (x_mask 0x%x, z_mask 0x%x) does not commute with the one-site translation"
+                         % (t, terms[t][0], terms[t][1]))
+    states, rep, l, period = _orbits_full(n_sites)
+    inb = (m * period) % n_sites == 0
+    isrep = (states == rep) & inb
+    reps = states[isrep]
+    col = np.where(inb, np.searchsorted(reps, rep), 0).astype(np.int64)
+    phases = _momentum_phases(n_sites, m)
+    ra = period[isrep].astype(np.float64)
+
+    def column_of(p):
+        k = p.astype(np.int64)   # the state is its own number: no sector to leave
+        return col[k], inb[k], np.sqrt(ra / period[k]) * phases[l[k]]
 
     return _pauli_rows(reps, terms, dtype, merge, column_of)
 
