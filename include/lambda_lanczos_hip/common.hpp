@@ -72,6 +72,10 @@ template <typename T> struct abi;
                                           ll_operator** o) {                                                             \
       return ll_op_create_pauli_momentum_full_##SFX(c, ns, m, nt, t, o);                                                 \
     }                                                                                                                    \
+    static int create_pauli_symmetric(ll_context* c, int32_t ns, int32_t nd, int32_t m, int32_t p, int32_t z, int64_t nt, \
+                                      const ll_pauli_term* t, ll_operator** o) {                                         \
+      return ll_op_create_pauli_symmetric_##SFX(c, ns, nd, m, p, z, nt, t, o);                                           \
+    }                                                                                                                    \
     static int create_host(ll_context* c, int64_t n, int (*fn)(const void*, void*, int64_t, void*), void* user,          \
                            ll_operator** o) {                                                                            \
       return ll_op_create_host_##SFX(c, n, reinterpret_cast<HOSTFN>(fn), user, o);                                       \
@@ -371,6 +375,33 @@ template <typename T> class PauliMomentumFullOperator : public DeviceOperator<T>
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum_full(ctx.get(), (int32_t)n_sites, (int32_t)momentum, (int64_t)terms.size(), terms.data(),
                                              &op));
+    int64_t n = 0, n_local = 0, n_terms = 0;
+    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
+    if (rc != LL_OK) (void)ll_op_destroy(op);
+    check(rc);
+    this->adopt(op, n, n_local);
+  }
+  int64_t device_bytes() const {
+    int64_t b = 0;
+    check(ll_op_device_bytes(this->get(), &b));
+    return b;
+  }
+};
+
+// One block of a ring under momentum, reflection and spin inversion: parity / inversion are 0 (not used), +1 or -1; n_down = -1
+// is the full space, else the S_z sector.  H must commute with the one-site translation and with every symmetry in use.  Vectors
+// hold the D amplitudes of |r; chi>, r running over the admitted representatives of the group's orbits, ascending; size()
+// returns D.  parity != 0 and real T take momentum 0 and n_sites / 2 only; an empty block is refused.  The image is O(D):
+// device_bytes() <= 8 D + 192 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
+// (ll_op_create_pauli_symmetric_*).
+template <typename T> class PauliSymmetricOperator : public DeviceOperator<T> {
+ public:
+  PauliSymmetricOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, int parity = 0, int inversion = 0,
+                         int n_down = -1, Context ctx = Context::default_context())
+      : DeviceOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli_symmetric(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int32_t)parity,
+                                         (int32_t)inversion, (int64_t)terms.size(), terms.data(), &op));
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
     if (rc != LL_OK) (void)ll_op_destroy(op);

@@ -58,7 +58,9 @@ extern "C" {
                              *    no struct changed, and callers that need these entry points find them by name);
                              *    also additive under minor 5, with the same note — ll_op_create_pauli_momentum_* (one momentum block
                              *    of an S_z sector of a ring) and ll_op_create_pauli_momentum_full_* (one momentum block of the full
-                             *    2^n_sites space of a ring: no S_z conservation asked) */
+                             *    2^n_sites space of a ring: no S_z conservation asked);
+                             *    also additive under minor 5, with the same note — ll_op_create_pauli_symmetric_* (momentum,
+                             *    reflection and spin-inversion blocks of a ring) */
 
 enum {
   LL_OK = 0,
@@ -399,6 +401,58 @@ int ll_op_create_pauli_momentum_full_s(ll_context* ctx, int32_t n_sites, int32_t
                                        const ll_pauli_term* terms_host, ll_operator** out);
 int ll_op_create_pauli_momentum_full_c(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
                                        const ll_pauli_term* terms_host, ll_operator** out);
+
+/* (10) the same sum on ONE BLOCK OF A RING UNDER MOMENTUM, REFLECTION AND SPIN INVERSION — the state labels k, p, z of exact
+ *     diagonalisation — of the full 2^n_sites space (n_down = -1) or of one S_z sector (0 <= n_down <= n_sites).  Conventions of
+ *     (6) - (9): bit j is site j, L = n_sites, T rotates a state LEFT by one bit; P is the reflection j -> L - 1 - j (the L bits
+ *     reversed); Z is the global flip prod_j X_j (s -> ~s & (2^L - 1)).  All three permute basis states without signs.
+ *     parity and inversion are 0 ("this symmetry is not used"), +1 or -1.  The group G is generated by T, by P if parity != 0 and by
+ *     Z if inversion != 0: |G| = L, 2 L or 4 L elements T^j P^rho Z^zeta, with the character
+ *         chi(T^j P^rho Z^zeta) = e^(-2 pi i m j / L) parity^rho inversion^zeta.
+ *     The representative of a G-orbit is its smallest integer; it is admitted iff chi(s) = 1 for every s of its stabiliser and, for
+ *     n_down >= 0, iff its popcount is n_down.  The basis is the admitted representatives r in ASCENDING order, D of them, each
+ *     standing for |r; chi> = N_r^(-1/2) sum_{g in G} chi(g) g |r>.  With B the matrix of these vectors — an isometry — THE
+ *     OPERATOR IS B^H H B, H the operator of (6) (of (7) for n_down >= 0).  On top of momentum 0 or L / 2 the two symmetries cut
+ *     the block of (9) by about 2 and 4, and the block stays real symmetric for a real H.  Equivalent gather form, which the kernel
+ *     evaluates: for representative a (number i) and every group of terms with x mask X_g write a ^ X_g = g b with b the
+ *     representative; if b is in the basis,
+ *         y(i) += w_g(a) sqrt(R_a / R_b) chi(g) v(number of b),
+ *     R = |G| / |stabiliser| the orbit length (at most 120), w_g the weight of (6), groups in ascending mask order.  With
+ *     parity = inversion = 0 and n_down = -1 the result has the same bits as (9).
+ *     LIMITS: those of (6); 0 <= momentum < n_sites; D < 2^27 - 1.  parity != 0 needs 2 m mod L = 0 for every type (the group of T
+ *     and P has one-dimensional characters only there); the real types (_d, _s) need 2 m mod L = 0 too, besides the even-nY rule.
+ *     REFUSALS (LL_ERR_INVALID, each naming its cause): those of (9); parity or inversion outside {0, +1, -1}; parity != 0 with
+ *     2 m mod L != 0; an H that does not commute with P (with equal masks merged, reversing the L bits of every term's masks must
+ *     map the term set onto itself with exactly equal coefficients: the first term at fault is named; a Dzyaloshinskii-Moriya ring
+ *     is refused this way); an H that does not commute with Z (a merged term of odd popcount(z_mask) with a coefficient != 0: a
+ *     longitudinal field); n_down outside [-1, L]; n_down >= 0 with an H that does not conserve S_z (the rule and the message of
+ *     (7)); n_down >= 0 with inversion != 0 and 2 n_down != L; an EMPTY block (L = 4, m = 0, parity = -1 has D = 0, and so does
+ *     L = 6, m = 0, parity = -1, inversion = +1); a context of more than one rank.
+ *     The image is O(D), with no table over the 2^L states nor over the sector: the term tables, the D representatives (4 D
+ *     bytes), their orbit lengths (D bytes), the bucket table of (9) (at most D / 2 bytes), sqrt(R_a / R_b) for every pair (121^2
+ *     doubles) and the L phases.  ll_op_device_bytes counts all of it and stays below 8 D + 192 KiB.  Creation enumerates the
+ *     binary necklaces as (9) does and, for each, walks the L rotations of rev(a), ~a and ~rev(a) — whichever are in use — to
+ *     decide whether a is the smallest of its G-orbit, to collect its stabiliser and to apply the popcount filter: O(L) per
+ *     necklace, O(2^L) steps overall on the host, also for n_down >= 0.  The kernel finds a partner's representative in registers
+ *     — L steps over up to four streams, the rotations of p, ~p, rev(p) and ~rev(p): about 6 L integer operations per stream and
+ *     partner —, counts the elements that reach it (the stabiliser's size, hence R_b, without a load), finds its number by the
+ *     bounded search of (9) and takes it iff the entry found equals it; a partner outside the sector is not found (its weight
+ *     is exactly 0 for a conserving H).  UNMEASURED: the apply time, creation time at large L, the block size of the kernel.
+ *     ACCURACY: that of (8) and (9) — component-wise against the exact block; w_g summed in double as in (6), times
+ *     sqrt(R_a / R_b) where the orbit lengths differ, times the phase where m != 0 (exact on the axes), a sign flip for
+ *     parity^rho inversion^zeta = -1 (exact), one double fma per group, one rounding to T; the single-type storage-product contract
+ *     is not claimed; the same bits run to run and for every block size, grid and buffer alignment.
+ *     Queries: as (9) — ll_op_info reports n = n_local = D and the number of TERMS as nnz_local; ll_op_inf_norm returns
+ *     sum_t |coef_t|, a bound of EVERY |EIGENVALUE| of the block; ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID,
+ *     ll_op_accuracy the component-wise class. */
+int ll_op_create_pauli_symmetric_d(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_symmetric_z(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_symmetric_s(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

@@ -27,6 +27,7 @@ from .engine import (  # noqa: F401
     PauliMomentumFullOperator,
     PauliMomentumOperator,
     PauliSectorOperator,
+    PauliSymmetricOperator,
     StencilOperator,
     LambdaLanczos,
     default_context,

@@ -172,6 +172,10 @@ PROTOTYPES = {
     "ll_op_create_pauli_momentum_z": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, i64, P(PauliTerm), P(vp)]),
     "ll_op_create_pauli_momentum_full_d": (C.c_int, [vp, C.c_int32, C.c_int32, i64, P(PauliTerm), P(vp)]),
     "ll_op_create_pauli_momentum_full_z": (C.c_int, [vp, C.c_int32, C.c_int32, i64, P(PauliTerm), P(vp)]),
+    "ll_op_create_pauli_symmetric_d": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, P(PauliTerm),
+                                                 P(vp)]),
+    "ll_op_create_pauli_symmetric_z": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, P(PauliTerm),
+                                                 P(vp)]),
     "ll_op_create_host_d": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_host_z": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_device_d": (C.c_int, [vp, i64, DEV_MV_FN, vp, P(vp)]),

@@ -68,6 +68,7 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "pauli_tile_bits") t.pauli_tile_bits = e ? d.pauli_tile_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "pauli_momentum_block_bits") t.pauli_momentum_block_bits = e ? d.pauli_momentum_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "pauli_momentum_full_block_bits") t.pauli_momentum_full_block_bits = e ? d.pauli_momentum_full_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
+  else if (key == "pauli_symmetric_block_bits") t.pauli_symmetric_block_bits = e ? d.pauli_symmetric_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "pauli_sector_block_bits") t.pauli_sector_block_bits = e ? d.pauli_sector_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "stencil_vec") t.stencil_vec = e ? d.stencil_vec : to_flag(v);
   else if (key == "tl_force") t.tl_force = e ? false : to_flag(v);
@@ -727,6 +728,22 @@ int ll_op_create_pauli_momentum_full_s(ll_context* ctx, int32_t n_sites, int32_t
 int ll_op_create_pauli_momentum_full_c(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms,
                                        const ll_pauli_term* terms, ll_operator** out) {
   return guarded([&] { create_pauli_momentum_full<cf>(ctx, n_sites, momentum, n_terms, terms, out); });
+}
+int ll_op_create_pauli_symmetric_d(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli_symmetric<double>(ctx, n_sites, n_down, momentum, parity, inversion, n_terms, terms, out); });
+}
+int ll_op_create_pauli_symmetric_z(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli_symmetric<zc>(ctx, n_sites, n_down, momentum, parity, inversion, n_terms, terms, out); });
+}
+int ll_op_create_pauli_symmetric_s(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli_symmetric<float>(ctx, n_sites, n_down, momentum, parity, inversion, n_terms, terms, out); });
+}
+int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
+                                   int32_t inversion, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] { create_pauli_symmetric<cf>(ctx, n_sites, n_down, momentum, parity, inversion, n_terms, terms, out); });
 }
 int ll_op_create_host_d(ll_context* ctx, int64_t n, ll_host_mv_mul_d fn, void* user, ll_operator** out) {
   return guarded([&] { create_cb<double>(ctx, n, reinterpret_cast<ll_host_mv_mul_z>(fn), nullptr, user, out); });

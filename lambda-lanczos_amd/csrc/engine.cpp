@@ -272,6 +272,8 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
     nparts = launch_pauli_momentum<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
   else if (op->kind == ll_operator::PAULI_MOMENTUM_FULL)  // one momentum block of the full space
     nparts = launch_pauli_momentum_full<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
+  else if (op->kind == ll_operator::PAULI_SYMMETRIC)  // one momentum / reflection / spin-inversion block
+    nparts = launch_pauli_symmetric<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
   else if (op->kind == ll_operator::DENSE)
     nparts = apply_rows(&launch_dense_mv<T>, ctx->tune.csr_split && dense_split_ok, x_local, x_padded, y, offset, dotp, sc);
   else if (op->kind != ll_operator::CSR) nparts = apply_callback(x_local, y, offset, dotp);

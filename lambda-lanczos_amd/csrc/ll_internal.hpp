@@ -273,6 +273,7 @@ struct Tuning {
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
   int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
   int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
+  int pauli_symmetric_block_bits = -1;  // key pauli_symmetric_block_bits = b: the same for the momentum / reflection / spin-inversion kernel (-1: kPauliSymmetricBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
@@ -558,11 +559,37 @@ struct PauliMomentumFullImage {
            phase.bytes();
   }
 };
+// One block of a ring under momentum, reflection and spin inversion, of the full space or of one S_z sector (pauli_symmetric.hip):
+// PauliMomentumFullImage with a larger group.  The basis is every representative (the smallest integer of its orbit under the
+// group G generated by the shift, by the reflection if parity != 0 and by the global flip if inversion != 0) on whose stabiliser
+// the character is 1 and, with n_down >= 0, whose popcount is n_down, ascending.  reps[], start[], prefix_shift, search_trips as
+// PauliMomentumFullImage; the kernel decides membership by comparing the entry it finds with the representative.
+// ratio[R_a * kPauliSymmetricRatioStride + c] = sqrt(R_a / (|G| / c)) for the stabiliser sizes c that divide |G| (R <= |G| <= 120).
+constexpr int kPauliSymmetricBlockBits = kPauliMomentumFullBlockBits;  // taken over from the full-momentum kernel, unmeasured
+constexpr unsigned kPauliSymmetricRatioStride = 121;
+struct PauliSymmetricImage {
+  int n_sites = 0, n_down = -1, momentum = 0, parity = 0, inversion = 0, group_size = 0;
+  int ngroups = 0, prefix_shift = 0, search_trips = 0;
+  int64_t nterms = 0, dim = 0, max_bucket = 0;
+  DevArray<uint32_t> gx;
+  DevArray<int32_t> gptr;
+  DevArray<uint32_t> tz;
+  DevArray<double> tc;
+  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
+  DevArray<uint8_t> orbit_len;   // [dim]                 their orbit lengths R = |G| / |stabiliser|
+  DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
+  DevArray<double> ratio;        // [121 * 121]
+  DevArray<double> phase;        // [n_sites][2]
+  int64_t device_bytes() const {
+    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + orbit_len.bytes() + start.bytes() + ratio.bytes() +
+           phase.bytes();
+  }
+};
 }  // namespace ll
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM, PAULI_MOMENTUM_FULL } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM, PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -593,11 +620,13 @@ struct ll_operator {
   ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
   ll::PauliMomentumImage pauli_momentum;  // one momentum block of an S_z sector of a ring (kind PAULI_MOMENTUM)
   ll::PauliMomentumFullImage pauli_momentum_full;  // one momentum block of the full space of a ring (kind PAULI_MOMENTUM_FULL)
+  ll::PauliSymmetricImage pauli_symmetric;  // one momentum / reflection / spin-inversion block of a ring (kind PAULI_SYMMETRIC)
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
            sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes() +
-           pauli_sector.device_bytes() + pauli_momentum.device_bytes() + pauli_momentum_full.device_bytes();
+           pauli_sector.device_bytes() + pauli_momentum.device_bytes() + pauli_momentum_full.device_bytes() +
+           pauli_symmetric.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -646,6 +675,11 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
 template <typename T>
 void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
                                 ll_operator** out);
+// n = D: the block (momentum, parity, inversion) of a ring — of all 2^n_sites states (n_down = -1) or of the sector n_down —
+// for an H that commutes with the shift and with the reflection / the global flip where parity / inversion != 0
+template <typename T>
+void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity, int32_t inversion,
+                            int64_t n_terms, const ll_pauli_term* terms, ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -655,7 +689,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -756,6 +790,10 @@ int launch_pauli_momentum(const ll_operator& op, const T* x, T* y, double offset
 template <typename T>
 int launch_pauli_momentum_full(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                                const ScaleIn<T>* sc = nullptr);
+// One momentum / reflection / spin-inversion block (op.kind == PAULI_SYMMETRIC; pauli_symmetric.hip): x, y hold D elements.
+template <typename T>
+int launch_pauli_symmetric(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                           const ScaleIn<T>* sc = nullptr);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

@@ -965,6 +965,86 @@ void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>
     phase[2 * (size_t)l + 1] = sn;
   }
 }
+// The binary necklaces of n_sites bits in ascending order with their periods, by the Fredricksen-Kessler-Maiorana enumeration: a
+// string read from site n_sites - 1 down to site 0 that is the lexicographically smallest of its rotations is the smallest
+// integer of its orbit, and the enumeration yields these strings in ascending order with their period (the length of the Lyndon
+// word they repeat) — one step per pre-necklace, about two steps per necklace, no pass over the 2^n_sites states.  A step: raise
+// the lowest 0 bit (position i from the top), drop what lies below it and repeat the top i bits downwards; the result is a
+// necklace iff i divides n_sites, and then its period is i.  visit(a, period) is called for every necklace, the string of zeros
+// (period 1) first.
+template <typename Visit> void for_each_necklace(int L, Visit visit) {
+  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
+  visit((uint32_t)0, 1);
+  uint32_t a = 0;
+  while (a != site_mask) {
+    const int low0 = __builtin_ctz(~a);  // the lowest 0 bit of a (a != all ones): string position i = L - low0 from the top
+    const int i = L - low0;
+    a = ((a >> low0) | 1u) << low0;      // raise it, clear what lies below
+    for (int sft = i; sft < L; sft *= 2) a |= a >> sft;  // repeat the top i bits downwards (bits shifted out fall off the end)
+    if (L % i != 0) continue;            // a pre-necklace only
+    visit(a, i);
+  }
+}
+// The bucket table over the top bits of ascending representatives (PauliMomentumFullImage): the largest power of two not above
+// dim / 8 buckets (the table stays below dim / 2 bytes), and the halvings that bring the largest bucket down to one candidate.
+struct RepBuckets {
+  std::vector<uint32_t> start;
+  int shift = 0, trips = 0;
+  int64_t max_bucket = 0;
+};
+RepBuckets rep_buckets(int L, const std::vector<uint32_t>& reps) {
+  const int64_t dim = (int64_t)reps.size();
+  RepBuckets rb;
+  int pb = 0;
+  while (pb < L && ((int64_t)2 << pb) <= dim / 8) ++pb;
+  rb.shift = L - pb;
+  rb.start.assign(((size_t)1 << pb) + 1, 0);
+  for (int64_t k = 0; k < dim; ++k) ++rb.start[(size_t)(reps[(size_t)k] >> rb.shift) + 1];
+  for (size_t q = 1; q < rb.start.size(); ++q) {
+    rb.max_bucket = std::max<int64_t>(rb.max_bucket, rb.start[q]);
+    rb.start[q] += rb.start[q - 1];
+  }
+  for (int64_t n = rb.max_bucket; n > 1; n -= n / 2) ++rb.trips;  // n -> n - n / 2
+  return rb;
+}
+// Reflection invariance: with the coefficients of equal (x_mask, z_mask) merged (summed in the caller's order), reversing the
+// n_sites bits of every term's masks must map the term set onto itself with exactly equal coefficients (a missing term counts
+// as coefficient 0).  A site permutation moves X, Y, Z factors without a sign, so the caller's coefficients are compared.
+void pauli_require_reflection_invariant(int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms) {
+  auto rev = [&](uint64_t v) {
+    uint64_t r = 0;
+    for (int j = 0; j < n_sites; ++j) r |= ((v >> j) & 1u) << (n_sites - 1 - j);
+    return r;
+  };
+  std::map<std::pair<uint64_t, uint64_t>, double> merged;
+  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask}, moved{rev(key.first), rev(key.second)};
+    const auto it = merged.find(moved);
+    const double there = it == merged.end() ? 0.0 : it->second;
+    if (there == merged[key]) continue;
+    char hex[64];
+    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
+    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the reflection of the ring (site j -> "
+                      "n_sites - 1 - j): reflected it meets a different coefficient (a Dzyaloshinskii-Moriya bond, or bonds that "
+                      "differ); a parity block needs a reflection-invariant H");
+  }
+}
+// Spin-inversion invariance: prod_j X_j anticommutes with every Y and Z factor, so a string commutes with it iff popcount(z_mask)
+// is even; with equal masks merged, a term of odd popcount(z_mask) must have the coefficient 0.
+void pauli_require_inversion_invariant(int64_t n_terms, const ll_pauli_term* terms) {
+  std::map<std::pair<uint64_t, uint64_t>, double> merged;
+  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
+  for (int64_t t = 0; t < n_terms; ++t) {
+    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask};
+    if ((__builtin_popcountll(key.second) & 1) == 0 || merged[key] == 0.0) continue;
+    char hex[64];
+    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
+    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the global spin flip (the product of all "
+                      "X_j): it holds an odd number of Y and Z factors (a longitudinal field, for example); a spin-inversion "
+                      "block needs an H that is even under the flip");
+  }
+}
 }  // namespace
 
 // One momentum block of that sector (pauli_momentum.hip).  One pass over the sector's states in ascending order, on the host: the
@@ -1044,11 +1124,7 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
 }
 
 // One momentum block of the full 2^n_sites space (pauli_momentum_full.hip).  The representatives and their periods come from the
-// Fredricksen-Kessler-Maiorana enumeration of binary necklaces: a string read from site n_sites - 1 down to site 0 that is the
-// lexicographically smallest of its rotations is the smallest integer of its orbit, and the enumeration yields these strings in
-// ascending order with their period (the length of the Lyndon word they repeat) — one step per pre-necklace, about two steps per
-// representative, no pass over the 2^n_sites states.  A step: raise the lowest 0 bit (position i from the top), drop what lies
-// below it and repeat the top i bits downwards; the result is a necklace iff i divides n_sites, and then its period is i.
+// necklace enumeration (for_each_necklace): ascending, about two steps per representative, no pass over the 2^n_sites states.
 template <typename T>
 void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
                                 ll_operator** out) {
@@ -1059,46 +1135,23 @@ void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t moment
              "storage type");
   pauli_require_translation_invariant(n_sites, n_terms, terms);
   const int L = n_sites;
-  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
   std::vector<uint32_t> reps;
   std::vector<uint8_t> period;
   {
     // a lower bound of D_m that saves most of the re-allocations: the orbits of full length alone, when the block takes them
     reps.reserve((size_t)(((uint64_t)1 << L) / (uint64_t)L) + 64);
     period.reserve(reps.capacity());
-    if (momentum == 0) {  // the first necklace, the string of zeros: period 1, in block 0 only
-      reps.push_back(0);
-      period.push_back(1);
-    }
-    uint32_t a = 0;
-    while (a != site_mask) {
-      const int low0 = __builtin_ctz(~a);  // the lowest 0 bit of a (a != all ones): string position i = L - low0 from the top
-      const int i = L - low0;
-      a = ((a >> low0) | 1u) << low0;      // raise it, clear what lies below
-      for (int sft = i; sft < L; sft *= 2) a |= a >> sft;  // repeat the top i bits downwards (bits shifted out fall off the end)
-      if (L % i != 0) continue;            // a pre-necklace only
-      if (((int64_t)momentum * i) % L != 0) continue;
+    for_each_necklace(L, [&](uint32_t a, int i) {  // the string of zeros (period 1) lies in block 0 only
+      if (((int64_t)momentum * i) % L != 0) return;
       LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "internal: a momentum block of 2^27 states or more");
       reps.push_back(a);
       period.push_back((uint8_t)i);
-    }
+    });
   }
   const int64_t dim = (int64_t)reps.size();
   // never empty: the state 0..01 has the full period n_sites, which every m admits (n_sites = 1: m = 0, and both states have R = 1)
   LL_REQUIRE(dim >= 1, "internal: an empty momentum block of the full space");
-  // buckets over the top bits: the largest power of two not above dim / 8 of them (the table stays below dim / 2 bytes)
-  int pb = 0;
-  while (pb < L && ((int64_t)2 << pb) <= dim / 8) ++pb;
-  const int shift = L - pb;
-  std::vector<uint32_t> start(((size_t)1 << pb) + 1, 0);
-  for (int64_t k = 0; k < dim; ++k) ++start[(size_t)(reps[(size_t)k] >> shift) + 1];
-  int64_t max_bucket = 0;
-  for (size_t q = 1; q < start.size(); ++q) {
-    max_bucket = std::max<int64_t>(max_bucket, start[q]);
-    start[q] += start[q - 1];
-  }
-  int trips = 0;  // halvings that bring the largest bucket down to one candidate (n -> n - n / 2)
-  for (int64_t n = max_bucket; n > 1; n -= n / 2) ++trips;
+  const RepBuckets rb = rep_buckets(L, reps);
   std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
   for (int a = 1; a < 32; ++a)
     for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
@@ -1110,16 +1163,115 @@ void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t moment
   im.n_sites = n_sites;
   im.momentum = momentum;
   im.dim = dim;
-  im.prefix_shift = shift;
-  im.search_trips = trips;
-  im.max_bucket = max_bucket;
+  im.prefix_shift = rb.shift;
+  im.search_trips = rb.trips;
+  im.max_bucket = rb.max_bucket;
   pauli_upload_tables(ctx, im, pt);
   pauli_upload(ctx, im.reps, reps, "momentum block representatives");
   pauli_upload(ctx, im.period, period, "momentum block orbit lengths");
-  pauli_upload(ctx, im.start, start, "momentum block bucket table");
+  pauli_upload(ctx, im.start, rb.start, "momentum block bucket table");
   pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
   pauli_upload(ctx, im.phase, phase, "momentum block phases");
   op->pauli_momentum_full = std::move(im);
+  *out = op.release();
+}
+
+// One block under momentum, reflection and spin inversion (pauli_symmetric.hip).  Every necklace a (the smallest of its
+// rotations) is the representative of its G-orbit iff it is not above the smallest rotation of rev(a), ~a and ~rev(a), whichever
+// are in use; walking the L rotations of each stream in use collects its stabiliser — the orbit length R = |G| / |stabiliser|
+// and whether the character is 1 on all of it — and the popcount filter follows: O(n_sites) per necklace, O(2^n_sites) steps
+// over all of them, on the host, with no table over the states.
+template <typename T>
+void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity, int32_t inversion,
+                            int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
+  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
+  LL_REQUIRE(parity >= -1 && parity <= 1, "parity must be 0 (the reflection is not used), +1 or -1");
+  LL_REQUIRE(inversion >= -1 && inversion <= 1, "inversion must be 0 (the global spin flip is not used), +1 or -1");
+  LL_REQUIRE(n_down >= -1 && n_down <= n_sites,
+             "n_down must lie in [-1, n_sites] (-1: the full space; else the number of flipped spins of the sector)");
+  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
+             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
+             "storage type");
+  LL_REQUIRE(parity == 0 || (2 * momentum) % n_sites == 0,
+             "parity != 0 takes momentum 0 and n_sites / 2 only (the reflection maps momentum k to -k: the group of shifts and "
+             "the reflection has one-dimensional characters only there); use parity = 0");
+  pauli_require_translation_invariant(n_sites, n_terms, terms);
+  if (parity != 0) pauli_require_reflection_invariant(n_sites, n_terms, terms);
+  if (inversion != 0) pauli_require_inversion_invariant(n_terms, terms);
+  if (n_down >= 0) {
+    pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
+    LL_REQUIRE(inversion == 0 || 2 * n_down == n_sites,
+               "inversion != 0 with n_down >= 0 needs 2 n_down = n_sites (the global spin flip maps the sector n_down onto "
+               "n_sites - n_down)");
+  }
+  const int L = n_sites;
+  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
+  const int group_size = L * (parity != 0 ? 2 : 1) * (inversion != 0 ? 2 : 1);
+  auto rot = [&](uint32_t v) { return ((v << 1) | (v >> (L - 1))) & site_mask; };
+  auto rev = [&](uint32_t v) {
+    uint32_t r = 0;
+    for (int j = 0; j < L; ++j) r |= ((v >> j) & 1u) << (L - 1 - j);
+    return r;
+  };
+  std::vector<uint32_t> reps;
+  std::vector<uint8_t> orbit_len;
+  for_each_necklace(L, [&](uint32_t a, int) {
+    if (n_down >= 0 && __builtin_popcount(a) != n_down) return;  // G keeps the popcount (inversion: 2 n_down = L)
+    int stab = 0;
+    bool least = true, admitted = true;
+    for (int rho = 0; rho <= (parity != 0 ? 1 : 0); ++rho)
+      for (int zeta = 0; zeta <= (inversion != 0 ? 1 : 0); ++zeta) {
+        uint32_t cur = rho ? rev(a) : a;
+        if (zeta) cur ^= site_mask;
+        const bool neg = (rho && parity < 0) != (zeta && inversion < 0);
+        for (int j = 0; j < L; ++j) {  // cur = T^j P^rho Z^zeta a; its character in units of pi / L: 2 m j, + L for a factor -1
+          if (cur < a) least = false;
+          if (cur == a) {
+            ++stab;
+            if ((2 * (int64_t)momentum * j + (neg ? L : 0)) % (2 * L) != 0) admitted = false;
+          }
+          cur = rot(cur);
+        }
+      }
+    if (!least || !admitted) return;
+    LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "a block of 2^27 - 1 states or more (32-bit indices with room for the search)");
+    reps.push_back(a);
+    orbit_len.push_back((uint8_t)(group_size / stab));
+  });
+  const int64_t dim = (int64_t)reps.size();
+  LL_REQUIRE(dim >= 1, "the block (momentum " + std::to_string(momentum) + ", parity " + std::to_string(parity) + ", inversion " +
+                           std::to_string(inversion) + ", n_down " + std::to_string(n_down) +
+                           ") is empty: no orbit carries this character");
+  const RepBuckets rb = rep_buckets(L, reps);
+  // ratio[R_a][c] = sqrt(R_a / R_b) for the orbit length R_b = |G| / c of a stabiliser of c elements
+  std::vector<double> ratio((size_t)kPauliSymmetricRatioStride * kPauliSymmetricRatioStride, 0.0), phase(2 * (size_t)n_sites);
+  for (int a = 1; a <= group_size; ++a)
+    for (int c = 1; c <= group_size; ++c)
+      if (group_size % c == 0)
+        ratio[(size_t)a * kPauliSymmetricRatioStride + (size_t)c] = std::sqrt((double)a / (double)(group_size / c));
+  momentum_phase_table(n_sites, momentum, phase);
+  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_SYMMETRIC, dim, 0, dim);
+  op->nnz = n_terms;
+  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
+  PauliSymmetricImage im;
+  im.n_sites = n_sites;
+  im.n_down = n_down;
+  im.momentum = momentum;
+  im.parity = parity;
+  im.inversion = inversion;
+  im.group_size = group_size;
+  im.dim = dim;
+  im.prefix_shift = rb.shift;
+  im.search_trips = rb.trips;
+  im.max_bucket = rb.max_bucket;
+  pauli_upload_tables(ctx, im, pt);
+  pauli_upload(ctx, im.reps, reps, "symmetry block representatives");
+  pauli_upload(ctx, im.orbit_len, orbit_len, "symmetry block orbit lengths");
+  pauli_upload(ctx, im.start, rb.start, "symmetry block bucket table");
+  pauli_upload(ctx, im.ratio, ratio, "symmetry block norm ratios");
+  pauli_upload(ctx, im.phase, phase, "symmetry block phases");
+  op->pauli_symmetric = std::move(im);
   *out = op.release();
 }
 
@@ -1148,6 +1300,8 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
   template void create_pauli_sector<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);             \
   template void create_pauli_momentum<T>(ll_context*, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);  \
   template void create_pauli_momentum_full<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);    \
+  template void create_pauli_symmetric<T>(ll_context*, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, \
+                                          ll_operator**);                                                                      \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 

@@ -228,6 +228,13 @@ def tfim_ground_energy(L, J, h):
     return -float(np.sum(np.linalg.svd(np.diag(np.full(L, float(h))) + np.diag(np.full(L - 1, float(J)), 1), compute_uv=False)))
 
 
+def tfim_ring_ground_energy(L, J, h):
+    """Exact ground-state energy of the transverse-field Ising RING -J sum Z_j Z_{j+1} - h sum X_j (J, h > 0, L even): the vacuum
+    of the even fermion-parity sector, minus the sum over k = (2 n + 1) pi / L of sqrt(J^2 + h^2 + 2 J h cos k)."""
+    k = (2 * np.arange(int(L)) + 1) * np.pi / int(L)
+    return -float(np.sum(np.sqrt(float(J) ** 2 + float(h) ** 2 + 2.0 * float(J) * float(h) * np.cos(k))))
+
+
 def _parity(v):
     """popcount(v) mod 2, element-wise (uint64 arrays)."""
     v = v.copy()
@@ -565,6 +572,183 @@ def pauli_momentum_full_csr(n_sites, m, terms, dtype=np.float64, merge=True):
     def column_of(p):
         k = p.astype(np.int64)   # the state is its own number: no sector to leave
         return col[k], inb[k], np.sqrt(ra / period[k]) * phases[l[k]]
+
+    return _pauli_rows(reps, terms, dtype, merge, column_of)
+
+
+# ------------------------------------------------------------------ momentum + reflection + spin-inversion blocks of a ring
+# The conventions above with two more symmetries of the ring: P reverses the n_sites bits (site j -> L - 1 - j), Z flips every
+# spin (s -> ~s & (2^L - 1)).  The group G is generated by T, by P if parity != 0 and by Z if inversion != 0 (|G| = L, 2 L or
+# 4 L elements T^j P^rho Z^zeta); its character is e^(-2 pi i m j / L) parity^rho inversion^zeta.  The representative of a G-orbit
+# is its smallest integer; it is in the block iff the character is 1 on its stabiliser (ll_op_create_pauli_symmetric_*).
+def _check_symmetric(n_sites, m, parity, inversion, n_down):
+    n_sites, m, parity, inversion = int(n_sites), int(m), int(parity), int(inversion)
+    n_down = None if n_down is None or int(n_down) < 0 else int(n_down)
+    if not (1 <= n_sites <= 30 and 0 <= m < n_sites):
+        raise ValueError("need 1 <= n_sites <= 30, 0 <= m < n_sites")
+    if parity not in (0, 1, -1) or inversion not in (0, 1, -1):
+        raise ValueError("parity and inversion must be 0, +1 or -1")
+    if parity and (2 * m) % n_sites:
+        raise ValueError("a reflection block needs m = 0 or m = n_sites / 2")
+    if n_down is not None and not 0 <= n_down <= n_sites:
+        raise ValueError("need 0 <= n_down <= n_sites")
+    if n_down is not None and inversion and 2 * n_down != n_sites:
+        raise ValueError("spin inversion maps the sector n_down onto n_sites - n_down: it needs 2 n_down = n_sites")
+    return n_sites, m, parity, inversion, n_down
+
+
+def _bit_reverse(L, v):
+    """The L low bits of v (uint64 array) in reverse order."""
+    out = np.zeros_like(v)
+    for j in range(L):
+        out |= ((v >> np.uint64(j)) & np.uint64(1)) << np.uint64(L - 1 - j)
+    return out
+
+
+def _orbits_symmetric(L, states, m, parity, inversion):
+    """For every state s of `states` (uint64, closed under G): (its representative b, l and sign with s = g b and
+    chi(g) = e^(-2 pi i m l / L) sign, the orbit length R = |G| / |stabiliser|, whether chi = 1 on the stabiliser).  4 L passes
+    over the array at most."""
+    mask = np.uint64((1 << L) - 1)
+    n = states.shape[0]
+    rep = np.full(n, mask + np.uint64(1), np.uint64)
+    first, sign = np.zeros(n, np.int64), np.ones(n, np.float64)
+    stab = np.zeros(n, np.int64)
+    admitted = np.ones(n, bool)
+    order = 0
+    for rho in ((0, 1) if parity else (0,)):
+        for zeta in ((0, 1) if inversion else (0,)):
+            cur = _bit_reverse(L, states) if rho else states.copy()
+            if zeta:
+                cur ^= mask
+            sg = (parity if rho else 1) * (inversion if zeta else 1)
+            for j in range(L):                       # cur = T^j P^rho Z^zeta s
+                if j:
+                    cur = ((cur << np.uint64(1)) | (cur >> np.uint64(L - 1))) & mask
+                # the character of this element in units of pi / L: 2 m j, plus L for a factor -1
+                angle = (2 * m * j + (L if sg < 0 else 0)) % (2 * L)
+                fixed = cur == states
+                stab += fixed
+                if angle:
+                    admitted &= ~fixed
+                less = cur < rep
+                rep = np.where(less, cur, rep)
+                first = np.where(less, j, first)
+                sign = np.where(less, float(sg), sign)
+                order += 1
+    # s = h^-1 b with h = T^first P^rho Z^zeta the first minimiser: chi(h^-1) = e^(-2 pi i m (L - first) / L) sign
+    return rep, (L - first) % L, sign, order // stab, admitted
+
+
+def _symmetric_states(n_sites, n_down):
+    if n_down is None:
+        return np.arange(1 << n_sites, dtype=np.uint64)
+    return sector_states(n_sites, n_down).astype(np.uint64)
+
+
+def _symmetric_orbits(n_sites, m, parity, inversion, n_down):
+    """(states, rep, l, sign, R, in the block) over the full space or the sector; admission is a property of the orbit."""
+    states = _symmetric_states(n_sites, n_down)
+    rep, l, sign, R, adm = _orbits_symmetric(n_sites, states, m, parity, inversion)
+    return states, rep, l, sign, R, adm
+
+
+def symmetric_basis(n_sites, m, parity, inversion, n_down=None):
+    """(representatives, orbit lengths) of the block (m, parity, inversion) of the full space (n_down None) or of the sector
+    n_down: the representatives r (uint32, ascending) of the G-orbits on whose stabiliser the character is 1, and R_r (int64).
+    With parity = inversion = 0 and n_down None this is full_momentum_basis."""
+    n_sites, m, parity, inversion, n_down = _check_symmetric(n_sites, m, parity, inversion, n_down)
+    states, rep, _, _, R, adm = _symmetric_orbits(n_sites, m, parity, inversion, n_down)
+    inb = (states == rep) & adm
+    return states[inb].astype(np.uint32), R[inb]
+
+
+def _symmetric_columns(n_sites, m, parity, inversion, n_down):
+    """(states, in the block, column of each state's representative, chi(g) / sqrt(R) for s = g b, reps, R of the reps)."""
+    states, rep, l, sign, R, adm = _symmetric_orbits(n_sites, m, parity, inversion, n_down)
+    isrep = (states == rep) & adm
+    reps = states[isrep]
+    col = np.where(adm, np.searchsorted(reps, rep), 0).astype(np.int64)
+    col = np.minimum(col, max(reps.shape[0] - 1, 0))
+    chi = _momentum_phases(n_sites, m)[l] * sign
+    return states, adm, col, chi, R, reps, R[isrep]
+
+
+def symmetric_embedding(n_sites, m, parity, inversion, n_down=None, dense=True):
+    """B: the basis vectors |r; chi> = N_r^(-1/2) sum_{g in G} chi(g) g |r> as the columns of a matrix over all 2^n_sites states
+    (n_down None) or over sector_states(n_sites, n_down) — an isometry.  A row holds at most one entry, chi(g) / sqrt(R_b) for the
+    state g b: dense=False returns (column of each row or -1, its value)."""
+    n_sites, m, parity, inversion, n_down = _check_symmetric(n_sites, m, parity, inversion, n_down)
+    states, adm, col, chi, R, reps, _ = _symmetric_columns(n_sites, m, parity, inversion, n_down)
+    col = np.where(adm, col, -1)
+    val = np.where(adm, chi / np.sqrt(R.astype(np.float64)), 0.0)
+    if not dense:
+        return col, val
+    B = np.zeros((states.shape[0], reps.shape[0]), np.complex128)
+    B[np.flatnonzero(adm), col[adm]] = val[adm]
+    return B
+
+
+def reflection_fault(n_sites, terms):
+    """None when H = sum of `terms` commutes with the reflection j -> n_sites - 1 - j by the rule of
+    ll_op_create_pauli_symmetric_* (coefficients of equal masks merged in list order; the bit-reversed masks meet exactly the same
+    coefficient, a missing term counting as 0); else the number of the first term at fault."""
+    L = int(n_sites)
+
+    def rev(v):
+        return int(format(v, "0%db" % L)[::-1], 2)
+
+    merged = {}
+    for x, z, c in terms:
+        merged[(int(x), int(z))] = merged.get((int(x), int(z)), 0.0) + float(c)
+    for t, (x, z, _) in enumerate(terms):
+        if merged.get((rev(int(x)), rev(int(z))), 0.0) != merged[(int(x), int(z))]:
+            return t
+    return None
+
+
+def inversion_fault(n_sites, terms):
+    """None when H = sum of `terms` commutes with the global spin flip prod_j X_j: after merging equal masks no term with an odd
+    popcount(z_mask) (an odd number of Y and Z factors) keeps a non-zero coefficient; else the number of the first term at fault."""
+    merged = {}
+    for x, z, c in terms:
+        merged[(int(x), int(z))] = merged.get((int(x), int(z)), 0.0) + float(c)
+    for t, (x, z, _) in enumerate(terms):
+        if bin(int(z)).count("1") & 1 and merged[(int(x), int(z))] != 0.0:
+            return t
+    return None
+
+
+def pauli_symmetric_csr(n_sites, m, parity, inversion, terms, dtype=np.float64, n_down=None, merge=True):
+    """The block B^H H B (B = symmetric_embedding; H = pauli_csr, or pauli_sector_csr with n_down) as CSR over symmetric_basis,
+    from the gather form, in double: row a holds, per x mask X whose partner a ^ X = g b has b in the block,
+    w(a) sqrt(R_a / R_b) chi(g) in the column of b, w as in pauli_csr.  merge as in pauli_csr (merge=False: one entry per term and
+    state).  A real dtype and parity != 0 need 2 m = 0 (mod n_sites); H must commute with the symmetries in use."""
+    n_sites, m, parity, inversion, n_down = _check_symmetric(n_sites, m, parity, inversion, n_down)
+    terms = list(terms)
+    if np.dtype(dtype).kind != "c" and (2 * m) % n_sites:
+        raise ValueError("a real dtype takes m = 0 and m = n_sites / 2 only")
+    for fault, what in ((translation_fault, "the one-site translation"), (reflection_fault if parity else None, "the reflection"),
+                        (inversion_fault if inversion else None, "the global spin flip")):
+        t = fault(n_sites, terms) if fault else None
+        if t is not None:
+            raise ValueError("term %d (x_mask 0x%x, z_mask 0x%x) does not commute with %s" % (t, terms[t][0], terms[t][1], what))
+    states, adm, col, chi, R, reps, ra = _symmetric_columns(n_sites, m, parity, inversion, n_down)
+    if reps.shape[0] == 0:
+        raise ValueError("the block is empty")
+    ra = ra.astype(np.float64)
+    if n_down is not None:
+        h = (n_sites + 1) // 2
+        lo, hi = sector_rank_tables(n_sites, n_down, h)
+
+    def column_of(p):
+        if n_down is None:
+            k = p.astype(np.int64)   # the state is its own number
+            return col[k], adm[k], np.sqrt(ra / R[k]) * chi[k]
+        inside = _popcount(p) == n_down
+        q = np.where(inside, p, states[0])
+        k = lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)]
+        return col[k], inside & adm[k], np.sqrt(ra / R[k]) * chi[k]
 
     return _pauli_rows(reps, terms, dtype, merge, column_of)
 
