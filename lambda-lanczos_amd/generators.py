@@ -251,12 +251,20 @@ def _popcount(v):
     return ((v * np.uint64(0x01010101)) >> np.uint64(24)) & np.uint64(0xFF)
 
 
-def pauli_csr(n_sites, terms, dtype=np.float64, merge=True):
+def pauli_csr(n_sites, terms, dtype=np.float64, merge=True, states=None):
     """The matrix of H = sum_t coef_t P_t as CSR, by the definition: row s holds coef_t i^nY_t (-1)^popcount((s ^ x_t) & z_t) in
     column s ^ x_t.  merge=True: one entry per row and distinct x mask (masks ascending; the coefficients summed in list
     order, exact zeros dropped).  merge=False: one entry per term and state, in list order, duplicate columns allowed — every
-    term's own magnitude stays visible to an error bound."""
-    return _pauli_rows(np.arange(1 << int(n_sites), dtype=np.uint64), terms, dtype, merge, None)
+    term's own magnitude stays visible to an error bound.  states (None: all 2^n_sites): the rows of these states only, in the
+    order given (row k of the result is the row of states[k]; the columns stay state numbers) — rings whose whole matrix does
+    not fit."""
+    if states is None:
+        s = np.arange(1 << int(n_sites), dtype=np.uint64)
+    else:
+        s = np.ascontiguousarray(states).astype(np.uint64).reshape(-1)
+        if s.size and int(s.max()) >> int(n_sites):
+            raise ValueError("a state at or above 2^n_sites")
+    return _pauli_rows(s, terms, dtype, merge, None)
 
 
 def _pauli_rows(s, terms, dtype, merge, column_of):
