@@ -7,6 +7,7 @@
 #include <hip/hip_ext.h>  // hipExtLaunchKernelGGL (device-code translation units only: the host-only sanitizer builds use g++)
 #endif
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -478,14 +479,20 @@ struct SymImage {
 constexpr int kPauliMaxSites = 30;               // 2^30 states: the local indices of the library are signed 32-bit (n_local < 2^31 - 1)
 constexpr int kPauliTileBytes = 32 << 10;        // LDS tile of one workgroup (four workgroups per CU beside their reduction scratch)
 constexpr int kPauliMaxTileBytes = 64 << 10;     // largest tile pauli_tile_bits may ask for
-struct PauliImage {
-  int n_sites = 0, ngroups = 0;
+// the term tables on the device: what every image below holds and every kernel's term loop reads
+struct PauliTermImage {
+  int ngroups = 0;
   int64_t nterms = 0;
   DevArray<uint32_t> gx;         // [ngroups]      x mask of the group
   DevArray<int32_t> gptr;        // [ngroups + 1]  first term of each group
   DevArray<uint32_t> tz;         // [nterms]       z mask
   DevArray<double> tc;           // [nterms] (real types) / [nterms][2] (complex: re, im): c_t i^nY_t
   int64_t device_bytes() const { return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes(); }
+};
+struct PauliImage {
+  int n_sites = 0;
+  PauliTermImage terms;
+  int64_t device_bytes() const { return terms.device_bytes(); }
 };
 // The same sum on one S_z sector (pauli_sector.hip): the term tables above, the sector's states in ascending order, and the
 // two tables that give a state's index back: rank(s) = lo_rank[s & (2^h - 1)] + hi_rank[s >> h].  With the set bits of s at
@@ -494,18 +501,13 @@ struct PauliImage {
 constexpr int kPauliSectorBlockBits = 10;        // indices of a workgroup's block: one pass of kBlock lanes with four states each
 constexpr int kPauliSectorMaxSupport = 20;       // creation's conservation check enumerates 2^|support| assignments per group
 struct PauliSectorImage {
-  int n_sites = 0, n_down = 0, ngroups = 0, h = 0;
-  int64_t nterms = 0, dim = 0;   // dim = C(n_sites, n_down)
-  DevArray<uint32_t> gx;
-  DevArray<int32_t> gptr;
-  DevArray<uint32_t> tz;
-  DevArray<double> tc;
+  int n_sites = 0, n_down = 0, h = 0;
+  int64_t dim = 0;               // dim = C(n_sites, n_down)
+  PauliTermImage terms;
   DevArray<uint32_t> states;     // [dim]                 the states of the sector, ascending
   DevArray<uint32_t> lo_rank;    // [2^h]
   DevArray<uint32_t> hi_rank;    // [2^(n_sites - h)]
-  int64_t device_bytes() const {
-    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + states.bytes() + lo_rank.bytes() + hi_rank.bytes();
-  }
+  int64_t device_bytes() const { return terms.device_bytes() + states.bytes() + lo_rank.bytes() + hi_rank.bytes(); }
 };
 // One momentum block of an S_z sector of a ring (pauli_momentum.hip): the basis is the representatives (smallest member of an orbit
 // under the one-site shift T) whose period R satisfies m R = 0 (mod n_sites), ascending.  orbit[rank(s)] packs, for every state s
@@ -515,75 +517,64 @@ constexpr uint32_t kPauliOrbitExcluded = 0xffffffffu;
 constexpr int kPauliMomentumBlockBits = 8;       // indices of a workgroup's block: one state per lane (blocks are L times fewer than the sector's: 2^8 fills the device sooner)
 constexpr int kPauliOrbitShiftBits = 5;          // l < n_sites <= 30 < 2^5; index of the representative < 2^27
 struct PauliMomentumImage {
-  int n_sites = 0, n_down = 0, momentum = 0, ngroups = 0, h = 0;
+  int n_sites = 0, n_down = 0, momentum = 0, h = 0;
   int nshort = 0;                // distinct primes q of n_sites: a state s has a short orbit iff T^(n_sites / q) s = s for one of them;
   int short_shift[3] = {0, 0, 0};  // the shifts n_sites / q (0 entries when the block holds no short orbit: nothing to test)
-  int64_t nterms = 0, dim = 0, sector_dim = 0;   // dim = D_m, sector_dim = C(n_sites, n_down)
-  DevArray<uint32_t> gx;
-  DevArray<int32_t> gptr;
-  DevArray<uint32_t> tz;
-  DevArray<double> tc;
+  int64_t dim = 0, sector_dim = 0;   // dim = D_m, sector_dim = C(n_sites, n_down)
+  PauliTermImage terms;
   DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
-  DevArray<uint8_t> period;      // [dim]                 their orbit lengths R
+  DevArray<uint8_t> orbit_len;   // [dim]                 their orbit lengths R
   DevArray<uint32_t> orbit;      // [sector_dim]          see above
   DevArray<uint32_t> lo_rank;    // [2^h]
   DevArray<uint32_t> hi_rank;    // [2^(n_sites - h)]
   DevArray<double> ratio;        // [32 * 32]
   DevArray<double> phase;        // [n_sites][2]
   int64_t device_bytes() const {
-    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + period.bytes() + orbit.bytes() + lo_rank.bytes() +
-           hi_rank.bytes() + ratio.bytes() + phase.bytes();
+    return terms.device_bytes() + reps.bytes() + orbit_len.bytes() + orbit.bytes() + lo_rank.bytes() + hi_rank.bytes() +
+           ratio.bytes() + phase.bytes();
   }
 };
-// One momentum block of the FULL 2^n_sites space of a ring (pauli_momentum_full.hip): no S_z sector and no table over the states.
-// The basis is every representative whose period R satisfies m R = 0 (mod n_sites), ascending.  The kernel rotates a partner to
-// its representative b in registers and finds b's number by a bounded binary search in reps[] inside one bucket of the top bits:
-// start[q] = the number of representatives below q << prefix_shift, 2^(n_sites - prefix_shift) + 1 entries (about dim / 8 buckets:
-// at most dim / 2 bytes); search_trips = the halvings the LARGEST bucket needs (measured at creation: representatives crowd at
-// small integers), the uniform length of the kernel's search loop.  ratio[], phase[] as PauliMomentumImage.
+// An ascending list of representatives that a kernel searches (pauli_shared.hpp pauli_bucket_search): no table over the states.
+// The kernel rotates a partner to its representative b in registers and finds b's number by a bounded binary search in reps[]
+// inside one bucket of the top bits: start[q] = the number of representatives below q << prefix_shift,
+// 2^(n_sites - prefix_shift) + 1 entries (about dim / 8 buckets: at most dim / 2 bytes); search_trips = the halvings the LARGEST
+// bucket needs (measured at creation: representatives crowd at small integers), the uniform length of the kernel's search loop.
+struct PauliRepImage {
+  int prefix_shift = 0, search_trips = 0;
+  int64_t max_bucket = 0;        // the most representatives under one prefix
+  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
+  DevArray<uint8_t> orbit_len;   // [dim]                 their orbit lengths R
+  DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
+  int64_t device_bytes() const { return reps.bytes() + orbit_len.bytes() + start.bytes(); }
+};
+// One momentum block of the FULL 2^n_sites space of a ring (pauli_momentum_full.hip): no S_z sector.  The basis is every
+// representative whose period R satisfies m R = 0 (mod n_sites), ascending.  ratio[], phase[] as PauliMomentumImage.
 constexpr int kPauliMomentumFullBlockBits = 8;   // indices of a workgroup's block: one state per lane, as kPauliMomentumBlockBits
 struct PauliMomentumFullImage {
-  int n_sites = 0, momentum = 0, ngroups = 0, prefix_shift = 0, search_trips = 0;
-  int64_t nterms = 0, dim = 0, max_bucket = 0;   // dim = D_m; max_bucket = the most representatives under one prefix
-  DevArray<uint32_t> gx;
-  DevArray<int32_t> gptr;
-  DevArray<uint32_t> tz;
-  DevArray<double> tc;
-  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
-  DevArray<uint8_t> period;      // [dim]                 their orbit lengths R
-  DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
+  int n_sites = 0, momentum = 0;
+  int64_t dim = 0;               // dim = D_m
+  PauliTermImage terms;
+  PauliRepImage basis;
   DevArray<double> ratio;        // [32 * 32]
   DevArray<double> phase;        // [n_sites][2]
-  int64_t device_bytes() const {
-    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + period.bytes() + start.bytes() + ratio.bytes() +
-           phase.bytes();
-  }
+  int64_t device_bytes() const { return terms.device_bytes() + basis.device_bytes() + ratio.bytes() + phase.bytes(); }
 };
 // One block of a ring under momentum, reflection and spin inversion, of the full space or of one S_z sector (pauli_symmetric.hip):
 // PauliMomentumFullImage with a larger group.  The basis is every representative (the smallest integer of its orbit under the
 // group G generated by the shift, by the reflection if parity != 0 and by the global flip if inversion != 0) on whose stabiliser
-// the character is 1 and, with n_down >= 0, whose popcount is n_down, ascending.  reps[], start[], prefix_shift, search_trips as
-// PauliMomentumFullImage; the kernel decides membership by comparing the entry it finds with the representative.
+// the character is 1 and, with n_down >= 0, whose popcount is n_down, ascending; orbit lengths R = |G| / |stabiliser|.  The
+// kernel decides membership by comparing the entry it finds with the representative.
 // ratio[R_a * kPauliSymmetricRatioStride + c] = sqrt(R_a / (|G| / c)) for the stabiliser sizes c that divide |G| (R <= |G| <= 120).
 constexpr int kPauliSymmetricBlockBits = kPauliMomentumFullBlockBits;  // taken over from the full-momentum kernel, unmeasured
 constexpr unsigned kPauliSymmetricRatioStride = 121;
 struct PauliSymmetricImage {
   int n_sites = 0, n_down = -1, momentum = 0, parity = 0, inversion = 0, group_size = 0;
-  int ngroups = 0, prefix_shift = 0, search_trips = 0;
-  int64_t nterms = 0, dim = 0, max_bucket = 0;
-  DevArray<uint32_t> gx;
-  DevArray<int32_t> gptr;
-  DevArray<uint32_t> tz;
-  DevArray<double> tc;
-  DevArray<uint32_t> reps;       // [dim]                 the representatives, ascending
-  DevArray<uint8_t> orbit_len;   // [dim]                 their orbit lengths R = |G| / |stabiliser|
-  DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
+  int64_t dim = 0;
+  PauliTermImage terms;
+  PauliRepImage basis;
   DevArray<double> ratio;        // [121 * 121]
   DevArray<double> phase;        // [n_sites][2]
-  int64_t device_bytes() const {
-    return gx.bytes() + gptr.bytes() + tz.bytes() + tc.bytes() + reps.bytes() + orbit_len.bytes() + start.bytes() + ratio.bytes() +
-           phase.bytes();
-  }
+  int64_t device_bytes() const { return terms.device_bytes() + basis.device_bytes() + ratio.bytes() + phase.bytes(); }
 };
 }  // namespace ll
 
@@ -689,7 +680,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip); everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -778,6 +769,12 @@ int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, co
 template <typename T>
 int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                  const ScaleIn<T>* sc = nullptr);
+// The four indexed-basis kernels (pauli_basis.hpp) take 2^b indices per workgroup block: the context's key if set (at most
+// 2^30), else the kernel's default
+inline int pauli_block_bits(const ll_operator& op, int ll::Tuning::*key, int dflt) {
+  const int forced = op.ctx ? op.ctx->tune.*key : -1;
+  return forced >= 0 ? std::min(forced, 30) : dflt;
+}
 // The same on one S_z sector (op.kind == PAULI_SECTOR; pauli_sector.hip): x, y hold C(n_sites, n_down) elements.
 template <typename T>
 int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,

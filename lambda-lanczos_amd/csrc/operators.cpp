@@ -785,12 +785,13 @@ PauliTables pauli_tables(ll_context* ctx, int32_t n_sites, int64_t n_terms, cons
   pt.gptr.push_back((int32_t)n_terms);
   return pt;
 }
-// the four term tables of an image (PauliImage, PauliSectorImage) on the device
+// a host table on the device
 template <typename V> void pauli_upload(ll_context* ctx, DevArray<V>& dst, const std::vector<V>& src, const char* what) {
   dst = ctx->dev_alloc<V>(std::max<size_t>(src.size(), 1), what);
   if (!src.empty()) LL_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
 }
-template <typename Image> void pauli_upload_tables(ll_context* ctx, Image& im, const PauliTables& pt) {
+// the four term tables of an image on the device
+void pauli_upload_tables(ll_context* ctx, PauliTermImage& im, const PauliTables& pt) {
   im.ngroups = (int)pt.gx.size();
   im.nterms = (int64_t)pt.tz.size();
   pauli_upload(ctx, im.gx, pt.gx, "Pauli x masks");
@@ -898,7 +899,7 @@ void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pa
   op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
   PauliImage im;
   im.n_sites = n_sites;
-  pauli_upload_tables(ctx, im, pt);
+  pauli_upload_tables(ctx, im.terms, pt);
   op->pauli = std::move(im);
   *out = op.release();
 }
@@ -921,7 +922,7 @@ void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64
   im.n_down = n_down;
   im.h = st.h;
   im.dim = dim;
-  pauli_upload_tables(ctx, im, pt);
+  pauli_upload_tables(ctx, im.terms, pt);
   pauli_upload(ctx, im.states, st.states, "S_z sector states");
   pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
   pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
@@ -950,7 +951,21 @@ void pauli_require_translation_invariant(int32_t n_sites, int64_t n_terms, const
                       "sector needs a translation-invariant H");
   }
 }
-// phase[l] = e^(-2 pi i m l / n_sites) as (re, im), l < n_sites, exact on the axes: the table of both momentum-block operators
+// the momentum argument of the three momentum-block operators
+template <typename T> void pauli_require_momentum(int32_t n_sites, int32_t momentum) {
+  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
+  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
+             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
+             "storage type");
+}
+// ratio[Ra * 32 + Rb] = sqrt(Ra / Rb) for the orbit lengths of a ring of at most 30 sites: the table of both momentum-block operators
+std::vector<double> momentum_ratio_table() {
+  std::vector<double> ratio(32 * 32, 0.0);
+  for (int a = 1; a < 32; ++a)
+    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
+  return ratio;
+}
+// phase[l] = e^(-2 pi i m l / n_sites) as (re, im), l < n_sites, exact on the axes: the table of the three momentum-block operators
 void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>& phase) {
   for (int l = 0; l < n_sites; ++l) {
     const int k = (int)(((int64_t)momentum * l) % n_sites);
@@ -1007,6 +1022,16 @@ RepBuckets rep_buckets(int L, const std::vector<uint32_t>& reps) {
   for (int64_t n = rb.max_bucket; n > 1; n -= n / 2) ++rb.trips;  // n -> n - n / 2
   return rb;
 }
+// the representatives, their orbit lengths and the bucket table of an image on the device, under the allocation names what[3]
+void pauli_upload_reps(ll_context* ctx, PauliRepImage& im, const std::vector<uint32_t>& reps, const std::vector<uint8_t>& orbit_len,
+                       const RepBuckets& rb, const char* const (&what)[3]) {
+  im.prefix_shift = rb.shift;
+  im.search_trips = rb.trips;
+  im.max_bucket = rb.max_bucket;
+  pauli_upload(ctx, im.reps, reps, what[0]);
+  pauli_upload(ctx, im.orbit_len, orbit_len, what[1]);
+  pauli_upload(ctx, im.start, rb.start, what[2]);
+}
 // Reflection invariance: with the coefficients of equal (x_mask, z_mask) merged (summed in the caller's order), reversing the
 // n_sites bits of every term's masks must map the term set onto itself with exactly equal coefficients (a missing term counts
 // as coefficient 0).  A site permutation moves X, Y, Z factors without a sign, so the caller's coefficients are compared.
@@ -1055,17 +1080,14 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
                            const ll_pauli_term* terms, ll_operator** out) {
   const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
   LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
-  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
-  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
-             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
-             "storage type");
+  pauli_require_momentum<T>(n_sites, momentum);
   pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
   pauli_require_translation_invariant(n_sites, n_terms, terms);
   const SectorTables st = sector_tables(n_sites, n_down);
   const uint32_t site_mask = (uint32_t)(((uint64_t)1 << n_sites) - 1);
   auto rot = [&](uint32_t v) { return ((v << 1) | (v >> (n_sites - 1))) & site_mask; };
   std::vector<uint32_t> orbit((size_t)st.dim, kPauliOrbitExcluded), reps;
-  std::vector<uint8_t> period;
+  std::vector<uint8_t> orbit_len;
   std::vector<bool> seen((size_t)st.dim, false);
   bool any_short = false;
   for (int64_t i = 0; i < st.dim; ++i) {
@@ -1083,16 +1105,15 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
     uint32_t t = r;
     for (int j = 0; j < R; ++j, t = rot(t)) orbit[(size_t)st.rank(t)] = (uint32_t)(idx << kPauliOrbitShiftBits) | (uint32_t)j;
     reps.push_back(r);
-    period.push_back((uint8_t)R);
+    orbit_len.push_back((uint8_t)R);
     any_short = any_short || R != n_sites;
   }
   static_assert(kPauliMaxSites < (1 << kPauliOrbitShiftBits), "the shift l of an orbit entry needs n_sites < 2^5");
   const int64_t dim = (int64_t)reps.size();
   LL_REQUIRE(dim >= 1, "the momentum block is empty: no orbit of the sector (n_sites " + std::to_string(n_sites) + ", n_down " +
                            std::to_string(n_down) + ") has a length R with momentum * R = 0 (mod n_sites)");
-  std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
-  for (int a = 1; a < 32; ++a)
-    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
+  const std::vector<double> ratio = momentum_ratio_table();
+  std::vector<double> phase(2 * (size_t)n_sites);
   momentum_phase_table(n_sites, momentum, phase);
   std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM, dim, 0, dim);
   op->nnz = n_terms;
@@ -1111,9 +1132,9 @@ void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int
         im.short_shift[im.nshort++] = n_sites / q;
         while (rest % q == 0) rest /= q;
       }
-  pauli_upload_tables(ctx, im, pt);
+  pauli_upload_tables(ctx, im.terms, pt);
   pauli_upload(ctx, im.reps, reps, "momentum block representatives");
-  pauli_upload(ctx, im.period, period, "momentum block orbit lengths");
+  pauli_upload(ctx, im.orbit_len, orbit_len, "momentum block orbit lengths");
   pauli_upload(ctx, im.orbit, orbit, "momentum block orbit table");
   pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
   pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
@@ -1129,32 +1150,28 @@ template <typename T>
 void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
                                 ll_operator** out) {
   const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
-  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
-             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
-             "storage type");
+  pauli_require_momentum<T>(n_sites, momentum);
   pauli_require_translation_invariant(n_sites, n_terms, terms);
   const int L = n_sites;
   std::vector<uint32_t> reps;
-  std::vector<uint8_t> period;
+  std::vector<uint8_t> orbit_len;
   {
     // a lower bound of D_m that saves most of the re-allocations: the orbits of full length alone, when the block takes them
     reps.reserve((size_t)(((uint64_t)1 << L) / (uint64_t)L) + 64);
-    period.reserve(reps.capacity());
+    orbit_len.reserve(reps.capacity());
     for_each_necklace(L, [&](uint32_t a, int i) {  // the string of zeros (period 1) lies in block 0 only
       if (((int64_t)momentum * i) % L != 0) return;
       LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "internal: a momentum block of 2^27 states or more");
       reps.push_back(a);
-      period.push_back((uint8_t)i);
+      orbit_len.push_back((uint8_t)i);
     });
   }
   const int64_t dim = (int64_t)reps.size();
   // never empty: the state 0..01 has the full period n_sites, which every m admits (n_sites = 1: m = 0, and both states have R = 1)
   LL_REQUIRE(dim >= 1, "internal: an empty momentum block of the full space");
   const RepBuckets rb = rep_buckets(L, reps);
-  std::vector<double> ratio(32 * 32, 0.0), phase(2 * (size_t)n_sites);
-  for (int a = 1; a < 32; ++a)
-    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
+  const std::vector<double> ratio = momentum_ratio_table();
+  std::vector<double> phase(2 * (size_t)n_sites);
   momentum_phase_table(n_sites, momentum, phase);
   std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM_FULL, dim, 0, dim);
   op->nnz = n_terms;
@@ -1163,13 +1180,9 @@ void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t moment
   im.n_sites = n_sites;
   im.momentum = momentum;
   im.dim = dim;
-  im.prefix_shift = rb.shift;
-  im.search_trips = rb.trips;
-  im.max_bucket = rb.max_bucket;
-  pauli_upload_tables(ctx, im, pt);
-  pauli_upload(ctx, im.reps, reps, "momentum block representatives");
-  pauli_upload(ctx, im.period, period, "momentum block orbit lengths");
-  pauli_upload(ctx, im.start, rb.start, "momentum block bucket table");
+  pauli_upload_tables(ctx, im.terms, pt);
+  pauli_upload_reps(ctx, im.basis, reps, orbit_len, rb,
+                    {"momentum block representatives", "momentum block orbit lengths", "momentum block bucket table"});
   pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
   pauli_upload(ctx, im.phase, phase, "momentum block phases");
   op->pauli_momentum_full = std::move(im);
@@ -1185,14 +1198,11 @@ template <typename T>
 void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity, int32_t inversion,
                             int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
   const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
   LL_REQUIRE(parity >= -1 && parity <= 1, "parity must be 0 (the reflection is not used), +1 or -1");
   LL_REQUIRE(inversion >= -1 && inversion <= 1, "inversion must be 0 (the global spin flip is not used), +1 or -1");
   LL_REQUIRE(n_down >= -1 && n_down <= n_sites,
              "n_down must lie in [-1, n_sites] (-1: the full space; else the number of flipped spins of the sector)");
-  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
-             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
-             "storage type");
+  pauli_require_momentum<T>(n_sites, momentum);
   LL_REQUIRE(parity == 0 || (2 * momentum) % n_sites == 0,
              "parity != 0 takes momentum 0 and n_sites / 2 only (the reflection maps momentum k to -k: the group of shifts and "
              "the reflection has one-dimensional characters only there); use parity = 0");
@@ -1262,13 +1272,9 @@ void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, in
   im.inversion = inversion;
   im.group_size = group_size;
   im.dim = dim;
-  im.prefix_shift = rb.shift;
-  im.search_trips = rb.trips;
-  im.max_bucket = rb.max_bucket;
-  pauli_upload_tables(ctx, im, pt);
-  pauli_upload(ctx, im.reps, reps, "symmetry block representatives");
-  pauli_upload(ctx, im.orbit_len, orbit_len, "symmetry block orbit lengths");
-  pauli_upload(ctx, im.start, rb.start, "symmetry block bucket table");
+  pauli_upload_tables(ctx, im.terms, pt);
+  pauli_upload_reps(ctx, im.basis, reps, orbit_len, rb,
+                    {"symmetry block representatives", "symmetry block orbit lengths", "symmetry block bucket table"});
   pauli_upload(ctx, im.ratio, ratio, "symmetry block norm ratios");
   pauli_upload(ctx, im.phase, phase, "symmetry block phases");
   op->pauli_symmetric = std::move(im);

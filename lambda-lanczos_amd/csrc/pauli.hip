@@ -141,6 +141,7 @@ template <typename T>
 int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s, const ScaleIn<T>* scp) {
   const ScaleIn<T> sc = scp ? *scp : ScaleIn<T>{};
   const PauliImage& im = op.pauli;
+  const PauliTermImage& tm = im.terms;
   // states per tile: the context's pauli_tile_bits, else what fills kPauliTileBytes of LDS; never more than the vector, and at
   // most kPauliMaxTileBytes (the LDS a launch may ask for without raising the kernel's limit)
   const int forced = op.ctx ? op.ctx->tune.pauli_tile_bits : -1;
@@ -154,11 +155,11 @@ int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double*
   auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = V > 1 && (1 << b) >= V && aligned16(x) && aligned16(y) && aligned16(sc.u_out);
   if (vec)
-    hipLaunchKernelGGL((pauli_kernel<T, V>), dim3(grid), dim3(kBlock), lds, s, b, ntiles, im.ngroups, im.gx.get(), im.gptr.get(),
-                       im.tz.get(), im.tc.get(), x, y, offset, dot_partials, sc);
+    hipLaunchKernelGGL((pauli_kernel<T, V>), dim3(grid), dim3(kBlock), lds, s, b, ntiles, tm.ngroups, tm.gx.get(), tm.gptr.get(),
+                       tm.tz.get(), tm.tc.get(), x, y, offset, dot_partials, sc);
   else
-    hipLaunchKernelGGL((pauli_kernel<T, 1>), dim3(grid), dim3(kBlock), lds, s, b, ntiles, im.ngroups, im.gx.get(), im.gptr.get(),
-                       im.tz.get(), im.tc.get(), x, y, offset, dot_partials, sc);
+    hipLaunchKernelGGL((pauli_kernel<T, 1>), dim3(grid), dim3(kBlock), lds, s, b, ntiles, tm.ngroups, tm.gx.get(), tm.gptr.get(),
+                       tm.tz.get(), tm.tc.get(), x, y, offset, dot_partials, sc);
   LL_HIP(hipGetLastError());
   return grid;
 }
