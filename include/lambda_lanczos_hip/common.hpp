@@ -291,48 +291,54 @@ template <typename T> class LatticeOperator : public DeviceOperator<T> {
   }
 };
 
-// Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t on n_sites spins (n = 2^n_sites): what a many-body user writes as an
-// mv_mul plugin, applied on the device from its list of Pauli strings.  Bit j of a basis state is site j; a term's site j
-// carries X (x_mask bit only), Z (z_mask bit only), Y (both).  A Heisenberg bond J S_j.S_k is {m, 0, J/4}, {m, m, J/4},
-// {0, m, J/4} with m = 2^j | 2^k.  Real T: an even number of Y per term.  Single-rank contexts only (ll_op_create_pauli_*).
-using PauliTerm = ll_pauli_term;
-template <typename T> class PauliOperator : public DeviceOperator<T> {
+// What the five Pauli-sum operators below share: size() and local_rows() are read from the created operator (ll_op_info), and
+// device_bytes().
+template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
  public:
-  PauliOperator(int n_sites, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : DeviceOperator<T>(ctx) {
-    ll_operator* op = nullptr;
-    check(abi<T>::create_pauli(ctx.get(), (int32_t)n_sites, (int64_t)terms.size(), terms.data(), &op));
-    const int64_t n = (int64_t)1 << n_sites;
-    this->adopt(op, n, n);
-  }
-  // sum_t |coef_t|: an upper bound of every absolute row sum (DeviceOperator::inf_norm() returns it)
   int64_t device_bytes() const {
     int64_t b = 0;
     check(ll_op_device_bytes(this->get(), &b));
     return b;
   }
-};
 
-// The same Hamiltonian on one magnetisation sector: vectors hold the C(n_sites, n_down) amplitudes of the states with n_down set
-// bits (a set bit is sigma_z = -1), in ascending integer order; size() returns that number.  H must conserve total S_z
-// (Heisenberg, XXZ, J1-J2, Dzyaloshinskii-Moriya, z fields): one that does not is refused with an Error that names the x mask
-// at fault (ll_op_create_pauli_sector_*).
-template <typename T> class PauliSectorOperator : public DeviceOperator<T> {
- public:
-  PauliSectorOperator(int n_sites, int n_down, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : DeviceOperator<T>(ctx) {
-    ll_operator* op = nullptr;
-    check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
+ protected:
+  explicit PauliFamilyOperator(Context ctx) : DeviceOperator<T>(ctx) {}
+  void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
     if (rc != LL_OK) (void)ll_op_destroy(op);
     check(rc);
     this->adopt(op, n, n_local);
   }
-  int64_t device_bytes() const {
-    int64_t b = 0;
-    check(ll_op_device_bytes(this->get(), &b));
-    return b;
+};
+
+// Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t on n_sites spins (n = 2^n_sites): what a many-body user writes as an
+// mv_mul plugin, applied on the device from its list of Pauli strings.  Bit j of a basis state is site j; a term's site j
+// carries X (x_mask bit only), Z (z_mask bit only), Y (both).  A Heisenberg bond J S_j.S_k is {m, 0, J/4}, {m, m, J/4},
+// {0, m, J/4} with m = 2^j | 2^k.  Real T: an even number of Y per term.  Single-rank contexts only (ll_op_create_pauli_*).
+using PauliTerm = ll_pauli_term;
+template <typename T> class PauliOperator : public PauliFamilyOperator<T> {
+ public:
+  PauliOperator(int n_sites, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : PauliFamilyOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli(ctx.get(), (int32_t)n_sites, (int64_t)terms.size(), terms.data(), &op));
+    this->adopt_created(op);
+  }
+  // inf_norm() returns sum_t |coef_t|: an upper bound of every absolute row sum
+};
+
+// The same Hamiltonian on one magnetisation sector: vectors hold the C(n_sites, n_down) amplitudes of the states with n_down set
+// bits (a set bit is sigma_z = -1), in ascending integer order; size() returns that number.  H must conserve total S_z
+// (Heisenberg, XXZ, J1-J2, Dzyaloshinskii-Moriya, z fields): one that does not is refused with an Error that names the x mask
+// at fault (ll_op_create_pauli_sector_*).
+template <typename T> class PauliSectorOperator : public PauliFamilyOperator<T> {
+ public:
+  PauliSectorOperator(int n_sites, int n_down, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : PauliFamilyOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
+    this->adopt_created(op);
   }
 };
 
@@ -341,24 +347,15 @@ template <typename T> class PauliSectorOperator : public DeviceOperator<T> {
 // orbit representatives (smallest member) whose orbit length R satisfies m R = 0 (mod n_sites), ascending; size() returns D_m.
 // 0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image holds 4 C(n_sites, n_down) bytes of look-up
 // table (device_bytes()); inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue| (ll_op_create_pauli_momentum_*).
-template <typename T> class PauliMomentumOperator : public DeviceOperator<T> {
+template <typename T> class PauliMomentumOperator : public PauliFamilyOperator<T> {
  public:
   PauliMomentumOperator(int n_sites, int n_down, int momentum, const std::vector<PauliTerm>& terms,
                         Context ctx = Context::default_context())
-      : DeviceOperator<T>(ctx) {
+      : PauliFamilyOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int64_t)terms.size(),
                                         terms.data(), &op));
-    int64_t n = 0, n_local = 0, n_terms = 0;
-    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
-    if (rc != LL_OK) (void)ll_op_destroy(op);
-    check(rc);
-    this->adopt(op, n, n_local);
-  }
-  int64_t device_bytes() const {
-    int64_t b = 0;
-    check(ll_op_device_bytes(this->get(), &b));
-    return b;
+    this->adopt_created(op);
   }
 };
 
@@ -368,23 +365,14 @@ template <typename T> class PauliMomentumOperator : public DeviceOperator<T> {
 // 2^n_sites / n_sites).  0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image is O(D_m) — no table
 // over the 2^n_sites states: device_bytes() <= 8 D_m + 64 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
 // (ll_op_create_pauli_momentum_full_*).
-template <typename T> class PauliMomentumFullOperator : public DeviceOperator<T> {
+template <typename T> class PauliMomentumFullOperator : public PauliFamilyOperator<T> {
  public:
   PauliMomentumFullOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : DeviceOperator<T>(ctx) {
+      : PauliFamilyOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum_full(ctx.get(), (int32_t)n_sites, (int32_t)momentum, (int64_t)terms.size(), terms.data(),
                                              &op));
-    int64_t n = 0, n_local = 0, n_terms = 0;
-    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
-    if (rc != LL_OK) (void)ll_op_destroy(op);
-    check(rc);
-    this->adopt(op, n, n_local);
-  }
-  int64_t device_bytes() const {
-    int64_t b = 0;
-    check(ll_op_device_bytes(this->get(), &b));
-    return b;
+    this->adopt_created(op);
   }
 };
 
@@ -394,24 +382,15 @@ template <typename T> class PauliMomentumFullOperator : public DeviceOperator<T>
 // returns D.  parity != 0 and real T take momentum 0 and n_sites / 2 only; an empty block is refused.  The image is O(D):
 // device_bytes() <= 8 D + 192 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
 // (ll_op_create_pauli_symmetric_*).
-template <typename T> class PauliSymmetricOperator : public DeviceOperator<T> {
+template <typename T> class PauliSymmetricOperator : public PauliFamilyOperator<T> {
  public:
   PauliSymmetricOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, int parity = 0, int inversion = 0,
                          int n_down = -1, Context ctx = Context::default_context())
-      : DeviceOperator<T>(ctx) {
+      : PauliFamilyOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_symmetric(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int32_t)parity,
                                          (int32_t)inversion, (int64_t)terms.size(), terms.data(), &op));
-    int64_t n = 0, n_local = 0, n_terms = 0;
-    const int rc = ll_op_info(op, &n, &n_local, &n_terms);
-    if (rc != LL_OK) (void)ll_op_destroy(op);
-    check(rc);
-    this->adopt(op, n, n_local);
-  }
-  int64_t device_bytes() const {
-    int64_t b = 0;
-    check(ll_op_device_bytes(this->get(), &b));
-    return b;
+    this->adopt_created(op);
   }
 };
 

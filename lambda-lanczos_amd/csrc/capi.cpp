@@ -25,6 +25,17 @@ namespace ll {
 namespace {
 long long to_ll(const std::string& v) { return std::atoll(v.c_str()); }
 bool to_flag(const std::string& v) { return std::atoi(v.c_str()) != 0; }
+// the block-geometry keys of the Pauli kernels: 2^b states or indices per workgroup
+int Tuning::*pauli_bits_key(const std::string& key) {
+  static const std::pair<const char*, int Tuning::*> keys[] = {
+      {"pauli_tile_bits", &Tuning::pauli_tile_bits}, {"pauli_sector_block_bits", &Tuning::pauli_sector_block_bits},
+      {"pauli_momentum_block_bits", &Tuning::pauli_momentum_block_bits},
+      {"pauli_momentum_full_block_bits", &Tuning::pauli_momentum_full_block_bits},
+      {"pauli_symmetric_block_bits", &Tuning::pauli_symmetric_block_bits}};
+  for (const auto& k : keys)
+    if (key == k.first) return k.second;
+  return nullptr;
+}
 }  // namespace
 bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   const Tuning d;  // defaults (an empty value restores the default of its key)
@@ -65,11 +76,7 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "pb_test_all_remote") t.pb_test_all_remote = e ? false : to_flag(v);
   else if (key == "force_rp64") t.force_rp64 = e ? false : to_flag(v);
   else if (key == "spmv_tile_balance") t.spmv_tile_balance = e ? d.spmv_tile_balance : to_flag(v);
-  else if (key == "pauli_tile_bits") t.pauli_tile_bits = e ? d.pauli_tile_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
-  else if (key == "pauli_momentum_block_bits") t.pauli_momentum_block_bits = e ? d.pauli_momentum_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
-  else if (key == "pauli_momentum_full_block_bits") t.pauli_momentum_full_block_bits = e ? d.pauli_momentum_full_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
-  else if (key == "pauli_symmetric_block_bits") t.pauli_symmetric_block_bits = e ? d.pauli_symmetric_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
-  else if (key == "pauli_sector_block_bits") t.pauli_sector_block_bits = e ? d.pauli_sector_block_bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
+  else if (int Tuning::*bits = pauli_bits_key(key)) t.*bits = e ? d.*bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
   else if (key == "stencil_vec") t.stencil_vec = e ? d.stencil_vec : to_flag(v);
   else if (key == "tl_force") t.tl_force = e ? false : to_flag(v);
   else if (key == "tl_xcd") t.tl_xcd_order = e ? d.tl_xcd_order : to_flag(v);
@@ -576,7 +583,7 @@ int ll_memset(ll_context* ctx, void* dst, int byte, size_t bytes) {
   });
 }
 
-// ---------------------------------------------------------------- operators (operators.cpp builds them)
+// ---------------------------------------------------------------- operators (operators.cpp, pauli_operators.cpp build them)
 int ll_op_create_csr_d(ll_context* ctx, int64_t nr, int64_t nc, int64_t rb, const int64_t* rp, const int32_t* ci,
                        const double* va, ll_operator** out) {
   return guarded([&] { create_csr<double>(ctx, nr, nc, rb, rp, ci, va, csr_options_default(false), out); });

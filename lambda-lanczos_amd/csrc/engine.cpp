@@ -264,16 +264,8 @@ void Engine<T>::apply(const T* x_local, T* y, double offset, double* d_alpha, bo
   const bool dense_split_ok = op->n % V == 0 && op->row_begin % V == 0 && (op->row_begin + op->n_local) % V == 0;
   int nparts;
   if (op->kind == ll_operator::STENCIL) nparts = apply_lattice(x_local, y, offset, dotp, sc);
-  else if (op->kind == ll_operator::PAULI)  // sum of Pauli strings: single GPU only (creation refuses sharded contexts)
-    nparts = launch_pauli<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
-  else if (op->kind == ll_operator::PAULI_SECTOR)  // the same on one S_z sector
-    nparts = launch_pauli_sector<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
-  else if (op->kind == ll_operator::PAULI_MOMENTUM)  // one momentum block of that sector
-    nparts = launch_pauli_momentum<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
-  else if (op->kind == ll_operator::PAULI_MOMENTUM_FULL)  // one momentum block of the full space
-    nparts = launch_pauli_momentum_full<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
-  else if (op->kind == ll_operator::PAULI_SYMMETRIC)  // one momentum / reflection / spin-inversion block
-    nparts = launch_pauli_symmetric<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
+  else if (op->is_pauli())  // a sum of Pauli strings, whole or on a block: single GPU only (creation refuses sharded contexts)
+    nparts = launch_pauli_op<T>(*op, x_local, y, offset, dotp, ctx->stream, sc);
   else if (op->kind == ll_operator::DENSE)
     nparts = apply_rows(&launch_dense_mv<T>, ctx->tune.csr_split && dense_split_ok, x_local, x_padded, y, offset, dotp, sc);
   else if (op->kind != ll_operator::CSR) nparts = apply_callback(x_local, y, offset, dotp);

@@ -66,9 +66,7 @@ struct InputCaps {
 inline InputCaps input_caps(int kind, int spmv_kind, bool sharded) {
   InputCaps c;
   if (kind == ll_operator::CSR && spmv_kind != LL_SPMV_CSR_STREAM) c.norm2 = true;
-  else if (kind == ll_operator::CSR || kind == ll_operator::STENCIL || kind == ll_operator::DENSE || kind == ll_operator::PAULI ||
-           kind == ll_operator::PAULI_SECTOR || kind == ll_operator::PAULI_MOMENTUM || kind == ll_operator::PAULI_MOMENTUM_FULL ||
-           kind == ll_operator::PAULI_SYMMETRIC)
+  else if (kind == ll_operator::CSR || kind == ll_operator::STENCIL || kind == ll_operator::DENSE || ll_operator::is_pauli(kind))
     c.scale_in = true;
   c.defer = c.scale_in && !sharded;
   return c;

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -547,32 +548,23 @@ struct PauliRepImage {
   DevArray<uint32_t> start;      // [2^(n_sites - prefix_shift) + 1]
   int64_t device_bytes() const { return reps.bytes() + orbit_len.bytes() + start.bytes(); }
 };
-// One momentum block of the FULL 2^n_sites space of a ring (pauli_momentum_full.hip): no S_z sector.  The basis is every
-// representative whose period R satisfies m R = 0 (mod n_sites), ascending.  ratio[], phase[] as PauliMomentumImage.
+// One block of a ring under momentum, reflection and spin inversion, of the full space or of one S_z sector: the image of both
+// searched-basis kinds.  The basis is every representative (the smallest integer of its orbit under the group G generated by the
+// shift, by the reflection if parity != 0 and by the global flip if inversion != 0) on whose stabiliser the character is 1 and,
+// with n_down >= 0, whose popcount is n_down, ascending; orbit lengths R = |G| / |stabiliser|; phase[] as PauliMomentumImage.
+// PAULI_SYMMETRIC (pauli_symmetric.hip): ratio[R_a * kPauliSymmetricRatioStride + c] = sqrt(R_a / (|G| / c)) for the stabiliser
+// sizes c that divide |G| (R <= |G| <= 120); the kernel decides membership by comparing the entry it finds with the representative.
+// PAULI_MOMENTUM_FULL (pauli_momentum_full.hip): the shift alone on the full space (n_down = -1, parity = inversion = 0, group_size
+// = n_sites: every representative whose period R satisfies m R = 0 mod n_sites); ratio[] as PauliMomentumImage.
 constexpr int kPauliMomentumFullBlockBits = 8;   // indices of a workgroup's block: one state per lane, as kPauliMomentumBlockBits
-struct PauliMomentumFullImage {
-  int n_sites = 0, momentum = 0;
-  int64_t dim = 0;               // dim = D_m
-  PauliTermImage terms;
-  PauliRepImage basis;
-  DevArray<double> ratio;        // [32 * 32]
-  DevArray<double> phase;        // [n_sites][2]
-  int64_t device_bytes() const { return terms.device_bytes() + basis.device_bytes() + ratio.bytes() + phase.bytes(); }
-};
-// One block of a ring under momentum, reflection and spin inversion, of the full space or of one S_z sector (pauli_symmetric.hip):
-// PauliMomentumFullImage with a larger group.  The basis is every representative (the smallest integer of its orbit under the
-// group G generated by the shift, by the reflection if parity != 0 and by the global flip if inversion != 0) on whose stabiliser
-// the character is 1 and, with n_down >= 0, whose popcount is n_down, ascending; orbit lengths R = |G| / |stabiliser|.  The
-// kernel decides membership by comparing the entry it finds with the representative.
-// ratio[R_a * kPauliSymmetricRatioStride + c] = sqrt(R_a / (|G| / c)) for the stabiliser sizes c that divide |G| (R <= |G| <= 120).
 constexpr int kPauliSymmetricBlockBits = kPauliMomentumFullBlockBits;  // taken over from the full-momentum kernel, unmeasured
 constexpr unsigned kPauliSymmetricRatioStride = 121;
-struct PauliSymmetricImage {
+struct PauliBlockImage {
   int n_sites = 0, n_down = -1, momentum = 0, parity = 0, inversion = 0, group_size = 0;
   int64_t dim = 0;
   PauliTermImage terms;
   PauliRepImage basis;
-  DevArray<double> ratio;        // [121 * 121]
+  DevArray<double> ratio;        // [121 * 121] (PAULI_SYMMETRIC) / [32 * 32] (PAULI_MOMENTUM_FULL)
   DevArray<double> phase;        // [n_sites][2]
   int64_t device_bytes() const { return terms.device_bytes() + basis.device_bytes() + ratio.bytes() + phase.bytes(); }
 };
@@ -610,14 +602,16 @@ struct ll_operator {
   ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
   ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
   ll::PauliMomentumImage pauli_momentum;  // one momentum block of an S_z sector of a ring (kind PAULI_MOMENTUM)
-  ll::PauliMomentumFullImage pauli_momentum_full;  // one momentum block of the full space of a ring (kind PAULI_MOMENTUM_FULL)
-  ll::PauliSymmetricImage pauli_symmetric;  // one momentum / reflection / spin-inversion block of a ring (kind PAULI_SYMMETRIC)
+  ll::PauliBlockImage pauli_block;   // one symmetry block of a ring by a searched basis (kinds PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC)
+  static_assert(PAULI_SECTOR == PAULI + 1 && PAULI_MOMENTUM == PAULI + 2 && PAULI_MOMENTUM_FULL == PAULI + 3 &&
+                    PAULI_SYMMETRIC == PAULI + 4, "is_pauli: the five Pauli kinds are one range of Kind (a sixth goes inside it)");
+  static bool is_pauli(int kind) { return kind >= PAULI && kind <= PAULI_SYMMETRIC; }
+  bool is_pauli() const { return is_pauli(kind); }
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
     return csr.device_bytes() + csr_own.device_bytes() + csr_rem.device_bytes() + pb.device_bytes() + tl.device_bytes() +
            sym.device_bytes() + dense.bytes() + onsite.bytes() + pauli.device_bytes() +
-           pauli_sector.device_bytes() + pauli_momentum.device_bytes() + pauli_momentum_full.device_bytes() +
-           pauli_symmetric.device_bytes();
+           pauli_sector.device_bytes() + pauli_momentum.device_bytes() + pauli_block.device_bytes();
   }
   // callbacks
   ll_host_mv_mul_z host_fn = nullptr;  // every host callback is stored under the void* signature
@@ -631,10 +625,12 @@ struct ll_operator {
 
 namespace ll {
 
-// ---------------------------------------------------------------- operator construction (operators.cpp)
+// ---------------------------------------------------------------- operator construction (operators.cpp, pauli_operators.cpp)
 // What the extern "C" entry points (capi.cpp) call.  create_csr takes resolved options: csr_options_default(false) for the plain
 // entry points, csr_options_default(true) for the _dev_ ones, the caller's for the _opt_ ones.
 void use(ll_context* ctx);  // null check, then the context's device (capi.cpp)
+template <typename T>  // the header of every operator: kind, storage type, context and the checked row range (operators.cpp)
+std::unique_ptr<ll_operator> new_operator(ll_context* ctx, ll_operator::Kind kind, int64_t n, int64_t row_begin, int64_t n_local);
 ll_csr_options csr_options_default(bool arrays_on_device);
 template <typename T>
 void create_csr(ll_context* ctx, int64_t nr, int64_t nc, int64_t row_begin, const int64_t* rp, const int32_t* ci, const void* va,
@@ -791,6 +787,8 @@ int launch_pauli_momentum_full(const ll_operator& op, const T* x, T* y, double o
 template <typename T>
 int launch_pauli_symmetric(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                            const ScaleIn<T>* sc = nullptr);
+template <typename T>  // whichever of the five op.kind names (pauli_operators.cpp): what Engine::apply calls
+int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s, const ScaleIn<T>* sc);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

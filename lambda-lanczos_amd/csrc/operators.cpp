@@ -1,6 +1,6 @@
 // Operator construction: the images of a CSR matrix (upload, SpMV tiles, the column split, the PB and tiled builds, their
-// creation-time timing and the kernel choice), the one-triangle and COO forms, the dense, lattice, Pauli-string and callback operators, and the
-// accuracy policy that gives every image its form.  The extern "C" entry points (capi.cpp, documented in include/lanczos_hip.h)
+// creation-time timing and the kernel choice), the one-triangle and COO forms, the dense, lattice and callback operators, and the
+// accuracy policy that gives every image its form (the Pauli-string operators: pauli_operators.cpp).  The extern "C" entry points (capi.cpp, documented in include/lanczos_hip.h)
 // call in here.
 #include <algorithm>
 #include <cmath>
@@ -328,6 +328,8 @@ template <typename Image, typename Build> bool build_optional_image(ll_context* 
   return ok;
 }
 
+}  // namespace
+
 // The header of every operator: kind, storage type, context and row range.  Sharded operators must use the ll_partition()
 // row ranges (equal shard strides); a single-GPU operator is whole.
 template <typename T>
@@ -352,6 +354,7 @@ std::unique_ptr<ll_operator> new_operator(ll_context* ctx, ll_operator::Kind kin
   return op;
 }
 
+namespace {
 // The caller's ll_csr_options: a known accuracy class and a kernel up to max_kernel (LL_SPMV_TILED for full storage,
 // LL_SPMV_SYM for one triangle)
 void check_options(const ll_csr_options& o, int max_kernel) {
@@ -728,559 +731,6 @@ void create_stencil(ll_context* ctx, const ll_stencil_desc* d, int64_t row_begin
   *out = op.release();
 }
 
-// Sum of Pauli strings (pauli.hip, pauli_sector.hip): validate, fold i^nY into the coefficient (a sign for the real types, one
-// of {1, i, -1, -i} for the complex ones), group the terms by x mask — groups by ascending mask, the terms of a group in the
-// caller's order.
-namespace {
-struct PauliTables {
-  std::vector<uint32_t> gx, tz;   // x mask per group, z mask per term
-  std::vector<int32_t> gptr;      // [groups + 1] first term of each group
-  std::vector<double> tc;         // per term: c i^nY (real types), (re, im) of it (complex types)
-  double norm = 0.0;              // sum_t |c_t|
-};
-template <typename T>
-PauliTables pauli_tables(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
-  use(ctx);
-  LL_REQUIRE(out != nullptr, "null argument (out)");
-  LL_REQUIRE(n_terms >= 0, "n_terms is negative");
-  LL_REQUIRE(terms != nullptr || n_terms == 0, "null argument (terms)");
-  LL_REQUIRE(n_sites >= 1 && n_sites <= kPauliMaxSites,
-             "n_sites must lie in [1, " + std::to_string(kPauliMaxSites) + "] (2^n_sites states, 32-bit local indices)");
-  LL_REQUIRE(ctx->nranks == 1,
-             "a sum of Pauli strings cannot be created on a sharded context (flips of the sites that would number the ranks are "
-             "exchanges between them, which are not built): use a single-GPU context");
-  LL_REQUIRE(n_terms < (int64_t)0x7fffffff, "too many terms");
-  constexpr bool cplx = scalar_traits<T>::is_complex;
-  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
-  std::vector<int64_t> order((size_t)n_terms);
-  PauliTables pt;
-  for (int64_t t = 0; t < n_terms; ++t) {
-    const ll_pauli_term& q = terms[t];
-    LL_REQUIRE(((q.x_mask | q.z_mask) & ~site_mask) == 0, "term " + std::to_string(t) + ": a mask bit at or above n_sites");
-    LL_REQUIRE(std::isfinite(q.coef), "term " + std::to_string(t) + ": the coefficient is not finite");
-    LL_REQUIRE(cplx || (__builtin_popcountll(q.x_mask & q.z_mask) & 1) == 0,
-               "term " + std::to_string(t) + ": an odd number of Y factors makes the matrix complex; use a complex storage type");
-    order[(size_t)t] = t;
-    pt.norm += std::fabs(q.coef);
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return terms[a].x_mask < terms[b].x_mask; });
-  pt.tz.resize((size_t)n_terms);
-  pt.tc.resize((size_t)n_terms * (cplx ? 2 : 1));
-  for (int64_t k = 0; k < n_terms; ++k) {
-    const ll_pauli_term& q = terms[order[(size_t)k]];
-    if (pt.gx.empty() || pt.gx.back() != (uint32_t)q.x_mask) {
-      pt.gx.push_back((uint32_t)q.x_mask);
-      pt.gptr.push_back((int32_t)k);
-    }
-    pt.tz[(size_t)k] = (uint32_t)q.z_mask;
-    const int ny = __builtin_popcountll(q.x_mask & q.z_mask) & 3;  // i^nY: 1, i, -1, -i
-    const double c = ny >= 2 ? -q.coef : q.coef;
-    if (cplx) {
-      pt.tc[2 * (size_t)k] = (ny & 1) ? 0.0 : c;
-      pt.tc[2 * (size_t)k + 1] = (ny & 1) ? c : 0.0;
-    } else {
-      pt.tc[(size_t)k] = c;
-    }
-  }
-  pt.gptr.push_back((int32_t)n_terms);
-  return pt;
-}
-// a host table on the device
-template <typename V> void pauli_upload(ll_context* ctx, DevArray<V>& dst, const std::vector<V>& src, const char* what) {
-  dst = ctx->dev_alloc<V>(std::max<size_t>(src.size(), 1), what);
-  if (!src.empty()) LL_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
-}
-// the four term tables of an image on the device
-void pauli_upload_tables(ll_context* ctx, PauliTermImage& im, const PauliTables& pt) {
-  im.ngroups = (int)pt.gx.size();
-  im.nterms = (int64_t)pt.tz.size();
-  pauli_upload(ctx, im.gx, pt.gx, "Pauli x masks");
-  pauli_upload(ctx, im.gptr, pt.gptr, "Pauli group offsets");
-  pauli_upload(ctx, im.tz, pt.tz, "Pauli z masks");
-  pauli_upload(ctx, im.tc, pt.tc, "Pauli coefficients");
-}
-
-// S_z conservation, group by group: over every assignment of the bits the group touches (its x mask and its z masks) for which
-// flipping the x mask changes the number of set bits, the group's weight — summed as the kernel sums it, in double, terms in
-// order — must be exactly 0.  R = doubles per coefficient (2: re, im, summed separately as the kernel does).
-void pauli_require_sz_conserving(const PauliTables& pt, int R) {
-  for (size_t g = 0; g < pt.gx.size(); ++g) {
-    const uint32_t X = pt.gx[g];
-    if (X == 0) continue;
-    char hex[16];
-    std::snprintf(hex, sizeof hex, "0x%x", (unsigned)X);
-    const std::string who = "the terms with x mask " + std::string(hex);
-    uint32_t U = X;
-    for (int32_t k = pt.gptr[g]; k < pt.gptr[g + 1]; ++k) U |= pt.tz[(size_t)k];
-    LL_REQUIRE(__builtin_popcount(U) <= kPauliSectorMaxSupport,
-               who + " act on " + std::to_string(__builtin_popcount(U)) + " sites: the S_z conservation check cannot be made for more than " +
-                   std::to_string(kPauliSectorMaxSupport) + " (it visits every assignment of them)");
-    const int px = __builtin_popcount(X);
-    uint32_t s = 0;
-    do {  // every subset s of U
-      if (2 * __builtin_popcount(s & X) != px) {
-        for (int r = 0; r < R; ++r) {
-          double w = 0.0;
-          for (int32_t k = pt.gptr[g]; k < pt.gptr[g + 1]; ++k) {
-            const double c = pt.tc[(size_t)k * R + r];
-            w += (__builtin_popcount((s ^ X) & pt.tz[(size_t)k]) & 1) ? -c : c;
-          }
-          LL_REQUIRE(w == 0.0, who + " do not conserve S_z (they change the number of flipped spins with a weight that is not "
-                                     "zero): a magnetisation sector needs an H that commutes with total S_z");
-        }
-      }
-      s = (s - U) & U;
-    } while (s != 0);
-  }
-}
-
-// The states of the sector of n_down set bits in ascending order and the two tables that give a state's index back
-// (ll_internal.hpp PauliSectorImage): one pass over the C(n_sites, n_down) states, on the host.
-struct SectorTables {
-  int h = 0;
-  int64_t dim = 0;
-  std::vector<uint32_t> states, lo_rank, hi_rank;
-  uint32_t rank(uint32_t s) const { return lo_rank[s & (((uint32_t)1 << h) - 1)] + hi_rank[s >> h]; }
-};
-SectorTables sector_tables(int32_t n_sites, int32_t n_down) {
-  // binom[p][k] = C(p, k), p <= n_sites <= 30: below 2^32
-  std::vector<std::vector<uint64_t>> binom((size_t)n_sites + 1, std::vector<uint64_t>((size_t)n_sites + 2, 0));
-  for (int p = 0; p <= n_sites; ++p) {
-    binom[(size_t)p][0] = 1;
-    for (int k = 1; k <= p; ++k) binom[(size_t)p][(size_t)k] = binom[(size_t)p - 1][(size_t)k - 1] + binom[(size_t)p - 1][(size_t)k];
-  }
-  SectorTables st;
-  st.dim = (int64_t)binom[(size_t)n_sites][(size_t)n_down];
-  const int h = st.h = (n_sites + 1) / 2, hb = n_sites - h;  // low / other bits: both tables at most 2^15 entries
-  // rank(s) = sum_k C(p_k, k) over the set bits p_1 < p_2 < ...: the low bits count k from 1, the others from
-  // n_down - popcount(others) + 1 (entries no state of the sector reaches stay 0)
-  std::vector<uint32_t>& lo_rank = st.lo_rank;
-  std::vector<uint32_t>& hi_rank = st.hi_rank;
-  lo_rank.assign((size_t)1 << h, 0);
-  hi_rank.assign((size_t)1 << hb, 0);
-  for (uint32_t lo = 0; lo < ((uint32_t)1 << h); ++lo) {
-    if (__builtin_popcount(lo) > n_down) continue;
-    uint64_t r = 0;
-    int k = 0;
-    for (int p = 0; p < h; ++p)
-      if (lo >> p & 1u) r += binom[(size_t)p][(size_t)++k];
-    lo_rank[lo] = (uint32_t)r;
-  }
-  for (uint32_t hi = 0; hi < ((uint32_t)1 << hb); ++hi) {
-    int k = n_down - __builtin_popcount(hi);
-    if (k < 0 || k > h) continue;
-    uint64_t r = 0;
-    for (int p = 0; p < hb; ++p)
-      if (hi >> p & 1u) r += binom[(size_t)(p + h)][(size_t)++k];
-    hi_rank[hi] = (uint32_t)r;
-  }
-  const int64_t dim = st.dim;
-  std::vector<uint32_t>& states = st.states;
-  states.resize((size_t)dim);
-  {
-    uint64_t s = ((uint64_t)1 << n_down) - 1;  // the smallest state; the next one with as many set bits follows (Gosper)
-    for (int64_t i = 0; i < dim; ++i) {
-      states[(size_t)i] = (uint32_t)s;
-      if (s == 0) break;
-      const uint64_t c = s & (0 - s), r = s + c;
-      s = (((r ^ s) >> 2) >> __builtin_ctzll(s)) | r;
-    }
-  }
-  return st;
-}
-}  // namespace
-
-template <typename T>
-void create_pauli(ll_context* ctx, int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
-  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  const int64_t n = (int64_t)1 << n_sites;
-  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI, n, 0, n);
-  op->nnz = n_terms;
-  op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
-  PauliImage im;
-  im.n_sites = n_sites;
-  pauli_upload_tables(ctx, im.terms, pt);
-  op->pauli = std::move(im);
-  *out = op.release();
-}
-
-// The same terms on the sector of n_down set bits (pauli_sector.hip).  The states and the two rank tables are built here, on the
-// host: one pass over the C(n_sites, n_down) states in ascending order.
-template <typename T>
-void create_pauli_sector(ll_context* ctx, int32_t n_sites, int32_t n_down, int64_t n_terms, const ll_pauli_term* terms,
-                         ll_operator** out) {
-  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
-  pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
-  const SectorTables st = sector_tables(n_sites, n_down);
-  const int64_t dim = st.dim;
-  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_SECTOR, dim, 0, dim);
-  op->nnz = n_terms;
-  op->inf_norm = pt.norm;  // sum_t |c_t|: a bound of every absolute row sum
-  PauliSectorImage im;
-  im.n_sites = n_sites;
-  im.n_down = n_down;
-  im.h = st.h;
-  im.dim = dim;
-  pauli_upload_tables(ctx, im.terms, pt);
-  pauli_upload(ctx, im.states, st.states, "S_z sector states");
-  pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
-  pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
-  op->pauli_sector = std::move(im);
-  *out = op.release();
-}
-
-namespace {
-// Translation invariance on the ring: with the coefficients of equal (x_mask, z_mask) merged (summed in the caller's order),
-// rotating every term's masks by one site must map the term set onto itself with exactly equal coefficients (a missing term
-// counts as coefficient 0).  i^nY does not change under the rotation, so the caller's coefficients are compared.
-void pauli_require_translation_invariant(int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms) {
-  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
-  auto rot = [&](uint64_t v) { return ((v << 1) | (v >> (n_sites - 1))) & site_mask; };
-  std::map<std::pair<uint64_t, uint64_t>, double> merged;
-  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
-  for (int64_t t = 0; t < n_terms; ++t) {
-    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask}, moved{rot(key.first), rot(key.second)};
-    const auto it = merged.find(moved);
-    const double there = it == merged.end() ? 0.0 : it->second;
-    if (there == merged[key]) continue;
-    char hex[64];
-    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
-    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the one-site translation of the ring: "
-                      "shifted by one site it meets a different coefficient (an open chain, or bonds that differ); a momentum "
-                      "sector needs a translation-invariant H");
-  }
-}
-// the momentum argument of the three momentum-block operators
-template <typename T> void pauli_require_momentum(int32_t n_sites, int32_t momentum) {
-  LL_REQUIRE(momentum >= 0 && momentum < n_sites, "momentum must lie in [0, n_sites) (the block of k = 2 pi momentum / n_sites)");
-  LL_REQUIRE(scalar_traits<T>::is_complex || (2 * momentum) % n_sites == 0,
-             "a real storage type takes momentum 0 and n_sites / 2 only (the other blocks are complex Hermitian); use a complex "
-             "storage type");
-}
-// ratio[Ra * 32 + Rb] = sqrt(Ra / Rb) for the orbit lengths of a ring of at most 30 sites: the table of both momentum-block operators
-std::vector<double> momentum_ratio_table() {
-  std::vector<double> ratio(32 * 32, 0.0);
-  for (int a = 1; a < 32; ++a)
-    for (int b = 1; b < 32; ++b) ratio[(size_t)a * 32 + (size_t)b] = std::sqrt((double)a / (double)b);
-  return ratio;
-}
-// phase[l] = e^(-2 pi i m l / n_sites) as (re, im), l < n_sites, exact on the axes: the table of the three momentum-block operators
-void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>& phase) {
-  for (int l = 0; l < n_sites; ++l) {
-    const int k = (int)(((int64_t)momentum * l) % n_sites);
-    const double th = 2.0 * M_PI * (double)k / (double)n_sites;
-    double c = std::cos(th), sn = -std::sin(th);
-    if (4 * k % n_sites == 0) {
-      const int quarter = 4 * k / n_sites;  // 0 .. 3
-      c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
-      sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
-    }
-    phase[2 * (size_t)l] = c;
-    phase[2 * (size_t)l + 1] = sn;
-  }
-}
-// The binary necklaces of n_sites bits in ascending order with their periods, by the Fredricksen-Kessler-Maiorana enumeration: a
-// string read from site n_sites - 1 down to site 0 that is the lexicographically smallest of its rotations is the smallest
-// integer of its orbit, and the enumeration yields these strings in ascending order with their period (the length of the Lyndon
-// word they repeat) — one step per pre-necklace, about two steps per necklace, no pass over the 2^n_sites states.  A step: raise
-// the lowest 0 bit (position i from the top), drop what lies below it and repeat the top i bits downwards; the result is a
-// necklace iff i divides n_sites, and then its period is i.  visit(a, period) is called for every necklace, the string of zeros
-// (period 1) first.
-template <typename Visit> void for_each_necklace(int L, Visit visit) {
-  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
-  visit((uint32_t)0, 1);
-  uint32_t a = 0;
-  while (a != site_mask) {
-    const int low0 = __builtin_ctz(~a);  // the lowest 0 bit of a (a != all ones): string position i = L - low0 from the top
-    const int i = L - low0;
-    a = ((a >> low0) | 1u) << low0;      // raise it, clear what lies below
-    for (int sft = i; sft < L; sft *= 2) a |= a >> sft;  // repeat the top i bits downwards (bits shifted out fall off the end)
-    if (L % i != 0) continue;            // a pre-necklace only
-    visit(a, i);
-  }
-}
-// The bucket table over the top bits of ascending representatives (PauliMomentumFullImage): the largest power of two not above
-// dim / 8 buckets (the table stays below dim / 2 bytes), and the halvings that bring the largest bucket down to one candidate.
-struct RepBuckets {
-  std::vector<uint32_t> start;
-  int shift = 0, trips = 0;
-  int64_t max_bucket = 0;
-};
-RepBuckets rep_buckets(int L, const std::vector<uint32_t>& reps) {
-  const int64_t dim = (int64_t)reps.size();
-  RepBuckets rb;
-  int pb = 0;
-  while (pb < L && ((int64_t)2 << pb) <= dim / 8) ++pb;
-  rb.shift = L - pb;
-  rb.start.assign(((size_t)1 << pb) + 1, 0);
-  for (int64_t k = 0; k < dim; ++k) ++rb.start[(size_t)(reps[(size_t)k] >> rb.shift) + 1];
-  for (size_t q = 1; q < rb.start.size(); ++q) {
-    rb.max_bucket = std::max<int64_t>(rb.max_bucket, rb.start[q]);
-    rb.start[q] += rb.start[q - 1];
-  }
-  for (int64_t n = rb.max_bucket; n > 1; n -= n / 2) ++rb.trips;  // n -> n - n / 2
-  return rb;
-}
-// the representatives, their orbit lengths and the bucket table of an image on the device, under the allocation names what[3]
-void pauli_upload_reps(ll_context* ctx, PauliRepImage& im, const std::vector<uint32_t>& reps, const std::vector<uint8_t>& orbit_len,
-                       const RepBuckets& rb, const char* const (&what)[3]) {
-  im.prefix_shift = rb.shift;
-  im.search_trips = rb.trips;
-  im.max_bucket = rb.max_bucket;
-  pauli_upload(ctx, im.reps, reps, what[0]);
-  pauli_upload(ctx, im.orbit_len, orbit_len, what[1]);
-  pauli_upload(ctx, im.start, rb.start, what[2]);
-}
-// Reflection invariance: with the coefficients of equal (x_mask, z_mask) merged (summed in the caller's order), reversing the
-// n_sites bits of every term's masks must map the term set onto itself with exactly equal coefficients (a missing term counts
-// as coefficient 0).  A site permutation moves X, Y, Z factors without a sign, so the caller's coefficients are compared.
-void pauli_require_reflection_invariant(int32_t n_sites, int64_t n_terms, const ll_pauli_term* terms) {
-  auto rev = [&](uint64_t v) {
-    uint64_t r = 0;
-    for (int j = 0; j < n_sites; ++j) r |= ((v >> j) & 1u) << (n_sites - 1 - j);
-    return r;
-  };
-  std::map<std::pair<uint64_t, uint64_t>, double> merged;
-  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
-  for (int64_t t = 0; t < n_terms; ++t) {
-    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask}, moved{rev(key.first), rev(key.second)};
-    const auto it = merged.find(moved);
-    const double there = it == merged.end() ? 0.0 : it->second;
-    if (there == merged[key]) continue;
-    char hex[64];
-    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
-    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the reflection of the ring (site j -> "
-                      "n_sites - 1 - j): reflected it meets a different coefficient (a Dzyaloshinskii-Moriya bond, or bonds that "
-                      "differ); a parity block needs a reflection-invariant H");
-  }
-}
-// Spin-inversion invariance: prod_j X_j anticommutes with every Y and Z factor, so a string commutes with it iff popcount(z_mask)
-// is even; with equal masks merged, a term of odd popcount(z_mask) must have the coefficient 0.
-void pauli_require_inversion_invariant(int64_t n_terms, const ll_pauli_term* terms) {
-  std::map<std::pair<uint64_t, uint64_t>, double> merged;
-  for (int64_t t = 0; t < n_terms; ++t) merged[{terms[t].x_mask, terms[t].z_mask}] += terms[t].coef;
-  for (int64_t t = 0; t < n_terms; ++t) {
-    const std::pair<uint64_t, uint64_t> key{terms[t].x_mask, terms[t].z_mask};
-    if ((__builtin_popcountll(key.second) & 1) == 0 || merged[key] == 0.0) continue;
-    char hex[64];
-    std::snprintf(hex, sizeof hex, "(x_mask 0x%llx, z_mask 0x%llx)", (unsigned long long)key.first, (unsigned long long)key.second);
-    LL_REQUIRE(false, "term " + std::to_string(t) + " " + hex + " does not commute with the global spin flip (the product of all "
-                      "X_j): it holds an odd number of Y and Z factors (a longitudinal field, for example); a spin-inversion "
-                      "block needs an H that is even under the flip");
-  }
-}
-}  // namespace
-
-// One momentum block of that sector (pauli_momentum.hip).  One pass over the sector's states in ascending order, on the host: the
-// first state of an orbit not seen before is its representative; walking the orbit gives its period R and, for the blocks's
-// orbits (m R = 0 mod n_sites), the entries orbit[rank(T^j r)] = (index of r << 5 | j).
-template <typename T>
-void create_pauli_momentum(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int64_t n_terms,
-                           const ll_pauli_term* terms, ll_operator** out) {
-  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  LL_REQUIRE(n_down >= 0 && n_down <= n_sites, "n_down must lie in [0, n_sites] (the number of flipped spins of the sector)");
-  pauli_require_momentum<T>(n_sites, momentum);
-  pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
-  pauli_require_translation_invariant(n_sites, n_terms, terms);
-  const SectorTables st = sector_tables(n_sites, n_down);
-  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << n_sites) - 1);
-  auto rot = [&](uint32_t v) { return ((v << 1) | (v >> (n_sites - 1))) & site_mask; };
-  std::vector<uint32_t> orbit((size_t)st.dim, kPauliOrbitExcluded), reps;
-  std::vector<uint8_t> orbit_len;
-  std::vector<bool> seen((size_t)st.dim, false);
-  bool any_short = false;
-  for (int64_t i = 0; i < st.dim; ++i) {
-    if (seen[(size_t)i]) continue;
-    const uint32_t r = st.states[(size_t)i];  // ascending order: the smallest state of a new orbit
-    int R = 0;
-    for (uint32_t t = r;;) {
-      seen[(size_t)st.rank(t)] = true;
-      ++R;
-      if ((t = rot(t)) == r) break;
-    }
-    if (((int64_t)momentum * R) % n_sites != 0) continue;  // the orbit's states keep kPauliOrbitExcluded
-    const uint64_t idx = reps.size();
-    LL_REQUIRE(idx < ((uint64_t)1 << (32 - kPauliOrbitShiftBits)) - 1, "internal: a momentum block of 2^27 states or more");
-    uint32_t t = r;
-    for (int j = 0; j < R; ++j, t = rot(t)) orbit[(size_t)st.rank(t)] = (uint32_t)(idx << kPauliOrbitShiftBits) | (uint32_t)j;
-    reps.push_back(r);
-    orbit_len.push_back((uint8_t)R);
-    any_short = any_short || R != n_sites;
-  }
-  static_assert(kPauliMaxSites < (1 << kPauliOrbitShiftBits), "the shift l of an orbit entry needs n_sites < 2^5");
-  const int64_t dim = (int64_t)reps.size();
-  LL_REQUIRE(dim >= 1, "the momentum block is empty: no orbit of the sector (n_sites " + std::to_string(n_sites) + ", n_down " +
-                           std::to_string(n_down) + ") has a length R with momentum * R = 0 (mod n_sites)");
-  const std::vector<double> ratio = momentum_ratio_table();
-  std::vector<double> phase(2 * (size_t)n_sites);
-  momentum_phase_table(n_sites, momentum, phase);
-  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM, dim, 0, dim);
-  op->nnz = n_terms;
-  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
-  PauliMomentumImage im;
-  im.n_sites = n_sites;
-  im.n_down = n_down;
-  im.momentum = momentum;
-  im.h = st.h;
-  im.dim = dim;
-  im.sector_dim = st.dim;
-  if (any_short)  // the primes q of n_sites: a state has a short orbit iff rotating it by n_sites / q gives it back for one of them
-    for (int q = 2, rest = n_sites; rest > 1; ++q)
-      if (rest % q == 0) {
-        LL_REQUIRE(im.nshort < 3, "internal: more than three primes in n_sites");
-        im.short_shift[im.nshort++] = n_sites / q;
-        while (rest % q == 0) rest /= q;
-      }
-  pauli_upload_tables(ctx, im.terms, pt);
-  pauli_upload(ctx, im.reps, reps, "momentum block representatives");
-  pauli_upload(ctx, im.orbit_len, orbit_len, "momentum block orbit lengths");
-  pauli_upload(ctx, im.orbit, orbit, "momentum block orbit table");
-  pauli_upload(ctx, im.lo_rank, st.lo_rank, "S_z sector rank table (low bits)");
-  pauli_upload(ctx, im.hi_rank, st.hi_rank, "S_z sector rank table (high bits)");
-  pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
-  pauli_upload(ctx, im.phase, phase, "momentum block phases");
-  op->pauli_momentum = std::move(im);
-  *out = op.release();
-}
-
-// One momentum block of the full 2^n_sites space (pauli_momentum_full.hip).  The representatives and their periods come from the
-// necklace enumeration (for_each_necklace): ascending, about two steps per representative, no pass over the 2^n_sites states.
-template <typename T>
-void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t momentum, int64_t n_terms, const ll_pauli_term* terms,
-                                ll_operator** out) {
-  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  pauli_require_momentum<T>(n_sites, momentum);
-  pauli_require_translation_invariant(n_sites, n_terms, terms);
-  const int L = n_sites;
-  std::vector<uint32_t> reps;
-  std::vector<uint8_t> orbit_len;
-  {
-    // a lower bound of D_m that saves most of the re-allocations: the orbits of full length alone, when the block takes them
-    reps.reserve((size_t)(((uint64_t)1 << L) / (uint64_t)L) + 64);
-    orbit_len.reserve(reps.capacity());
-    for_each_necklace(L, [&](uint32_t a, int i) {  // the string of zeros (period 1) lies in block 0 only
-      if (((int64_t)momentum * i) % L != 0) return;
-      LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "internal: a momentum block of 2^27 states or more");
-      reps.push_back(a);
-      orbit_len.push_back((uint8_t)i);
-    });
-  }
-  const int64_t dim = (int64_t)reps.size();
-  // never empty: the state 0..01 has the full period n_sites, which every m admits (n_sites = 1: m = 0, and both states have R = 1)
-  LL_REQUIRE(dim >= 1, "internal: an empty momentum block of the full space");
-  const RepBuckets rb = rep_buckets(L, reps);
-  const std::vector<double> ratio = momentum_ratio_table();
-  std::vector<double> phase(2 * (size_t)n_sites);
-  momentum_phase_table(n_sites, momentum, phase);
-  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_MOMENTUM_FULL, dim, 0, dim);
-  op->nnz = n_terms;
-  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
-  PauliMomentumFullImage im;
-  im.n_sites = n_sites;
-  im.momentum = momentum;
-  im.dim = dim;
-  pauli_upload_tables(ctx, im.terms, pt);
-  pauli_upload_reps(ctx, im.basis, reps, orbit_len, rb,
-                    {"momentum block representatives", "momentum block orbit lengths", "momentum block bucket table"});
-  pauli_upload(ctx, im.ratio, ratio, "momentum block norm ratios");
-  pauli_upload(ctx, im.phase, phase, "momentum block phases");
-  op->pauli_momentum_full = std::move(im);
-  *out = op.release();
-}
-
-// One block under momentum, reflection and spin inversion (pauli_symmetric.hip).  Every necklace a (the smallest of its
-// rotations) is the representative of its G-orbit iff it is not above the smallest rotation of rev(a), ~a and ~rev(a), whichever
-// are in use; walking the L rotations of each stream in use collects its stabiliser — the orbit length R = |G| / |stabiliser|
-// and whether the character is 1 on all of it — and the popcount filter follows: O(n_sites) per necklace, O(2^n_sites) steps
-// over all of them, on the host, with no table over the states.
-template <typename T>
-void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity, int32_t inversion,
-                            int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
-  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
-  LL_REQUIRE(parity >= -1 && parity <= 1, "parity must be 0 (the reflection is not used), +1 or -1");
-  LL_REQUIRE(inversion >= -1 && inversion <= 1, "inversion must be 0 (the global spin flip is not used), +1 or -1");
-  LL_REQUIRE(n_down >= -1 && n_down <= n_sites,
-             "n_down must lie in [-1, n_sites] (-1: the full space; else the number of flipped spins of the sector)");
-  pauli_require_momentum<T>(n_sites, momentum);
-  LL_REQUIRE(parity == 0 || (2 * momentum) % n_sites == 0,
-             "parity != 0 takes momentum 0 and n_sites / 2 only (the reflection maps momentum k to -k: the group of shifts and "
-             "the reflection has one-dimensional characters only there); use parity = 0");
-  pauli_require_translation_invariant(n_sites, n_terms, terms);
-  if (parity != 0) pauli_require_reflection_invariant(n_sites, n_terms, terms);
-  if (inversion != 0) pauli_require_inversion_invariant(n_terms, terms);
-  if (n_down >= 0) {
-    pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
-    LL_REQUIRE(inversion == 0 || 2 * n_down == n_sites,
-               "inversion != 0 with n_down >= 0 needs 2 n_down = n_sites (the global spin flip maps the sector n_down onto "
-               "n_sites - n_down)");
-  }
-  const int L = n_sites;
-  const uint32_t site_mask = (uint32_t)(((uint64_t)1 << L) - 1);
-  const int group_size = L * (parity != 0 ? 2 : 1) * (inversion != 0 ? 2 : 1);
-  auto rot = [&](uint32_t v) { return ((v << 1) | (v >> (L - 1))) & site_mask; };
-  auto rev = [&](uint32_t v) {
-    uint32_t r = 0;
-    for (int j = 0; j < L; ++j) r |= ((v >> j) & 1u) << (L - 1 - j);
-    return r;
-  };
-  std::vector<uint32_t> reps;
-  std::vector<uint8_t> orbit_len;
-  for_each_necklace(L, [&](uint32_t a, int) {
-    if (n_down >= 0 && __builtin_popcount(a) != n_down) return;  // G keeps the popcount (inversion: 2 n_down = L)
-    int stab = 0;
-    bool least = true, admitted = true;
-    for (int rho = 0; rho <= (parity != 0 ? 1 : 0); ++rho)
-      for (int zeta = 0; zeta <= (inversion != 0 ? 1 : 0); ++zeta) {
-        uint32_t cur = rho ? rev(a) : a;
-        if (zeta) cur ^= site_mask;
-        const bool neg = (rho && parity < 0) != (zeta && inversion < 0);
-        for (int j = 0; j < L; ++j) {  // cur = T^j P^rho Z^zeta a; its character in units of pi / L: 2 m j, + L for a factor -1
-          if (cur < a) least = false;
-          if (cur == a) {
-            ++stab;
-            if ((2 * (int64_t)momentum * j + (neg ? L : 0)) % (2 * L) != 0) admitted = false;
-          }
-          cur = rot(cur);
-        }
-      }
-    if (!least || !admitted) return;
-    LL_REQUIRE(reps.size() < (((size_t)1 << 27) - 1), "a block of 2^27 - 1 states or more (32-bit indices with room for the search)");
-    reps.push_back(a);
-    orbit_len.push_back((uint8_t)(group_size / stab));
-  });
-  const int64_t dim = (int64_t)reps.size();
-  LL_REQUIRE(dim >= 1, "the block (momentum " + std::to_string(momentum) + ", parity " + std::to_string(parity) + ", inversion " +
-                           std::to_string(inversion) + ", n_down " + std::to_string(n_down) +
-                           ") is empty: no orbit carries this character");
-  const RepBuckets rb = rep_buckets(L, reps);
-  // ratio[R_a][c] = sqrt(R_a / R_b) for the orbit length R_b = |G| / c of a stabiliser of c elements
-  std::vector<double> ratio((size_t)kPauliSymmetricRatioStride * kPauliSymmetricRatioStride, 0.0), phase(2 * (size_t)n_sites);
-  for (int a = 1; a <= group_size; ++a)
-    for (int c = 1; c <= group_size; ++c)
-      if (group_size % c == 0)
-        ratio[(size_t)a * kPauliSymmetricRatioStride + (size_t)c] = std::sqrt((double)a / (double)(group_size / c));
-  momentum_phase_table(n_sites, momentum, phase);
-  std::unique_ptr<ll_operator> op = new_operator<T>(ctx, ll_operator::PAULI_SYMMETRIC, dim, 0, dim);
-  op->nnz = n_terms;
-  op->inf_norm = pt.norm;  // sum_t |c_t| >= ||H||_2 >= ||B^H H B||_2: a bound of every |eigenvalue| of the block
-  PauliSymmetricImage im;
-  im.n_sites = n_sites;
-  im.n_down = n_down;
-  im.momentum = momentum;
-  im.parity = parity;
-  im.inversion = inversion;
-  im.group_size = group_size;
-  im.dim = dim;
-  pauli_upload_tables(ctx, im.terms, pt);
-  pauli_upload_reps(ctx, im.basis, reps, orbit_len, rb,
-                    {"symmetry block representatives", "symmetry block orbit lengths", "symmetry block bucket table"});
-  pauli_upload(ctx, im.ratio, ratio, "symmetry block norm ratios");
-  pauli_upload(ctx, im.phase, phase, "symmetry block phases");
-  op->pauli_symmetric = std::move(im);
-  *out = op.release();
-}
-
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out) {
   LL_REQUIRE(host_fn != nullptr || dev_fn != nullptr, "null callback");
@@ -1295,6 +745,7 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
 }
 
 #define LL_INST_OPERATORS(T)                                                                                                     \
+  template std::unique_ptr<ll_operator> new_operator<T>(ll_context*, ll_operator::Kind, int64_t, int64_t, int64_t);           \
   template void create_csr<T>(ll_context*, int64_t, int64_t, int64_t, const int64_t*, const int32_t*, const void*,              \
                               const ll_csr_options&, ll_operator**);                                                            \
   template void create_coo<T>(ll_context*, int64_t, int64_t, const int32_t*, const int32_t*, const void*, ll_operator**);       \
@@ -1302,12 +753,6 @@ void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_m
                                   ll_operator**);                                                                               \
   template void create_dense<T>(ll_context*, int64_t, int64_t, int64_t, const void*, ll_operator**);                            \
   template void create_stencil<T>(ll_context*, const ll_stencil_desc*, int64_t, int64_t, const double*, ll_operator**);        \
-  template void create_pauli<T>(ll_context*, int32_t, int64_t, const ll_pauli_term*, ll_operator**);                             \
-  template void create_pauli_sector<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);             \
-  template void create_pauli_momentum<T>(ll_context*, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);  \
-  template void create_pauli_momentum_full<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);    \
-  template void create_pauli_symmetric<T>(ll_context*, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, \
-                                          ll_operator**);                                                                      \
   template void create_cb<T>(ll_context*, int64_t, ll_host_mv_mul_z, ll_dev_mv_mul, void*, ll_operator**);
 LL_FOR_EACH_SCALAR(LL_INST_OPERATORS)
 

@@ -3,7 +3,7 @@
 //
 // Basis state s, bit j of s = site j, bit 0 = sigma_z +1.  A term (x, z, c): site j carries X (x bit only), Z (z bit only), Y (both);
 //   (H v)(s) = sum_t c_t i^nY_t (-1)^popcount((s ^ x_t) & z_t) v(s ^ x_t),   nY_t = popcount(x_t & z_t).
-// Creation (operators.cpp create_pauli) folds i^nY into the coefficient, groups the terms by x mask (groups by ascending mask, the
+// Creation (pauli_operators.cpp create_pauli) folds i^nY into the coefficient, groups the terms by x mask (groups by ascending mask, the
 // terms of a group in the caller's order), and the kernel forms for every state, in that fixed order and in double,
 //   y(s) = sum_g w_g(s) v(s ^ X_g),   w_g(s) = sum_{t in g} coef_t (-1)^popcount((s ^ X_g) & z_t):
 // the same bits run to run, for every tile size, grid and alignment of the vectors.

@@ -1,6 +1,6 @@
 // The sum of Pauli strings H = sum_t c_t P_t (pauli.hip) on one momentum block of one magnetisation sector of a ring, for gfx950.
 // T is the one-site shift (a basis state rotated left by one bit); H conserves total S_z and commutes with T (creation checks
-// both: operators.cpp create_pauli_momentum).  The basis of block m (momentum 2 pi m / n_sites) is the representatives r — the
+// both: pauli_operators.cpp create_pauli_momentum).  The basis of block m (momentum 2 pi m / n_sites) is the representatives r — the
 // smallest member of each orbit {T^j s} — of the sector whose orbit length R_r satisfies m R_r = 0 (mod n_sites), ascending;
 // basis vector |r; m> = (R_r^(1/2) / n_sites) sum_j e^(-2 pi i m j / n_sites) T^j |r>.
 //

@@ -1,7 +1,7 @@
 // The sum of Pauli strings H = sum_t c_t P_t (pauli.hip) on one momentum block of the FULL 2^n_sites space of a ring, for gfx950:
 // the block of pauli_momentum.hip without the magnetisation sector, for an H that commutes with the one-site shift T (a basis
 // state rotated left by one bit) but need not conserve S_z — the transverse-field Ising ring, XYZ rings, transverse fields
-// (creation checks the commutation: operators.cpp create_pauli_momentum_full).  The basis of block m (momentum
+// (creation checks the commutation: pauli_operators.cpp create_pauli_momentum_full).  The basis of block m (momentum
 // 2 pi m / n_sites) is the representatives r — the smallest member of each orbit {T^j s} — of ALL states whose orbit length R_r
 // satisfies m R_r = 0 (mod n_sites), ascending; basis vector |r; m> = (R_r^(1/2) / n_sites) sum_j e^(-2 pi i m j / n_sites) T^j |r>.
 //
@@ -86,7 +86,7 @@ struct PauliMomentumFullPartner {
 template <typename T>
 int launch_pauli_momentum_full(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                                const ScaleIn<T>* scp) {
-  const PauliMomentumFullImage& im = op.pauli_momentum_full;
+  const PauliBlockImage& im = op.pauli_block;
   unsigned in_block = 0u;
   for (int R = 1; R <= im.n_sites; ++R)
     if (im.n_sites % R == 0 && (im.momentum * R) % im.n_sites == 0) in_block |= 1u << R;

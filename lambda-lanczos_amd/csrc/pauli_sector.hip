@@ -1,6 +1,6 @@
 // The sum of Pauli strings H = sum_t c_t P_t (pauli.hip) restricted to one magnetisation sector for gfx950: the basis is the
 // D = C(n_sites, n_down) states with n_down set bits (set bit = sigma_z -1), in ascending integer order, for an H that conserves
-// total S_z (creation checks it: operators.cpp create_pauli_sector).
+// total S_z (creation checks it: pauli_operators.cpp create_pauli_sector).
 //
 // With s_i the i-th state of the sector and the groups, term order, folded i^nY and weights w_g of pauli.hip,
 //   y(i) = sum_g w_g(s_i) v(rank(s_i ^ X_g)),   over the groups whose partner s_i ^ X_g stays in the sector,

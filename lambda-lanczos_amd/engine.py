@@ -6,7 +6,6 @@ tests read like the reference's own tests; the C++ twin of this file is include/
 All numerics run in liblanczos_hip.so on the GPU — there is no CPU path in this package.
 """
 import ctypes as C
-import math
 import weakref
 
 import numpy as np
@@ -395,54 +394,52 @@ class StencilOperator(_Operator):
     inf_norm = CsrOperator.inf_norm
 
 
-class PauliOperator(_Operator):
-    """Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t (ll_op_create_pauli_*): `terms` is a sequence of
-    (x_mask, z_mask, coef); bit j of a basis state is site j, a site carries X (x bit only), Z (z bit only) or Y (both).
-    n = 2^n_sites; single-GPU contexts; the real dtypes take terms with an even number of Y only."""
+class _PauliFamily(_Operator):
+    """What the five Pauli-sum operators share: the term array and the create call, ll_op_create_pauli<kind>_<suffix>(ctx,
+    *args, n_terms, terms, out).  n is what creation counted."""
 
-    def __init__(self, ctx, n_sites, terms, dtype=np.float64):
+    def _create(self, ctx, kind, dtype, terms, *args):
         terms = list(terms)
         arr = (capi.PauliTerm * max(len(terms), 1))()
         for k, (xm, zm, c) in enumerate(terms):
             arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
         self.ctx, self.dtype = ctx, np.dtype(dtype)
-        self.n_sites = int(n_sites)
-        self.n = self.n_local = 1 << self.n_sites if 0 <= self.n_sites < 63 else 0
         self.row_begin, self.nnz = 0, len(terms)
         h = C.c_void_p()
-        fn = getattr(lib(), "ll_op_create_pauli_" + _suffix(self.dtype))
-        check(fn(ctx.handle, self.n_sites, len(terms), arr, C.byref(h)))
+        fn = getattr(lib(), "ll_op_create_pauli" + kind + "_" + _suffix(self.dtype))
+        check(fn(ctx.handle, *args, len(terms), arr, C.byref(h)))
         self.handle = h
+        self.n = self.n_local = self.info()[0]
+
+
+class PauliOperator(_PauliFamily):
+    """Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t (ll_op_create_pauli_*): `terms` is a sequence of
+    (x_mask, z_mask, coef); bit j of a basis state is site j, a site carries X (x bit only), Z (z bit only) or Y (both).
+    n = 2^n_sites; single-GPU contexts; the real dtypes take terms with an even number of Y only."""
+
+    def __init__(self, ctx, n_sites, terms, dtype=np.float64):
+        self.n_sites = int(n_sites)
+        self._create(ctx, "", dtype, terms, self.n_sites)
 
     def inf_norm(self):
         """sum_t |coef_t|: an upper bound of every absolute row sum (a safe |eigenvalue_offset|)."""
         return CsrOperator.inf_norm(self)
 
 
-class PauliSectorOperator(_Operator):
+class PauliSectorOperator(_PauliFamily):
     """The same Hamiltonian on one magnetisation sector (ll_op_create_pauli_sector_*): the basis is the comb(n_sites, n_down)
     states with n_down set bits (a set bit is sigma_z = -1) in ascending integer order (generators.sector_states), and H must
     conserve total S_z — creation refuses one that does not, naming the x mask at fault.  Terms, dtypes and limits as
     PauliOperator; 0 <= n_down <= n_sites."""
 
     def __init__(self, ctx, n_sites, n_down, terms, dtype=np.float64):
-        terms = list(terms)
-        arr = (capi.PauliTerm * max(len(terms), 1))()
-        for k, (xm, zm, c) in enumerate(terms):
-            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
-        self.ctx, self.dtype = ctx, np.dtype(dtype)
         self.n_sites, self.n_down = int(n_sites), int(n_down)
-        self.n = self.n_local = math.comb(self.n_sites, self.n_down) if 0 <= self.n_down <= self.n_sites else 0
-        self.row_begin, self.nnz = 0, len(terms)
-        h = C.c_void_p()
-        fn = getattr(lib(), "ll_op_create_pauli_sector_" + _suffix(self.dtype))
-        check(fn(ctx.handle, self.n_sites, self.n_down, len(terms), arr, C.byref(h)))
-        self.handle = h
+        self._create(ctx, "_sector", dtype, terms, self.n_sites, self.n_down)
 
     inf_norm = PauliOperator.inf_norm
 
 
-class PauliMomentumOperator(_Operator):
+class PauliMomentumOperator(_PauliFamily):
     """One momentum block of one magnetisation sector of a ring (ll_op_create_pauli_momentum_*): the operator B^H H_sector B with
     B = generators.momentum_embedding(n_sites, n_down, momentum); the basis is the orbit representatives of
     generators.momentum_basis, ascending.  H must conserve total S_z and commute with the one-site translation — creation
@@ -450,26 +447,15 @@ class PauliMomentumOperator(_Operator):
     n_sites / 2 only.  Holds 4 comb(n_sites, n_down) bytes of look-up table on the device (device_bytes)."""
 
     def __init__(self, ctx, n_sites, n_down, momentum, terms, dtype=np.float64):
-        terms = list(terms)
-        arr = (capi.PauliTerm * max(len(terms), 1))()
-        for k, (xm, zm, c) in enumerate(terms):
-            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
-        self.ctx, self.dtype = ctx, np.dtype(dtype)
         self.n_sites, self.n_down, self.momentum = int(n_sites), int(n_down), int(momentum)
-        self.n = self.n_local = 0
-        self.row_begin, self.nnz = 0, len(terms)
-        h = C.c_void_p()
-        fn = getattr(lib(), "ll_op_create_pauli_momentum_" + _suffix(self.dtype))
-        check(fn(ctx.handle, self.n_sites, self.n_down, self.momentum, len(terms), arr, C.byref(h)))
-        self.handle = h
-        self.n = self.n_local = self.info()[0]   # D_m: counted at creation
+        self._create(ctx, "_momentum", dtype, terms, self.n_sites, self.n_down, self.momentum)  # n = D_m
 
     def inf_norm(self):
         """sum_t |coef_t|: an upper bound of every |eigenvalue| of the block (a safe |eigenvalue_offset|)."""
         return CsrOperator.inf_norm(self)
 
 
-class PauliMomentumFullOperator(_Operator):
+class PauliMomentumFullOperator(_PauliFamily):
     """One momentum block of the full 2^n_sites space of a ring (ll_op_create_pauli_momentum_full_*): the operator B^H H B with
     B = generators.full_momentum_embedding(n_sites, momentum) and H the PauliOperator of the same terms; the basis is the orbit
     representatives of generators.full_momentum_basis, ascending.  H must commute with the one-site translation — creation
@@ -478,24 +464,13 @@ class PauliMomentumFullOperator(_Operator):
     2^n_sites states (device_bytes <= 8 n + 64 KiB)."""
 
     def __init__(self, ctx, n_sites, momentum, terms, dtype=np.float64):
-        terms = list(terms)
-        arr = (capi.PauliTerm * max(len(terms), 1))()
-        for k, (xm, zm, c) in enumerate(terms):
-            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
-        self.ctx, self.dtype = ctx, np.dtype(dtype)
         self.n_sites, self.momentum = int(n_sites), int(momentum)
-        self.n = self.n_local = 0
-        self.row_begin, self.nnz = 0, len(terms)
-        h = C.c_void_p()
-        fn = getattr(lib(), "ll_op_create_pauli_momentum_full_" + _suffix(self.dtype))
-        check(fn(ctx.handle, self.n_sites, self.momentum, len(terms), arr, C.byref(h)))
-        self.handle = h
-        self.n = self.n_local = self.info()[0]   # D_m: counted at creation
+        self._create(ctx, "_momentum_full", dtype, terms, self.n_sites, self.momentum)  # n = D_m
 
     inf_norm = PauliMomentumOperator.inf_norm
 
 
-class PauliSymmetricOperator(_Operator):
+class PauliSymmetricOperator(_PauliFamily):
     """One block of a ring under momentum, reflection and spin inversion (ll_op_create_pauli_symmetric_*): the operator B^H H B
     with B = generators.symmetric_embedding(n_sites, momentum, parity, inversion, n_down) and H the PauliOperator (n_down None)
     or the PauliSectorOperator (n_down) of the same terms; the basis is generators.symmetric_basis, ascending.  parity and
@@ -504,22 +479,11 @@ class PauliSymmetricOperator(_Operator):
     at fault — and an empty block is refused.  The image is O(n): no table over the states (device_bytes <= 8 n + 192 KiB)."""
 
     def __init__(self, ctx, n_sites, momentum, terms, dtype=np.float64, parity=0, inversion=0, n_down=None):
-        terms = list(terms)
-        arr = (capi.PauliTerm * max(len(terms), 1))()
-        for k, (xm, zm, c) in enumerate(terms):
-            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
-        self.ctx, self.dtype = ctx, np.dtype(dtype)
         self.n_sites, self.momentum = int(n_sites), int(momentum)
         self.parity, self.inversion = int(parity), int(inversion)
         self.n_down = None if n_down is None else int(n_down)
-        self.n = self.n_local = 0
-        self.row_begin, self.nnz = 0, len(terms)
-        h = C.c_void_p()
-        fn = getattr(lib(), "ll_op_create_pauli_symmetric_" + _suffix(self.dtype))
-        check(fn(ctx.handle, self.n_sites, -1 if self.n_down is None else self.n_down, self.momentum, self.parity, self.inversion,
-                 len(terms), arr, C.byref(h)))
-        self.handle = h
-        self.n = self.n_local = self.info()[0]   # D: counted at creation
+        self._create(ctx, "_symmetric", dtype, terms, self.n_sites, -1 if self.n_down is None else self.n_down, self.momentum,
+                     self.parity, self.inversion)  # n = D
 
     inf_norm = PauliMomentumOperator.inf_norm
 

@@ -16,23 +16,16 @@ import pytest
 import contract_cases as K
 import exact_ref as E
 import lambda_lanczos_amd as L
-import oracle_lib
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
+from pauli_cases import TYPES, TYPE_IDS, WIDE, _checker, _cplx, _run_lanczos, _set_block_bits
 from test_gpu_accuracy_contracts import OFFSETS, _check_spmv, _guarded, _unguard
 from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TYPE_IDS = ["d", "z", "s", "c"]
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
 TILE_BITS = [None, 6, 9]          # default (one tile holds every vector below), 64 and 512 states per tile
 SITES = [1, 2, 3, 5, 6, 9, 11, 14]  # 2^1 .. 2^14 states: shorter than a tile, one tile, many tiles with remote groups
-
-
-def _cplx(dtype):
-    return np.dtype(dtype).kind == "c"
 
 
 def j1j2_terms(n_sites, j1=1.0, j2=0.4):
@@ -81,10 +74,6 @@ def _reference_rows(model, n_sites, tid):
     return _REF[key]
 
 
-def _set_tile_bits(ctx, bits):
-    ctx.set_tuning("pauli_tile_bits", None if bits is None else str(bits))   # None removes the setting
-
-
 # ------------------------------------------------------------------ 2. apply against the exact reference
 @pytest.mark.parametrize("dtype", TYPES, ids=TYPE_IDS)
 @pytest.mark.parametrize("model", ["heisenberg", "tfim", "j1j2", "random"])
@@ -98,7 +87,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, dtype):
             op = L.PauliOperator(ctx, n_sites, terms, dtype)
             assert op.info() == (n, n, len(terms))
             for bits in TILE_BITS:
-                _set_tile_bits(ctx, bits)
+                _set_block_bits(ctx, "pauli", bits)
                 for shift in (0, 1):
                     xb, xv = _guarded(ctx, x, shift)
                     yb, yv = _guarded(ctx, np.zeros(n, dtype), shift)
@@ -113,7 +102,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, dtype):
                     yb.free()
             op.close()
     finally:
-        _set_tile_bits(ctx, None)
+        _set_block_bits(ctx, "pauli", None)
     print("ratios error/bound (class, storage, alpha)", model, tid, worst)
 
 
@@ -128,7 +117,7 @@ def test_same_bits_for_every_tile_size_and_alignment(ctx, dtype):
             op = L.PauliOperator(ctx, n_sites, terms, dtype)
             first = None
             for bits in [None, 0, 1, 2, 6, 9, 12]:
-                _set_tile_bits(ctx, bits)
+                _set_block_bits(ctx, "pauli", bits)
                 for shift in (0, 1):
                     for rep in range(2):
                         xb, xv = _guarded(ctx, x, shift)
@@ -142,17 +131,7 @@ def test_same_bits_for_every_tile_size_and_alignment(ctx, dtype):
                         assert np.array_equal(first.view(np.uint8), y.view(np.uint8)), (model, bits, shift, rep)
             op.close()
     finally:
-        _set_tile_bits(ctx, None)
-
-
-def _run_lanczos(op, n, init, find_max, offset, num_eigs=1, max_iteration=None):
-    eng = L.LambdaLanczos(op, n, find_max, num_eigs)
-    eng.eigenvalue_offset = offset
-    eng.init_vector = lambda v, *_: np.copyto(v, init)
-    if max_iteration is not None:
-        eng.max_iteration = max_iteration
-    vals, vecs = eng.run()
-    return eng, vals, vecs
+        _set_block_bits(ctx, "pauli", None)
 
 
 def test_deferred_normalisation_path_against_separate_launches(ctx):
@@ -194,10 +173,6 @@ def test_deferred_normalisation_path_against_separate_launches(ctx):
 
 
 # ------------------------------------------------------------------ 4. whole runs against the real reference
-def _checker():
-    return oracle_lib.reference() if oracle_lib.have_reference() else oracle_lib.oracle()
-
-
 Y_TERMS = [(0b11, 0b01, 0.35), (0b110, 0b100, -0.2), (1 << 13 | 1, 1 << 13, 0.45), (1 << 7, 1 << 7, 0.3)]   # odd numbers of Y
 
 

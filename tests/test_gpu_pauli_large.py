@@ -19,15 +19,12 @@ import exact_ref as E
 import lambda_lanczos_amd as L
 import pauli_large_cases as C
 from lambda_lanczos_amd import generators as G
+from pauli_cases import BITS_KEY, WIDE, _apply, _check_apply, _checker, _class_bound, _run_lanczos
 from test_gpu_accuracy_contracts import OFFSETS, _eps
-from test_gpu_pauli_momentum import _apply, _check_apply, _checker, _class_bound, _run_lanczos
 
 pytestmark = pytest.mark.gpu
 
 TYPES = {"d": np.float64, "z": np.complex128, "s": np.float32, "c": np.complex64}
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
-BITS_KEY = {"sector": "pauli_sector_block_bits", "momentum": "pauli_momentum_block_bits",
-            "momentum_full": "pauli_momentum_full_block_bits", "symmetric": "pauli_symmetric_block_bits"}
 
 
 def _momentum_of(kind, shape):

@@ -19,38 +19,21 @@ import pytest
 import contract_cases as K
 import exact_ref as E
 import lambda_lanczos_amd as L
-import oracle_lib
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
-from test_gpu_accuracy_contracts import OFFSETS, _eps, _guarded, _unguard
+from pauli_cases import (TYPES, TYPE_IDS, WIDE, _apply, _check_apply, _checker, _class_bound, _cplx, _run_lanczos, _runs,
+                         _set_block_bits, _tid, dm_ring)
+from test_gpu_accuracy_contracts import OFFSETS, _eps
 from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TYPE_IDS = ["d", "z", "s", "c"]
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
 BLOCK_BITS = [None, 4, 8, 10]      # default, 16, 256 and 1024 indices per block (1024: four states per lane; D_m = 2704 still takes three blocks)
 # (n_sites, n_down, momentum): short orbits inside the block ((4,2,0), (6,3,0), (6,2,3), (12,6,0), (12,6,6), (16,8,0), (9,3,3): R = 3) and
 # excluded from it ((4,2,1), (4,2,3), (6,3,3) drops R = 2, (12,6,5), (16,8,5), (8,4,3)), blocks of one state ((1,0,0), (2,1,0), (2,1,1),
 # (4,2,1), (4,2,3)), complex phases, real blocks at m = 0 and L / 2; D_m = 810 at L = 16, 2704 at (18,9,9): more than one block at every setting
 SHAPES = [(1, 0, 0), (2, 1, 0), (2, 1, 1), (3, 1, 1), (4, 2, 0), (4, 2, 1), (4, 2, 2), (4, 2, 3), (5, 2, 1), (6, 3, 0), (6, 3, 2),
           (6, 3, 3), (6, 2, 3), (8, 4, 3), (9, 3, 3), (12, 6, 0), (12, 6, 6), (12, 6, 5), (16, 8, 0), (16, 8, 5), (18, 9, 9)]
-
-
-def _cplx(dtype):
-    return np.dtype(dtype).kind == "c"
-
-
-def _tid(dtype):
-    return TYPE_IDS[TYPES.index(dtype)]
-
-
-def dm_ring(n_sites, D):
-    """One Dzyaloshinskii-Moriya bond j -> (j + 1) mod L per site; generators.dm_terms keeps ONE bond at L = 2 (an open chain)."""
-    if n_sites != 2:
-        return G.dm_terms(n_sites, D, periodic=True)
-    return [(3, 2, float(D)), (3, 1, -float(D)), (3, 1, float(D)), (3, 2, -float(D))]
 
 
 def model_terms(model, n_sites):
@@ -61,11 +44,6 @@ def model_terms(model, n_sites):
     if model == "xxz_dm":
         return G.heisenberg_terms(n_sites, 1.0, 0.8, periodic=True) + dm_ring(n_sites, 0.35)
     raise KeyError(model)
-
-
-def _runs(dtype, n_sites, m):
-    """d / s run only where the block is real."""
-    return _cplx(dtype) or (2 * m) % n_sites == 0
 
 
 _REF = {}
@@ -81,41 +59,6 @@ def _reference_rows(model, shape, tid):
         x = K.start_x(csr[0].shape[0] - 1, dtype)
         _REF[key] = (terms, csr, x, E.rows_exact(csr, x))
     return _REF[key]
-
-
-def _set_block_bits(ctx, bits):
-    ctx.set_tuning("pauli_momentum_block_bits", None if bits is None else str(bits))   # None removes the setting
-
-
-def _apply(ctx, op, x, shift, offset, want_dot):
-    n = x.shape[0]
-    xb, xv = _guarded(ctx, x, shift)
-    yb, yv = _guarded(ctx, np.zeros(n, x.dtype), shift)
-    alpha = L.spmv(op, xv, yv, offset=offset, want_dot=want_dot)
-    y = _unguard(yb, n, shift).copy()
-    assert np.array_equal(_unguard(xb, n, shift), x), "the apply changed its input"
-    xb.free()
-    yb.free()
-    return y, alpha
-
-
-def _class_bound(dtype, x, ex, y, offset):
-    """The component-wise class exactly as test_gpu_accuracy_contracts._check_spmv forms `cls`: componentwise_bound plus the offset
-    and narrowing terms.  Holds by derivation: a kernel entry carries at most about 4 double roundings (weight x sqrt factor x phase,
-    complex) and the chain adds nnz / 2 — below the class's 8 (nnz + 2)."""
-    eps = _eps(dtype)
-    xw = x.astype(np.complex128 if _cplx(dtype) else np.float64)
-    cls = E.componentwise_bound(ex, eps)
-    return cls + eps * (np.abs(offset) * (np.abs(xw.real) + np.abs(xw.imag)) + np.abs(y.real) + np.abs(np.imag(y))) + 1e-300, xw
-
-
-def _check_apply(dtype, x, ex, y, alpha, offset, what):
-    cls, xw = _class_bound(dtype, x, ex, y, offset)
-    ok, r_cls = E.within(E.part_errors(y, ex.y + offset * xw), (cls, cls))
-    assert ok, "%s: class bound violated (ratio %.3g)" % (what, r_cls)
-    d, db = E.dot_exact(x, y), E.dot_bound(x, y)   # alpha = Re<x, y> of the RETURNED y, accumulated in double
-    assert abs(alpha - np.real(d)) <= db, (what, alpha, d, db)
-    return r_cls, abs(alpha - np.real(d)) / db
 
 
 # ------------------------------------------------------------------ 1. apply against the exact reference
@@ -141,7 +84,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             assert (op.n, op.n_local, op.n_sites, op.n_down, op.momentum) == (n, n, n_sites, n_down, m)
             assert op.device_bytes() >= 4 * math.comb(n_sites, n_down) + 5 * n    # orbit[], the representatives, their periods
             for bits in BLOCK_BITS:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "momentum", bits)
                 for shift in (0, 1):
                     for offset in OFFSETS:
                         y, alpha = _apply(ctx, op, x, shift, offset, True)
@@ -150,7 +93,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             op.close()
             ran += 1
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "momentum", None)
     assert ran == (len(SHAPES) if _cplx(dtype) else sum(1 for s in SHAPES if (2 * s[2]) % s[0] == 0))
     print("ratios error/bound (class, alpha)", model, tid, worst)
 
@@ -168,7 +111,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             op = L.PauliMomentumOperator(ctx, *shape, terms, dtype)
             first = None
             for bits in [None, 0, 1, 4, 8, 12]:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "momentum", bits)
                 for shift in (0, 1):
                     for rep in range(2):
                         y, _ = _apply(ctx, op, x, shift, -2.5, False)      # _apply asserts that the input is left unchanged
@@ -178,7 +121,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             assert np.any(first != 0)
             op.close()
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "momentum", None)
 
 
 # ------------------------------------------------------------------ 3. consistency with the sector operator on the GPU
@@ -228,16 +171,6 @@ def test_consistent_with_the_sector_operator_through_the_embedding(ctx, dtype, m
     print("momentum apply against B^H (sector apply) B: worst error / bound", model, tid, worst)
 
 
-def _run_lanczos(op, n, init, find_max, offset, num_eigs=1, max_iteration=None):
-    eng = L.LambdaLanczos(op, n, find_max, num_eigs)
-    eng.eigenvalue_offset = offset
-    eng.init_vector = lambda v, *_: np.copyto(v, init)
-    if max_iteration is not None:
-        eng.max_iteration = max_iteration
-    vals, vecs = eng.run()
-    return eng, vals, vecs
-
-
 # ------------------------------------------------------------------ 4. deferred normalisation
 def test_deferred_normalisation_path_against_separate_launches(ctx):
     """fuse_launches = 1 and 2 (the kernel normalises its input on the fly through ScaleIn) against 0 (a launch of its own) on
@@ -276,10 +209,6 @@ def test_deferred_normalisation_path_against_separate_launches(ctx):
 
 
 # ------------------------------------------------------------------ 5. whole runs against the real reference
-def _checker():
-    return oracle_lib.reference() if oracle_lib.have_reference() else oracle_lib.oracle()
-
-
 # d, s at m = 0 and m = L / 2 (real blocks); z, c at m = 5 of the XXZ + DM ring (complex phases, complex H)
 EIGEN_CASES = [("d", "xxz_field", 0), ("d", "xxz_field", 6), ("s", "xxz_field", 0), ("s", "xxz_field", 6), ("z", "xxz_dm", 5),
                ("c", "xxz_dm", 5)]
@@ -431,8 +360,8 @@ def test_refused_on_a_sharded_context(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     name = "/ll_shm_pmom_" + uuid.uuid4().hex[:12]
     env = dict(os.environ, LL_COMM_PLUGIN=SHM_TRANSPORT, OMP_NUM_THREADS="2")
-    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_momentum_worker.py"), str(r), "2", name,
-                               str(tmp_path)], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_refused_worker.py"), str(r), "2", name,
+                               str(tmp_path), "momentum"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
              for r in range(2)]
     outs = [p.communicate(timeout=300)[0] for p in procs]
     for p, o in zip(procs, outs):

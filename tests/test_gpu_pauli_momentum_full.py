@@ -21,15 +21,13 @@ import exact_ref as E
 import lambda_lanczos_amd as L
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
+from pauli_cases import (TYPES, TYPE_IDS, WIDE, _apply, _check_apply, _checker, _class_bound, _cplx, _run_lanczos, _runs,
+                         _set_block_bits, _tid, dm_ring)
 from test_gpu_accuracy_contracts import OFFSETS, _eps
-from test_gpu_pauli_momentum import _apply, _check_apply, _checker, _class_bound, _run_lanczos, dm_ring
 from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TYPE_IDS = ["d", "z", "s", "c"]
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
 BLOCK_BITS = [None, 4, 8, 10]      # default, 16, 256 and 1024 indices per block (1024: four states per lane)
 # (n_sites, momentum).  D_m = 2, 3, 1, 2: one-state and tiny blocks; (4, *): D_m = 6, 3, 4, 3 with R = 1, 2 inside and excluded;
 # (5, 2): prime L, complex phases; (6, *): D_m = 14, 11, 10 with R = 2, 3 in and out; (8, 3), (9, 3): R = 3 inside at L = 9;
@@ -40,14 +38,6 @@ SHAPES = [(1, 0), (2, 0), (2, 1), (3, 1), (4, 0), (4, 1), (4, 2), (4, 3), (5, 2)
 DIMS = {(1, 0): 2, (2, 0): 3, (2, 1): 1, (3, 1): 2, (4, 0): 6, (4, 1): 3, (4, 2): 4, (4, 3): 3, (6, 0): 14, (6, 2): 11, (6, 3): 10,
         (12, 0): 352, (12, 6): 348, (16, 0): 4116, (16, 8): 4114, (18, 9): 14542}
 COMPLEX_MODELS = ("xyz_dm_x",)     # the Dzyaloshinskii-Moriya terms carry one Y each
-
-
-def _cplx(dtype):
-    return np.dtype(dtype).kind == "c"
-
-
-def _tid(dtype):
-    return TYPE_IDS[TYPES.index(dtype)]
 
 
 def model_terms(model, n_sites):
@@ -64,11 +54,6 @@ def model_terms(model, n_sites):
     raise KeyError(model)
 
 
-def _runs(dtype, n_sites, m):
-    """d / s run only where the block is real."""
-    return _cplx(dtype) or (2 * m) % n_sites == 0
-
-
 _REF = {}
 
 
@@ -82,10 +67,6 @@ def _reference_rows(model, shape, tid):
         x = K.start_x(csr[0].shape[0] - 1, dtype)
         _REF[key] = (terms, csr, x, E.rows_exact(csr, x))
     return _REF[key]
-
-
-def _set_block_bits(ctx, bits):
-    ctx.set_tuning("pauli_momentum_full_block_bits", None if bits is None else str(bits))   # None removes the setting
 
 
 # ------------------------------------------------------------------ 1. apply against the exact reference
@@ -113,7 +94,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             if n_sites == 16:
                 assert op.device_bytes() < 4 * 2 ** 16       # a table over the 2^16 states alone would be that large
             for bits in BLOCK_BITS:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "momentum_full", bits)
                 for shift in (0, 1):
                     for offset in OFFSETS:
                         y, alpha = _apply(ctx, op, x, shift, offset, True)
@@ -122,7 +103,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             op.close()
             ran += 1
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "momentum_full", None)
     assert ran == (len(SHAPES) if _cplx(dtype) else sum(1 for s in SHAPES if (2 * s[1]) % s[0] == 0))
     print("ratios error/bound (class, alpha)", model, tid, worst)
 
@@ -141,7 +122,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             x = K.start_x(op.n, dtype)
             first = None
             for bits in [None, 0, 1, 4, 8, 12]:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "momentum_full", bits)
                 for shift in (0, 1):
                     for rep in range(2):
                         y, _ = _apply(ctx, op, x, shift, -2.5, False)      # _apply asserts that the input is left unchanged
@@ -151,7 +132,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             assert np.any(first != 0)
             op.close()
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "momentum_full", None)
 
 
 # ------------------------------------------------------------------ 3. consistency with PauliOperator on the GPU
@@ -261,14 +242,14 @@ def test_deferred_normalisation_path_against_separate_launches(ctx, shape, model
     norm = op.inf_norm()
     runs = {}
     try:
-        _set_block_bits(ctx, 4)
+        _set_block_bits(ctx, "momentum_full", 4)
         for level in ("0", "1", "2"):
             ctx.set_tuning("fuse_launches", level)
             eng, vals, _ = _run_lanczos(op, n, init, False, -norm)
             runs[level] = (eng.last_alpha, eng.last_beta, vals[0], eng.getIterationCounts())
     finally:
         ctx.set_tuning("fuse_launches", None)
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "momentum_full", None)
     op.close()
     base = runs["0"]
     for level in ("1", "2"):
@@ -435,8 +416,8 @@ def test_refused_on_a_sharded_context(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     name = "/ll_shm_pmf_" + uuid.uuid4().hex[:12]
     env = dict(os.environ, LL_COMM_PLUGIN=SHM_TRANSPORT, OMP_NUM_THREADS="2")
-    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_momentum_full_worker.py"), str(r), "2", name,
-                               str(tmp_path)], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_refused_worker.py"), str(r), "2", name,
+                               str(tmp_path), "momentum_full"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
              for r in range(2)]
     outs = [p.communicate(timeout=300)[0] for p in procs]
     for p, o in zip(procs, outs):

@@ -16,23 +16,16 @@ import pytest
 import contract_cases as K
 import exact_ref as E
 import lambda_lanczos_amd as L
-import oracle_lib
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
-from test_gpu_accuracy_contracts import OFFSETS, _check_spmv, _guarded, _unguard
+from pauli_cases import TYPES, TYPE_IDS, WIDE, _apply, _checker, _cplx, _run_lanczos, _set_block_bits
+from test_gpu_accuracy_contracts import OFFSETS, _check_spmv
 from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TYPE_IDS = ["d", "z", "s", "c"]
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
 BLOCK_BITS = [None, 4, 8]          # default (one block holds every sector below but the largest), 16 and 256 indices per block
 SECTORS = [(1, 0), (1, 1), (2, 1), (4, 2), (5, 0), (5, 5), (6, 3), (9, 4), (12, 6), (14, 7), (16, 3)]   # D = 1 .. 3432
-
-
-def _cplx(dtype):
-    return np.dtype(dtype).kind == "c"
 
 
 def j1j2_terms(n_sites, j1=1.0, j2=0.4, delta=0.7):
@@ -69,22 +62,6 @@ def _reference_rows(model, n_sites, n_down, tid):
     return _REF[key]
 
 
-def _set_block_bits(ctx, bits):
-    ctx.set_tuning("pauli_sector_block_bits", None if bits is None else str(bits))   # None removes the setting
-
-
-def _apply(ctx, op, x, shift, offset, want_dot):
-    n = x.shape[0]
-    xb, xv = _guarded(ctx, x, shift)
-    yb, yv = _guarded(ctx, np.zeros(n, x.dtype), shift)
-    alpha = L.spmv(op, xv, yv, offset=offset, want_dot=want_dot)
-    y = _unguard(yb, n, shift).copy()
-    assert np.array_equal(_unguard(xb, n, shift), x), "the apply changed its input"
-    xb.free()
-    yb.free()
-    return y, alpha
-
-
 # ------------------------------------------------------------------ 1. apply against the exact reference
 # (the Dzyaloshinskii-Moriya terms carry one Y each: complex types only)
 APPLY_CASES = [(m, t) for m in ("heisenberg", "j1j2_field", "dm") for t in TYPE_IDS if m != "dm" or t in ("z", "c")]
@@ -101,7 +78,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             op = L.PauliSectorOperator(ctx, n_sites, n_down, terms, dtype)
             assert op.info() == (n, n, len(terms)) and (op.n, op.n_local, op.n_sites, op.n_down) == (n, n, n_sites, n_down)
             for bits in BLOCK_BITS:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "sector", bits)
                 for shift in (0, 1):
                     for offset in OFFSETS:
                         y, alpha = _apply(ctx, op, x, shift, offset, True)
@@ -110,7 +87,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
                         worst = tuple(max(a, b) for a, b in zip(worst, r))
             op.close()
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "sector", None)
     print("ratios error/bound (class, storage, alpha)", model, tid, worst)
 
 
@@ -124,7 +101,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             op = L.PauliSectorOperator(ctx, n_sites, n_down, terms, dtype)
             first = None
             for bits in [None, 0, 1, 4, 8, 12]:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "sector", bits)
                 for shift in (0, 1):
                     for rep in range(2):
                         y, _ = _apply(ctx, op, x, shift, -2.5, False)
@@ -133,7 +110,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
                         assert np.array_equal(first.view(np.uint8), y.view(np.uint8)), (model, bits, shift, rep)
             op.close()
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "sector", None)
 
 
 # ------------------------------------------------------------------ 3. the same bits as the full-space operator
@@ -158,16 +135,6 @@ def test_same_bits_as_the_full_space_operator_on_an_embedded_vector(ctx, dtype):
         assert np.any(y != 0)
         sec.close()
         full.close()
-
-
-def _run_lanczos(op, n, init, find_max, offset, num_eigs=1, max_iteration=None):
-    eng = L.LambdaLanczos(op, n, find_max, num_eigs)
-    eng.eigenvalue_offset = offset
-    eng.init_vector = lambda v, *_: np.copyto(v, init)
-    if max_iteration is not None:
-        eng.max_iteration = max_iteration
-    vals, vecs = eng.run()
-    return eng, vals, vecs
 
 
 # ------------------------------------------------------------------ 4. deferred normalisation
@@ -208,10 +175,6 @@ def test_deferred_normalisation_path_against_separate_launches(ctx):
 
 
 # ------------------------------------------------------------------ 5. whole runs against the real reference
-def _checker():
-    return oracle_lib.reference() if oracle_lib.have_reference() else oracle_lib.oracle()
-
-
 def _spmv_csr(csr, x):
     rp, ci, va = csr
     return np.add.reduceat(va * x[ci], rp[:-1]) if rp[-1] else np.zeros_like(x)
@@ -370,8 +333,8 @@ def test_refused_on_a_sharded_context(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     name = "/ll_shm_psec_" + uuid.uuid4().hex[:12]
     env = dict(os.environ, LL_COMM_PLUGIN=SHM_TRANSPORT, OMP_NUM_THREADS="2")
-    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_sector_worker.py"), str(r), "2", name,
-                               str(tmp_path)], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_refused_worker.py"), str(r), "2", name,
+                               str(tmp_path), "sector"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
              for r in range(2)]
     outs = [p.communicate(timeout=300)[0] for p in procs]
     for p, o in zip(procs, outs):

@@ -21,15 +21,13 @@ import exact_ref as E
 import lambda_lanczos_amd as L
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
+from pauli_cases import (TYPES, TYPE_IDS, WIDE, _apply, _check_apply, _checker, _class_bound, _cplx, _run_lanczos,
+                         _set_block_bits, _tid, dm_ring)
 from test_gpu_accuracy_contracts import OFFSETS, _eps
-from test_gpu_pauli_momentum import _apply, _check_apply, _checker, _class_bound, _run_lanczos, dm_ring
 from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TYPE_IDS = ["d", "z", "s", "c"]
-WIDE = {"d": np.float64, "z": np.complex128, "s": np.float64, "c": np.complex128}
 BLOCK_BITS = [None, 4, 8, 10]      # default, 16, 256 and 1024 indices per block (1024: four states per lane)
 SIGNS = [(1, 1), (1, -1), (-1, 1), (-1, -1)]
 # (n_sites, m, parity, inversion) -> D, pinned: the cases of the issue at 12 sites, and at 16 sites from the host generator, tied
@@ -37,14 +35,6 @@ SIGNS = [(1, 1), (1, -1), (-1, 1), (-1, -1)]
 DIMS = {(12, 0, 1, 1): 122, (12, 6, -1, -1): 102, (12, 0, 1, 0): 224, (16, 0, 1, 1): 1162, (16, 8, -1, -1): 1088}
 DIMS_HALF = {(12, 0, 1, 1): 35, (12, 6, -1, -1): 27, (12, 0, 1, 0): 50}        # with n_down = 6
 COMPLEX_MODELS = ("xyz_dm_x",)     # the Dzyaloshinskii-Moriya terms carry one Y each
-
-
-def _cplx(dtype):
-    return np.dtype(dtype).kind == "c"
-
-
-def _tid(dtype):
-    return TYPE_IDS[TYPES.index(dtype)]
 
 
 def model_terms(model, n_sites):
@@ -114,10 +104,6 @@ def _reference_rows(model, shape, tid):
     return _REF[key]
 
 
-def _set_block_bits(ctx, bits):
-    ctx.set_tuning("pauli_symmetric_block_bits", None if bits is None else str(bits))   # None removes the setting
-
-
 def _op(ctx, shape, terms, dtype, n_down=None):
     n_sites, m, p, z = shape
     return L.PauliSymmetricOperator(ctx, n_sites, m, terms, dtype, parity=p, inversion=z, n_down=n_down)
@@ -160,7 +146,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             assert (op.n, op.n_local, op.n_sites, op.momentum, op.parity, op.inversion, op.n_down) == (n, n, n_sites, m, p, z, nd)
             assert op.device_bytes() <= 8 * n + 192 * 1024   # reps, orbit lengths, the bucket table, the small tables: O(D)
             for bits in BLOCK_BITS:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "symmetric", bits)
                 for shift in (0, 1):
                     for offset in OFFSETS:
                         y, alpha = _apply(ctx, op, x, shift, offset, True)
@@ -169,7 +155,7 @@ def test_apply_meets_the_componentwise_contract(ctx, model, tid):
             op.close()
             ran += 1
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "symmetric", None)
     assert ran + empty == len(_shapes(model, dtype)) and ran >= 9
     if model not in COMPLEX_MODELS and model != "heisenberg_sector":
         assert empty >= 3                                 # (4, 0, -1, *) at least
@@ -190,7 +176,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             x = K.start_x(op.n, dtype)
             first = None
             for bits in [None, 0, 1, 4, 8, 12]:
-                _set_block_bits(ctx, bits)
+                _set_block_bits(ctx, "symmetric", bits)
                 for shift in (0, 1):
                     for rep in range(2):
                         y, _ = _apply(ctx, op, x, shift, -2.5, False)      # _apply asserts that the input is left unchanged
@@ -200,7 +186,7 @@ def test_same_bits_for_every_block_size_and_alignment(ctx, dtype):
             assert np.any(first != 0)
             op.close()
     finally:
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "symmetric", None)
 
 
 # ------------------------------------------------------------------ 3. the same bits as the full-space momentum operator
@@ -290,14 +276,14 @@ def test_deferred_normalisation_path_against_separate_launches(ctx, shape, model
     norm = op.inf_norm()
     runs = {}
     try:
-        _set_block_bits(ctx, 4)
+        _set_block_bits(ctx, "symmetric", 4)
         for level in ("0", "1", "2"):
             ctx.set_tuning("fuse_launches", level)
             eng, vals, _ = _run_lanczos(op, n, init, False, -norm)
             runs[level] = (eng.last_alpha, eng.last_beta, vals[0], eng.getIterationCounts())
     finally:
         ctx.set_tuning("fuse_launches", None)
-        _set_block_bits(ctx, None)
+        _set_block_bits(ctx, "symmetric", None)
     op.close()
     base = runs["0"]
     for level in ("1", "2"):
@@ -492,8 +478,8 @@ def test_refused_on_a_sharded_context(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     name = "/ll_shm_psy_" + uuid.uuid4().hex[:12]
     env = dict(os.environ, LL_COMM_PLUGIN=SHM_TRANSPORT, OMP_NUM_THREADS="2")
-    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_symmetric_worker.py"), str(r), "2", name,
-                               str(tmp_path)], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    procs = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "shm_pauli_refused_worker.py"), str(r), "2", name,
+                               str(tmp_path), "symmetric"], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
              for r in range(2)]
     outs = [p.communicate(timeout=300)[0] for p in procs]
     for p, o in zip(procs, outs):
