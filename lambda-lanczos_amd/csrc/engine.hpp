@@ -1,10 +1,13 @@
-// Host drivers of the device-resident Lanczos loop (templated on the scalar type; instantiated for double and
-// complex<double> in engine.cpp).  See DESIGN.md for the data flow.
+// Host drivers of the device-resident Lanczos loop (templated on the scalar type; Engine, Basis and RunList are instantiated
+// in engine.cpp, the whole-loop drivers in lanczos_run.cpp and expo_run.cpp).  See DESIGN.md for the data flow.
 #pragma once
 
+#include <chrono>
 #include <complex>
 #include <functional>
 #include <map>
+#include <system_error>
+#include <thread>
 
 #include "ll_internal.hpp"
 
@@ -17,6 +20,57 @@ namespace ll {
 //   [32]      spare scalar (dot results)
 //   [63]      constant 0
 constexpr int kScalAlpha = 0, kScalNorms = 8, kScalScratch = 24, kScalSpare = 32, kScalZero = 63, kScalCount = 64;
+
+// ---------------------------------------------------------------- host helpers shared by Engine and the whole-loop drivers
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// Whole-loop entry points accept host OR device memory for their n-sized inputs and outputs (start vector, Ritz
+// vectors, Exponentiator input/output): a device pointer keeps the vector in HBM (no PCIe crossing, no staging).
+inline bool is_device_ptr(const void* p) {
+  if (p == nullptr) return false;
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // plain (unregistered) host memory
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice;
+}
+// n-sized copies between two HOST buffers at the reference's std::vector boundary (pinned staging buffer -> the caller's vector):
+// one thread moves 8-10 GB/s, which made this copy the longest single item of a run's epilogue (80 MB: 9 ms); four threads
+// share it from 8 MiB up.
+inline void host_copy(void* dst, const void* src, size_t bytes) {
+  constexpr size_t kParallelFrom = (size_t)8 << 20;
+  constexpr int kThreads = 4;
+  if (bytes < kParallelFrom) {
+    std::memcpy(dst, src, bytes);
+    return;
+  }
+  const size_t piece = ((bytes / kThreads) + 4095) & ~(size_t)4095;
+  std::thread th[kThreads - 1];
+  int started = 0;
+  for (int t = 1; t < kThreads; ++t) {
+    const size_t off = std::min(bytes, (size_t)t * piece), len = std::min(bytes, (size_t)(t + 1) * piece) - off;
+    try {
+      th[t - 1] = std::thread([=] {
+        if (len) std::memcpy((char*)dst + off, (const char*)src + off, len);
+      });
+      ++started;
+    } catch (const std::system_error&) {
+      // no thread to be had (thread limit, cgroup pids): this and the remaining ranges are copied here — never std::terminate
+      // out of a joinable thread's destructor, never an error for what is only a slower copy
+      const size_t rest = std::min(bytes, (size_t)t * piece);
+      std::memcpy((char*)dst + rest, (const char*)src + rest, bytes - rest);
+      break;
+    }
+  }
+  std::memcpy(dst, src, std::min(bytes, piece));
+  for (int t = 0; t < started; ++t) th[t].join();
+}
+// LDS budget of mdot / lagged_kernel: 4 waves x ncols doubles in the 160 KB of a CU (one workgroup per CU then, which is
+// how the streaming kernels run on long vectors anyway)  =>  reals * nb <= 5000
+template <typename T> inline int max_vecs_per_launch() { return kLaggedMaxCols / scalar_traits<T>::reals; }
 
 // ---------------------------------------------------------------- chunked device slab for the Krylov basis
 // The reference keeps one heap std::vector per Lanczos vector (LL:221,250; reserve(200) LL:181).  Here the basis
@@ -52,6 +106,13 @@ template <typename T> struct RunList {
   // launch groups of at most kMaxSegs runs and max_vecs vectors each (runs are split when needed)
   std::vector<BasisSegs<T>> groups(int max_vecs) const;
 };
+
+template <typename T> inline BasisSegs<T> no_segs(int64_t ld) {  // no basis vectors (a launch without Gram-Schmidt columns)
+  BasisSegs<T> none;
+  none.nseg = 0;
+  none.ld = ld;
+  return none;
+}
 
 // What an operator image takes as its input x besides a normalised vector: the one statement that Engine::apply and the
 // loops' choice of form (can_scale_input, can_defer_scale) read.  Every device operator can take its input unnormalised
@@ -96,7 +157,7 @@ template <typename T> struct Engine {
   // sc (nullable): deferred normalisation — x_local is the unnormalised w_k (ScaleIn, ll_internal.hpp); only where
   // can_defer_scale() holds.
   // xnorm2 (nullable device scalar; device operators): x_local is an unnormalised vector w with
-  // ||w||^2 = *xnorm2 and the operator works with w / ||w|| (lagged Gram-Schmidt, LoopState).
+  // ||w||^2 = *xnorm2 and the operator works with w / ||w|| (lagged Gram-Schmidt, LoopState in lanczos_loop.hpp).
   void apply(const T* x_local, T* y, double offset, double* d_alpha, bool x_padded = false, DeferredAlpha* defer = nullptr,
              const ScaleIn<T>* sc = nullptr, const double* xnorm2 = nullptr);
   bool can_scale_input() const { return input_caps().norm2 || input_caps().scale_in; }  // xnorm2 is accepted
@@ -189,10 +250,11 @@ template <typename T> struct IterationSpec {
   const T* orth_host;
 };
 
-// Bytes of one Krylov-basis slab of a default run on an operator of this shape (engine.cpp)
+// Vectors per basis slab of a run, and the bytes of one slab of a default run on an operator of this shape (engine.cpp)
+int64_t pick_chunk_vecs(int64_t initial_vector_size, int64_t max_iteration, int64_t vec_bytes, int64_t cap_bytes);
 int64_t default_slab_bytes(int64_t n, int64_t n_local, int64_t n_shard, int elem_bytes, const Tuning& tune);
 
-// Whole-loop drivers
+// Whole-loop drivers (lanczos_run.cpp; expo_run.cpp)
 template <typename T>
 void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P, double* eigvals, T* eigvecs,
                  int64_t* n_found, int64_t* iter_counts, int64_t iter_cap, double* alpha_out, double* beta_out,

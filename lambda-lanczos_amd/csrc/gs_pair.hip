@@ -120,7 +120,7 @@ struct PairScalars {
   int e2_nparts;
 };
 // Columns: L locked eigenvectors first (A z_i = lambda_i z_i + r_i: their image is lambda_i times the coefficient, the residual
-// term is what LoopState::begin_pass gates), then the P Lanczos vectors u_0 .. u_{P-1}; K = L + P.
+// term is what LoopState::begin_pass in lanczos_loop.hpp gates), then the P Lanczos vectors u_0 .. u_{P-1}; K = L + P.
 __global__ __launch_bounds__(256) void pair_predict_kernel(int P, int L, int reals, const double* __restrict__ g1,
                                                            const double* __restrict__ g2, PairScalars sc,
                                                            const double* __restrict__ hist_alpha,

@@ -248,7 +248,7 @@ LL_FOR_EACH_SCALAR(LL_INST_MDOT_MAXPY)
 // alpha / beta agree with the two-sweep form to ~1e-14 relative.  t = Tbar c comes from the fold kernel below
 // (lagged_fold_kernel); d_j = t_j - alpha c_j is formed here because alpha is only known now.
 // The DGKS case (|g|^2 > ||r||^2 / 2: cancellation, the derived norm is inaccurate) is detected by the host from the
-// published norms like before and repaired with the two-sweep kernels on the then complete u_{k-1} (engine.cpp,
+// published norms like before and repaired with the two-sweep kernels on the then complete u_{k-1} (lanczos_loop.hpp,
 // LoopState).
 template <typename T, int NV, int PC>
 __device__ __forceinline__ void lagged_trip(const T* __restrict__ u0, int64_t ld, int64_t i0, int64_t n,

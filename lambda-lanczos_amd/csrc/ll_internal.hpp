@@ -252,7 +252,7 @@ struct Tuning {
   bool comm_overlap = true;        // LL_COMM_OVERLAP=0: exchange and compute on one stream (serial A/B reference)
   // --- the loops
   bool tridiag_thread = true;      // LL_TRIDIAG_THREAD=0: host Ritz step inline instead of on the helper thread
-  int tridiag_lag = 3;             // LL_TRIDIAG_LAG: fixed verdict lag of sharded runs (engine.cpp)
+  int tridiag_lag = 3;             // LL_TRIDIAG_LAG: fixed verdict lag of sharded runs (lanczos_loop.hpp)
   double dgks_threshold = 0.5;     // LL_DGKS_THRESHOLD: second Gram-Schmidt pass when ||w'||^2 < thr * ||w||^2
   bool sharded_norm_measured = false;  // LL_SHARDED_NORM=measured: all-reduce the post-pass norm instead of deriving it
   int64_t slab_bytes = (int64_t)4 << 30;       // LL_SLAB_BYTES: cap of one Krylov-basis slab
@@ -851,7 +851,7 @@ int launch_lagged(int64_t n, T* w, const BasisSegs<T>& segs, const Lagged<T>& lg
 // The pair form (two iterations per sweep; gs_pair.hip; tools/pair_gs_model.py is the executable specification).
 // Streaming geometry only; 2 * reals * K + 5 * reals + 1 <= kLaggedMaxCols columns per workgroup (K stored columns).
 constexpr double kPairGate = 1e-8;  // largest relative coefficient the pair form accepts in double precision (second-order terms
-                                    // stay below 1e-16; float storage: 2e-4, engine.cpp)
+                                    // stay below 1e-16; float storage: 2e-4, lanczos_loop.hpp)
 template <typename T>
 int launch_pair_three_term(int64_t n, T* y, const T* x, const T* p, double* e, const double* e_partials, int e_nparts,
                            const double* cx2, const double* cp2, double* partials, bool colmajor,

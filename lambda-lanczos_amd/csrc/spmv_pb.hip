@@ -1542,7 +1542,7 @@ int launch_spmv_tiled(const ll_operator& op, const T* x, T* y, double offset, do
   return op.tl.nrb;
 }
 
-// Sharded contexts (engine.cpp apply_operator): the maximum of |x| over the rank's own shard, one double at
+// Sharded contexts (engine.cpp, Engine::gather_x): the maximum of |x| over the rank's own shard, one double at
 // op.tl.xmax[tl_xmax_local_slot()] — the ranks' maxima are then all-gathered into op.tl.xmax[0, nranks), the table the kernel
 // folds (a maximum does not depend on how the vector is cut, so every partition scales its fixed-point grid exactly like one GPU).
 template <typename T> void launch_tl_xmax_local(const ll_operator& op, const T* x_own, hipStream_t s) {

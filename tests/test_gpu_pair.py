@@ -1,5 +1,5 @@
 """The pair form of the Gram-Schmidt step — TWO Lanczos iterations per sweep over the basis (gs_pair.hip, gs_small.hip,
-LoopState::enqueue_pair; tools/pair_gs_model.py is the executable specification) — against the reference's sequential
+LoopState::enqueue_pair in lanczos_loop.hpp; tools/pair_gs_model.py is the executable specification) — against the reference's sequential
 modified Gram-Schmidt (LL:260 -> LA:132-144) through the oracle, and against the two forms it replaces on the same operator:
     LL_FUSE_LAUNCHES=1   two sweeps per iteration (multi-dot, multi-axpy)
     LL_PAIR_GS=0         one sweep per iteration (lagged, compensated)

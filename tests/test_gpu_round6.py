@@ -188,7 +188,7 @@ def test_run_iteration_with_eigenvectors_in_orthogonalize_to_takes_the_one_sweep
 def test_pending_pair_enters_the_ritz_gemv_through_its_raw_vectors(ctx, oracle, name, window, num_eigs):
     """At the end of a pass the last pair's vectors u_P (and u_{P+1}) exist only as raw vectors with their measured coefficients.
     They are not completed by sweeps of their own any more: the late update is folded into the coefficients of the Ritz GEMV
-    (LoopState::PairTail; compute_eigenvectors, LL:33-62).  Windows that end on the first and on the second vector of a pair, runs
+    (LoopState::take_tail; compute_eigenvectors, LL:33-62).  Windows that end on the first and on the second vector of a pair, runs
     to convergence, restart passes behind locked eigenvectors, real and complex: the eigenvectors equal those of the flush path
     (setting ritz_tail = 0) to rounding and the oracle's to the usual tolerance; eigenvalues and traces are the same bits."""
     if name == "randsym":

@@ -1,5 +1,5 @@
 """Executable specification (numpy) of the TWO-ITERATIONS-PER-SWEEP Gram-Schmidt form of the Lanczos loop, written kernel by
-kernel the way csrc/gs_pair.hip and csrc/engine.cpp implement it (pair_* kernels, LoopState::enqueue_pair).  Successor of
+kernel the way csrc/gs_pair.hip and csrc/lanczos_loop.hpp implement it (pair_* kernels, LoopState::enqueue_pair).  Successor of
 tools/lagged2_pipeline_model.py (round 4): same algebra, restructured into the launches of the device code, real AND complex
 Hermitian operators, entry from the one-sweep ("lagged") state, exit (flush) to a complete basis, and a self-check of every
 folded quantity against the directly computed truth.
