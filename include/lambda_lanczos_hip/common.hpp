@@ -89,6 +89,10 @@ template <typename T> struct abi;
       return ll_lanczos_run_iteration_##SFX(c, op, p, nroot, n_orth, orth, vals, vecs, found, itern, nullptr, nullptr,   \
                                             st);                                                                         \
     }                                                                                                                    \
+    static int two_pass(ll_context* c, ll_operator* op, const ll_lanczos_params* p, double* val, T* vec, int64_t* itern, \
+                        double* residual, ll_run_stats* st) {                                                            \
+      return ll_lanczos_two_pass_##SFX(c, op, p, val, vec, itern, residual, nullptr, nullptr, st);                       \
+    }                                                                                                                    \
   };
 LL_FACADE_ABI(double, d, ll_host_mv_mul_d)
 LL_FACADE_ABI(float, s, ll_host_mv_mul_s)

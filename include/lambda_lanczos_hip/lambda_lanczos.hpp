@@ -165,6 +165,14 @@ template <typename T> class LambdaLanczos {
     eigenvector = std::move(eigenvectors[0]);
   }
 
+  // Addition: the extreme eigenpair WITHOUT a stored Krylov basis (two-pass Lanczos, ll_lanczos_two_pass_*): three or four
+  // n-sized device vectors whatever the iteration count, every operator application twice, no re-orthogonalisation — one pair
+  // only, num_eigs is not consulted.  The overload without the vector runs the first pass alone.  Returns the iteration count;
+  // getLastResidual() is ||A x - lambda x|| of the returned pair (NaN after the overload without the vector).
+  size_t run_two_pass(real_t<T>& eigenvalue, std::vector<T>& eigenvector) { return two_pass(eigenvalue, &eigenvector); }
+  size_t run_two_pass(real_t<T>& eigenvalue) { return two_pass(eigenvalue, nullptr); }
+  double getLastResidual() const { return last_residual_; }
+
   // Latest iteration counts, one entry per restart pass (lambda_lanczos.hpp:412-414)
   const std::vector<size_t>& getIterationCounts() const { return iter_counts_; }
   const ll_run_stats& getLastStats() const { return last_stats_; }
@@ -183,6 +191,30 @@ template <typename T> class LambdaLanczos {
     p.init_vector_dev = init_vector_device;
     return p;
   }
+  size_t two_pass(real_t<T>& eigenvalue, std::vector<T>* eigenvector) {
+    const size_t n_local = csr_ ? (size_t)csr_->local_rows() : matrix_size;
+    ll_lanczos_params p = make_params(1);
+    detail::InitHook<T> hook{init_vector};
+    if (init_vector) {
+      p.init_vector = &detail::InitHook<T>::call;
+      p.init_user = &hook;
+    }
+    detail::HostOp<T> host{mv_mul, {}, {}};
+    ll_operator* op = csr_ ? csr_->get() : detail::make_host_operator<T>(ctx_.get(), (int64_t)matrix_size, &host);
+    std::vector<T> vec(eigenvector ? n_local : 0);
+    double val = 0.0, residual = 0.0;
+    int64_t itern = 0;
+    ll_run_stats st;
+    const int rc = abi<T>::two_pass(ctx_.get(), op, &p, &val, eigenvector ? vec.data() : nullptr, &itern, &residual, &st);
+    if (!csr_) ll_op_destroy(op);
+    check(rc);
+    eigenvalue = (real_t<T>)val;
+    if (eigenvector) *eigenvector = std::move(vec);
+    iter_counts_.assign(1, (size_t)itern);
+    last_stats_ = st;
+    last_residual_ = residual;
+    return (size_t)itern;
+  }
   int call_run(ll_operator* op, const ll_lanczos_params* p, double* vals, T* vecs, int64_t* found, int64_t* counts,
                int64_t cap, ll_run_stats* st) {
     return abi<T>::run(ctx_.get(), op, p, vals, vecs, found, counts, cap, st);
@@ -190,6 +222,7 @@ template <typename T> class LambdaLanczos {
   Context ctx_;
   std::shared_ptr<DeviceOperator<T>> csr_;
   std::vector<size_t> iter_counts_;
+  double last_residual_ = 0.0;
   mutable ll_run_stats last_stats_{};  // run_iteration is const like the reference's (lambda_lanczos.hpp:216-220)
 };
 

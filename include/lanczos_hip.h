@@ -623,6 +623,12 @@ int ll_three_term_d(ll_context* ctx, int64_t n_local, double* w_dev, const doubl
                     const double* u_cur_dev, double beta, double alpha);
 int ll_three_term_z(ll_context* ctx, int64_t n_local, void* w_dev, const void* u_prev_dev, const void* u_cur_dev,
                     double beta, double alpha);
+/* One replayed step of the two-pass recurrence (ll_lanczos_two_pass_*), for tests and for callers who write their own loops:
+ * y = y - a*x - b*p, then psi = psi + g*y, in one sweep; p_dev may be NULL (first step: y = y - a*x).  a, b, g are real. */
+int ll_recur_accum_d(ll_context* ctx, int64_t n_local, double* y_dev, const double* x_dev, const double* p_dev, double a,
+                     double b, double g, double* psi_dev);
+int ll_recur_accum_z(ll_context* ctx, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev, double a, double b,
+                     double g, void* psi_dev);
 /* a5+a6+a7: orthogonalise w against nb orthonormal vectors stored row-major with leading dimension ld
  * (vector j at basis_dev + j*ld elements) and return ||w|| afterwards (LA:132-144 at LL:259-262, EX:121,145).
  * mode: LL_ORTH_CGS_DGKS (default, block classical Gram-Schmidt + a second pass when the norm drops below
@@ -722,7 +728,11 @@ typedef struct ll_run_stats {
                                   * iterations per sweep; taken from the reserved tail: same struct size) */
   int64_t pair_gate_trips;       /* times a pass left the two-iterations-per-sweep form because a coefficient of a raw vector
                                   * exceeded its gate (exhausted Krylov space / breakdown): 0 in ordinary runs */
-  int64_t reserved[6];           /* zero; later statistics are taken from here, so the struct size stays what it is */
+  int64_t workspace_vectors;     /* ll_lanczos_two_pass_*: n-sized device vectors the call allocated (3 or 4, whatever the iteration
+                                  * count; taken from the reserved tail like the two above) */
+  int64_t replay_mismatches;     /* ll_lanczos_two_pass_*: replayed iterations whose alpha differed, as bits, from the recorded
+                                  * one: 0 unless the operator is not reproducible from call to call */
+  int64_t reserved[4];           /* zero; later statistics are taken from here, so the struct size stays what it is */
 } ll_run_stats;
 int ll_ctx_set_profiling(ll_context* ctx, int enabled);
 
@@ -759,6 +769,24 @@ int ll_lanczos_run_iteration_z(ll_context* ctx, ll_operator* op, const ll_lanczo
                                int64_t n_orth, const void* orth_host, double* eigvals_host, void* eigvecs_host,
                                int64_t* n_found, int64_t* itern_out, double* alpha_out, double* beta_out,
                                ll_run_stats* stats);
+
+/* The extreme eigenpair WITHOUT a stored Krylov basis (two-pass Lanczos): pass 1 runs the plain three-term recurrence with the
+ * stop and breakdown tests of ll_lanczos_run_* and records its coefficients; pass 2 replays it and accumulates the Ritz vector.
+ * Device memory: 3 n-sized vectors (no eigenvector wanted, or eigvec in device memory: the Ritz vector is accumulated there) or 4,
+ * whatever the iteration count, against one vector per iteration for ll_lanczos_run_*; every operator application runs twice.
+ * There is no re-orthogonalisation, so only the EXTREME pair (lowest, or highest with find_maximum) is trustworthy:
+ * p->num_eigs must be 1 (LL_ERR_INVALID otherwise); orth_mode, num_eigs_per_iteration and initial_vector_size are ignored.
+ * Single rank only: a context with a communicator is refused with LL_ERR_INVALID.
+ *   eigval_out     : the eigenvalue (eigenvalue_offset removed)
+ *   eigvec         : n_local values of T in HOST or DEVICE memory; NULL: no eigenvector, no second pass
+ *   itern_out      : Lanczos iterations of pass 1 (nullable)
+ *   residual_out   : ||(A + offset) psi - theta psi|| from one more operator application (nullable; NaN without eigvec)
+ *   alpha_out/beta_out : the tridiagonal (capacity max_iteration each); nullable
+ * p->init_vector is called once per call; p->init_vector_dev is read twice and never modified. */
+int ll_lanczos_two_pass_d(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval_out, double* eigvec,
+                          int64_t* itern_out, double* residual_out, double* alpha_out, double* beta_out, ll_run_stats* stats);
+int ll_lanczos_two_pass_z(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval_out, void* eigvec,
+                          int64_t* itern_out, double* residual_out, double* alpha_out, double* beta_out, ll_run_stats* stats);
 
 typedef struct ll_expo_params {
   /* the reference's public fields (EX:41-71) */
@@ -829,6 +857,10 @@ int ll_three_term_c(ll_context* ctx, int64_t n_local, void* w_dev, const void* u
                     double beta, double alpha);
 int ll_three_term_s(ll_context* ctx, int64_t n_local, float* w_dev, const float* u_prev_dev, const float* u_cur_dev,
                     double beta, double alpha);
+int ll_recur_accum_c(ll_context* ctx, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev, double a, double b,
+                     double g, void* psi_dev);
+int ll_recur_accum_s(ll_context* ctx, int64_t n_local, float* y_dev, const float* x_dev, const float* p_dev, double a, double b,
+                     double g, float* psi_dev);
 int ll_orth_block_c(ll_context* ctx, int64_t n_local, int64_t nb, const void* basis_dev, int64_t ld, void* w_dev,
                     int mode, double* norm_host, double* h_host);
 int ll_orth_block_s(ll_context* ctx, int64_t n_local, int64_t nb, const float* basis_dev, int64_t ld, float* w_dev,
@@ -851,6 +883,10 @@ int ll_lanczos_run_iteration_s(ll_context* ctx, ll_operator* op, const ll_lanczo
                                int64_t n_orth, const float* orth_host, double* eigvals_host, float* eigvecs_host,
                                int64_t* n_found, int64_t* itern_out, double* alpha_out, double* beta_out,
                                ll_run_stats* stats);
+int ll_lanczos_two_pass_c(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval_out, void* eigvec,
+                          int64_t* itern_out, double* residual_out, double* alpha_out, double* beta_out, ll_run_stats* stats);
+int ll_lanczos_two_pass_s(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval_out, float* eigvec,
+                          int64_t* itern_out, double* residual_out, double* alpha_out, double* beta_out, ll_run_stats* stats);
 int ll_expo_run_c(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im,
                   const void* input_host, void* output_host, int64_t* itern_out, ll_run_stats* stats);
 int ll_expo_run_s(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a, const float* input_host,

@@ -39,6 +39,7 @@ from .engine import (  # noqa: F401
     nrm2,
     orth_block,
     partition,
+    recur_accum,
     scal,
     spmv,
     three_term,

@@ -108,7 +108,9 @@ class RunStats(C.Structure):
         ("lagged_iterations", i64),
         ("pair_iterations", i64),
         ("pair_gate_trips", i64),
-        ("reserved", i64 * 6),
+        ("workspace_vectors", i64),
+        ("replay_mismatches", i64),
+        ("reserved", i64 * 4),
     ]
 
     def as_dict(self):
@@ -199,6 +201,8 @@ PROTOTYPES = {
     "ll_normalize_z": (C.c_int, [vp, i64, vp, P(f64)]),
     "ll_three_term_d": (C.c_int, [vp, i64, vp, vp, vp, f64, f64]),
     "ll_three_term_z": (C.c_int, [vp, i64, vp, vp, vp, f64, f64]),
+    "ll_recur_accum_d": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
+    "ll_recur_accum_z": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
     "ll_orth_block_d": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_orth_block_z": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_gemv_basis_d": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, vp, i64]),
@@ -215,6 +219,8 @@ PROTOTYPES = {
                                              P(RunStats)]),
     "ll_lanczos_run_iteration_z": (C.c_int, [vp, vp, P(LanczosParams), i64, i64, vp, vp, vp, P(i64), P(i64), vp, vp,
                                              P(RunStats)]),
+    "ll_lanczos_two_pass_d": (C.c_int, [vp, vp, P(LanczosParams), P(f64), vp, P(i64), P(f64), vp, vp, P(RunStats)]),
+    "ll_lanczos_two_pass_z": (C.c_int, [vp, vp, P(LanczosParams), P(f64), vp, P(i64), P(f64), vp, vp, P(RunStats)]),
     "ll_expo_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64), P(RunStats)]),
     "ll_expo_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64), P(RunStats)]),
     "ll_expo_taylor_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64)]),

@@ -955,6 +955,52 @@ int ll_three_term_z(ll_context* ctx, int64_t n, void* w, const void* up, const v
     launch_three_term<zc>(n, (zc*)w, (const zc*)up, (const zc*)uc, beta, alpha, ctx->stream);
   });
 }
+extern "C++" {
+namespace {
+template <typename T>
+void recur_accum_impl(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, double g, void* psi) {
+  use(ctx);
+  LL_REQUIRE(n >= 0 && y && x && psi, "null vector");
+  launch_recur_accum<T>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, g, nullptr, 0, nullptr, ctx->stream);
+}
+template <typename T>
+void two_pass_impl(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval, void* eigvec, int64_t* itern,
+                   double* residual, double* alpha_out, double* beta_out, ll_run_stats* stats) {
+  LL_REQUIRE(ctx && p && eigval, "null argument");
+  two_pass_run<T>(ctx, op, *p, eigval, (T*)eigvec, itern, residual, alpha_out, beta_out, stats);
+}
+}  // namespace
+}  // extern "C++"
+int ll_recur_accum_d(ll_context* ctx, int64_t n, double* y, const double* x, const double* p, double a, double b, double g,
+                     double* psi) {
+  return guarded([&] { recur_accum_impl<double>(ctx, n, y, x, p, a, b, g, psi); });
+}
+int ll_recur_accum_z(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, double g, void* psi) {
+  return guarded([&] { recur_accum_impl<zc>(ctx, n, y, x, p, a, b, g, psi); });
+}
+int ll_recur_accum_c(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, double g, void* psi) {
+  return guarded([&] { recur_accum_impl<cf>(ctx, n, y, x, p, a, b, g, psi); });
+}
+int ll_recur_accum_s(ll_context* ctx, int64_t n, float* y, const float* x, const float* p, double a, double b, double g,
+                     float* psi) {
+  return guarded([&] { recur_accum_impl<float>(ctx, n, y, x, p, a, b, g, psi); });
+}
+int ll_lanczos_two_pass_d(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval, double* eigvec,
+                          int64_t* itern, double* residual, double* alpha_out, double* beta_out, ll_run_stats* stats) {
+  return guarded([&] { two_pass_impl<double>(ctx, op, p, eigval, eigvec, itern, residual, alpha_out, beta_out, stats); });
+}
+int ll_lanczos_two_pass_z(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval, void* eigvec,
+                          int64_t* itern, double* residual, double* alpha_out, double* beta_out, ll_run_stats* stats) {
+  return guarded([&] { two_pass_impl<zc>(ctx, op, p, eigval, eigvec, itern, residual, alpha_out, beta_out, stats); });
+}
+int ll_lanczos_two_pass_c(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval, void* eigvec,
+                          int64_t* itern, double* residual, double* alpha_out, double* beta_out, ll_run_stats* stats) {
+  return guarded([&] { two_pass_impl<cf>(ctx, op, p, eigval, eigvec, itern, residual, alpha_out, beta_out, stats); });
+}
+int ll_lanczos_two_pass_s(ll_context* ctx, ll_operator* op, const ll_lanczos_params* p, double* eigval, float* eigvec,
+                          int64_t* itern, double* residual, double* alpha_out, double* beta_out, ll_run_stats* stats) {
+  return guarded([&] { two_pass_impl<float>(ctx, op, p, eigval, eigvec, itern, residual, alpha_out, beta_out, stats); });
+}
 int ll_orth_block_d(ll_context* ctx, int64_t n, int64_t nb, const double* basis, int64_t ld, double* w, int mode,
                     double* norm_out, double* h_out) {
   return guarded([&] { orth_impl<double>(ctx, n, nb, basis, ld, w, mode, norm_out, h_out); });

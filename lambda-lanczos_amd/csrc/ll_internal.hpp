@@ -678,7 +678,7 @@ int op_accuracy(const ll_operator* op);
 // ---------------------------------------------------------------- kernel launchers
 // Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip); everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
-// launch_maxpy_folding: gs_small.hip).
+// launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
 
 // Deferred normalisation (a8 folded into the next a1; single-GPU whole-loop drivers, operators that gather x themselves):
@@ -924,6 +924,24 @@ int launch_scale_publish(int64_t n, T* v, const double* partials, int nparts, do
 // Plain three-term update with host scalars (primitive API).
 template <typename T>
 void launch_three_term(int64_t n, T* w, const T* u_prev, const T* u_cur, double beta, double alpha, hipStream_t s);
+// The two-pass recurrence without a stored basis (recur.hip; two_pass_run.cpp).  rec: one record of kRecurRec doubles per
+// iteration k on the device — alpha_k, a_k, b_k, c_k = ||r_k||^2.
+constexpr int kRecurRec = 4;
+// pass 1: y <- y - a x - b p (p nullable) with alpha folded from the operator kernel's partials, a = alpha / sqrt(c_k),
+// b = sqrt(c_k / c_{k-1}) (normalised: x and p were scaled to unit norm in place: a = alpha, b = sqrt(c_k)); (alpha, a, b) ->
+// rec[k]; partials[workgroup] = its share of ||y||^2.  Returns the grid.
+template <typename T>
+int launch_recur_step(int64_t n, T* y, const T* x, const T* p, const double* alpha_partials, int alpha_nparts, double* rec,
+                      int64_t k, bool normalised, double* partials, hipStream_t s);
+// ... folded by one workgroup: rec[k + 1].c = sum; host_mapped[0..4) = {alpha_k, sum, 0, sum}
+void launch_recur_fold(const double* partials, int nparts, double* rec, int64_t k, double* host_mapped, hipStream_t s);
+// pass 2: the same update with (a, b) read from rec[k] (rec == nullptr: the values a, b), then psi += g y with g = gvec[k + 1]
+// (gvec == nullptr: the value g).  alpha_partials (nullable, needs rec): workgroup 0 folds them and adds 1 to *mismatches
+// when the sum differs as bits from rec[k].alpha.
+template <typename T>
+void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const double* gvec, int64_t k,
+                        double a, double b, double g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
+                        hipStream_t s);
 // partials of <a,b> (reals per workgroup). Returns grid.
 template <typename T> int launch_dot(int64_t n, const T* a, const T* b, double* partials, hipStream_t s);
 // out_r = sum_{k=m-1..0} coeff[r*m+k] * u_k, r < nout; coeff on device, type acc_t<T>; the sums are carried in acc_t<T> and

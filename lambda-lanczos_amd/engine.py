@@ -560,6 +560,14 @@ def three_term(ctx, w_dev, u_prev_dev, u_cur_dev, beta, alpha, n=None):
              float(alpha)))
 
 
+def recur_accum(ctx, y_dev, x_dev, p_dev, a, b, g, psi_dev, n=None):
+    """One replayed step of the two-pass recurrence: y -= a x + b p (p_dev may be None), then psi += g y, in one sweep."""
+    n = int(n if n is not None else y_dev.shape[-1])
+    fn = getattr(lib(), "ll_recur_accum_" + _suffix(y_dev.dtype))
+    check(fn(ctx.handle, n, y_dev.ptr, x_dev.ptr, None if p_dev is None else p_dev.ptr, float(a), float(b), float(g),
+             psi_dev.ptr))
+
+
 def orth_block(ctx, basis_dev, nb, ld, w_dev, n, mode=capi.ORTH_CGS_DGKS, want_h=False):
     sfx = _suffix(w_dev.dtype)
     norm = C.c_double()
@@ -689,10 +697,8 @@ class LambdaLanczos:
         Returns (eigenvalues, eigenvectors, iteration_count); no restart loop, no EigenPairManager filtering."""
         return self._drive(int(nroot), int(nroot), orthogonalize_to)
 
-    def _drive(self, k, nroot, orth):
-        op, owned = _as_operator(self.mv_mul, self.matrix_size, self.dtype, self.context)
-        sfx = _suffix(self.dtype)
-        p = self._params(1 if nroot is not None else k)
+    def _set_start_vector(self, p, op):
+        """Point the params at self.init_vector (DeviceArray or hook); returns what must stay alive during the call."""
         keep = None
         if isinstance(self.init_vector, DeviceArray):  # start vector already in HBM
             assert self.init_vector.dtype == self.dtype and self.init_vector.nbytes >= op.n_local * self.dtype.itemsize
@@ -709,6 +715,13 @@ class LambdaLanczos:
 
             keep = capi.INIT_FN(tramp)
             p.init_vector = keep
+        return keep
+
+    def _drive(self, k, nroot, orth):
+        op, owned = _as_operator(self.mv_mul, self.matrix_size, self.dtype, self.context)
+        sfx = _suffix(self.dtype)
+        p = self._params(1 if nroot is not None else k)
+        keep = self._set_start_vector(p, op)
         n_local = op.n_local
         vals = np.zeros(k, dtype=np.float64)
         dev_out = self.eigenvectors_out
@@ -756,6 +769,41 @@ class LambdaLanczos:
         self.last_stats = stats.as_dict()
         self.last_alpha, self.last_beta = alpha[: stats.last_alpha_len].copy(), beta[: stats.last_alpha_len].copy()
         return vals[:nf], (vecs if dev_out is not None else vecs[:nf]), int(itern.value)
+
+    def run_two_pass(self, want_vector=True):
+        """The extreme eigenpair WITHOUT a stored Krylov basis (two-pass Lanczos, ll_lanczos_two_pass_*): three or four
+        n-sized device vectors whatever the iteration count, every operator application twice, no re-orthogonalisation
+        (one pair only; num_eigs is not consulted).  Returns (eigenvalue, eigenvector or None, info) with info =
+        {"iterations", "residual" (None without the vector), "stats"}.  init_vector and eigenvectors_out act as in run():
+        with a DeviceArray in eigenvectors_out the Ritz vector is accumulated there and that array is returned."""
+        op, owned = _as_operator(self.mv_mul, self.matrix_size, self.dtype, self.context)
+        p = self._params(1)
+        keep = self._set_start_vector(p, op)
+        vec, vec_p = None, None
+        if want_vector:
+            dev_out = self.eigenvectors_out
+            if dev_out is not None:
+                assert dev_out.dtype == self.dtype and dev_out.nbytes >= op.n_local * self.dtype.itemsize
+                vec, vec_p = dev_out, C.c_void_p(dev_out.ptr)
+            else:
+                vec = np.empty(op.n_local, dtype=self.dtype)
+                vec_p = ptr(vec)
+        trace_cap = int(min(self.max_iteration, 1 << 24))
+        alpha, beta = np.zeros(trace_cap), np.zeros(trace_cap)
+        val, res, itern, stats = C.c_double(), C.c_double(), C.c_int64(), capi.RunStats()
+        try:
+            fn = getattr(lib(), "ll_lanczos_two_pass_" + _suffix(self.dtype))
+            check(fn(self.context.handle, op.handle, C.byref(p), C.byref(val), vec_p, C.byref(itern), C.byref(res),
+                     ptr(alpha), ptr(beta), C.byref(stats)))
+        finally:
+            if owned:
+                op.close()
+        del keep
+        self._iter_counts = [int(itern.value)]
+        self.last_stats = stats.as_dict()
+        self.last_alpha, self.last_beta = alpha[: stats.last_alpha_len].copy(), beta[: stats.last_alpha_len].copy()
+        info = {"iterations": int(itern.value), "residual": res.value if want_vector else None, "stats": self.last_stats}
+        return val.value, vec, info
 
     def run_single(self):
         """run(eigenvalue, eigenvector): one pair regardless of num_eigs (LL:394-407)."""
