@@ -101,6 +101,22 @@ struct Failure {
     }                                                                              \
   } while (0)
 
+// exception -> status: the body of every extern "C" entry point (capi.cpp, context.cpp) runs inside it
+template <typename F> int guarded(F&& f) {
+  try {
+    f();
+    return LL_OK;
+  } catch (const Failure& e) {
+    return e.code;
+  } catch (const std::bad_alloc&) {
+    set_error("host allocation failed");
+    return LL_ERR_ALLOC;
+  } catch (const std::exception& e) {
+    set_error(std::string("unexpected exception: ") + e.what());
+    return LL_ERR_INVALID;
+  }
+}
+
 // ---------------------------------------------------------------- owned device memory
 // The one owner of a library allocation: freed (Free: hipFree, or hipHostFree for pinned host memory) when reset, replaced or
 // destroyed; moved, never copied.  A BORROWED handle (the caller's arrays of ll_op_create_csr_dev_*) is forgotten instead
@@ -229,25 +245,25 @@ struct GatherPlan {
 // (ll_ctx_create*), into the context; operators copy what shapes their image when THEY are created.  Nothing on a launch path
 // calls getenv.  ll_ctx_reload_env() reads them again.  Every other field below — geometry overrides, forced code paths, the
 // hooks of the test suite — is NOT read from the environment: it is set per context through ll_ctx_set_tuning(ctx, key, value)
-// (capi.cpp tuning_apply holds the one parser; the comments below name the key).
+// (context.cpp tuning_apply holds the one parser; the comments below name the key).
 namespace ll {
 struct Tuning {
   // --- operator creation
   int spmv_kernel = -1;            // LL_SPMV_KERNEL = csr | pb | tiled: that LL_SPMV_* kernel; anything else -1 (auto: time the candidates, keep the fastest)
   bool keep_both = false;          // LL_SPMV_KEEP_BOTH=1: keep the image that lost the timing (ll_op_select_spmv A/B)
   int pb_phase2 = 4;               // LL_PB_PHASE2 = fixed (4, default) | ordered (1) | atomic (0); with the accuracy request: operators.cpp image_forms
-  int pb_block = 0;                // LL_PB_BLOCK: rows AND columns per block (0: automatic); tests force ragged blocks
-  int pb_row_block = 0;            // LL_PB_ROW_BLOCK / LL_PB_COL_BLOCK: one of the two only
+  int pb_block = 0;                // key pb_block = n: rows AND columns per block (0: automatic); tests force ragged blocks
+  int pb_row_block = 0;            // keys pb_row_block = n / pb_col_block = n: one of the two only
   int pb_col_block = 0;
   int pair_max_stored = 0;         // key pair_max_stored = n: the pair form hands over to the one-sweep form beyond n stored vectors (test hook; by itself at 4 992 real / 2 492 complex)
   int pair_split_vecs = 0;         // key pair_split = n: at most n stored vectors per launch of the pair sweep (test hook: split sweeps on small problems)
-  int pb_threads1 = 0;             // LL_PB_THREADS1 = 256 | 512 | 1024: lanes per workgroup of PB phase 1 (0: automatic — 512 for the thin column blocks of a sharded image, 1024 on one GPU); read at creation
-  int pb_pad = 0;                  // LL_PB_PAD = 4 | 16: entries every segment of the PB image is padded to (0: automatic — 4 sharded, 16 on one GPU); read at creation
+  int pb_threads1 = 0;             // key pb_threads1 = 256 | 512 | 1024: lanes per workgroup of PB phase 1 (0: automatic — 512 for the thin column blocks of a sharded image, 1024 on one GPU); read at creation
+  int pb_pad = 0;                  // key pb_pad = 4 | 16: entries every segment of the PB image is padded to (0: automatic — 4 sharded, 16 on one GPU); read at creation
   int pb_placements = 8;           // LL_PB_PLACEMENTS: arena placements timed at creation (1: keep the first; LL_PB_PLACEMENT_TRACE=1 prints every draw); operators.cpp
-  bool pb_xpre = true;             // LL_PB_XPRE=0: phase 2 of the PB SpMV loads x_i in its epilogue (A/B of the early request)
+  bool pb_xpre = true;             // key pb_xpre = 0: phase 2 of the PB SpMV loads x_i in its epilogue (A/B of the early request)
   bool pb_diag = true;             // LL_PB_DIAG=0: the diagonal entries travel through the PB streams like every other entry (A/B)
   int gather_chunks = 0;           // LL_GATHER_CHUNKS: pieces of the all-gather (0: 4 on two ranks, 2 on more)
-  bool spmv_tile_balance = true;   // LL_SPMV_TILE_BALANCE=0: CSR-stream tiles always hold up to 1024 nonzeros (operators.cpp build_tiles)
+  bool spmv_tile_balance = true;   // key spmv_tile_balance = 0: CSR-stream tiles always hold up to 1024 nonzeros (operators.cpp build_tiles)
   bool csr_split = true;           // LL_CSR_SPLIT=0: sharded CSR-stream / dense operators gather first, then multiply (round-3 form)
   bool comm_overlap = true;        // LL_COMM_OVERLAP=0: exchange and compute on one stream (serial A/B reference)
   // --- the loops
@@ -266,24 +282,24 @@ struct Tuning {
   int sweep_pipeline = 1;          // key sweep_pipeline: 1 (default) the software-pipelined pair sweep on streaming vectors (> ~9 MiB), 0 never (A/B: same bits), 2 on every length (parity tests on small cases)
   bool pair_gs = true;             // LL_PAIR_GS=0: never two iterations per sweep (the one-sweep form throughout; A/B and parity hunts)
   // --- test hooks (not for users)
-  bool force_rp64 = false;         // LL_FORCE_RP64=1: 64-bit row offsets on small matrices
-  bool tl_xcd_order = true;        // LL_TL_XCD=0: row blocks of the tiled kernel in launch order instead of one contiguous eighth per XCD (A/B)
-  bool tl_walk_modulo = true;      // LL_TL_WALK=0: a row block's tiles in ascending column order instead of by column index modulo the longest tile list (A/B; read at creation)
-  bool tl_force = false;           // LL_TL_FORCE=1: build the tiled image even for matrices that are not eligible (parity tests on small cases)
-  bool pb_test_all_remote = false; // LL_PB_TEST_ALL_REMOTE=1: own columns are read from the gathered buffer too
-  int tridiag_test_jitter_us = 0;  // LL_TRIDIAG_TEST_JITTER_US: random delay of every helper-thread verdict
+  bool force_rp64 = false;         // key force_rp64 = 1: 64-bit row offsets on small matrices
+  bool tl_xcd_order = true;        // key tl_xcd = 0: row blocks of the tiled kernel in launch order instead of one contiguous eighth per XCD (A/B)
+  bool tl_walk_modulo = true;      // key tl_walk = 0: a row block's tiles in ascending column order instead of by column index modulo the longest tile list (A/B; read at creation)
+  bool tl_force = false;           // key tl_force = 1: build the tiled image even for matrices that are not eligible (parity tests on small cases)
+  bool pb_test_all_remote = false; // key pb_test_all_remote = 1: own columns are read from the gathered buffer too
+  int tridiag_test_jitter_us = 0;  // key tridiag_test_jitter_us = n: random delay of every helper-thread verdict
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
   int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
   int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
   int pauli_symmetric_block_bits = -1;  // key pauli_symmetric_block_bits = b: the same for the momentum / reflection / spin-inversion kernel (-1: kPauliSymmetricBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
-  bool stencil_vec = true;         // LL_STENCIL_VEC=0: scalar lattice kernel on shapes the vector kernel would take
-  double stall_trace_ms = -1.0;    // LL_STALL_TRACE: print where a whole-loop call longer than this spent its time
+  bool stencil_vec = true;         // key stencil_vec = 0: scalar lattice kernel on shapes the vector kernel would take
+  double stall_trace_ms = -1.0;    // key stall_trace = ms: print where a whole-loop call longer than this spent its time
   std::string iter_trace;          // LL_ITER_TRACE=path: the eigen-solver loop appends one line per collected iteration
                                    // (pass k alpha beta^2 c0 c1 second-pass) and one per stop verdict — for parity hunts
   bool pb_placement_trace = false; // LL_PB_PLACEMENT_TRACE=1: print every placement draw of the PB image (operators.cpp)
 };
-// capi.cpp: defaults <- the user-facing environment switches <- the context's overrides (ll_ctx_set_tuning), in that order
+// context.cpp: defaults <- the user-facing environment switches <- the context's overrides (ll_ctx_set_tuning), in that order
 Tuning read_tuning(const std::map<std::string, std::string>* overrides);
 bool tuning_apply(Tuning& t, const std::string& key, const std::string& value);  // false: unknown key
 
@@ -411,7 +427,7 @@ struct PbImage {
   int phase2 = 4;                // form of phase 2 (ll::LL_PB_FIXED / _ORDERED / _ATOMIC): set when the image is built,
                                  // changed by ll_op_set_accuracy (both forms read the same image)
   int threads1 = 1024;           // lanes per workgroup of phase 1 (1024; 512 for the thin column blocks of a sharded image)
-  bool xpre = true;              // fixed-point phase 2 requests the epilogue's x_i before its stream (LL_PB_XPRE)
+  bool xpre = true;              // fixed-point phase 2 requests the epilogue's x_i before its stream (key pb_xpre)
   int own_count = 0;             // table range [0, own_count)
   int chunk_first[kMaxGatherChunks] = {0};  // remote blocks of gather chunk c: [first, first + count)
   int chunk_count[kMaxGatherChunks] = {0};
@@ -620,7 +636,7 @@ struct ll_operator {
   ll_operator() = default;
   ll_operator(const ll_operator&) = delete;
   ll_operator& operator=(const ll_operator&) = delete;
-  ~ll_operator();  // selects the device; the images free their arrays (capi.cpp)
+  ~ll_operator();  // selects the device; the images free their arrays (context.cpp)
 };
 
 namespace ll {
@@ -628,7 +644,7 @@ namespace ll {
 // ---------------------------------------------------------------- operator construction (operators.cpp, pauli_operators.cpp)
 // What the extern "C" entry points (capi.cpp) call.  create_csr takes resolved options: csr_options_default(false) for the plain
 // entry points, csr_options_default(true) for the _dev_ ones, the caller's for the _opt_ ones.
-void use(ll_context* ctx);  // null check, then the context's device (capi.cpp)
+void use(ll_context* ctx);  // null check, then the context's device (context.cpp)
 template <typename T>  // the header of every operator: kind, storage type, context and the checked row range (operators.cpp)
 std::unique_ptr<ll_operator> new_operator(ll_context* ctx, ll_operator::Kind kind, int64_t n, int64_t row_begin, int64_t n_local);
 ll_csr_options csr_options_default(bool arrays_on_device);

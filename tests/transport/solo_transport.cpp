@@ -37,7 +37,7 @@ __global__ void replicate16(const uint4* __restrict__ src, uint4* __restrict__ d
 int solo_all_gather(void* self, const void* send, void* recv, size_t bytes, void* stream) {
   Solo* c = (Solo*)self;
   hipStream_t s = (hipStream_t)stream;
-  if (bytes == sizeof(double)) {  // the self-check's rank tags (capi.cpp: finish_comm_setup)
+  if (bytes == sizeof(double)) {  // the self-check's rank tags (context.cpp: finish_comm_setup)
     std::vector<double> tags((size_t)c->nranks);
     for (int r = 0; r < c->nranks; ++r) tags[(size_t)r] = (double)(r + 1);
     if (hipMemcpyAsync(recv, tags.data(), tags.size() * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) return 1;
@@ -63,7 +63,7 @@ int solo_all_reduce(void* self, double* buf, size_t count, void* stream) {
   Solo* c = (Solo*)self;
   if (count == 0) return 0;
   double f = 1.0;
-  if (!c->self_check_answered) {  // the first call is the self-check's sum of ones (capi.cpp: finish_comm_setup)
+  if (!c->self_check_answered) {  // the first call is the self-check's sum of ones (context.cpp: finish_comm_setup)
     c->self_check_answered = true;
     f = (double)c->nranks;
   }
