@@ -634,7 +634,8 @@ int ll_recur_accum_z(ll_context* ctx, int64_t n_local, void* y_dev, const void* 
  * mode: LL_ORTH_CGS_DGKS (default, block classical Gram-Schmidt + a second pass when the norm drops below
  * 1/sqrt(2)), LL_ORTH_CGS2 (always two passes), LL_ORTH_MGS (sequential dot->axpy per vector: the reference's
  * operation order, 2*nb launches). h_host (nullable) receives the nb projection coefficients summed over passes
- * (re,im pairs for _z). */
+ * (re,im pairs for _z).  Elements [n_local, ld) of a row, and rows beyond nb, are neither read nor written: they may hold
+ * anything (NaN included). */
 enum { LL_ORTH_CGS_DGKS = 0, LL_ORTH_CGS2 = 1, LL_ORTH_MGS = 2 };
 int ll_orth_block_d(ll_context* ctx, int64_t n_local, int64_t nb, const double* basis_dev, int64_t ld,
                     double* w_dev, int mode, double* norm_host, double* h_host);
@@ -643,7 +644,9 @@ int ll_orth_block_z(ll_context* ctx, int64_t n_local, int64_t nb, const void* ba
 /* a9+a10: out_r = sum_{k=m-1..0} coeff[r*m + k] * basis_k for r < nout in ONE pass over the basis
  * (the sums are carried in double / complex double for every type and rounded to T once; the _s / _c coefficients stay double)
  * (LL:51-57: Ritz vectors, real coefficients; EX:166-170: exp(aA)v, coefficients of type T).
- * coeff_host: nout*m values of type T (re,im pairs for _z).  out_dev: nout vectors, leading dimension ld_out. */
+ * coeff_host: nout*m values of type T (re,im pairs for _z).  out_dev: nout vectors, leading dimension ld_out.
+ * Elements [n_local, ld) of a basis row, and rows beyond m, are neither read nor written (they may hold anything, NaN
+ * included); elements [n_local, ld_out) of an output row are not written. */
 int ll_gemv_basis_d(ll_context* ctx, int64_t n_local, int64_t m, const double* basis_dev, int64_t ld, int64_t nout,
                     const double* coeff_host, double* out_dev, int64_t ld_out);
 int ll_gemv_basis_z(ll_context* ctx, int64_t n_local, int64_t m, const void* basis_dev, int64_t ld, int64_t nout,

@@ -87,6 +87,7 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "lagged_pieces") t.lagged_pieces = e ? 0 : (int)to_ll(v);
   else if (key == "lagged_min_bytes") t.lagged_min_bytes = e ? -1 : to_ll(v);
   else if (key == "tridiag_test_jitter_us") t.tridiag_test_jitter_us = e ? 0 : (int)to_ll(v);
+  else if (key == "test_workspace_fill") t.test_workspace_fill = e ? -1 : (int)std::max<long long>(0, std::min<long long>(255, to_ll(v)));
   else if (key == "stall_trace") t.stall_trace_ms = e ? -1.0 : std::atof(v.c_str());
   else return false;
   return true;
@@ -131,6 +132,11 @@ void ll_context::dev_malloc(void** out, size_t bytes, const char* what) {
     set_error(std::string("out of device memory: ") + what + " (" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
     throw Failure{LL_ERR_ALLOC};
   }
+}
+void ll_context::test_fill(void* p, size_t bytes) {
+  // on the context's stream, then waited for: the buffer may be used first on the exchange stream
+  LL_HIP(hipMemsetAsync(p, tune.test_workspace_fill, bytes, stream));
+  LL_HIP(hipStreamSynchronize(stream));
 }
 void ll_context::cache_put(void* p, size_t bytes) {
   slab_cache.emplace_back(p, bytes);

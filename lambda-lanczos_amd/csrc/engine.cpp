@@ -35,6 +35,7 @@ template <typename T> T* Basis<T>::vec(int64_t k) {
         break;
       }
     if (p) {
+      ctx->test_fill_if_set(p, (size_t)chunk_vecs * (size_t)ld);
       chunks.push_back(p);
       continue;
     }
@@ -52,6 +53,7 @@ template <typename T> T* Basis<T>::vec(int64_t k) {
                 " vectors of " + std::to_string(ld * sizeof(T)) + " bytes: " + hipGetErrorString(e));
       throw Failure{LL_ERR_ALLOC};
     }
+    ctx->test_fill_if_set(p, (size_t)chunk_vecs * (size_t)ld);
     chunks.push_back(p);
   }
   return chunks[ci] + (k % chunk_vecs) * ld;

@@ -154,7 +154,7 @@ void taylor_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P, typen
     E.norm2_dev(V.vec(k), E.S(kScalScratch) + 1);
     double nn = 0.0;
     E.fetch(E.S(kScalScratch) + 1, &nn, 1);
-    if (std::sqrt(nn) * std::abs(factor) < P.eps) break;
+    if (!(std::sqrt(nn) * std::abs(factor) >= P.eps)) break;  // (a term that is not a number ends the series too: the output then says so)
   }
   std::vector<T> c((size_t)terms);
   for (int64_t k = terms; k-- > 0;) {  // backward sum with the reference's factor recurrence (EX:198-206)

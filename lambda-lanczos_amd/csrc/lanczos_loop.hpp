@@ -47,9 +47,10 @@ template <typename T> struct DevBuf {
       if (ctx->slab_cache[i].second == bytes) {
         p = (T*)ctx->slab_cache[i].first;
         ctx->slab_cache.erase(ctx->slab_cache.begin() + (long)i);
-        return;
+        break;
       }
-    ctx->dev_malloc((void**)&p, bytes, "work vectors");
+    if (!p) ctx->dev_malloc((void**)&p, bytes, "work vectors");
+    ctx->test_fill_if_set(p, bytes / sizeof(T));
   }
 };
 

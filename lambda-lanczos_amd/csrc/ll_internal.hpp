@@ -76,6 +76,9 @@ template <typename T> using acc_t = typename scalar_traits<T>::acc;
 // Explicit instantiation for the four storage types: every translation unit lists the templates it defines ONCE, in a macro
 // M(T) per file section, and instantiates them with LL_FOR_EACH_SCALAR(M).
 #define LL_FOR_EACH_SCALAR(M) M(double) M(zc) M(float) M(cf)
+// The floating-point element types of device buffers (what the test hook test_workspace_fill fills; never an index type).
+template <typename T>
+inline constexpr bool is_float_elem_v = std::is_same_v<T, double> || std::is_same_v<T, float> || std::is_same_v<T, zc> || std::is_same_v<T, cf>;
 
 // ---------------------------------------------------------------- errors
 void set_error(const std::string& msg);
@@ -293,6 +296,7 @@ struct Tuning {
   int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
   int pauli_symmetric_block_bits = -1;  // key pauli_symmetric_block_bits = b: the same for the momentum / reflection / spin-inversion kernel (-1: kPauliSymmetricBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
+  int test_workspace_fill = -1;    // key test_workspace_fill = 0..255: every device buffer of floating-point element type that the context hands out (dev_alloc<T>, Krylov slabs, DevBuf<T>; new or from the slab cache) is filled with that byte before use (-1, unset: not touched); tests poison the workspace with it
   bool stencil_vec = true;         // key stencil_vec = 0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // key stall_trace = ms: print where a whole-loop call longer than this spent its time
   std::string iter_trace;          // LL_ITER_TRACE=path: the eigen-solver loop appends one line per collected iteration
@@ -347,11 +351,20 @@ struct ll_context {
   // hipMalloc that makes room first when the device is full: the cached Krylov slabs of earlier runs are returned to
   // the device and the allocation is retried; LL_ERR_ALLOC (with the size in the message) if it still fails.
   void dev_malloc(void** out, size_t bytes, const char* what);
+  // Test hook test_workspace_fill: fill a buffer that is about to be handed out (context.cpp; call it only when the key is set).
+  void test_fill(void* p, size_t bytes);
+  template <typename T> void test_fill_if_set(T* p, size_t count) {
+    if constexpr (ll::is_float_elem_v<T>)
+      if (tune.test_workspace_fill >= 0) test_fill((void*)p, count * sizeof(T));
+  }
   // the same, owned: count elements of T (bytes for void)
   template <typename T> ll::DevArray<T> dev_alloc(size_t count, const char* what) {
     void* p = nullptr;
     if constexpr (std::is_void_v<T>) dev_malloc(&p, count, what);
-    else dev_malloc(&p, count * sizeof(T), what);
+    else {
+      dev_malloc(&p, count * sizeof(T), what);
+      test_fill_if_set((T*)p, count);
+    }
     return ll::DevArray<T>((T*)p);
   }
   // Grow a device workspace buffer to at least `count` elements: geometrically (1.5 x + 64) or to exactly `count`.

@@ -236,6 +236,8 @@ template <typename T> double tune_pb_placement(ll_operator* op) {
         (void)hipGetLastError();
         break;
       }
+      if (ctx->tune.test_workspace_fill >= 0)  // (test hook: the product buffer behind the copied matrix streams)
+        ctx->test_fill((char*)cand.back().get() + pb.arena_static_bytes, cand_bytes - pb.arena_static_bytes);
       LL_HIP(hipMemcpyAsync(cand.back().get(), cand[best_i].get(), pb.arena_static_bytes, hipMemcpyDeviceToDevice, s));
       pb.rebase(cand.back().get());
       const double ms = time_pb();

@@ -964,7 +964,11 @@ template <typename T> bool pb_build_device(ll_operator* op, int phase2) {
         const bool own = sr == m.rank;
         const int idx = own ? m.own_base[c] + b
                             : m.rem_base[c] + ((m.rank >= 0 && sr > m.rank) ? sr - 1 : sr) * m.nb[c] + b;
-        ncols[(size_t)idx] = (int32_t)std::min<int64_t>(m.bl[c], gp.len[c] - (int64_t)b * m.bl[c]);
+        // the slice ends with the vector: the last rank's shard is shorter than the stride S, and what the padded all-gather ships
+        // behind it is no part of x (the max |x| scan of phase 1 would take it into the fixed-point scale)
+        const int64_t first_col = (int64_t)sr * S + gp.start[c] + (int64_t)b * m.bl[c];
+        ncols[(size_t)idx] = (int32_t)std::max<int64_t>(
+            0, std::min<int64_t>({(int64_t)m.bl[c], gp.len[c] - (int64_t)b * m.bl[c], op->n - first_col}));
         xoff[(size_t)idx] = own ? gp.start[c] + (int64_t)b * m.bl[c]
                                 : (int64_t)P * gp.start[c] + (int64_t)sr * gp.len[c] + (int64_t)b * m.bl[c];
       }
@@ -1073,6 +1077,8 @@ template <typename T> bool pb_build_device(ll_operator* op, int phase2) {
     im.row = (uint16_t*)(base + o_row);
     im.prod = base + o_prod;
   }
+  ctx->test_fill_if_set((T*)im.val, cap);   // (test hook: the two streams of T inside the untyped arena; the indices are never filled)
+  ctx->test_fill_if_set((T*)im.prod, cap);
   LL_HIP(hipMemsetAsync(im.val, 0, cap * sizeof(T), s));  // padding entries: value 0, local indices 0
   LL_HIP(hipMemsetAsync(im.col, 0, cap * sizeof(uint16_t), s));
   LL_HIP(hipMemsetAsync(im.row, 0, cap * sizeof(uint16_t), s));

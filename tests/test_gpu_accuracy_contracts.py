@@ -4,7 +4,6 @@ against the correctly rounded A x, and for float / complex float the sharper "ea
 sum in double or fixed point" contract against the exact sum of those rounded products.  x and y are also passed one element
 into larger buffers whose guard zones must come back untouched, and the fixed-point forms must give the same bits under every
 geometry knob."""
-import types
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import contract_cases as K
 import exact_ref as E
 import lambda_lanczos_amd as L
+from guarded import GUARD, guarded as _guarded, unguard as _unguard  # noqa: F401 (fill 0xA5)
 from lambda_lanczos_amd import _capi as capi
 from util import check_orth_h
 
@@ -20,7 +20,6 @@ pytestmark = pytest.mark.gpu
 TYPES = [np.float64, np.complex128, np.float32, np.complex64]
 TYPE_IDS = ["d", "z", "s", "c"]
 OFFSETS = [0.0, -2.5, 0.1]
-GUARD = 64
 
 
 def _eps(dtype):
@@ -29,30 +28,6 @@ def _eps(dtype):
 
 def _single(dtype):
     return np.dtype(dtype) in (np.float32, np.complex64)
-
-
-def _guarded(ctx, host, shift):
-    """Device buffer of GUARD + shift + n + GUARD elements filled with a byte pattern, `host` written at element GUARD + shift;
-    returns (buffer, view at that element)."""
-    host = np.ascontiguousarray(host)
-    n = host.shape[0]
-    total = GUARD + shift + n + GUARD
-    buf = ctx.empty(total, host.dtype)
-    fill = np.frombuffer(np.full(total * host.dtype.itemsize, 0xA5, dtype=np.uint8).tobytes(), dtype=host.dtype).copy()
-    fill[GUARD + shift: GUARD + shift + n] = host
-    buf.set(fill)
-    view = types.SimpleNamespace(ptr=buf.ptr + (GUARD + shift) * host.dtype.itemsize, dtype=host.dtype, shape=(n,))
-    return buf, view
-
-
-def _unguard(buf, n, shift):
-    """The n elements of the view, after asserting that every byte outside them still holds the pattern."""
-    raw = buf.get()
-    b = raw.view(np.uint8)
-    isz = raw.dtype.itemsize
-    lo, hi = (GUARD + shift) * isz, (GUARD + shift + n) * isz
-    assert np.all(b[:lo] == 0xA5) and np.all(b[hi:] == 0xA5), "a kernel wrote outside its output vector"
-    return raw[GUARD + shift: GUARD + shift + n]
 
 
 # ------------------------------------------------------------------ SpMV: every form x type x offset x pointer shift

@@ -76,11 +76,18 @@ _EXTRA_WORLDS = [int(w) for w in os.environ.get("LL_MULTIRANK_WORLDS", "").split
                                          (2, {"LL_BLAS_SMALL_BYTES": "0", "LL_DGKS_THRESHOLD": "2.0"}),
                                          (3, {"LL_BLAS_SMALL_BYTES": "0", "LL_TRIDIAG_TEST_JITTER_US": "3000"}),
                                          (2, {"LL_TEST_LAGGED_MIN_BYTES": "0"}), (3, {"LL_TEST_LAGGED_MIN_BYTES": "0"}),
-                                         (3, {"LL_CSR_SPLIT": "0"})],
+                                         (3, {"LL_CSR_SPLIT": "0"}),
+                                         # the ranks' workspace poisoned (util.HOOK_KEYS; tests/test_gpu_poisoned_workspace.py): the last
+                                         # rank's shard is shorter than n_shard, so the padded all-gather ships pad elements
+                                         # (the 127 case found the PB image's column slices running to the padded stride: phase 1's
+                                         # max |x| scan took the pad into the fixed-point scale and the eigenvalues came back as 0)
+                                         (3, {"LL_TEST_WORKSPACE_FILL": "255"}),
+                                         (2, {"LL_TEST_WORKSPACE_FILL": "127", "LL_BLAS_SMALL_BYTES": "0"})],
                          ids=["stress-%d" % w for w in _EXTRA_WORLDS] + ["2", "3", "4", "2-forced-second-pass", "2-measured-norm", "3-one-chunk",
                               "3-verdict-jitter", "2-verdict-jitter-lag0", "2-one-sweep", "3-one-sweep",
                               "2-one-sweep-forced-second-pass", "3-one-sweep-verdict-jitter", "2-one-sweep-small-geometry",
-                              "3-one-sweep-small-geometry", "3-csr-gather-then-multiply"])
+                              "3-one-sweep-small-geometry", "3-csr-gather-then-multiply", "3-workspace-filled-ff",
+                              "2-one-sweep-workspace-filled-7f"])
 def test_sharded_engine_with_several_ranks_on_one_gpu(tmp_path, oracle, ctx, world, extra, llenv):
     ranks = run_ranks(tmp_path, world, **extra)
 

@@ -6,7 +6,6 @@ import json
 import os
 import subprocess
 import sys
-import types
 import uuid
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 import contract_cases as K
 import exact_ref as E
 import lambda_lanczos_amd as L
+from guarded import GUARD, guarded as _guarded, unguard as _unguard  # noqa: F401 (fill 0xA5)
 from lambda_lanczos_amd import _capi as capi
 from lambda_lanczos_amd import generators as G
 from util import csr_matvec, inf_norm
@@ -22,7 +22,6 @@ from util import csr_matvec, inf_norm
 pytestmark = pytest.mark.gpu
 
 TYPES = {"d": np.float64, "z": np.complex128, "s": np.float32, "c": np.complex64}
-GUARD = 64
 
 
 def _single(dtype):
@@ -35,31 +34,6 @@ def _cplx(dtype):
 
 def _eps(dtype):
     return E.EPS_F if _single(dtype) else E.EPS_D
-
-
-# (the guarded buffers of tests/test_gpu_accuracy_contracts.py)
-def _guarded(ctx, host, shift):
-    """Device buffer of GUARD + shift + n + GUARD elements filled with a byte pattern, `host` written at element GUARD + shift;
-    returns (buffer, view at that element)."""
-    host = np.ascontiguousarray(host)
-    n = host.shape[0]
-    total = GUARD + shift + n + GUARD
-    buf = ctx.empty(total, host.dtype)
-    fill = np.frombuffer(np.full(total * host.dtype.itemsize, 0xA5, dtype=np.uint8).tobytes(), dtype=host.dtype).copy()
-    fill[GUARD + shift: GUARD + shift + n] = host
-    buf.set(fill)
-    view = types.SimpleNamespace(ptr=buf.ptr + (GUARD + shift) * host.dtype.itemsize, dtype=host.dtype, shape=(n,))
-    return buf, view
-
-
-def _unguard(buf, n, shift):
-    """The n elements of the view, after asserting that every byte outside them still holds the pattern."""
-    raw = buf.get()
-    b = raw.view(np.uint8)
-    isz = raw.dtype.itemsize
-    lo, hi = (GUARD + shift) * isz, (GUARD + shift + n) * isz
-    assert np.all(b[:lo] == 0xA5) and np.all(b[hi:] == 0xA5), "a kernel wrote outside its vector"
-    return raw[GUARD + shift: GUARD + shift + n]
 
 
 # ------------------------------------------------------------------ 1. the replayed step against exact arithmetic

@@ -60,6 +60,7 @@ HOOK_KEYS = {
     "LL_TEST_PAIR_SPLIT": "pair_split", "LL_TEST_PAIR_MAX_STORED": "pair_max_stored",
     "LL_TEST_LAGGED_PIECES": "lagged_pieces", "LL_TEST_LAGGED_MIN_BYTES": "lagged_min_bytes",
     "LL_TRIDIAG_TEST_JITTER_US": "tridiag_test_jitter_us", "LL_STALL_TRACE": "stall_trace",
+    "LL_TEST_WORKSPACE_FILL": "test_workspace_fill",
 }
 
 
