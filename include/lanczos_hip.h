@@ -735,7 +735,11 @@ typedef struct ll_run_stats {
                                   * count; taken from the reserved tail like the two above) */
   int64_t replay_mismatches;     /* ll_lanczos_two_pass_*: replayed iterations whose alpha differed, as bits, from the recorded
                                   * one: 0 unless the operator is not reproducible from call to call */
-  int64_t reserved[4];           /* zero; later statistics are taken from here, so the struct size stays what it is */
+  int64_t reserved[4];           /* later statistics are taken from here, so the struct size stays what it is.  In use, unnamed:
+                                  * [0] block_iterations: iterations that ran in the raw-basis block form (up to four per sweep,
+                                  * DESIGN.md 3.2; pair_iterations counts those of them that shared a sweep),
+                                  * [1] block_flushed_vectors: raw vectors completed in place when a pass left that form (one
+                                  * multi-axpy over the basis each; 0 in ordinary runs).  The rest is zero. */
 } ll_run_stats;
 int ll_ctx_set_profiling(ll_context* ctx, int enabled);
 

@@ -114,7 +114,10 @@ class RunStats(C.Structure):
     ]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["block_iterations"] = int(self.reserved[0])        # (unnamed in the C struct: taken from the reserved tail)
+        d["block_flushed_vectors"] = int(self.reserved[1])
+        return d
 
 
 P = C.POINTER

@@ -50,6 +50,7 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "iter_trace") t.iter_trace = v;
   else if (key == "sharded_norm") t.sharded_norm_measured = v == "measured";
   else if (key == "pair_gs") t.pair_gs = e ? d.pair_gs : to_flag(v);
+  else if (key == "block_gs") t.block_gs = e ? d.block_gs : to_flag(v);
   else if (key == "pb_diag") t.pb_diag = e ? d.pb_diag : to_flag(v);
   else if (key == "fuse_launches") {
     const long long level = e ? 2 : to_ll(v);

@@ -14,12 +14,12 @@
 namespace ll {
 
 // Device scalar area (ctx->scal, 64 doubles):
-//   [0..4)    alpha ring (slot = k % 4)
-//   [8..20)   norm triples (c0,c1,c2) ring, slot s at 8 + 3*s
-//   [24..27)  scratch triple for one-off orthogonalisations (start vector, primitives)
-//   [32]      spare scalar (dot results)
+//   [0..8)    alpha ring (slot = k % 8: kRingSlots, lanczos_loop.hpp)
+//   [8..32)   norm triples (c0,c1,c2) ring, slot s at 8 + 3*s
+//   [32..35)  scratch triple for one-off orthogonalisations (start vector, primitives)
+//   [40]      spare scalar (dot results)
 //   [63]      constant 0
-constexpr int kScalAlpha = 0, kScalNorms = 8, kScalScratch = 24, kScalSpare = 32, kScalZero = 63, kScalCount = 64;
+constexpr int kScalAlpha = 0, kScalNorms = 8, kScalScratch = 32, kScalSpare = 40, kScalZero = 63, kScalCount = 64;
 
 // ---------------------------------------------------------------- host helpers shared by Engine and the whole-loop drivers
 inline double now_s() {

@@ -89,7 +89,10 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
            [](int64_t, const typename LoopState<T>::Scalars&) {});
   itern = last.m;
   coeff_prev = last.coeff;
-  LS.pair_flush((int64_t)coeff_prev.size());  // (a pending pair: the output below needs u_0 .. u_{m-1} complete in the basis)
+  // (a pending pair: the output below needs u_0 .. u_{m-1} complete in the basis; a raw basis of the block form enters the GEMV
+  // through transformed coefficients instead)
+  if (!LS.block_pending() || !ctx->tune.ritz_tail) LS.pair_flush((int64_t)coeff_prev.size());
+  const typename LoopState<T>::Tail tail = LS.take_tail((int64_t)coeff_prev.size());
   alpha.resize((size_t)itern);
   beta.resize((size_t)itern);
   st.at("loop");
@@ -102,9 +105,7 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   for (int64_t l = 0; l < m; ++l) from_std(H(in_norm) * coeff_prev[l], &c[l]);
   DevBuf<T> d_out;
   d_out.alloc(ctx, (size_t)ld);
-  RunList<T> basis;
-  basis.ld = ld;
-  basis.add_basis(U, m);
+  const RunList<T> basis = LS.ritz_basis(tail, m, 1, c);
   st.at("out-alloc");
   E.gemv(basis, m, 1, c.data(), d_out.p, ld);
   LL_HIP(hipMemcpyAsync(output, d_out.p, (size_t)nl * sizeof(T), hipMemcpyDefault, s));

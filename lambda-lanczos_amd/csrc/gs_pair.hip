@@ -212,33 +212,6 @@ void launch_pair_predict(int P, int L, int reals, const double* g1, const double
   LL_HIP(hipGetLastError());
 }
 
-// Address-space casts for the pipelined sweeps.  A pointer that reaches a load through a table or a lambda has lost what lets
-// the compiler pick the cheap instruction: uniform reads of data no kernel writes while it runs (coefficients, the pointer table)
-// go through the CONSTANT address space (s_load: scalar cache, no vmcnt slot — a vector load in the middle of a trip would be
-// younger than the prefetched strips and turn the trip's wait into a full drain), strips through the GLOBAL one (global_load with
-// an SGPR base instead of flat_load, which also occupies the LDS counter).
-__device__ __forceinline__ double ld_const(const double* p, int i) {
-  return reinterpret_cast<const __attribute__((address_space(4))) double*>(reinterpret_cast<uintptr_t>(p))[i];
-}
-template <typename T> __device__ __forceinline__ const T* ld_const_ptr(const T* const* tab, int i) {
-  return reinterpret_cast<const T*>(reinterpret_cast<const __attribute__((address_space(4))) uintptr_t*>(reinterpret_cast<uintptr_t>(tab))[i]);
-}
-typedef unsigned int ll_u4v __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) char* ll_gcp;
-typedef __attribute__((address_space(1))) char* ll_gp;
-__device__ __forceinline__ uint4 ld_global16(const char* uniform_base, unsigned lane_off) {
-  const ll_gcp g = (ll_gcp)uniform_base;  // generic -> global
-  const ll_u4v v = *(const __attribute__((address_space(1))) ll_u4v*)(g + lane_off);
-  uint4 r;
-  __builtin_memcpy(&r, &v, sizeof(r));
-  return r;
-}
-__device__ __forceinline__ void st_global16(char* uniform_base, unsigned lane_off, uint4 x) {
-  const ll_gp g = (ll_gp)uniform_base;
-  ll_u4v v;
-  __builtin_memcpy(&v, &x, sizeof(v));
-  *(__attribute__((address_space(1))) ll_u4v*)(g + lane_off) = v;
-}
 // One trip of the pair sweep: NV basis strips; two late updates, the compensation of r4, two measured column sets.
 // nv <= NV of the strips are real (a prefix): the others are re-reads of the last real vector that the pipelined loop below issues
 // to keep every trip's loads unconditional — their coefficients are zero (x - 0 u = x exactly) and their column sums are dropped.
@@ -467,34 +440,6 @@ __global__ __launch_bounds__(kBlock) void pair_sweep_kernel(int64_t n, BasisSegs
 //   * a lane's address is a uniform base plus a 32-bit lane offset (global_load with an SGPR base): no 64-bit address
 //     arithmetic per load.
 // Same additions in the same order as the kernel above: identical bits (tests/test_gpu_pair.py compares the two).
-template <typename T, int PC, bool FULL>
-__device__ __forceinline__ void load_lstrip_u(const T* __restrict__ v, int64_t base, int64_t n, T (&r)[strip<T, PC>::EPT]) {
-  if constexpr (FULL) {
-    constexpr int EPT = strip<T, PC>::EPT;
-    const char* sb = reinterpret_cast<const char*>(v + base);  // uniform
-    const unsigned off = threadIdx.x * (unsigned)(EPT * sizeof(T));
-    uint4 c[PC];
-#pragma unroll
-    for (int e = 0; e < PC; ++e) c[e] = ld_global16(sb, off + 16u * e);
-    __builtin_memcpy(&r[0], c, sizeof(c));
-  } else {
-    load_strip<T, PC>(v, base + (int64_t)threadIdx.x * strip<T, PC>::EPT, n, r);
-  }
-}
-template <typename T, int PC, bool FULL>
-__device__ __forceinline__ void store_lstrip_u(T* __restrict__ v, int64_t base, int64_t n, const T (&r)[strip<T, PC>::EPT]) {
-  if constexpr (FULL) {
-    constexpr int EPT = strip<T, PC>::EPT;
-    char* sb = reinterpret_cast<char*>(v + base);
-    const unsigned off = threadIdx.x * (unsigned)(EPT * sizeof(T));
-    uint4 c[PC];
-    __builtin_memcpy(c, &r[0], sizeof(c));
-#pragma unroll
-    for (int e = 0; e < PC; ++e) st_global16(sb, off + 16u * e, c[e]);
-  } else {
-    store_strip<T, PC>(v, base + (int64_t)threadIdx.x * strip<T, PC>::EPT, n, r);
-  }
-}
 template <typename T>
 __global__ void fill_ptrs_kernel(const T** tab, int start, int count, const T* base, long long ld) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -55,9 +55,10 @@ template <typename T> struct DevBuf {
 };
 
 // The host's read-back area (ctx->pinned, pinned and device-mapped): iteration k publishes its four scalars (alpha, beta^2, c0, c1)
-// into ring slot k % kRingSlots; the gate values of the pair form follow the slots, one per slot.
-constexpr int kRingSlots = 4, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
-constexpr size_t kPinnedScalars = 32;  // (kGateAt + kRingSlots used)
+// into ring slot k % kRingSlots; the gate values of the pair and block forms follow the slots, one per slot.  Eight slots: a
+// block of four iterations is enqueued while the four of the block before it are still being collected.
+constexpr int kRingSlots = 8, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
+constexpr size_t kPinnedScalars = 48;  // (kGateAt + kRingSlots used)
 
 struct EventRing {
   hipEvent_t ev[kRingSlots];
@@ -160,7 +161,10 @@ template <typename T> struct LoopState {
     int set = 0;                                // which pair of buffers holds r[0] / r[1]: 0 = work, 1 = pwork
     int rec = 0;                                // records pb.rec[2 * rec], pb.rec[2 * rec + 1] hold g[0] / g[1]
   };
-  std::variant<None, DeferredIter, LaggedIter, PairIter> pending;
+  struct BlockIter {  // a_0 .. a_k in their basis slots, raw from a_{blk_k0} on (block form, see below)
+    int64_t k = 0;
+  };
+  std::variant<None, DeferredIter, LaggedIter, PairIter, BlockIter> pending;
   template <typename Kind> const Kind* pending_as() const { return std::get_if<Kind>(&pending); }
   NormRefs refs_prev{nullptr, nullptr, nullptr, 0};
   double t_enqueue = 0.0, t_wait = 0.0;
@@ -211,8 +215,55 @@ template <typename T> struct LoopState {
                               // (alternating); [16 ..]: |r3|^2, <r1, r3>
     static constexpr size_t kDoubles = 10 * kPairRec + 64;
   } pb;
-  bool slot_pair[kRingSlots] = {false, false, false, false};  // the scalars of this ring slot came from a pair fold (its gate is valid)
-  int ev_of_slot[kRingSlots] = {0, 1, 2, 3};                  // the event that covers a ring slot's scalars (a pair's two slots share one)
+  bool slot_pair[kRingSlots] = {};                    // the scalars of this ring slot came from a pair or block fold (its gate is valid)
+  int ev_of_slot[kRingSlots] = {0, 1, 2, 3, 4, 5, 6, 7};  // the event that covers a ring slot's scalars (the slots of a pair or block share one)
+  // Block form (gs_block.hip; tools/block_gs_model.py): UP TO FOUR iterations per sweep over a basis that is never rewritten.  The
+  // slots U.vec(j), j >= blk_k0, hold the RAW three-term vectors a_j; bb.rho2[j] and row j of the packed triangle bb.cpk (at
+  // R j (j - 1) / 2) hold rho_j^2 and the measured coefficients C_j[l] = <u_l, a_j>, and the orthonormal u_j = (a_j - sum_l C_j[l] u_l)
+  // / rho_j exist only implicitly: the Ritz GEMV takes transformed coefficients (ritz_basis), and leaving the form completes the raw
+  // vectors in place with one multi-axpy each (block_flush: an O(P^2) pass over the basis — a gate trip, a DGKS repair or the
+  // pair_max_stored hook, none of which an ordinary pass meets).  That cost and the R K^2 / 2 coefficients are why the form is
+  // bounded by kBlockMaxVecs vectors and only taken by passes whose max_iteration stays within the bound (configure); the others
+  // keep the pair form.
+  bool block_enabled = false;
+  bool block_allowed = true;   // this pass: a gate trip switches the form off for the rest of the pass
+  int64_t blk_k0 = 0;          // first raw vector of the pass (the vectors in front of it are complete: rho = 1, zero rows)
+  int64_t n_block = 0;         // iterations enqueued in the block form (statistics)
+  int64_t n_block_flushed = 0; // raw vectors completed by block_flush (statistics: multi-axpys over the basis)
+  DevBuf<double> bbuf;
+  DevBuf<T> bsplit[2];         // hand-over vectors of a split block sweep
+  struct BlockBuf {            // the regions of bbuf (enable_block)
+    double* rho2 = nullptr;    // cap entries
+    double* cpk = nullptr;     // packed rows 0 .. cap - 1
+    double* dk = nullptr;      // predict scratch, a record
+    double* p = nullptr;       // predictions, four records
+    double *prA = nullptr, *prB = nullptr;    // compensation coefficients, a record each
+    double *raw0 = nullptr, *raw1 = nullptr;  // fold scratch, a record each
+    double* cols = nullptr;    // folded columns: four records and the Gram tail
+    double* nsq = nullptr;     // |b_s|^2 (and <x_prev, b_s>) of the block's three-term updates, 4 doubles apart
+    int64_t cap = 0;           // vectors the records are sized for
+    size_t rec = 0;            // doubles per record
+  } bb;
+  static size_t block_row_at(int64_t j) { return (size_t)Engine<T>::R * (size_t)j * (size_t)(j > 0 ? j - 1 : 0) / 2; }
+  void enable_block() {
+    constexpr size_t R = (size_t)Engine<T>::R;
+    block_enabled = true;
+    bb.cap = std::min<int64_t>(max_k_hint, (int64_t)kBlockMaxVecs) + 8;
+    bb.rec = R * (size_t)(bb.cap + 8);
+    const size_t tri = block_row_at(bb.cap) + R * (size_t)bb.cap;
+    bbuf.alloc(E.ctx, (size_t)bb.cap + tri + 13 * bb.rec + 64);
+    double* b = bbuf.p;
+    bb.rho2 = carve(b, (size_t)bb.cap);
+    bb.cpk = carve(b, tri);
+    bb.dk = carve(b, bb.rec);
+    bb.p = carve(b, 4 * bb.rec);
+    bb.prA = carve(b, bb.rec);
+    bb.prB = carve(b, bb.rec);
+    bb.raw0 = carve(b, bb.rec);
+    bb.raw1 = carve(b, bb.rec);
+    bb.cols = carve(b, 4 * bb.rec + 32);
+    bb.nsq = carve(b, 16);
+  }
   // the gate of the pair form: what is neglected is the SQUARE of a relative coefficient, which must stay below the rounding of the
   // storage type (float vectors carry coefficients of ~1e-6 by rounding alone)
   static constexpr double kGate = sizeof(typename scalar_traits<T>::real) == 4 ? 2e-4 : kPairGate;
@@ -258,6 +309,11 @@ template <typename T> struct LoopState {
     if (lagged) bind_buffers();
     // two iterations per sweep (device operators, streaming vectors; enqueue_pair decides per iteration)
     if (lagged && tune.pair_gs && vec_bytes() >= pair_min_bytes()) enable_pair();
+    // up to four per sweep over a raw basis: where the pipelined pair sweep runs (pointer table, streaming vectors: enqueue_block
+    // decides), double precision, one rank, and only for passes that cannot outgrow the form's bound
+    if (pair_enabled && tune.block_gs && vtab.p && sizeof(typename scalar_traits<T>::real) == 8 && E.ctx->comm == nullptr &&
+        max_iteration >= 1 && max_iteration <= (int64_t)kBlockMaxVecs)
+      enable_block();
   }
   // the vector length the forms are chosen by (sharded: the shard stride, the same on every rank)
   int64_t vec_bytes() const { return (E.ctx->comm != nullptr ? E.op->n_shard : nl) * (int64_t)sizeof(T); }
@@ -340,6 +396,8 @@ template <typename T> struct LoopState {
     locked = locked_vecs;
     n_locked = n_lock;
     pair_allowed = true;
+    block_allowed = true;
+    blk_k0 = 0;
     for (auto& b : slot_pair) b = false;
     // (lambda_shifted == nullptr with locked vectors — a caller's orthogonalizeTo list, run_iteration LL:216-220,259: their Rayleigh
     // quotients theta_i = <z_i, (A + offset) z_i> are MEASURED below and take the eigenvalues' place; the residual gate then decides
@@ -356,7 +414,7 @@ template <typename T> struct LoopState {
       // against 0.62 s for the second call.
       constexpr size_t R = (size_t)Engine<T>::R;
       const size_t reach = (size_t)std::max<int64_t>(0, std::min<int64_t>(max_k_hint, (int64_t)kLaggedMaxCols)) + (size_t)n_lock + 2;
-      const size_t cols = std::min<size_t>(kPresizeCols, 2 * R * reach + 5 * R + 1);  // (longer runs: powers of two, enqueue_pair)
+      const size_t cols = std::min<size_t>(kPresizeCols, (block_enabled ? 4 : 2) * R * reach + 6 * R + 4);  // (longer runs: powers of two, enqueue_pair)
       E.ctx->ensure_partials((size_t)kMaxGrid * cols);
     }
     if (!lag_ok || n_lock == 0) return;
@@ -446,6 +504,8 @@ template <typename T> struct LoopState {
   void make_final(int64_t j) {
     if (const PairIter* pr = pending_as<PairIter>()) {
       if (j >= pr->P) pair_flush(j + 1);
+    } else if (pending_as<BlockIter>()) {
+      block_flush(j);
     } else if (const LaggedIter* lg = pending_as<LaggedIter>()) {
       if (lg->k == j) flush_lag();
     }
@@ -455,6 +515,10 @@ template <typename T> struct LoopState {
   // count: only the vectors u_j with j < count are needed (end of a pass: the Ritz vectors use u_0 .. u_{m-1}; a repair of u_j:
   // nothing behind u_j survives it) — a pending vector beyond that is dropped instead of completed.
   void pair_flush(int64_t count = std::numeric_limits<int64_t>::max()) {
+    if (pending_as<BlockIter>()) {
+      block_flush(count - 1);
+      return;
+    }
     const PairIter* pr = pending_as<PairIter>();
     if (!pr) return;
     // (g[1]: R * P coefficients against the basis, then <u_P, r[1]>: one contiguous list)
@@ -467,12 +531,76 @@ template <typename T> struct LoopState {
   // vectors with their measured coefficients.  Instead of completing them with a sweep of their own (pair_flush: the whole basis
   // read once per pending vector — 1.4 ms of a 131 ms step on config 3), ritz_basis folds the late update into the COEFFICIENTS of the
   // Ritz GEMV:  u_P = (r1 - S g1) / rho1,  u_{P+1} = (r2 - S g2 - gam u_P) / rho2  =>  sum_k s_k u_k is a combination of S, r1, r2.
+  struct BlockRows {  // the record of the raw vectors a_k0 .. a_{end-1} on the host
+    int64_t k0 = 0, end = 0;
+    std::vector<double> rows;  // rows k0 .. end - 1 of the packed triangle
+    std::vector<double> rho;   // rho_k0 .. rho_{end-1}
+    const double* row(int64_t j) const { return rows.data() + (block_row_at(j) - block_row_at(k0)); }
+  };
+  BlockRows fetch_block_rows(int64_t end) {
+    BlockRows br;
+    br.k0 = blk_k0;
+    br.end = std::max(end, blk_k0);
+    const size_t cnt = (size_t)(br.end - br.k0);
+    if (cnt == 0) return br;
+    br.rows.resize(block_row_at(br.end) - block_row_at(br.k0) + 1);
+    br.rho.resize(cnt);
+    if (br.rows.size() > 1) E.fetch(bb.cpk + block_row_at(br.k0), br.rows.data(), br.rows.size() - 1);
+    E.fetch(bb.rho2 + br.k0, br.rho.data(), cnt);
+    for (auto& r : br.rho) r = std::sqrt(r);
+    return br;
+  }
+  // Leave the block form: the raw vectors a_k0 .. a_last are completed and normalised IN PLACE, from the highest index down —
+  //   u_j = (a_j - sum_{l<j} (C_j[l] / rho_l) a_l) / rho_j    (first order in C)
+  // uses only raw vectors of lower index, which the descending order has not touched yet.  Whatever lies behind a_last (later vectors
+  // of a block that a gate, a repair or a stop cut) is dropped.  One multi-axpy over the basis per raw vector.
+  void block_flush(int64_t last) {
+    constexpr int R = Engine<T>::R;
+    const BlockIter* bi = pending_as<BlockIter>();
+    if (!bi) return;
+    last = std::min(last, bi->k);
+    if (last >= blk_k0) {
+      BlockRows br = fetch_block_rows(last + 1);
+      for (int64_t j = br.k0; j <= last; ++j) {  // C_j[l] / rho_l, in place
+        double* row = br.rows.data() + (block_row_at(j) - block_row_at(br.k0));
+        for (int64_t l = br.k0; l < j; ++l)
+          for (int q = 0; q < R; ++q) row[(size_t)R * l + q] /= br.rho[(size_t)(l - br.k0)];
+      }
+      if (br.rows.size() > 1) {
+        LL_HIP(hipMemcpyAsync(bb.cpk + block_row_at(br.k0), br.rows.data(), (br.rows.size() - 1) * sizeof(double), hipMemcpyHostToDevice, s));
+        LL_HIP(hipStreamSynchronize(s));  // (pageable source)
+      }
+      for (int64_t j = last; j >= br.k0; --j) {
+        T* dst = U.vec(j);
+        const RunList<T> runs = basis_runs(j);
+        int off = 0;
+        for (auto& grp : runs.groups(max_vecs_per_launch<T>())) {
+          launch_maxpy<T>(nl, dst, grp, bb.cpk + block_row_at(j) + (size_t)R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
+          for (int i = 0; i < grp.nseg; ++i) off += grp.count[i];
+        }
+        launch_scale<T>(nl, dst, 1.0 / br.rho[(size_t)(j - br.k0)], nullptr, s);
+        ++n_block_flushed;
+      }
+    }
+    const double* r2 = bb.rho2 + std::max<int64_t>(last, 0);
+    pending = None{};
+    refs_prev = NormRefs{r2, r2, r2, 0};  // beta^2 of the last completed vector, for the next three-term update
+  }
+  bool block_pending() const { return pending_as<BlockIter>() != nullptr; }
   struct Tail {
     PairIter pair;
     int nvec = 0;  // pending vectors the result needs (0: none, no tail; 1: u_P; 2: u_P and u_{P+1})
+    bool block = false;  // the basis is raw: the GEMV's coefficients are transformed with `rows`
+    BlockRows rows;
   };
   Tail take_tail(int64_t count) {
     Tail t;
+    if (const BlockIter* bi = pending_as<BlockIter>()) {
+      t.block = true;
+      t.rows = fetch_block_rows(std::min<int64_t>(count, bi->k + 1));
+      pending = None{};
+      return t;
+    }
     if (const PairIter* pr = pending_as<PairIter>()) {
       t.pair = *pr;
       t.nvec = (int)std::max<int64_t>(0, std::min<int64_t>(2, count - pr->P));
@@ -486,12 +614,44 @@ template <typename T> struct LoopState {
   RunList<T> ritz_basis(const Tail& tail, int64_t m, int64_t nw, std::vector<T>& coeff) {
     RunList<T> basis;
     basis.ld = ld;
+    constexpr int R = Engine<T>::R;
+    typedef std::complex<double> Z;
+    if (tail.block) {
+      // raw basis: sum_j q_j u_j = sum_j c'_j a_j with c'_j = (q_j - sum_{k>j} C_k[j] q_k / rho_k) / rho_j, first order in C
+      const BlockRows& br = tail.rows;
+      const int64_t end = std::min<int64_t>(br.end, m);
+      std::vector<Z> cs((size_t)m);
+      for (int64_t w = 0; w < nw; ++w) {
+        T* q = coeff.data() + (size_t)w * m;
+        for (int64_t j = 0; j < m; ++j) {
+          if constexpr (scalar_traits<T>::is_complex) cs[(size_t)j] = Z((double)q[j].re, (double)q[j].im);
+          else cs[(size_t)j] = Z((double)q[j], 0.0);
+        }
+        for (int64_t kk = br.k0; kk < end; ++kk) {
+          Z qk;
+          if constexpr (scalar_traits<T>::is_complex) qk = Z((double)q[kk].re, (double)q[kk].im);
+          else qk = Z((double)q[kk], 0.0);
+          const Z f = qk / br.rho[(size_t)(kk - br.k0)];
+          const double* row = br.row(kk);
+          for (int64_t l = 0; l < kk; ++l) cs[(size_t)l] -= (R == 2 ? Z(row[2 * l], row[2 * l + 1]) : Z(row[l], 0.0)) * f;
+        }
+        for (int64_t j = 0; j < m; ++j) {
+          const Z v = j >= br.k0 && j < end ? cs[(size_t)j] / br.rho[(size_t)(j - br.k0)] : cs[(size_t)j];
+          if constexpr (scalar_traits<T>::is_complex) {
+            q[j].re = (decltype(q[j].re))v.real();
+            q[j].im = (decltype(q[j].im))v.imag();
+          } else {
+            q[j] = (T)v.real();
+          }
+        }
+      }
+      basis.add_basis(U, m);
+      return basis;
+    }
     if (tail.nvec == 0) {
       basis.add_basis(U, m);
       return basis;
     }
-    constexpr int R = Engine<T>::R;
-    typedef std::complex<double> Z;
     const int64_t Pt = tail.pair.P, L = n_locked, K = L + Pt;
     std::vector<double> g1h((size_t)R * K + 1), g2h((size_t)R * (K + 1) + 1), rho(2, 1.0);
     if (K > 0) E.fetch(tail.pair.g[0], g1h.data(), (size_t)R * K);
@@ -538,6 +698,102 @@ template <typename T> struct LoopState {
     basis.add(tail.pair.r[0], 1);
     if (tail.nvec == 2) basis.add(tail.pair.r[1], 1);
     return basis;
+  }
+  // Iterations kk .. kk + m - 1 in the block form, m = 4, or 2 or 1 where fewer remain before max_iteration.  Entered from the
+  // one-sweep state (iteration kk - 1 pending with its measured coefficients, u_0 .. u_{kk-2} complete) or continued from a block.
+  // Returns m; 0: not taken.
+  int64_t enqueue_block(int64_t kk, double offset) {
+    if constexpr (sizeof(typename scalar_traits<T>::real) != 8) {
+      return 0;  // (single precision keeps the pair form: the block kernels exist for double and complex double)
+    } else {
+    constexpr int R = Engine<T>::R;
+    const Tuning& tune = E.ctx->tune;
+    if (!block_enabled || !block_allowed || !pair_allowed || !lag_ok || n_locked != 0) return 0;
+    const BlockIter* const bi = pending_as<BlockIter>();
+    const LaggedIter* const lg = pending_as<LaggedIter>();
+    int64_t k;  // index of the last stored vector
+    if (bi) {
+      if (bi->k + 1 != kk) return 0;
+      k = bi->k;
+    } else if (lg && lg->k == kk - 1 && kk >= 3) {
+      k = kk - 1;
+    } else {
+      return 0;
+    }
+    const int64_t remaining = max_k_hint - (kk - 1);  // never beyond the loop's max_iteration
+    if (remaining < 1) return 0;
+    const int m = remaining >= 4 ? 4 : (remaining >= 2 ? 2 : 1);
+    // the streaming geometry of the pipelined pair sweep (launch_pair_sweep), within the records
+    const int64_t strips16k = (nl * (int64_t)sizeof(T) + 16383) / 16384;
+    const bool streaming = tune.sweep_pipeline >= 2 || strips16k > 2 * kCUs + kCUs / 4;
+    if (!streaming || vec_bytes() < stream_bytes() || k + m + 1 > bb.cap || (size_t)(k + m + 1) > kVtabCap) return 0;
+    if (tune.pair_max_stored > 0 && k + 1 > tune.pair_max_stored) return 0;  // (test hook: the hand-over to the one-sweep form)
+    const int W = (int)(k + 1);
+    const int ncols = m * R * W + R * m * (m - 1) / 2 + m;
+    int per_launch = block_sweep_max_vecs<T>(m);
+    if (tune.pair_split_vecs > 0) per_launch = std::min(per_launch, std::max(1, tune.pair_split_vecs));
+    if (W > per_launch)
+      for (auto& b : bsplit)
+        if (!b.p) b.alloc(E.ctx, (size_t)ld);
+    const double te0 = now_s();
+    want_partial_cols((size_t)std::max(ncols, 1 + R));
+    if (!bi) {  // a_k moves from its work buffer into its basis slot; the records start here
+      LL_HIP(hipMemcpyAsync(U.vec(k), work[k & 1].p, (size_t)nl * sizeof(T), hipMemcpyDeviceToDevice, s));
+      launch_block_enter((int)k, R, lb.g[k & 1], lg->c1, bb.rho2, bb.cpk, s);
+      blk_k0 = k;
+    }
+    BlockVecs<T> bv{};
+    for (int i = 0; i < m; ++i) bv.b[i] = U.vec(k + 1 + i);  // (may add a slab: the pointer table is brought up to date after it)
+    bv.part[0] = bsplit[0].p;
+    bv.part[1] = bsplit[1].p;
+    const T* const* vt = vtab_sync();
+    BlockScalars sc{};
+    BlockHost host{};
+    int slots[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) {
+      const int ii = std::min(i, m - 1);
+      slots[i] = (int)((kk + ii) % kRingSlots);
+      sc.e[i] = E.S(kScalAlpha + slots[i]);
+      sc.nsq[i] = bb.nsq + 4 * ii;
+      host.slot[i] = pinned_slot(slots[i]);
+      host.gate[i] = pinned_gate(slots[i]);
+    }
+    // ---- m x (operator on the previous vector / its norm, raw three-term update, |b|^2)
+    for (int i = 0; i < m; ++i) {
+      const T* x = i == 0 ? U.vec(k) : bv.b[i - 1];
+      const T* xp = i == 0 ? U.vec(k - 1) : (i == 1 ? U.vec(k) : bv.b[i - 2]);
+      const double* xn2 = i == 0 ? bb.rho2 + k : bb.nsq + 4 * (i - 1);
+      const double* pn2 = i == 0 ? bb.rho2 + k - 1 : (i == 1 ? bb.rho2 + k : bb.nsq + 4 * (i - 2));
+      double* e = E.S(kScalAlpha + slots[i]);
+      timer.mark();
+      typename Engine<T>::DeferredAlpha da;
+      E.apply(x, bv.b[i], offset, e, true, fuse_launches ? &da : nullptr, nullptr, xn2);
+      timer.mark();
+      const int g3 = launch_pair_three_term<T>(nl, bv.b[i], x, xp, e, da.nparts > 0 ? da.partials : nullptr, da.nparts, xn2, pn2,
+                                               E.ctx->partials.get(), false, s);
+      launch_reduce_cols(E.ctx->partials.get(), g3, 1 + R, bb.nsq + 4 * i, nullptr, s);
+      if (i + 1 < m) timer.mark();
+    }
+    // ---- one sweep for all of them
+    launch_block_predict((int)k, m, R, sc, bb.rho2, bb.cpk, lb.hist_alpha, lb.hist_beta, bb.dk, bb.p, (int)bb.rec, bb.prA, bb.prB, s);
+    const int grid = launch_block_sweep<T>(nl, vt, W, m, bv, bb.prA, bb.prB, E.ctx->partials.get(), tune.lagged_pieces, per_launch, s);
+    launch_reduce_cols(E.ctx->partials.get(), grid, ncols, bb.cols, nullptr, s);
+    const int ev = slots[m - 1];  // ONE event for the block: its scalars are published by the same fold kernel
+    launch_block_fold(bb.cols, (int)k, m, R, sc, bb.p, (int)bb.rec, bb.rho2, bb.cpk, lb.hist_alpha, lb.hist_beta, bb.raw0, bb.raw1, host, s,
+                      tune.event_in_launch ? ring.ev[ev] : nullptr);
+    if (!tune.event_in_launch) LL_HIP(hipEventRecord(ring.ev[ev], s));
+    timer.mark();
+    for (int i = 0; i < m; ++i) {
+      ev_of_slot[slots[i]] = ev;
+      slot_pair[slots[i]] = true;
+    }
+    pending = BlockIter{k + m};
+    n_block += m;
+    if (m >= 2) n_pair += m;  // (iterations that shared a sweep with a neighbour)
+    n_lagged += m;
+    t_enqueue += now_s() - te0;
+    return m;
+    }
   }
   // Iterations k and k + 1 in the pair form.  Entered from the one-sweep state (iteration k - 1 pending with its measured
   // coefficients: u_{k-2} plays the part of an already complete first vector, g1 = 0, rho1 = 1) or continued from a pair.
@@ -782,7 +1038,10 @@ template <typename T> struct LoopState {
   // Enqueue the next iteration(s) from k on: two at once where the pair form applies (one sweep over the basis for both), else
   // one, orthogonalised against the locked vectors and u_0 .. u_{k-1} (full) or against nothing.  Returns how many.
   int64_t enqueue_group(int64_t k, double offset, int mode, bool full) {
-    if (dgks && !pending_as<DeferredIter>() && enqueue_pair(k, offset)) return 2;
+    if (dgks && !pending_as<DeferredIter>()) {
+      if (const int64_t m = enqueue_block(k, offset)) return m;
+      if (enqueue_pair(k, offset)) return 2;
+    }
     RunList<T> runs;
     runs.ld = ld;
     if (full) runs = basis_runs(k);
@@ -843,6 +1102,7 @@ template <typename T> struct LoopState {
       // second-order inaccurate: u_j is completed with its measured coefficients, everything after it is enqueued again, and
       // the rest of the pass runs in the one-sweep form (exact for coefficients of any size).
       pair_allowed = false;
+      block_allowed = false;
       ++n_gate_trips;
       make_final(j);
       launch_set_scalar(beta2_dev, r.beta2, s);
@@ -960,6 +1220,8 @@ void fill_stats(ll_run_stats* stats, LoopState<T>& loop, int64_t total_iteration
     stats->lagged_iterations = loop.n_lagged;
     stats->pair_iterations = loop.n_pair;
     stats->pair_gate_trips = loop.n_gate_trips;
+    stats->reserved[0] = loop.n_block;          // block_iterations
+    stats->reserved[1] = loop.n_block_flushed;  // block_flushed_vectors
     loop.timer.collect(stats->seconds_spmv, stats->seconds_orth);
     ctx->drain_comm_events(&stats->seconds_comm_gather, &stats->seconds_comm_allreduce);
     stats->seconds_total = now_s() - t_start;

@@ -283,6 +283,7 @@ struct Tuning {
   bool event_in_launch = true;     // key event_in_launch = 0: iteration events as marker packets behind the publishing kernel (A/B)
   bool ritz_tail = true;           // key ritz_tail = 0: a pair pending at the end of a pass is completed by sweeps of its own instead of entering the Ritz GEMV through its raw vectors (A/B)
   int sweep_pipeline = 1;          // key sweep_pipeline: 1 (default) the software-pipelined pair sweep on streaming vectors (> ~9 MiB), 0 never (A/B: same bits), 2 on every length (parity tests on small cases)
+  bool block_gs = true;            // key block_gs = 0: never the raw-basis block form (up to four iterations per sweep); the pair form where it applies (A/B)
   bool pair_gs = true;             // LL_PAIR_GS=0: never two iterations per sweep (the one-sweep form throughout; A/B and parity hunts)
   // --- test hooks (not for users)
   bool force_rp64 = false;         // key force_rp64 = 1: 64-bit row offsets on small matrices
@@ -920,6 +921,36 @@ void launch_pair_fold(const double* m, int P, int L, int reals, const double* la
                       const double* rho2sq, const double* n3sq, const double* e1, const double* e2, double* rec3, double* rec4,
                       double* nxt, double* hist_alpha, double* hist_beta, double* scratch, double* host_a, double* host_b,
                       double* gate_a, double* gate_b, hipStream_t s, hipEvent_t stop = nullptr);
+// The block form (up to four iterations per sweep over a RAW basis; gs_block.hip; tools/block_gs_model.py is the executable
+// specification).  Streaming geometry, double and complex double, no locked columns.  The form keeps reals * K^2 / 2 coefficients
+// for a pass of K vectors and leaving it costs one multi-axpy per raw vector, so it is bounded by a vector count and only taken by
+// passes that cannot outgrow it (LoopState::enqueue_block).
+constexpr int kBlockMaxVecs = 1024;
+struct BlockScalars {
+  const double* e[4];    // <x, A x> of the block's operator applications
+  const double* nsq[4];  // |b_s|^2 of the raw three-term vectors
+};
+struct BlockHost {
+  double* slot[4];  // host slots of the block's iterations (alpha, beta^2, ||w||^2 before, after)
+  double* gate[4];  // ... and their gate values
+};
+template <typename T> struct BlockVecs {
+  T* b[4];     // the new vectors in their basis slots; the sweep rewrites the last two
+  T* part[2];  // hand-over vectors of a split sweep (touched only when there is more than one launch)
+};
+template <typename T> constexpr int block_sweep_max_vecs(int m) {  // stored vectors per launch: 4 x (m reals Wl + Gram) doubles of LDS
+  return (kLaggedMaxCols - (scalar_traits<T>::reals * m * (m - 1) / 2 + m)) / (m * scalar_traits<T>::reals);
+}
+void launch_block_enter(int k, int reals, const double* g, const double* c1, double* rho2, double* cpk, hipStream_t s);
+void launch_block_predict(int k, int m, int reals, const BlockScalars& sc, const double* rho2, const double* cpk, double* hist_alpha,
+                          const double* hist_beta, double* dk, double* p, int pstride, double* prA, double* prB, hipStream_t s);
+// vtab: column c -> pointer of stored vector c (W of them); per_launch: at most that many stored vectors per launch
+template <typename T>
+int launch_block_sweep(int64_t n, const T* const* vtab, int W, int m, const BlockVecs<T>& bv, const double* prA, const double* prB,
+                       double* partials, int pieces, int per_launch, hipStream_t s);
+void launch_block_fold(const double* cols, int k, int m, int reals, const BlockScalars& sc, const double* p, int pstride, double* rho2,
+                       double* cpk, double* hist_alpha, double* hist_beta, double* raw0, double* raw1, const BlockHost& host, hipStream_t s,
+                       hipEvent_t stop = nullptr);
 // Fold of a lagged iteration (K = L + k columns: L locked eigenvectors with eigenvalues lambda[0..L), then k Lanczos
 // vectors; m: reals * K folded columns, *c0 = ||w||^2, copied to *c0_out): compensated coefficients in place,
 // *c1 = *c0 - |g|^2, t_out (reals * (K + 1) + 1) for the next sweep, alpha / beta appended to hist_*[k - 1], *alpha
