@@ -14,7 +14,7 @@
 namespace ll {
 
 // Device scalar area (ctx->scal, 64 doubles):
-//   [0..8)    alpha ring (slot = k % 8: kRingSlots, lanczos_loop.hpp)
+//   [0..8)    alpha ring (slot = k % 8: kRingSlots, loop_support.hpp)
 //   [8..32)   norm triples (c0,c1,c2) ring, slot s at 8 + 3*s
 //   [32..35)  scratch triple for one-off orthogonalisations (start vector, primitives)
 //   [40]      spare scalar (dot results)

@@ -25,11 +25,6 @@ struct StallTrace {
   }
 };
 
-inline void from_std(double v, double* o) { *o = v; }
-inline void from_std(std::complex<double> v, zc* o) { o->re = v.real(); o->im = v.imag(); }
-inline void from_std(double v, float* o) { *o = (float)v; }
-inline void from_std(std::complex<double> v, cf* o) { o->re = (float)v.real(); o->im = (float)v.imag(); }
-
 }  // namespace
 
 // ================================================================= Exponentiator<T>::run
@@ -89,10 +84,9 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
            [](int64_t, const typename LoopState<T>::Scalars&) {});
   itern = last.m;
   coeff_prev = last.coeff;
-  // (a pending pair: the output below needs u_0 .. u_{m-1} complete in the basis; a raw basis of the block form enters the GEMV
-  // through transformed coefficients instead)
-  if (!LS.block_pending() || !ctx->tune.ritz_tail) LS.pair_flush((int64_t)coeff_prev.size());
-  const typename LoopState<T>::Tail tail = LS.take_tail((int64_t)coeff_prev.size());
+  // (the output below needs u_0 .. u_{m-1}: a pending pair is completed in the basis, a raw basis of the block form enters the GEMV
+  // through transformed coefficients)
+  const typename LoopState<T>::Tail tail = LS.end_pass((int64_t)coeff_prev.size(), false);
   alpha.resize((size_t)itern);
   beta.resize((size_t)itern);
   st.at("loop");
@@ -102,7 +96,7 @@ void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P_in, type
   // output = ||input|| * sum_l coeff_prev[l] u[l]  (EX:163-170)
   const int64_t m = (int64_t)coeff_prev.size();
   std::vector<T> c((size_t)m);
-  for (int64_t l = 0; l < m; ++l) from_std(H(in_norm) * coeff_prev[l], &c[l]);
+  for (int64_t l = 0; l < m; ++l) from_z(H(in_norm) * coeff_prev[l], &c[l]);
   DevBuf<T> d_out;
   d_out.alloc(ctx, (size_t)ld);
   const RunList<T> basis = LS.ritz_basis(tail, m, 1, c);
@@ -159,7 +153,7 @@ void taylor_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P, typen
   }
   std::vector<T> c((size_t)terms);
   for (int64_t k = terms; k-- > 0;) {  // backward sum with the reference's factor recurrence (EX:198-206)
-    from_std(factor, &c[k]);
+    from_z(factor, &c[k]);
     factor *= H((double)k) / a;
   }
   DevBuf<T> d_out;

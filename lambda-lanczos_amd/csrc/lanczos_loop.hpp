@@ -3,10 +3,13 @@
 // and two diagnostics) through pinned, device-mapped memory and runs the k x k tridiagonal step (a11/a12) while
 // the device already executes iteration k+1 (lag-1 speculation: a speculative iteration only writes basis slots
 // the results never read, so stopping one iteration "late" on the device is harmless).
-// This header is the loop machinery both drivers share (lanczos_run.cpp, expo_run.cpp): nothing else includes it.
+// This header is the loop machinery both drivers share (lanczos_run.cpp, expo_run.cpp; two_pass_run.cpp takes the argument checks and
+// the speculation policy at its end).  Run-scoped resources: loop_support.hpp; the host algebra of the raw-basis forms: raw_basis.hpp.
 #pragma once
 
 #include "engine.hpp"
+#include "loop_support.hpp"
+#include "raw_basis.hpp"
 #include "ritz_tracker.hpp"
 #include "trace.hpp"
 
@@ -14,7 +17,6 @@
 #include <cmath>
 #include <limits>
 #include <string>
-#include <utility>
 #include <variant>
 
 namespace ll {
@@ -26,103 +28,6 @@ namespace ll {
 //                   (StepWorker::consume); each stop costs that many speculative iterations, a slow host step is hidden
 //                   for that many (LL_TRIDIAG_LAG; negative: the single-process opportunistic policy — unsafe with more
 //                   than one rank, kept to demonstrate the hang).
-
-// A run-scoped device buffer.  Like the Krylov slabs it comes from, and goes back to, the context's slab cache: a
-// hipMalloc / hipFree pair per run() costs hundreds of microseconds (hipFree synchronises the device) — most of a run on
-// the small problems the reference is used for.
-template <typename T> struct DevBuf {
-  T* p = nullptr;
-  ll_context* owner = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p && owner) owner->cache_put((void*)p, bytes);
-    p = nullptr;
-  }
-  void alloc(ll_context* ctx, size_t count) {
-    release();
-    owner = ctx;
-    bytes = std::max<size_t>(count * sizeof(T), 16);
-    for (size_t i = 0; i < ctx->slab_cache.size(); ++i)
-      if (ctx->slab_cache[i].second == bytes) {
-        p = (T*)ctx->slab_cache[i].first;
-        ctx->slab_cache.erase(ctx->slab_cache.begin() + (long)i);
-        break;
-      }
-    if (!p) ctx->dev_malloc((void**)&p, bytes, "work vectors");
-    ctx->test_fill_if_set(p, bytes / sizeof(T));
-  }
-};
-
-// The host's read-back area (ctx->pinned, pinned and device-mapped): iteration k publishes its four scalars (alpha, beta^2, c0, c1)
-// into ring slot k % kRingSlots; the gate values of the pair and block forms follow the slots, one per slot.  Eight slots: a
-// block of four iterations is enqueued while the four of the block before it are still being collected.
-constexpr int kRingSlots = 8, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
-constexpr size_t kPinnedScalars = 48;  // (kGateAt + kRingSlots used)
-
-struct EventRing {
-  hipEvent_t ev[kRingSlots];
-  EventRing() {
-    for (auto& e : ev) LL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  ~EventRing() {
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
-};
-
-struct PhaseTimer {  // optional per-phase device timing (HIP events on the context's stream)
-  // Marks come in triples — start, after the operator, end of the iteration (or pair) — and are recorded into a RING of events
-  // that the context keeps between runs: a triple is read back (its events completed long ago: the host runs a group or two ahead
-  // of the device) when its slot comes round again.  (One fresh event per mark — 900 for config 3's run to convergence, 10 000 for
-  // config 2's — cost the first profiled run of a process up to 0.5 s of host time in hipEventCreate on some boxes.)
-  static constexpr size_t kTriples = 128;
-  bool on;
-  hipStream_t s;
-  std::vector<hipEvent_t>& evs;
-  size_t n = 0;  // marks so far
-  double acc_op = 0.0, acc_rest = 0.0;
-  PhaseTimer(ll_context* ctx, hipStream_t st) : on(ctx->profiling), s(st), evs(ctx->timer_events) {}
-  void read(size_t first) {
-    float a = 0, b = 0;
-    if (hipEventSynchronize(evs[first + 2]) != hipSuccess) return;
-    if (hipEventElapsedTime(&a, evs[first], evs[first + 1]) == hipSuccess) acc_op += a * 1e-3;
-    if (hipEventElapsedTime(&b, evs[first + 1], evs[first + 2]) == hipSuccess) acc_rest += b * 1e-3;
-  }
-  void mark() {
-    if (!on) return;
-    const size_t slot = n % (3 * kTriples);
-    if (slot % 3 == 0 && n >= 3 * kTriples) read(slot);  // the triple that used these events
-    if (slot >= evs.size()) {
-      hipEvent_t e;
-      LL_HIP(hipEventCreate(&e));
-      evs.push_back(e);
-    }
-    LL_HIP(hipEventRecord(evs[slot], s));
-    ++n;
-  }
-  void collect(double& t_op, double& t_rest) {
-    if (!on) return;
-    // complete triples still in the ring: the last min(n / 3, kTriples) ones, minus those already read when their slot was reused
-    const size_t triples = n / 3, done = n >= 3 * kTriples ? (n - 3 * kTriples) / 3 + ((n % 3) ? 1 : 0) : 0;
-    for (size_t t = done; t < triples; ++t) read((t % kTriples) * 3);
-    t_op += acc_op;
-    t_rest += acc_rest;
-    acc_op = acc_rest = 0.0;
-    n = 0;
-  }
-};
-
-// ll_context::stop_next for one operator application: set on entry, cleared on every exit — a throwing apply included, so that no later
-// launch on the context is handed an event of a ring that has gone away (~EventRing)
-struct StopNext {
-  ll_context* ctx;
-  StopNext(ll_context* c, hipEvent_t ev) : ctx(c) { ctx->stop_next = ev; }
-  ~StopNext() { ctx->stop_next = nullptr; }
-  bool taken() const { return ctx->stop_next == nullptr; }  // the launcher hung the event on its kernel
-};
-
-// The next `count` doubles of a buffer that is carved into regions (LoopState::PairBuf, LoopState::LagBuf)
-inline double* carve(double*& at, size_t count) { return std::exchange(at, at + count); }
 
 // One Lanczos iteration as the device sees it, shared by the eigen-solver and the Exponentiator loops:
 //   y = A u_{k-1} + offset u_{k-1}, alpha (a1-a3)  ->  three-term update + Gram-Schmidt against `runs` + norm (a4-a7)
@@ -244,7 +149,7 @@ template <typename T> struct LoopState {
     int64_t cap = 0;           // vectors the records are sized for
     size_t rec = 0;            // doubles per record
   } bb;
-  static size_t block_row_at(int64_t j) { return (size_t)Engine<T>::R * (size_t)j * (size_t)(j > 0 ? j - 1 : 0) / 2; }
+  static size_t block_row_at(int64_t j) { return ll::block_row_at(Engine<T>::R, j); }
   void enable_block() {
     constexpr size_t R = (size_t)Engine<T>::R;
     block_enabled = true;
@@ -478,17 +383,21 @@ template <typename T> struct LoopState {
     }
     return tt;
   }
+  // dst -= [locked, u_0 .. u_{j-1}] c with the device coefficients c (reals per stored vector): one multi-axpy per launch group
+  void subtract_basis(T* dst, int64_t j, const double* c) {
+    const RunList<T> runs = basis_runs(j);
+    int off = 0;
+    for (auto& grp : runs.groups(max_vecs_per_launch<T>())) {
+      launch_maxpy<T>(nl, dst, grp, c + Engine<T>::R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
+      for (int i = 0; i < grp.nseg; ++i) off += grp.count[i];
+    }
+  }
   // u_j = (raw - [locked, u_0 .. u_{j-1}] g) / rho in its basis slot, with the two-sweep kernels: a raw vector completed with its
   // measured coefficients g (reals per stored vector) and the squared norm *rho2 of its orthogonal part
   void complete_raw(int64_t j, const T* raw, const double* g, const double* rho2) {
     T* dst = U.vec(j);
     if (dst != raw) LL_HIP(hipMemcpyAsync(dst, raw, (size_t)nl * sizeof(T), hipMemcpyDeviceToDevice, s));
-    const RunList<T> runs = basis_runs(j);
-    int off = 0;
-    for (auto& grp : runs.groups(max_vecs_per_launch<T>())) {
-      launch_maxpy<T>(nl, dst, grp, g + Engine<T>::R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
-      for (int i = 0; i < grp.nseg; ++i) off += grp.count[i];
-    }
+    subtract_basis(dst, j, g);
     const NormRefs nr{rho2, rho2, rho2, 0};
     launch_scale<T>(nl, dst, 0.0, &nr, s);
   }
@@ -514,11 +423,7 @@ template <typename T> struct LoopState {
   // u_0 .. u_{P+1} are complete, nothing is pending, and iteration P + 2 can be enqueued from a clean state.
   // count: only the vectors u_j with j < count are needed (end of a pass: the Ritz vectors use u_0 .. u_{m-1}; a repair of u_j:
   // nothing behind u_j survives it) — a pending vector beyond that is dropped instead of completed.
-  void pair_flush(int64_t count = std::numeric_limits<int64_t>::max()) {
-    if (pending_as<BlockIter>()) {
-      block_flush(count - 1);
-      return;
-    }
+  void pair_flush(int64_t count) {
     const PairIter* pr = pending_as<PairIter>();
     if (!pr) return;
     // (g[1]: R * P coefficients against the basis, then <u_P, r[1]>: one contiguous list)
@@ -527,18 +432,14 @@ template <typename T> struct LoopState {
     pending = None{};
     refs_prev = NormRefs{rho2, rho2, rho2, 0};  // beta^2 of the last completed vector, for the next three-term update
   }
-  // End of a pass with a pair pending: the Ritz vectors need u_0 .. u_{count-1}, of which u_P (and u_{P+1}) exist only as raw
-  // vectors with their measured coefficients.  Instead of completing them with a sweep of their own (pair_flush: the whole basis
-  // read once per pending vector — 1.4 ms of a 131 ms step on config 3), ritz_basis folds the late update into the COEFFICIENTS of the
-  // Ritz GEMV:  u_P = (r1 - S g1) / rho1,  u_{P+1} = (r2 - S g2 - gam u_P) / rho2  =>  sum_k s_k u_k is a combination of S, r1, r2.
-  struct BlockRows {  // the record of the raw vectors a_k0 .. a_{end-1} on the host
-    int64_t k0 = 0, end = 0;
-    std::vector<double> rows;  // rows k0 .. end - 1 of the packed triangle
-    std::vector<double> rho;   // rho_k0 .. rho_{end-1}
-    const double* row(int64_t j) const { return rows.data() + (block_row_at(j) - block_row_at(k0)); }
-  };
+  // Leave whichever of the two forms is pending: the raw vectors among u_0 .. u_{count-1} are completed, those behind are dropped
+  void flush_raw(int64_t count = std::numeric_limits<int64_t>::max()) {
+    if (pending_as<BlockIter>()) block_flush(count - 1);
+    else pair_flush(count);
+  }
   BlockRows fetch_block_rows(int64_t end) {
     BlockRows br;
+    br.R = Engine<T>::R;
     br.k0 = blk_k0;
     br.end = std::max(end, blk_k0);
     const size_t cnt = (size_t)(br.end - br.k0);
@@ -555,29 +456,19 @@ template <typename T> struct LoopState {
   // uses only raw vectors of lower index, which the descending order has not touched yet.  Whatever lies behind a_last (later vectors
   // of a block that a gate, a repair or a stop cut) is dropped.  One multi-axpy over the basis per raw vector.
   void block_flush(int64_t last) {
-    constexpr int R = Engine<T>::R;
     const BlockIter* bi = pending_as<BlockIter>();
     if (!bi) return;
     last = std::min(last, bi->k);
     if (last >= blk_k0) {
       BlockRows br = fetch_block_rows(last + 1);
-      for (int64_t j = br.k0; j <= last; ++j) {  // C_j[l] / rho_l, in place
-        double* row = br.rows.data() + (block_row_at(j) - block_row_at(br.k0));
-        for (int64_t l = br.k0; l < j; ++l)
-          for (int q = 0; q < R; ++q) row[(size_t)R * l + q] /= br.rho[(size_t)(l - br.k0)];
-      }
+      block_rows_over_raw(br, last);
       if (br.rows.size() > 1) {
         LL_HIP(hipMemcpyAsync(bb.cpk + block_row_at(br.k0), br.rows.data(), (br.rows.size() - 1) * sizeof(double), hipMemcpyHostToDevice, s));
         LL_HIP(hipStreamSynchronize(s));  // (pageable source)
       }
       for (int64_t j = last; j >= br.k0; --j) {
         T* dst = U.vec(j);
-        const RunList<T> runs = basis_runs(j);
-        int off = 0;
-        for (auto& grp : runs.groups(max_vecs_per_launch<T>())) {
-          launch_maxpy<T>(nl, dst, grp, bb.cpk + block_row_at(j) + (size_t)R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
-          for (int i = 0; i < grp.nseg; ++i) off += grp.count[i];
-        }
+        subtract_basis(dst, j, bb.cpk + block_row_at(j));
         launch_scale<T>(nl, dst, 1.0 / br.rho[(size_t)(j - br.k0)], nullptr, s);
         ++n_block_flushed;
       }
@@ -586,7 +477,9 @@ template <typename T> struct LoopState {
     pending = None{};
     refs_prev = NormRefs{r2, r2, r2, 0};  // beta^2 of the last completed vector, for the next three-term update
   }
-  bool block_pending() const { return pending_as<BlockIter>() != nullptr; }
+  // End of a pass with raw vectors pending: of the u_0 .. u_{count-1} the Ritz vectors need, u_P (and u_{P+1}) of a pair, or a_k0 .. of a
+  // block, exist only as raw vectors with their measured coefficients.  Instead of completing them (flush_raw: the whole basis read once
+  // per pending vector — 1.4 ms of a 131 ms step on config 3), ritz_basis folds the late update into the GEMV's COEFFICIENTS (raw_basis.hpp).
   struct Tail {
     PairIter pair;
     int nvec = 0;  // pending vectors the result needs (0: none, no tail; 1: u_P; 2: u_P and u_{P+1})
@@ -608,92 +501,31 @@ template <typename T> struct LoopState {
     }
     return t;
   }
+  // The end of a pass, the one entry of both drivers: what is raw among u_0 .. u_{count-1} goes into the returned tail, or is completed
+  // first (flush_raw): with ritz_tail = 0 (A/B), and a pair where the caller takes no pair tail (the Exponentiator calls its GEMV with m columns).
+  Tail end_pass(int64_t count, bool pair_tail_ok) {
+    if (!E.ctx->tune.ritz_tail || !(pair_tail_ok || pending_as<BlockIter>())) flush_raw(count);
+    return take_tail(count);
+  }
   // The GEMV of the Ritz vectors x_w = sum_{k<m} s_wk u_k (coeff: nw rows of m): returns the basis runs the GEMV reads and rewrites
-  // coeff to match them, one row of runs.total() per vector.  Without a tail those are u_0 .. u_{m-1}; with one, the stored columns of
-  // the last sweep (locked vectors first, then u_0 .. u_{P-1}), then r1 (and r2).
+  // coeff to match them, one row of runs.total() per vector.  Without a pair tail those are u_0 .. u_{m-1} (raw from a_k0 on with a
+  // block tail); with one, the stored columns of the last sweep (locked vectors first, then u_0 .. u_{P-1}), then r1 (and r2).
   RunList<T> ritz_basis(const Tail& tail, int64_t m, int64_t nw, std::vector<T>& coeff) {
     RunList<T> basis;
     basis.ld = ld;
+    if (tail.block || tail.nvec == 0) {
+      if (tail.block) block_coeff_over_raw(tail.rows, m, nw, coeff.data());
+      basis.add_basis(U, m);
+      return basis;
+    }
     constexpr int R = Engine<T>::R;
-    typedef std::complex<double> Z;
-    if (tail.block) {
-      // raw basis: sum_j q_j u_j = sum_j c'_j a_j with c'_j = (q_j - sum_{k>j} C_k[j] q_k / rho_k) / rho_j, first order in C
-      const BlockRows& br = tail.rows;
-      const int64_t end = std::min<int64_t>(br.end, m);
-      std::vector<Z> cs((size_t)m);
-      for (int64_t w = 0; w < nw; ++w) {
-        T* q = coeff.data() + (size_t)w * m;
-        for (int64_t j = 0; j < m; ++j) {
-          if constexpr (scalar_traits<T>::is_complex) cs[(size_t)j] = Z((double)q[j].re, (double)q[j].im);
-          else cs[(size_t)j] = Z((double)q[j], 0.0);
-        }
-        for (int64_t kk = br.k0; kk < end; ++kk) {
-          Z qk;
-          if constexpr (scalar_traits<T>::is_complex) qk = Z((double)q[kk].re, (double)q[kk].im);
-          else qk = Z((double)q[kk], 0.0);
-          const Z f = qk / br.rho[(size_t)(kk - br.k0)];
-          const double* row = br.row(kk);
-          for (int64_t l = 0; l < kk; ++l) cs[(size_t)l] -= (R == 2 ? Z(row[2 * l], row[2 * l + 1]) : Z(row[l], 0.0)) * f;
-        }
-        for (int64_t j = 0; j < m; ++j) {
-          const Z v = j >= br.k0 && j < end ? cs[(size_t)j] / br.rho[(size_t)(j - br.k0)] : cs[(size_t)j];
-          if constexpr (scalar_traits<T>::is_complex) {
-            q[j].re = (decltype(q[j].re))v.real();
-            q[j].im = (decltype(q[j].im))v.imag();
-          } else {
-            q[j] = (T)v.real();
-          }
-        }
-      }
-      basis.add_basis(U, m);
-      return basis;
-    }
-    if (tail.nvec == 0) {
-      basis.add_basis(U, m);
-      return basis;
-    }
-    const int64_t Pt = tail.pair.P, L = n_locked, K = L + Pt;
+    const int64_t Pt = tail.pair.P, K = n_locked + Pt;
     std::vector<double> g1h((size_t)R * K + 1), g2h((size_t)R * (K + 1) + 1), rho(2, 1.0);
     if (K > 0) E.fetch(tail.pair.g[0], g1h.data(), (size_t)R * K);
     E.fetch(tail.pair.g[1], g2h.data(), (size_t)R * (K + 1));
     E.fetch(tail.pair.rho2[0], &rho[0], 1);
     E.fetch(tail.pair.rho2[1], &rho[1], 1);
-    const double rho1 = std::sqrt(rho[0]), rho2 = std::sqrt(rho[1]);
-    auto gz = [&](const std::vector<double>& g, int64_t j) { return R == 2 ? Z(g[(size_t)2 * j], g[(size_t)2 * j + 1]) : Z(g[(size_t)j], 0.0); };
-    auto to_t = [&](Z v, T* o) {
-      if constexpr (scalar_traits<T>::is_complex) {
-        o->re = (decltype(o->re))v.real();
-        o->im = (decltype(o->im))v.imag();
-      } else {
-        *o = (T)v.real();
-      }
-    };
-    auto from_t = [&](const T& v) {
-      if constexpr (scalar_traits<T>::is_complex) return Z((double)v.re, (double)v.im);
-      else return Z((double)v, 0.0);
-    };
-    const int64_t mm = K + tail.nvec;
-    std::vector<T> c2((size_t)nw * mm);
-    std::vector<Z> cs((size_t)K);
-    for (int64_t w = 0; w < nw; ++w) {
-      const T* sw = coeff.data() + (size_t)w * m;
-      for (int64_t j = 0; j < K; ++j) cs[(size_t)j] = j < L ? Z(0.0, 0.0) : from_t(sw[j - L]);
-      Z a = from_t(sw[Pt]);                                              // coefficient of u_P
-      Z b = tail.nvec == 2 ? from_t(sw[Pt + 1]) : Z(0.0, 0.0);           // ... of u_{P+1}
-      Z on_r2(0.0, 0.0);
-      if (tail.nvec == 2) {
-        on_r2 = b / rho2;
-        for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r2 * gz(g2h, j);
-        a -= on_r2 * gz(g2h, K);                                         // gam = <u_P, r2>
-      }
-      const Z on_r1 = a / rho1;
-      for (int64_t j = 0; j < K; ++j) cs[(size_t)j] -= on_r1 * gz(g1h, j);
-      T* out = c2.data() + (size_t)w * mm;
-      for (int64_t j = 0; j < K; ++j) to_t(cs[(size_t)j], out + j);
-      to_t(on_r1, out + K);
-      if (tail.nvec == 2) to_t(on_r2, out + K + 1);
-    }
-    coeff.swap(c2);
+    coeff = pair_coeff_over_raw(R, g1h, g2h, std::sqrt(rho[0]), std::sqrt(rho[1]), n_locked, Pt, tail.nvec, m, nw, coeff);
     basis = basis_runs(Pt);
     basis.add(tail.pair.r[0], 1);
     if (tail.nvec == 2) basis.add(tail.pair.r[1], 1);
@@ -703,9 +535,10 @@ template <typename T> struct LoopState {
   // one-sweep state (iteration kk - 1 pending with its measured coefficients, u_0 .. u_{kk-2} complete) or continued from a block.
   // Returns m; 0: not taken.
   int64_t enqueue_block(int64_t kk, double offset) {
-    if constexpr (sizeof(typename scalar_traits<T>::real) != 8) {
-      return 0;  // (single precision keeps the pair form: the block kernels exist for double and complex double)
-    } else {
+    if constexpr (sizeof(typename scalar_traits<T>::real) == 8) return enqueue_block_f64(kk, offset);
+    else return 0;  // (single precision keeps the pair form: the block kernels, and enqueue_block_f64, exist for double and complex double)
+  }
+  int64_t enqueue_block_f64(int64_t kk, double offset) {
     constexpr int R = Engine<T>::R;
     const Tuning& tune = E.ctx->tune;
     if (!block_enabled || !block_allowed || !pair_allowed || !lag_ok || n_locked != 0) return 0;
@@ -793,7 +626,6 @@ template <typename T> struct LoopState {
     n_lagged += m;
     t_enqueue += now_s() - te0;
     return m;
-    }
   }
   // Iterations k and k + 1 in the pair form.  Entered from the one-sweep state (iteration k - 1 pending with its measured
   // coefficients: u_{k-2} plays the part of an already complete first vector, g1 = 0, rho1 = 1) or continued from a pair.
@@ -967,7 +799,7 @@ template <typename T> struct LoopState {
     return true;
   }
   void enqueue(int64_t k, double offset, const RunList<T>& runs, int mode) {
-    pair_flush();  // (a pending pair is completed first: the forms below start from complete vectors)
+    flush_raw();  // (a pending pair or block is completed first: the forms below start from complete vectors)
     if (mode == LL_ORTH_CGS_DGKS && !pending_as<DeferredIter>() && enqueue_lagged(k, offset, runs.total())) return;
     flush_lag();  // (leaving the lagged form: u_{k-1} must be complete)
     lag_ok = false;

@@ -40,11 +40,6 @@ template <> void default_init<zc>(zc* v, int64_t n) {
   }
 }
 
-inline double as_real_coeff(double v, double*) { return v; }
-inline zc as_real_coeff(double v, zc*) { return zc{v, 0.0}; }
-inline float as_real_coeff(double v, float*) { return (float)v; }
-inline cf as_real_coeff(double v, cf*) { return cf{(float)v, 0.0f}; }
-
 }  // namespace
 
 // ================================================================= LambdaLanczos<T>::run
@@ -179,9 +174,8 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
                                                    (long long)j, sc.alpha, sc.beta2, sc.c0, sc.c1, sc.redone ? 2 : 0);
                                   });
     itern = last.m;  // == max_iteration without a stop (LL:239,312)
-    // (a pending pair: the Ritz vectors below need u_0 .. u_{itern-1}; the pending ones enter the GEMV through their raw vectors)
-    if (!ctx->tune.ritz_tail) LS.pair_flush(itern);  // (A/B: complete the pending vectors with a sweep of their own)
-    const typename LoopState<T>::Tail tail = LS.take_tail(itern);
+    // (the Ritz vectors below need u_0 .. u_{itern-1}; the ones still raw enter the GEMV through their raw vectors)
+    const typename LoopState<T>::Tail tail = LS.end_pass(itern, true);
     if (trace_file) {
       std::fprintf(trace_file, "stop %lld %lld %d collected %zu\n", (long long)passes, (long long)itern, (int)stopped, alpha.size());
       std::fflush(trace_file);
@@ -258,11 +252,11 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
         const double t0 = now_s();
         tridiag_inverse_iteration(m, alpha.data(), beta.data(), nw, lam.data(), sv.data());
         t_tridiag += now_s() - t0;
-        for (size_t i = 0; i < sv.size(); ++i) coeff[i] = as_real_coeff(sv[i], (T*)nullptr);
+        for (size_t i = 0; i < sv.size(); ++i) from_z(sv[i], &coeff[i]);
       } else {
         for (int64_t w = 0; w < nw; ++w) {
           const int64_t it = P.find_maximum ? m - want[w] - 1 : want[w];
-          for (int64_t k = 0; k < m; ++k) coeff[(size_t)w * m + k] = as_real_coeff(tq[(size_t)it * m + k], (T*)nullptr);
+          for (int64_t k = 0; k < m; ++k) from_z(tq[(size_t)it * m + k], &coeff[(size_t)w * m + k]);
         }
       }
       const RunList<T> basis = LS.ritz_basis(tail, m, nw, coeff);

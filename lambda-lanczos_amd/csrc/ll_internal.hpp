@@ -19,6 +19,7 @@
 
 #include "../../include/lanczos_hip.h"
 #include "../../include/lanczos_hip_transport.h"
+#include "scalar_types.hpp"
 
 #if defined(__HIPCC__)
 // A launch whose completion IS an event: hipExtLaunchKernelGGL hangs the event on the kernel's own dispatch packet; hipEventRecord
@@ -33,49 +34,7 @@
 
 namespace ll {
 
-// ---------------------------------------------------------------- scalar types
-// Device-side complex<double>: interleaved (re, im), 16-byte aligned so that one element is one dwordx4 access.
-struct alignas(16) zc {
-  double re, im;
-};
-
-// Device-side complex<float>: interleaved (re, im), 8-byte aligned.
-struct alignas(8) cf {
-  float re, im;
-};
-
-// `reals` = doubles per REDUCED value (all reductions, coefficients and norms are carried in double / zc whatever the
-// storage type: float inputs are widened at the first accumulation, which is at least the reference's accuracy);
-// `acc` = that accumulator type.
-template <typename T> struct scalar_traits;
-template <> struct scalar_traits<double> {
-  static constexpr bool is_complex = false;
-  static constexpr int reals = 1;
-  typedef double acc;
-  typedef double real;
-};
-template <> struct scalar_traits<zc> {
-  static constexpr bool is_complex = true;
-  static constexpr int reals = 2;
-  typedef zc acc;
-  typedef double real;
-};
-template <> struct scalar_traits<float> {
-  static constexpr bool is_complex = false;
-  static constexpr int reals = 1;
-  typedef double acc;
-  typedef float real;
-};
-template <> struct scalar_traits<cf> {
-  static constexpr bool is_complex = true;
-  static constexpr int reals = 2;
-  typedef zc acc;
-  typedef float real;
-};
-template <typename T> using acc_t = typename scalar_traits<T>::acc;
-// Explicit instantiation for the four storage types: every translation unit lists the templates it defines ONCE, in a macro
-// M(T) per file section, and instantiates them with LL_FOR_EACH_SCALAR(M).
-#define LL_FOR_EACH_SCALAR(M) M(double) M(zc) M(float) M(cf)
+// ---------------------------------------------------------------- scalar types: scalar_types.hpp
 // The floating-point element types of device buffers (what the test hook test_workspace_fill fills; never an index type).
 template <typename T>
 inline constexpr bool is_float_elem_v = std::is_same_v<T, double> || std::is_same_v<T, float> || std::is_same_v<T, zc> || std::is_same_v<T, cf>;

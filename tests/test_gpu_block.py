@@ -14,7 +14,7 @@ from util import overlap
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("blas_small_bytes", "sweep_pipeline", "block_gs", "pair_split", "lagged_pieces", "test_workspace_fill")
+KEYS = ("blas_small_bytes", "sweep_pipeline", "block_gs", "pair_split", "lagged_pieces", "test_workspace_fill", "ritz_tail")
 
 
 def chain(n, t, cplx):
@@ -38,7 +38,7 @@ def fixed_init(v):
     return lambda out, *_: np.copyto(out, v)
 
 
-def run(ctx, csr, init, window, *, block=True, split=None, pieces=None, ivs=None, fill=None):
+def run(ctx, csr, init, window, *, block=True, split=None, pieces=None, ivs=None, fill=None, tail=True):
     n = len(init)
     settings = {"blas_small_bytes": "0", "sweep_pipeline": "2", "block_gs": "1" if block else "0"}
     if split:
@@ -47,6 +47,8 @@ def run(ctx, csr, init, window, *, block=True, split=None, pieces=None, ivs=None
         settings["lagged_pieces"] = str(pieces)
     if fill is not None:
         settings["test_workspace_fill"] = str(fill)
+    if not tail:
+        settings["ritz_tail"] = "0"
     try:
         for k, v in settings.items():
             ctx.set_tuning(k, v)
@@ -198,6 +200,27 @@ def test_off_switch_and_poisoned_workspace(ctx, oracle, cplx):
     took_the_form(poisoned["stats"], window)
     assert np.array_equal(poisoned["alpha"], on["alpha"]) and np.array_equal(poisoned["beta"], on["beta"])
     assert np.array_equal(poisoned["vals"], on["vals"]) and np.array_equal(poisoned["vecs"][0], on["vecs"][0])
+
+
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_block_pending_at_the_end_of_a_pass_is_completed_in_place_without_the_ritz_tail(ctx, oracle, cplx):
+    """ritz_tail = 0 while a block is pending at the end of the pass: the raw vectors are completed in place (block_flush, one
+    multi-axpy each) and the Ritz GEMV reads them with the plain coefficients, where the default run transforms the coefficients and
+    leaves the basis raw.  The loop is the same up to there — alpha, beta and the eigenvalue are the default run's bits — and the
+    eigenvector agrees with the default run's and the oracle's to the file's tolerance."""
+    n, window = 2048 * 3 + 5, 41
+    csr, init = chain(n, 0.1, cplx), G.start_vector(n, 5, np.complex128 if cplx else np.float64)
+    ora = oracle.lanczos(csr, init, True, max_iteration=window)
+    default = run(ctx, csr, init, window)
+    flushed = run(ctx, csr, init, window, tail=False)
+    check_against(default, ora, norm_inf(0.1), "default")
+    check_against(flushed, ora, norm_inf(0.1), "ritz_tail = 0")
+    assert np.array_equal(flushed["alpha"], default["alpha"]) and np.array_equal(flushed["beta"], default["beta"])
+    assert np.array_equal(flushed["vals"], default["vals"]) and flushed["iters"] == default["iters"]
+    ov = 1 - overlap(flushed["vecs"][0], default["vecs"][0])
+    print("1-overlap against the default run %.2e" % ov)
+    assert ov <= 1e-8
+    assert flushed["stats"]["block_flushed_vectors"] >= 1 and default["stats"]["block_flushed_vectors"] == 0
 
 
 @pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
