@@ -43,10 +43,12 @@ make_problem, reference, tri_apply = _pair.make_problem, _pair.reference, _pair.
 class BlockLoop:
     """The device loop.  Every method below is one kernel launch (or one host step) of a device implementation."""
 
-    def __init__(self, A, v0, K, both_seeds=True, plant=None):
+    def __init__(self, A, v0, K, both_seeds=True, plant=None, mutate=None):
         """plant = (relative size, index of the first new vector of the block it goes into, position i in that block): a known
-        perturbation along stored vectors in the raw b_i, to exercise the gate."""
-        self.A, self.K, self.plant = A, K, plant
+        perturbation along stored vectors in the raw b_i, to exercise the gate.
+        mutate(p, M): called in every block once the predictions p (m x W) and the measured columns M (W x m) are formed, to
+        change them in place: a stand-in for a device kernel that gets part of them wrong (tests/test_block_model.py)."""
+        self.A, self.K, self.plant, self.mutate = A, K, plant, mutate
         n = v0.shape[0]
         self.a = np.zeros((K + 10, n), dtype=v0.dtype)   # the stored raw vectors
         self.a[0] = v0
@@ -122,6 +124,8 @@ class BlockLoop:
         # ---- ONE sweep over the stored raw vectors; the stored basis is not touched
         S = a[:W]
         M = S.conj() @ b.T                               # M[j, i] = <a_j, b_i>, raw
+        if self.mutate is not None:
+            self.mutate(p, M)
         comp = [m - 1] + ([m - 2] if (m >= 2 and self.both_seeds) else [])
         irho = 1.0 / np.asarray(rho[:W])
         for i in comp:
@@ -210,11 +214,11 @@ class BlockLoop:
 GATE = 1e-8   # kPairGate
 
 
-def run_loop(A, v0, K, m, both_seeds=True, plant=None, gate=GATE):
+def run_loop(A, v0, K, m, both_seeds=True, plant=None, gate=GATE, mutate=None):
     """K recorded iterations: blocks of m, then of 2 while two remain, an odd last iteration single after the flush.  A vector
     whose gate value exceeds `gate` stands (its coefficients were measured), everything behind it is dropped, the basis is flushed
     and the pass finishes with single iterations, like the pair form's gate trip."""
-    L = BlockLoop(A, v0, K, both_seeds, plant)
+    L = BlockLoop(A, v0, K, both_seeds, plant, mutate)
     L.start()
     L.gate_trips = 0
     while len(L.al) + 2 <= K and not L.gate_trips:
