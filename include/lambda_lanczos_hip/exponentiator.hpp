@@ -31,6 +31,11 @@ template <typename T> class Exponentiator {
 
   // exp(a*A) input -> output (resized by the library, exponentiator_test.cpp:131); returns the iteration count (:87-173)
   size_t run(const T& a, const std::vector<T>& input, std::vector<T>& output) const { return call(a, input, output, false); }
+  // Addition: run() WITHOUT a stored Krylov basis (two-pass form, ll_expo_two_pass): three or four n-sized device vectors whatever
+  // the iteration count, every operator application twice; full_orthogonalize must be false (Error LL_ERR_INVALID otherwise).
+  size_t run_two_pass(const T& a, const std::vector<T>& input, std::vector<T>& output) const {
+    return call(a, input, output, false, true);
+  }
   // plain Taylor series (:175-210); returns the number of terms
   size_t taylor_run(const T& a, const std::vector<T>& input, std::vector<T>& output) const {
     return call(a, input, output, true);
@@ -42,6 +47,14 @@ template <typename T> class Exponentiator {
     ll_expo_params p = make_params();
     int64_t count = 0;
     check(dispatch(csr_->get(), &p, a, d_input, d_output, &count, false));
+    return (size_t)count;
+  }
+  // ... and the two-pass form on device buffers: three n-sized vectors beside them, whatever the iteration count
+  size_t run_two_pass_device(const T& a, const T* d_input, T* d_output) const {
+    if (!csr_) throw Error(LL_ERR_INVALID, "run_two_pass_device needs a device operator");
+    ll_expo_params p = make_params();
+    int64_t count = 0;
+    check(two_pass(csr_->get(), &p, a, d_input, d_output, &count));
     return (size_t)count;
   }
 
@@ -56,7 +69,7 @@ template <typename T> class Exponentiator {
     p.initial_vector_size = (int64_t)initial_vector_size;
     return p;
   }
-  size_t call(const T& a, const std::vector<T>& input, std::vector<T>& output, bool taylor) const {
+  size_t call(const T& a, const std::vector<T>& input, std::vector<T>& output, bool taylor, bool basis_free = false) const {
     const size_t n_local = csr_ ? (size_t)csr_->local_rows() : matrix_size;
     if (input.size() != n_local) throw Error(LL_ERR_INVALID, "input size differs from matrix_size (exponentiator.hpp:88)");
     ll_expo_params p = make_params();
@@ -64,10 +77,16 @@ template <typename T> class Exponentiator {
     ll_operator* op = csr_ ? csr_->get() : detail::make_host_operator<T>(ctx_.get(), (int64_t)matrix_size, &host);
     output.assign(n_local, T());
     int64_t count = 0;
-    const int rc = dispatch(op, &p, a, input.data(), output.data(), &count, taylor);
+    const int rc = basis_free ? two_pass(op, &p, a, input.data(), output.data(), &count)
+                              : dispatch(op, &p, a, input.data(), output.data(), &count, taylor);
     if (!csr_) ll_op_destroy(op);
     check(rc);
     return (size_t)count;
+  }
+  // untyped entry point: the storage type is the operator's, a always travels as (re, im)
+  int two_pass(ll_operator* op, const ll_expo_params* p, const T& a, const T* in, T* out, int64_t* count) const {
+    const std::complex<double> az(a);
+    return ll_expo_two_pass(ctx_.get(), op, p, az.real(), az.imag(), in, out, count, nullptr);
   }
   int dispatch(ll_operator* op, const ll_expo_params* p, const double& a, const double* in, double* out, int64_t* count,
                bool taylor) const {

@@ -60,7 +60,11 @@ extern "C" {
                              *    of an S_z sector of a ring) and ll_op_create_pauli_momentum_full_* (one momentum block of the full
                              *    2^n_sites space of a ring: no S_z conservation asked);
                              *    also additive under minor 5, with the same note — ll_op_create_pauli_symmetric_* (momentum,
-                             *    reflection and spin-inversion blocks of a ring) */
+                             *    reflection and spin-inversion blocks of a ring);
+                             *    also additive under minor 5, with the same note — ll_expo_two_pass (the Exponentiator without a
+                             *    stored Krylov basis) and ll_recur_accum_scaled (its replayed step with a complex coefficient): two
+                             *    UNTYPED entry points, the storage type comes from the operator / from an argument; ll_run_stats
+                             *    keeps its size (workspace_vectors and replay_mismatches are filled by ll_expo_two_pass too) */
 
 enum {
   LL_OK = 0,
@@ -629,6 +633,11 @@ int ll_recur_accum_d(ll_context* ctx, int64_t n_local, double* y_dev, const doub
                      double b, double g, double* psi_dev);
 int ll_recur_accum_z(ll_context* ctx, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev, double a, double b,
                      double g, void* psi_dev);
+/* The same step with a COMPLEX g = g_re + i g_im (the replayed step of ll_expo_two_pass; an addition within minor 5, untyped):
+ * storage is 'd', 'z', 's' or 'c' and says what y, x, p and psi hold.  On 'z' and 'c' g is rounded to the storage type and g*y is
+ * the complex product; on 'd' and 's' g_im must be 0 (LL_ERR_INVALID otherwise) and the call is ll_recur_accum_d / _s. */
+int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev,
+                          double a, double b, double g_re, double g_im, void* psi_dev);
 /* a5+a6+a7: orthogonalise w against nb orthonormal vectors stored row-major with leading dimension ld
  * (vector j at basis_dev + j*ld elements) and return ||w|| afterwards (LA:132-144 at LL:259-262, EX:121,145).
  * mode: LL_ORTH_CGS_DGKS (default, block classical Gram-Schmidt + a second pass when the norm drops below
@@ -819,6 +828,23 @@ int ll_expo_taylor_run_d(ll_context* ctx, ll_operator* op, const ll_expo_params*
                          const double* input_host, double* output_host, int64_t* nterms_out);
 int ll_expo_taylor_run_z(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im,
                          const void* input_host, void* output_host, int64_t* nterms_out);
+
+/* Exponentiator<T>::run WITHOUT a stored Krylov basis (two-pass form; an addition within minor 5, untyped: the storage type is the
+ * operator's, and a is always passed as (a_re, a_im) — a_im != 0 with a real operator is LL_ERR_INVALID).  With the reference's
+ * default full_orthogonalize = false, EX:107-118 is the plain three-term recurrence: pass 1 runs it on three rotating vectors with
+ * the stop rule of EX:124-158 and records its coefficients, pass 2 replays it bit for bit and accumulates
+ * output = ||input|| sum_l coeff[l] u_l (EX:163-170) directly.  Device memory: 3 n-sized vectors when output is device memory
+ * (output == input included), 4 when it is host memory, whatever the iteration count, against one vector per iteration plus one
+ * for ll_expo_run_*; every operator application runs twice.  The results agree with ll_expo_run_* to rounding.
+ *   p->full_orthogonalize != 0 is refused with LL_ERR_INVALID (there is no basis to orthogonalise against); orth_mode and
+ *   initial_vector_size are ignored; max_iteration and eps act as in ll_expo_run_*.
+ *   input / output : n_local values of the operator's storage type, HOST or DEVICE memory, decided per pointer; they may be the
+ *                    same buffer; input is never modified unless it is also the output.
+ *   stats          : nullable; n_passes = 1, total_iterations, workspace_vectors (3 or 4), replay_mismatches and the timing fields
+ *                    ll_lanczos_two_pass_* fills.
+ * Single rank only: a context with a communicator is refused with LL_ERR_INVALID. */
+int ll_expo_two_pass(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im, const void* input,
+                     void* output, int64_t* itern_out, ll_run_stats* stats);
 
 /* ------------------------------------------------------------------ float storage types (_s float, _c complex float)
  * Same entry points as above; see the comments on the _d / _z versions. */

@@ -206,6 +206,7 @@ PROTOTYPES = {
     "ll_three_term_z": (C.c_int, [vp, i64, vp, vp, vp, f64, f64]),
     "ll_recur_accum_d": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
     "ll_recur_accum_z": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
+    "ll_recur_accum_scaled": (C.c_int, [vp, C.c_int, i64, vp, vp, vp, f64, f64, f64, f64, vp]),  # untyped: storage is an argument
     "ll_orth_block_d": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_orth_block_z": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_gemv_basis_d": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, vp, i64]),
@@ -226,6 +227,7 @@ PROTOTYPES = {
     "ll_lanczos_two_pass_z": (C.c_int, [vp, vp, P(LanczosParams), P(f64), vp, P(i64), P(f64), vp, vp, P(RunStats)]),
     "ll_expo_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64), P(RunStats)]),
     "ll_expo_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64), P(RunStats)]),
+    "ll_expo_two_pass": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64), P(RunStats)]),  # untyped: the operator's type
     "ll_expo_taylor_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64)]),
     "ll_expo_taylor_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64)]),
 }

@@ -147,6 +147,32 @@ void taylor_run_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, 
   LL_REQUIRE(ctx && p && input && output && nterms, "null argument");
   taylor_run<T>(ctx, op, *p, a, input, output, nterms);
 }
+template <typename T>
+void recur_accum_scaled_impl(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, double g_re,
+                             double g_im, void* psi) {
+  LL_REQUIRE(n >= 0 && y && x && psi, "null vector");
+  if constexpr (scalar_traits<T>::is_complex) {
+    launch_recur_accum_cplx<T>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, zc{g_re, g_im}, nullptr, 0,
+                               nullptr, ctx->stream);
+  } else {
+    LL_REQUIRE(g_im == 0.0, "g_im must be 0 for the real storage types 'd' and 's'");
+    launch_recur_accum<T>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, g_re, nullptr, 0, nullptr, ctx->stream);
+  }
+}
+// the storage type is the operator's
+template <typename T>
+void expo_two_pass_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im, const void* input,
+                        void* output, int64_t* itern, ll_run_stats* stats) {
+  typedef typename host_scalar<T>::type H;
+  H a;
+  if constexpr (scalar_traits<T>::is_complex) {
+    a = H(a_re, a_im);
+  } else {
+    LL_REQUIRE(a_im == 0.0, "a_im must be 0 with a real operator");
+    a = a_re;
+  }
+  expo_two_pass_run<T>(ctx, op, *p, a, (const T*)input, (T*)output, itern, stats);
+}
 }  // namespace
 
 extern "C" {
@@ -448,5 +474,31 @@ LL_CAPI_REAL(LL_DEF_EXPO_TAYLOR_RUN_REAL)
                                  taylor_run_impl<T>(ctx, op, p, std::complex<double>(a_re, a_im), (const T*)input, (T*)output, \
                                      nterms))
 LL_CAPI_COMPLEX(LL_DEF_EXPO_TAYLOR_RUN_COMPLEX)
+
+// ---------------------------------------------------------------- untyped additions within minor 5 (the storage type is an argument)
+int ll_expo_two_pass(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im, const void* input,
+                     void* output, int64_t* itern_out, ll_run_stats* stats) {
+  return guarded([&] {
+    LL_REQUIRE(ctx && op && p && input && output && itern_out, "null argument");
+    const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
+    if (op->is_complex && wide) expo_two_pass_impl<zc>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
+    else if (op->is_complex) expo_two_pass_impl<cf>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
+    else if (wide) expo_two_pass_impl<double>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
+    else expo_two_pass_impl<float>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
+  });
+}
+int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n, void* y, const void* x, const void* p, double a, double b,
+                          double g_re, double g_im, void* psi) {
+  return guarded([&] {
+    use(ctx);
+    switch (storage) {
+      case 'd': recur_accum_scaled_impl<double>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
+      case 'z': recur_accum_scaled_impl<zc>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
+      case 's': recur_accum_scaled_impl<float>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
+      case 'c': recur_accum_scaled_impl<cf>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
+      default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
+    }
+  });
+}
 
 }  // extern "C"

@@ -3,8 +3,8 @@
 // and two diagnostics) through pinned, device-mapped memory and runs the k x k tridiagonal step (a11/a12) while
 // the device already executes iteration k+1 (lag-1 speculation: a speculative iteration only writes basis slots
 // the results never read, so stopping one iteration "late" on the device is harmless).
-// This header is the loop machinery both drivers share (lanczos_run.cpp, expo_run.cpp; two_pass_run.cpp takes the argument checks and
-// the speculation policy at its end).  Run-scoped resources: loop_support.hpp; the host algebra of the raw-basis forms: raw_basis.hpp.
+// This header is the loop machinery both drivers share (lanczos_run.cpp, expo_run.cpp; the basis-free drivers — recurrence.hpp,
+// two_pass_run.cpp, expo_two_pass_run.cpp — take the argument checks and the speculation policy at its end).  Run-scoped resources: loop_support.hpp; the host algebra of the raw-basis forms: raw_basis.hpp.
 #pragma once
 
 #include "engine.hpp"

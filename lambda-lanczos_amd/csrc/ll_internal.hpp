@@ -961,6 +961,16 @@ template <typename T>
 void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const double* gvec, int64_t k,
                         double a, double b, double g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
                         hipStream_t s);
+// ... with a complex g (T = zc, cf only): gvec holds (re, im) pairs, g is rounded to T and the product g y is the complex one.  The
+// update of y is the same code, so a replay with either coefficient type reproduces pass 1's vectors.
+template <typename T>
+void launch_recur_accum_cplx(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const zc* gvec, int64_t k,
+                             double a, double b, zc g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
+                             hipStream_t s);
+// psi = g x, out of place, with the product of the accumulate above: the first term of pass 2's sum (real g: T = double, float;
+// complex g: T = zc, cf)
+template <typename T> void launch_recur_seed(int64_t n, T* psi, const T* x, double g, hipStream_t s);
+template <typename T> void launch_recur_seed_cplx(int64_t n, T* psi, const T* x, zc g, hipStream_t s);
 // partials of <a,b> (reals per workgroup). Returns grid.
 template <typename T> int launch_dot(int64_t n, const T* a, const T* b, double* partials, hipStream_t s);
 // out_r = sum_{k=m-1..0} coeff[r*m+k] * u_k, r < nout; coeff on device, type acc_t<T>; the sums are carried in acc_t<T> and

@@ -1,20 +1,28 @@
-// The two-pass Lanczos recurrence without a stored basis (two_pass_run.cpp): the plain three-term update on
-// UNNORMALISED vectors, once with its coefficient record and norm (pass 1) and once replayed from the record while the Ritz
-// vector is accumulated (pass 2).  Streaming strip kernels in the geometry of kernels.hip (strip<T>, 16 KiB strips, balanced
-// persistent grid); both passes go through ONE element update (recur_update), so pass 2 reproduces pass 1's vectors bit for bit.
+// The two-pass Lanczos recurrence without a stored basis (two_pass_run.cpp, expo_two_pass_run.cpp): the plain
+// three-term update on UNNORMALISED vectors, once with its coefficient record and norm (pass 1) and once replayed from the record
+// while the result — the Ritz vector, or exp(a A) v — is accumulated (pass 2).  Streaming strip kernels in the geometry of
+// kernels.hip (strip<T>, 16 KiB strips, balanced persistent grid); both passes go through ONE element update (recur_update), so
+// pass 2 reproduces pass 1's vectors bit for bit.
 //
 // Reference rows:
 //   a4     recur_step / recur_accum   three-term update (LL:251-257) on r_k = ||r_k|| u_k
 //   a7     recur_step + recur_fold    ||w||^2 (LA:56-60 at LL:262); a8 is left to the next operator kernel (its input scale)
-//   a9     recur_accum                Ritz vector sum_k s_k u_k (LL:51-57), one term per replayed iteration
+//   a9     recur_accum                Ritz vector sum_k s_k u_k (LL:51-57), one term per replayed iteration; with a complex
+//                                     coefficient the Exponentiator's output sum_l coeff[l] u_l (EX:163-170)
 //
 // Bytes and launches per iteration beyond the operator (s = sizeof(T), n elements):
 //   pass 1  recur_step_kernel   reads y, x, p, writes y: 4 s n bytes (3 s n at k = 0), one launch; the fold of the workgroups'
 //           partial ||y||^2 and the publish step are recur_fold_kernel, a second launch of ONE workgroup (8 bytes per workgroup
 //           of the first).
 //   pass 2  recur_accum_kernel  reads y, x, p, psi, writes y, psi: 6 s n bytes (5 s n at k = 0), one launch, no reduction.
+//           The complex-coefficient instantiations (T = zc, cf with G = zc) move the same bytes; recur_seed_kernel (psi = g_0 r_0,
+//           once per Exponentiator run) reads x and writes psi: 2 s n bytes.
+// Registers (compiler's resource-usage remarks, gfx950, 256 threads): recur_accum_kernel<T, double> 76 / 72 / 80 / 82 VGPRs for
+// d / z / s / c, as before the coefficient type became a parameter; <zc, zc> 72, <cf, zc> 84; recur_seed_kernel 28 to 48.  No
+// instantiation uses scratch.
 // Kernel times and shares of peak: unmeasured.  Whole passes (tools/two_pass_rate.py): 2 015 and 1 845 it/s on
-// 128 MiB vectors with the Pauli-sum operator of 24 sites.
+// 128 MiB vectors with the Pauli-sum operator of 24 sites; the Exponentiator's two passes together (tools/expo_two_pass_rate.py):
+// 488 it/s on 256 MiB complex vectors, 11 iterations, against 832 it/s for the stored-basis run.
 #include "gs_strips.hpp"
 
 namespace ll {
@@ -85,22 +93,30 @@ __global__ __launch_bounds__(kBlock) void recur_fold_kernel(const double* __rest
   }
 }
 
-// Pass 2.  The same update with (a, b) READ from the record (a, b given by value when rec == nullptr: the primitive
-// ll_recur_accum_*), then psi += g y with g = gvec[k + 1] (or by value).  Nothing is recomputed and nothing is reduced over
-// the vector.  Workgroup 0 folds the alpha the operator kernel left behind and counts, in *mismatches, the iterations whose
-// alpha differs AS BITS from the recorded one (the replay invariant; alpha_partials == nullptr: no check).
-template <typename T>
+// The accumulate's coefficient g is real (the eigen-solver's Ritz vector) or complex (the Exponentiator's exp(a T_m) e_1 on complex
+// vectors): g y in T.  Real: the two real products of rmul.  Complex: g is rounded to T once, then the four products, one subtraction
+// and one addition of mul, each rounded on its own (the library is built without contraction).
+template <typename T> __device__ __forceinline__ T gmul(double g, T y) { return rmul(g, y); }
+__device__ __forceinline__ zc gmul(zc g, zc y) { return mul(g, y); }
+__device__ __forceinline__ cf gmul(zc g, cf y) { return mul(cf{(float)g.re, (float)g.im}, y); }
+
+// Pass 2.  The same update with (a, b) READ from the record (a, b given by value when rec == nullptr: the primitives
+// ll_recur_accum_* and ll_recur_accum_scaled), then psi += g y with g = gvec[k + 1] (or by value); G = double, or zc on complex
+// vectors.  Nothing is recomputed and nothing is reduced over the vector.  Workgroup 0 folds the alpha the operator kernel left
+// behind and counts, in *mismatches, the iterations whose alpha differs AS BITS from the recorded one (the replay invariant;
+// alpha_partials == nullptr: no check).
+template <typename T, typename G>
 __global__ __launch_bounds__(kBlock) void recur_accum_kernel(int64_t n, T* __restrict__ y, const T* __restrict__ x,
                                                              const T* __restrict__ p, T* __restrict__ psi,
-                                                             const double* __restrict__ rec, const double* __restrict__ gvec,
-                                                             int64_t k, double a_val, double b_val, double g_val,
+                                                             const double* __restrict__ rec, const G* __restrict__ gvec,
+                                                             int64_t k, double a_val, double b_val, G g_val,
                                                              const double* __restrict__ alpha_partials, int alpha_nparts,
                                                              long long* __restrict__ mismatches) {
   constexpr int EPT = strip<T>::EPT;
   constexpr int ELEMS = strip<T>::ELEMS;
   const double a = rec ? rec[kRecurRec * k + 1] : a_val;
   const double b = rec ? rec[kRecurRec * k + 2] : b_val;
-  const double g = gvec ? gvec[k + 1] : g_val;
+  const G g = gvec ? gvec[k + 1] : g_val;
   if (alpha_partials != nullptr && blockIdx.x == 0) {  // (uniform over the workgroup)
     __shared__ double fold_scratch[5];
     const double alpha = fold_partials_all(alpha_partials, alpha_nparts, fold_scratch);
@@ -117,9 +133,26 @@ __global__ __launch_bounds__(kBlock) void recur_accum_kernel(int64_t n, T* __res
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
       yr[e] = recur_update(yr[e], xr[e], p ? pr[e] : xr[e], a, b, p != nullptr);
-      qr[e] = add(qr[e], rmul(g, yr[e]));
+      qr[e] = add(qr[e], gmul(g, yr[e]));
     }
     store_strip<T>(y, i0, n, yr);
+    store_strip<T>(psi, i0, n, qr);
+  }
+}
+
+// The first term of pass 2's sum where g is not a real host value: psi = g x, out of place, with the product of the accumulate.
+// Reads x, writes psi: 2 s n bytes, once per run.
+template <typename T, typename G>
+__global__ __launch_bounds__(kBlock) void recur_seed_kernel(int64_t n, T* __restrict__ psi, const T* __restrict__ x, G g) {
+  constexpr int EPT = strip<T>::EPT;
+  constexpr int ELEMS = strip<T>::ELEMS;
+  const int64_t nstrips = (n + ELEMS - 1) / ELEMS;
+  for (int64_t sidx = blockIdx.x; sidx < nstrips; sidx += gridDim.x) {
+    const int64_t i0 = sidx * ELEMS + (int64_t)threadIdx.x * EPT;
+    T xr[EPT], qr[EPT];
+    load_strip<T>(x, i0, n, xr);
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) qr[e] = gmul(g, xr[e]);
     store_strip<T>(psi, i0, n, qr);
   }
 }
@@ -137,13 +170,38 @@ void launch_recur_fold(const double* partials, int nparts, double* rec, int64_t 
   hipLaunchKernelGGL(recur_fold_kernel, dim3(1), dim3(kBlock), 0, s, partials, nparts, rec, k, host_mapped);
   LL_HIP(hipGetLastError());
 }
+namespace {
+template <typename T, typename G>
+void launch_recur_accum_g(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const G* gvec, int64_t k, double a,
+                          double b, G g, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s) {
+  hipLaunchKernelGGL((recur_accum_kernel<T, G>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, y, x, p, psi, rec,
+                     gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches);
+  LL_HIP(hipGetLastError());
+}
+template <typename T, typename G> void launch_recur_seed_g(int64_t n, T* psi, const T* x, G g, hipStream_t s) {
+  hipLaunchKernelGGL((recur_seed_kernel<T, G>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, psi, x, g);
+  LL_HIP(hipGetLastError());
+}
+}  // namespace
 template <typename T>
 void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const double* gvec, int64_t k,
                         double a, double b, double g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
                         hipStream_t s) {
-  hipLaunchKernelGGL((recur_accum_kernel<T>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, y, x, p, psi, rec,
-                     gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches);
-  LL_HIP(hipGetLastError());
+  launch_recur_accum_g<T, double>(n, y, x, p, psi, rec, gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches, s);
+}
+template <typename T>
+void launch_recur_accum_cplx(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const zc* gvec, int64_t k,
+                             double a, double b, zc g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
+                             hipStream_t s) {
+  static_assert(scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
+  launch_recur_accum_g<T, zc>(n, y, x, p, psi, rec, gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches, s);
+}
+template <typename T> void launch_recur_seed(int64_t n, T* psi, const T* x, double g, hipStream_t s) {
+  launch_recur_seed_g<T, double>(n, psi, x, g, s);
+}
+template <typename T> void launch_recur_seed_cplx(int64_t n, T* psi, const T* x, zc g, hipStream_t s) {
+  static_assert(scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
+  launch_recur_seed_g<T, zc>(n, psi, x, g, s);
 }
 
 #define LL_INST_RECUR(T)                                                                                                       \
@@ -152,5 +210,14 @@ void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const d
   template void launch_recur_accum<T>(int64_t, T*, const T*, const T*, T*, const double*, const double*, int64_t, double,      \
                                       double, double, const double*, int, long long*, hipStream_t);
 LL_FOR_EACH_SCALAR(LL_INST_RECUR)
+// the Exponentiator's coefficients: real on real vectors, complex on complex ones
+template void launch_recur_seed<double>(int64_t, double*, const double*, double, hipStream_t);
+template void launch_recur_seed<float>(int64_t, float*, const float*, double, hipStream_t);
+#define LL_INST_RECUR_CPLX(T)                                                                                                  \
+  template void launch_recur_accum_cplx<T>(int64_t, T*, const T*, const T*, T*, const double*, const zc*, int64_t, double,     \
+                                           double, zc, const double*, int, long long*, hipStream_t);                           \
+  template void launch_recur_seed_cplx<T>(int64_t, T*, const T*, zc, hipStream_t);
+LL_INST_RECUR_CPLX(zc)
+LL_INST_RECUR_CPLX(cf)
 
 }  // namespace ll

@@ -1,0 +1,114 @@
+// The plain three-term recurrence on three rotating, UNNORMALISED vectors that both basis-free drivers run:
+// two_pass_run.cpp (the extreme eigenpair) and expo_two_pass_run.cpp (exp(a A) v).  Here: the buffers and the operator call of one
+// iteration (Recurrence), and the host side of pass 1 (recur_pass1: enqueue, collect the scalars, hand T_k to the tracker's worker).
+// What differs between the two drivers is the tracker (RitzTracker / ExpoTracker) and what pass 2 accumulates.  Kernels: recur.hip.
+#pragma once
+
+#include "lanczos_loop.hpp"
+
+namespace ll {
+
+// The recurrence both passes run: r_k lives in buf[k % 3] (pass 1 and pass 2 use the same buffers in the same rotation), its
+// scalars in rec[k] (recur.hip).
+template <typename T> struct Recurrence {
+  Engine<T>& E;
+  hipStream_t s;
+  int64_t nl;
+  double offset;
+  bool op_scales;  // the operator takes r_k with ||r_k||^2; else (callbacks) r_k is normalised in place in front of it
+  DevBuf<T> buf[3];
+  DevBuf<double> rec;
+  int64_t rec_cap = 0;  // records
+
+  T* vec(int64_t k) { return buf[k % 3].p; }
+  double* c(int64_t k) { return rec.p + kRecurRec * k + 3; }
+  // records 0 .. upto exist.  Growth (doubling, from 4096 iterations) drains the stream: rare, and never inside pass 2
+  void ensure_rec(int64_t upto) {
+    if (upto < rec_cap) return;
+    int64_t cap = std::max<int64_t>(rec_cap, 4096);
+    while (cap <= upto) cap *= 2;
+    DevBuf<double> grown;
+    grown.alloc(E.ctx, (size_t)cap * kRecurRec);
+    if (rec.p) {
+      LL_HIP(hipStreamSynchronize(s));
+      LL_HIP(hipMemcpy(grown.p, rec.p, (size_t)rec_cap * kRecurRec * sizeof(double), hipMemcpyDeviceToDevice));
+    }
+    std::swap(rec.p, grown.p);
+    std::swap(rec.owner, grown.owner);
+    std::swap(rec.bytes, grown.bytes);
+    rec_cap = cap;
+  }
+  // buf[(k + 1) % 3] = (A + offset)(r_k / ||r_k||); returns where the partial sums of alpha_k are
+  typename Engine<T>::DeferredAlpha operate(int64_t k) {
+    typename Engine<T>::DeferredAlpha da;
+    double* const alpha = E.S(kScalAlpha + (int)(k % kRingSlots));
+    if (op_scales) {
+      E.apply(vec(k), vec(k + 1), offset, alpha, true, &da, nullptr, c(k));
+    } else {
+      const NormRefs nr = E.plain_norm(c(k));
+      launch_scale<T>(nl, vec(k), 0.0, &nr, s);
+      E.apply(vec(k), vec(k + 1), offset, alpha, true, &da);
+    }
+    if (da.nparts == 0) {  // apply folded alpha itself: a list of one
+      da.partials = alpha;
+      da.nparts = 1;
+    }
+    return da;
+  }
+};
+
+// Host time of pass 1, by where it went (ll_run_stats)
+struct RecurPassTimes {
+  double tridiag = 0.0, enqueue = 0.0, wait = 0.0;
+};
+
+// Pass 1: iterations 0 .. max_iteration - 1 of the recurrence, from r_0 in rc.vec(0) with c_0 in rc.c(0) and csq = {c_0}.  Per
+// iteration: the operator, recur_step_kernel, recur_fold_kernel, an event; alpha_k, beta_k = ||r_{k+1}|| and c_{k+1} are appended to
+// alpha / beta / csq as they arrive and T_k goes to the worker's tracker, whose verdicts are absorbed into `last` (the first stop
+// verdict wins; else the last iteration's values).  Device operators run one iteration ahead of the scalars that are read
+// (speculates): the caller drops what the device ran beyond last.m.
+template <typename T, typename Tracker>
+void recur_pass1(Recurrence<T>& rc, StepWorker<Tracker>& worker, EventRing& ring, int64_t max_iteration, std::vector<double>& alpha,
+                 std::vector<double>& beta, std::vector<double>& csq, typename Tracker::Out& last, RecurPassTimes& t) {
+  ll_context* const ctx = rc.E.ctx;
+  const bool ahead = speculates(rc.E.op);  // device operators: iteration k + 1 is enqueued before k's scalars are read
+  const size_t max_lag = worker.threaded() ? 24 : 0;
+  bool stopped = false;
+  auto absorb = [&](typename Tracker::Out& o) {
+    t.tridiag += o.seconds;
+    last = std::move(o);
+    return last.stop;
+  };
+  int64_t enq = 0, col = 0;  // iterations enqueued / collected
+  while (!stopped && col < max_iteration) {
+    const int64_t target = ahead ? std::min(col + 2, max_iteration) : col + 1;
+    const double te0 = now_s();
+    for (; enq < target; ++enq) {
+      const int64_t k = enq;
+      const int slot = (int)(k % kRingSlots);
+      rc.ensure_rec(k + 1);
+      const typename Engine<T>::DeferredAlpha da = rc.operate(k);
+      const int grid = launch_recur_step<T>(rc.nl, rc.vec(k + 1), rc.vec(k), k > 0 ? rc.vec(k + 2) : nullptr, da.partials, da.nparts,
+                                            rc.rec.p, k, !rc.op_scales, ctx->partials.get(), rc.s);
+      launch_recur_fold(ctx->partials.get(), grid, rc.rec.p, k, ctx->pinned.get() + kSlotScalars * slot, rc.s);
+      LL_HIP(hipEventRecord(ring.ev[slot], rc.s));
+    }
+    t.enqueue += now_s() - te0;
+    const int slot = (int)(col % kRingSlots);
+    const double tw0 = now_s();
+    LL_HIP(hipEventSynchronize(ring.ev[slot]));
+    t.wait += now_s() - tw0;
+    const volatile double* hp = ctx->pinned.get() + kSlotScalars * slot;
+    const double a_k = hp[0], c_next = hp[1];
+    alpha.push_back(a_k);
+    beta.push_back(std::sqrt(c_next));  // beta_k = ||r_{k+1}||
+    csq.push_back(c_next);
+    ++col;
+    worker.submit(col, alpha.data(), beta.data());
+    stopped = worker.consume(col, -1, max_lag, absorb);
+  }
+  typename Tracker::Out r;
+  while (!stopped && worker.wait_pop(r)) stopped = absorb(r);  // the first stop verdict wins; else the last iteration's values
+}
+
+}  // namespace ll

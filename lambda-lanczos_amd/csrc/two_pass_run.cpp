@@ -2,8 +2,9 @@
 // vectors and records its coefficients; the host takes the eigenvector s of T_m; pass 2 replays the same recurrence from the record and
 // accumulates psi = sum_k s_k u_k.  Memory is three or four vectors whatever the iteration count, against m + 1 for lanczos_run; the
 // price is every operator application twice and no re-orthogonalisation (only the extreme pair is trustworthy: num_eigs = 1).
-// Kernels: recur.hip.  Host side: the stop and breakdown tests of the eigen-solver loop (StepWorker<RitzTracker>, LL:264-309).
-#include "lanczos_loop.hpp"
+// Kernels: recur.hip.  The recurrence and the loop of pass 1: recurrence.hpp, shared with expo_two_pass_run.cpp.  Host side: the stop
+// and breakdown tests of the eigen-solver loop (StepWorker<RitzTracker>, LL:264-309).
+#include "recurrence.hpp"
 
 #include <random>
 
@@ -19,55 +20,6 @@ template <typename T> void random_start(T* v, int64_t n) {
   Real* f = reinterpret_cast<Real*>(v);
   for (int64_t i = 0; i < n * scalar_traits<T>::reals; ++i) f[i] = r(mt);
 }
-
-// The recurrence both passes run: r_k lives in buf[k % 3] (pass 1 and pass 2 use the same buffers in the same rotation), its
-// scalars in rec[k] (recur.hip).
-template <typename T> struct Recurrence {
-  Engine<T>& E;
-  hipStream_t s;
-  int64_t nl;
-  double offset;
-  bool op_scales;  // the operator takes r_k with ||r_k||^2; else (callbacks) r_k is normalised in place in front of it
-  DevBuf<T> buf[3];
-  DevBuf<double> rec;
-  int64_t rec_cap = 0;  // records
-
-  T* vec(int64_t k) { return buf[k % 3].p; }
-  double* c(int64_t k) { return rec.p + kRecurRec * k + 3; }
-  // records 0 .. upto exist.  Growth (doubling, from 4096 iterations) drains the stream: rare, and never inside pass 2
-  void ensure_rec(int64_t upto) {
-    if (upto < rec_cap) return;
-    int64_t cap = std::max<int64_t>(rec_cap, 4096);
-    while (cap <= upto) cap *= 2;
-    DevBuf<double> grown;
-    grown.alloc(E.ctx, (size_t)cap * kRecurRec);
-    if (rec.p) {
-      LL_HIP(hipStreamSynchronize(s));
-      LL_HIP(hipMemcpy(grown.p, rec.p, (size_t)rec_cap * kRecurRec * sizeof(double), hipMemcpyDeviceToDevice));
-    }
-    std::swap(rec.p, grown.p);
-    std::swap(rec.owner, grown.owner);
-    std::swap(rec.bytes, grown.bytes);
-    rec_cap = cap;
-  }
-  // buf[(k + 1) % 3] = (A + offset)(r_k / ||r_k||); returns where the partial sums of alpha_k are
-  typename Engine<T>::DeferredAlpha operate(int64_t k) {
-    typename Engine<T>::DeferredAlpha da;
-    double* const alpha = E.S(kScalAlpha + (int)(k % kRingSlots));
-    if (op_scales) {
-      E.apply(vec(k), vec(k + 1), offset, alpha, true, &da, nullptr, c(k));
-    } else {
-      const NormRefs nr = E.plain_norm(c(k));
-      launch_scale<T>(nl, vec(k), 0.0, &nr, s);
-      E.apply(vec(k), vec(k + 1), offset, alpha, true, &da);
-    }
-    if (da.nparts == 0) {  // apply folded alpha itself: a list of one
-      da.partials = alpha;
-      da.nparts = 1;
-    }
-    return da;
-  }
-};
 
 }  // namespace
 
@@ -136,44 +88,11 @@ void two_pass_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_i
   double t_tridiag = 0.0, t_enqueue = 0.0, t_wait = 0.0;
   {
     TridiagWorker worker(cfg, threaded_verdicts(ctx, op), ctx->tune.tridiag_test_jitter_us);
-    const bool ahead = speculates(op);  // device operators: iteration k + 1 is enqueued before k's scalars are read
-    const size_t max_lag = worker.threaded() ? 24 : 0;
-    bool stopped = false;
-    auto absorb = [&](RitzTracker::Out& o) {
-      t_tridiag += o.seconds;
-      last = std::move(o);
-      return last.stop;
-    };
-    int64_t enq = 0, col = 0;  // iterations enqueued / collected
-    while (!stopped && col < P.max_iteration) {
-      const int64_t target = ahead ? std::min(col + 2, P.max_iteration) : col + 1;
-      const double te0 = now_s();
-      for (; enq < target; ++enq) {
-        const int64_t k = enq;
-        const int slot = (int)(k % kRingSlots);
-        rc.ensure_rec(k + 1);
-        const typename Engine<T>::DeferredAlpha da = rc.operate(k);
-        const int grid = launch_recur_step<T>(nl, rc.vec(k + 1), rc.vec(k), k > 0 ? rc.vec(k + 2) : nullptr, da.partials, da.nparts,
-                                              rc.rec.p, k, !rc.op_scales, ctx->partials.get(), s);
-        launch_recur_fold(ctx->partials.get(), grid, rc.rec.p, k, ctx->pinned.get() + kSlotScalars * slot, s);
-        LL_HIP(hipEventRecord(ring.ev[slot], s));
-      }
-      t_enqueue += now_s() - te0;
-      const int slot = (int)(col % kRingSlots);
-      const double tw0 = now_s();
-      LL_HIP(hipEventSynchronize(ring.ev[slot]));
-      t_wait += now_s() - tw0;
-      const volatile double* hp = ctx->pinned.get() + kSlotScalars * slot;
-      const double a_k = hp[0], c_next = hp[1];
-      alpha.push_back(a_k);
-      beta.push_back(std::sqrt(c_next));  // beta_k = ||r_{k+1}||
-      csq.push_back(c_next);
-      ++col;
-      worker.submit(col, alpha.data(), beta.data());
-      stopped = worker.consume(col, -1, max_lag, absorb);
-    }
-    RitzTracker::Out r;
-    while (!stopped && worker.wait_pop(r)) stopped = absorb(r);  // the first stop verdict wins; else the last iteration's values
+    RecurPassTimes pt;
+    recur_pass1(rc, worker, ring, P.max_iteration, alpha, beta, csq, last, pt);
+    t_tridiag += pt.tridiag;
+    t_enqueue = pt.enqueue;
+    t_wait = pt.wait;
   }
   const int64_t m = last.m;  // iterations the device ran ahead of the verdict are dropped
   alpha.resize((size_t)m);

@@ -561,9 +561,16 @@ def three_term(ctx, w_dev, u_prev_dev, u_cur_dev, beta, alpha, n=None):
 
 
 def recur_accum(ctx, y_dev, x_dev, p_dev, a, b, g, psi_dev, n=None):
-    """One replayed step of the two-pass recurrence: y -= a x + b p (p_dev may be None), then psi += g y, in one sweep."""
+    """One replayed step of the two-pass recurrence: y -= a x + b p (p_dev may be None), then psi += g y, in one sweep.  g is real,
+    or complex on complex arrays (the Exponentiator's replay, ll_recur_accum_scaled)."""
     n = int(n if n is not None else y_dev.shape[-1])
-    fn = getattr(lib(), "ll_recur_accum_" + _suffix(y_dev.dtype))
+    sfx = _suffix(y_dev.dtype)
+    if isinstance(g, (complex, np.complexfloating)):
+        assert sfx in "zc", "a complex g needs complex arrays"
+        check(lib().ll_recur_accum_scaled(ctx.handle, ord(sfx), n, y_dev.ptr, x_dev.ptr, None if p_dev is None else p_dev.ptr,
+                                          float(a), float(b), float(g.real), float(g.imag), psi_dev.ptr))
+        return
+    fn = getattr(lib(), "ll_recur_accum_" + sfx)
     check(fn(ctx.handle, n, y_dev.ptr, x_dev.ptr, None if p_dev is None else p_dev.ptr, float(a), float(b), float(g),
              psi_dev.ptr))
 
@@ -839,7 +846,7 @@ class Exponentiator:
         p.initial_vector_size = int(self.initial_vector_size)
         return p
 
-    def _call(self, name, a, input, want_stats, out=None):
+    def _call(self, name, a, input, want_stats, out=None, typed=True):
         op, owned = _as_operator(self.mv_mul, self.matrix_size, self.dtype, self.context)
         sfx = _suffix(self.dtype)
         if isinstance(input, DeviceArray):  # psi stays in HBM: device input, device output (out= or a new DeviceArray)
@@ -855,9 +862,9 @@ class Exponentiator:
         p = self._params()
         stats = capi.RunStats()
         try:
-            fn = getattr(lib(), name + sfx)
+            fn = getattr(lib(), name + sfx if typed else name)
             args = [self.context.handle, op.handle, C.byref(p)]
-            args += [float(a)] if sfx in "ds" else [float(np.real(a)), float(np.imag(a))]
+            args += [float(a)] if typed and sfx in "ds" else [float(np.real(a)), float(np.imag(a))]
             args += [in_p, out_p, C.byref(it)]
             if want_stats:
                 args.append(C.byref(stats))
@@ -873,6 +880,12 @@ class Exponentiator:
         """Returns (output, iteration_count) (EX:87-173).  A DeviceArray input keeps the vector in HBM (output: `out`,
         which may be `input` itself, or a new DeviceArray)."""
         return self._call("ll_expo_run_", a, input, True, out)
+
+    def run_two_pass(self, a, input, out=None):
+        """run() WITHOUT a stored Krylov basis (ll_expo_two_pass): three n-sized device vectors whatever the iteration count (four
+        when the output is a host array), every operator application twice; full_orthogonalize must be False.  Same buffer
+        conventions and return value as run(); last_stats carries workspace_vectors and replay_mismatches."""
+        return self._call("ll_expo_two_pass", a, input, True, out, typed=False)
 
     def taylor_run(self, a, input, out=None):
         """Returns (output, number_of_terms) (EX:175-210)."""

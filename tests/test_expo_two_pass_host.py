@@ -1,0 +1,56 @@
+"""CPU-side checks of the two-pass Exponentiator's surface: ll_expo_two_pass and ll_recur_accum_scaled are declared in
+include/lanczos_hip.h, exported by the library and bound in the ctypes table; they are untyped additions within ABI minor 5 (no
+struct changed size, ll_version() is what it was); an all-null call is refused before any device call.  No device compute here."""
+import ctypes as C
+import re
+
+import lambda_lanczos_amd as L
+from lambda_lanczos_amd import _capi as capi
+
+NAMES = ("ll_expo_two_pass", "ll_recur_accum_scaled")
+TYPED_SUFFIXES = ("_d", "_z", "_s", "_c")
+
+
+def _null(argtype):
+    if issubclass(argtype, (C._Pointer, C.c_void_p, C.c_char_p)):
+        return None
+    return 0.0 if argtype is C.c_double else 0
+
+
+def test_both_entry_points_are_declared_exported_and_bound():
+    with open(capi.HEADER_PATH) as f:
+        text = f.read()
+    declared = set(re.findall(r"^\s*int\s+(ll_[a-z0-9_]+)\s*\(", text, flags=re.M))
+    lib = capi.lib()
+    for name in NAMES:
+        assert name in declared, name
+        assert hasattr(lib, name), name
+        assert name in capi.PROTOTYPES, name
+        assert not name.endswith(TYPED_SUFFIXES), name   # untyped: the typed families keep their count
+    assert "additive under minor 5" in text[:text.index("enum {")] and "ll_expo_two_pass" in text[:text.index("enum {")]
+
+
+def test_all_null_calls_are_refused_before_any_device_call():
+    lib = capi.lib()
+    for name, text in (("ll_expo_two_pass", "invalid argument: null argument"), ("ll_recur_accum_scaled", "invalid argument: null context")):
+        res, argtypes = capi.PROTOTYPES[name]
+        assert res is C.c_int
+        assert lib.ll_partition(-1, 0, 0, None, None) == capi.LL_ERR_INVALID   # another text: what is read below is this call's
+        assert getattr(lib, name)(*[_null(t) for t in argtypes]) == capi.LL_ERR_INVALID
+        assert lib.ll_last_error().decode() == text
+
+
+def test_the_abi_is_still_minor_five_with_the_same_structs():
+    lib = capi.lib()
+    assert lib.ll_version() == 5 and capi.ABI_VERSION == (0, 5)
+    # ll_run_stats: 19 named eight-byte fields and reserved[4], the size every caller since minor 3 was built with
+    assert C.sizeof(capi.RunStats) == 8 * 23
+    assert C.sizeof(capi.ExpoParams) == 40
+    assert lib.ll_abi_check(0, 5, C.sizeof(capi.RunStats), C.sizeof(capi.LanczosParams)) == capi.LL_OK
+
+
+def test_the_python_methods_exist():
+    assert callable(L.Exponentiator.run_two_pass)
+    import inspect
+
+    assert list(inspect.signature(L.Exponentiator.run_two_pass).parameters) == ["self", "a", "input", "out"]
