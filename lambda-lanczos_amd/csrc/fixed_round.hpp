@@ -1,6 +1,6 @@
 // Rounding a double to the nearest 64-bit integer (ties to even) without the f64 -> i64 conversion sequence.
 //
-// The fixed-point SpMV kernels (spmv_pb.hip: pb_phase2_fixed, tl_spmv_kernel) turn every product into an integer of up to 63
+// The fixed-point SpMV kernels (spmv_pb.hip: pb_phase2_fixed; spmv_tiled.hip: tl_spmv_kernel) turn every product into an integer of up to 63
 // bits.  gfx950 has no f64 -> i64 instruction: `(long long)rint(v)` compiles to v_rndne, v_ldexp, v_floor, v_fma, v_cvt_i32,
 // v_cvt_u32 — five of them quarter-rate.  The same integer falls out of four full-rate additions:
 //     t1 = v + 1.5 * 2^84     the sum is rounded to the ulp of [2^84, 2^85) = 2^32: the low mantissa word of t1 holds

@@ -1,7 +1,7 @@
 // Hand-written HIP kernels for gfx950 (MI355X / CDNA4): the BLAS-1 side of the Lanczos hot path in the STREAMING geometry —
 // multi-dot / multi-axpy, the one-sweep (lagged) Gram-Schmidt form and its fold, the folds of workgroup partials, scale /
 // three-term / dot / offset-dot, the basis GEMV, the tiny scalar kernels and the bandwidth probe.  Beside it: op_kernels.hip,
-// spmv_pb.hip, spmv_sym.hip, pauli.hip (operators), gs_pair.hip (two iterations per sweep), gs_small.hip (all Gram-Schmidt
+// spmv_pb.hip, spmv_tiled.hip, spmv_sym.hip, pauli.hip (operators), gs_pair.hip (two iterations per sweep), gs_small.hip (all Gram-Schmidt
 // forms on short vectors), gs_strips.hpp (what these share).
 //
 // Every kernel here is HBM-bandwidth bound (BLAS-1 <= 0.25 flop/B, ridge ~10 flop/B), so there is no MFMA

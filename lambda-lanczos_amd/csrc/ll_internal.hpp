@@ -8,6 +8,7 @@
 #endif
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include "../../include/lanczos_hip.h"
 #include "../../include/lanczos_hip_transport.h"
 #include "scalar_types.hpp"
+#include "spmv_plan.hpp"  // GatherPlan, PbColMap, kPbLdsCap: the host-side planning of the PB and tiled images
 
 #if defined(__HIPCC__)
 // A launch whose completion IS an event: hipExtLaunchKernelGGL hangs the event on the kernel's own dispatch packet; hipEventRecord
@@ -150,6 +152,20 @@ constexpr int kSpmvTileNnz = 1024;   // nonzeros staged through LDS per SpMV til
 constexpr int kXmaxParts = 512;      // maxima of |x| the pre-pass of the tiled and one-triangle kernels leaves (one per workgroup)
 constexpr int kMaxSegs = 26;         // basis segments (slabs) per multi-dot / multi-axpy launch: 5000 vectors in slabs of 200
 
+// f() once per device and mask (a static of the caller: one bit per device).  The opt-in to > 64 KiB of dynamic LDS is per device
+// and per kernel symbol: pb_opt_in is what f calls for each kernel of a family (spmv_pb.hip, spmv_tiled.hip).
+template <typename F> void once_per_device(std::atomic<unsigned long long>& mask, F&& f) {
+  int dev = 0;
+  LL_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (mask.load(std::memory_order_acquire) & bit) return;
+  f();
+  mask.fetch_or(bit, std::memory_order_release);
+}
+template <typename K> void pb_opt_in(K kernel) {
+  LL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPbLdsCap));
+}
+
 // A run of basis vectors stored with a common leading dimension: vector j at base + j*ld.
 template <typename T> struct BasisSegs {
   const T* base[kMaxSegs];
@@ -187,19 +203,6 @@ void comm_allreduce_sum(Comm*, double* buf, size_t n_doubles, hipStream_t s);
 void comm_halo_exchange(Comm*, const void* send_prev, void* recv_prev, int prev, const void* send_next, void* recv_next,
                         int next, size_t bytes, hipStream_t s);
 
-}  // namespace ll
-
-// ---------------------------------------------------------------- exchange plan of a sharded vector
-// The all-gather of a vector whose shards have the stride n_shard is cut into nchunks pieces: piece c = elements
-// [start[c], start[c] + len[c]) of EVERY shard.  Region c of the gathered buffer starts at nranks * start[c] elements
-// and holds rank s's piece at + s * len[c].  One chunk => the buffer is the vector in global order.
-namespace ll {
-constexpr int kMaxGatherChunks = 8;
-struct GatherPlan {
-  int nchunks = 1;
-  int64_t start[kMaxGatherChunks] = {0};
-  int64_t len[kMaxGatherChunks] = {0};
-};
 }  // namespace ll
 
 // ---------------------------------------------------------------- tuning: environment switches and per-context settings
@@ -377,7 +380,8 @@ template <typename F> void for_row_ptr_type(bool rp64, F&& f) {
   else f(int32_t{});
 }
 
-// Propagation-blocked image (spmv_pb.hip).  Column-block table order: the blocks over the rank's OWN columns first (their x
+// Propagation-blocked image (kernels: spmv_pb.hip; built by spmv_image_build.hip from the plan of spmv_plan.hpp).
+// Column-block table order: the blocks over the rank's OWN columns first (their x
 // slice is the local shard, no exchange needed), then, gather chunk by gather chunk, the blocks over the other ranks' columns
 // (x slice in the gathered buffer).  One phase-1 launch per range, so own-column work runs under the all-gather.
 struct PbImage {
@@ -395,7 +399,7 @@ struct PbImage {
   void* prod = nullptr;          // product buffer P (nnz elements of T), row-block order
   DevArray<int16_t> rexp;        // LL_PB_PHASE2=fixed: exponent of every local row's absolute sum
   DevArray<double> blockmax;     // LL_PB_PHASE2=fixed: max |x| per column block, left by phase 1
-  DevArray<void> diag;           // a_ii of every local row (T): the diagonal is kept outside the streams (spmv_pb.hip pb_diag_kernel)
+  DevArray<void> diag;           // a_ii of every local row (T): the diagonal is kept outside the streams (pb_diag_kernel)
   int64_t entries = 0;           // padded entry count of the image
   int phase2 = 4;                // form of phase 2 (ll::LL_PB_FIXED / _ORDERED / _ATOMIC): set when the image is built,
                                  // changed by ll_op_set_accuracy (both forms read the same image)
@@ -420,7 +424,8 @@ struct PbImage {
   }
 };
 
-// 2-D tiled image (spmv_pb.hip, tl_*): row blocks with the y slice in LDS, each walking its non-empty column tiles of 16 KiB of x;
+// 2-D tiled image (kernel: spmv_tiled.hip; built by spmv_image_build.hip): row blocks with the y slice in LDS, each walking its
+// non-empty column tiles of 16 KiB of x;
 // entries = value (pre-scaled by the row's exponent) + packed 16-bit local column / row
 struct TiledImage {
   int nrb = 0, rb_rows = 0, ncb = 0;
@@ -578,7 +583,7 @@ struct ll_operator {
   int spmv_kind = 0;                 // LL_SPMV_*
   float tune_ms[3] = {-1.f, -1.f, -1.f};  // what the creation-time autotune measured per LL_SPMV_* kernel (-1: not timed)
   ll::PbImage pb;                    // propagation-blocked image (spmv_pb.hip pb_phase1 / pb_phase2)
-  ll::TiledImage tl;                 // 2-D tiled image (spmv_pb.hip tl_*; LL_SPMV_TILED)
+  ll::TiledImage tl;                 // 2-D tiled image (spmv_tiled.hip; LL_SPMV_TILED)
   int64_t sym_stored = -1;           // entries of the triangle the operator was created from (ll_op_info); -1: full storage
   ll::SymImage sym;                  // one-triangle image (spmv_sym.hip; LL_SPMV_SYM, ll_op_create_csr_sym_*)
   // dense row-major block (kind DENSE): n_local x n values of T
@@ -665,7 +670,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip); everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip); everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -712,10 +717,12 @@ int launch_pb_phase2(const ll_operator& op, const T* x_local, T* y, double offse
                      const double* xnorm2 = nullptr);
 // forms of PB phase 2 (Tuning::pb_phase2, PbImage::phase2)
 constexpr int LL_PB_ATOMIC = 0, LL_PB_ORDERED = 1, LL_PB_FIXED = 4;
-// Build the propagation-blocked image on the device from the operator's CSR arrays, phase 2 in the form `phase2` (LL_PB_*,
+// Build the propagation-blocked image on the device from the operator's CSR arrays (spmv_image_build.hip), phase 2 in the form
+// `phase2` (LL_PB_*,
 // resolved by operators.cpp image_forms); false: shape not supported.
 template <typename T> bool pb_build_device(ll_operator* op, int phase2);
-// The 2-D tiled kernel for matrices with column locality (spmv_pb.hip): same contract as launch_spmv on a single GPU
+// The 2-D tiled kernel for matrices with column locality (spmv_tiled.hip; its image: spmv_image_build.hip): same contract as
+// launch_spmv on a single GPU
 // (x = the whole vector); build returns false when the matrix is not eligible (too many column tiles per row block).
 template <typename T> bool tl_build_device(ll_operator* op);
 template <typename T>
@@ -727,7 +734,7 @@ int tl_xmax_local_slot();
 template <typename T>
 int launch_spmv_tiled_pass(const ll_operator& op, int pass, const T* x, int64_t col0, int64_t col_end, const T* x_local, T* y,
                            double offset, double* dot_partials, hipStream_t s, const double* xnorm2, int n_xmax);
-// Column range check + max absolute row sum of the local rows (sets op->inf_norm), on the device.
+// Column range check + max absolute row sum of the local rows (sets op->inf_norm), on the device (spmv_image_build.hip).
 template <typename T> void csr_check_device(ll_operator* op);
 // maxima of |x| over n elements, one per workgroup, into parts [kXmaxParts]; returns how many were written (tl_xmax_kernel)
 template <typename T> int launch_x_max(int64_t n, const T* x, double* parts, hipStream_t s);

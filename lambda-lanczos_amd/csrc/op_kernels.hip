@@ -1,5 +1,5 @@
 // The operator kernels that need no image of their own: the CSR-stream SpMV with the column split of a sharded CSR image, the
-// dense row block and the matrix-free lattice stencil (beside spmv_pb.hip, spmv_sym.hip and pauli.hip).
+// dense row block and the matrix-free lattice stencil (beside spmv_pb.hip, spmv_tiled.hip, spmv_sym.hip and pauli.hip).
 //
 // All are HBM-bandwidth bound (SpMV 0.15 flop/B); offset, the write of y and the alpha partial are fused into the
 // one pass over the operator.  Reference rows:

@@ -1,4 +1,5 @@
-// Device pieces shared by the row-block SpMV kernels (spmv_pb.hip: PB phase 2, tiled; spmv_sym.hip: one-triangle kernel):
+// Device pieces shared by the row-block SpMV kernels (spmv_pb.hip: PB phase 2; spmv_tiled.hip; spmv_sym.hip: one-triangle kernel)
+// and the kernels that build their images (spmv_image_build.hip):
 // workgroup geometry, 16-byte entry quads, the fixed-point rounding of a product and the common epilogue
 // (y = row sum + offset x_i, partial Re<x, y> per workgroup).
 #pragma once
@@ -12,6 +13,21 @@ constexpr int kPbThreads = 1024;
 constexpr int kPbWaves = kPbThreads / 64;
 
 __device__ __forceinline__ void lds_add(double* p, double v) { unsafeAtomicAdd(p, v); }
+// one element of the storage type into a y slice of doubles (PB phase 2 and the tiled kernel in their floating-point forms)
+template <typename T> __device__ __forceinline__ void lds_add_elem(double* lds, int rl, const T& v) {
+  if constexpr (scalar_traits<T>::is_complex) {
+    lds_add(&lds[2 * rl], (double)v.re);
+    lds_add(&lds[2 * rl + 1], (double)v.im);
+  } else {
+    lds_add(&lds[rl], (double)v);
+  }
+}
+// v * 2^k, exact: the tiled image stores its values scaled by the row's exponent (pb_scatter_kernel<TILED>) and the tiled kernel
+// scales the staged x to its fixed-point grid
+__device__ __forceinline__ double scale_pow2(double v, int k) { return ldexp(v, k); }
+__device__ __forceinline__ float scale_pow2(float v, int k) { return ldexpf(v, k); }
+__device__ __forceinline__ zc scale_pow2(zc v, int k) { return zc{ldexp(v.re, k), ldexp(v.im, k)}; }
+__device__ __forceinline__ cf scale_pow2(cf v, int k) { return cf{ldexpf(v.re, k), ldexpf(v.im, k)}; }
 
 // Entries are handled in QUADS: every segment is padded to a multiple of 16 entries (zero value, local index 0), so
 // a lane always moves four consecutive entries with 16-byte accesses (2 x dwordx4 of values / products, one dwordx2

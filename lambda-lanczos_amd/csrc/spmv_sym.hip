@@ -12,7 +12,7 @@
 //
 // Sums: the fixed-point class of pb_phase2_fixed.  Every product is rounded to the grid of its DESTINATION row,
 // q_i = 2^(er_i + e_x + 1 - 62), where sum_j |a_ij| < 2^er_i over the FULL row of A (computed when the operator is created,
-// on the expanded matrix in increasing column order: pb_rowexp_kernel) and max|x| < 2^e_x (tl_xmax_kernel pre-pass).  The
+// on the expanded matrix in increasing column order: pb_rowexp_kernel, spmv_image_build.hip) and max|x| < 2^e_x (tl_xmax_kernel pre-pass, spmv_tiled.hip).  The
 // mirrored product is the same multiply the full-storage kernels apply to the stored a_jk = conj(a_kj) (negating an imaginary
 // part is exact), so the integers added are the ones pb_phase2_fixed adds on the expanded matrix and y is the same bits.
 // The epilogue (offset x_i, the dot partials, the scaled input) is pb_phase2_epilogue itself.
