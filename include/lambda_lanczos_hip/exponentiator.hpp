@@ -36,6 +36,23 @@ template <typename T> class Exponentiator {
   size_t run_two_pass(const T& a, const std::vector<T>& input, std::vector<T>& output) const {
     return call(a, input, output, false, true);
   }
+  // ... for several a from ONE Krylov space (ll_expo_two_pass_multi, at most LL_EXPO_MULTI_MAX per call): outputs[j] = exp(a[j]*A) input
+  // and the returned counts are what run_two_pass gives for a[j] alone, for the operator applications of the longest run.
+  std::vector<size_t> run_two_pass(const std::vector<T>& a, const std::vector<T>& input, std::vector<std::vector<T>>& outputs) const {
+    const size_t n_local = csr_ ? (size_t)csr_->local_rows() : matrix_size;
+    if (input.size() != n_local) throw Error(LL_ERR_INVALID, "input size differs from matrix_size (exponentiator.hpp:88)");
+    ll_expo_params p = make_params();
+    detail::HostOp<T> host{mv_mul, {}, {}};
+    ll_operator* op = csr_ ? csr_->get() : detail::make_host_operator<T>(ctx_.get(), (int64_t)matrix_size, &host);
+    outputs.assign(a.size(), std::vector<T>(n_local, T()));
+    std::vector<T*> ptrs;
+    for (auto& o : outputs) ptrs.push_back(o.data());
+    std::vector<size_t> counts;
+    const int rc = two_pass_multi(op, &p, a, input.data(), ptrs.data(), counts);
+    if (!csr_) ll_op_destroy(op);
+    check(rc);
+    return counts;
+  }
   // plain Taylor series (:175-210); returns the number of terms
   size_t taylor_run(const T& a, const std::vector<T>& input, std::vector<T>& output) const {
     return call(a, input, output, true);
@@ -56,6 +73,14 @@ template <typename T> class Exponentiator {
     int64_t count = 0;
     check(two_pass(csr_->get(), &p, a, d_input, d_output, &count));
     return (size_t)count;
+  }
+  // ... and for several a: d_outputs is a host array of a.size() device pointers, pairwise distinct; one may be d_input
+  std::vector<size_t> run_two_pass_device(const std::vector<T>& a, const T* d_input, T* const* d_outputs) const {
+    if (!csr_) throw Error(LL_ERR_INVALID, "run_two_pass_device needs a device operator");
+    ll_expo_params p = make_params();
+    std::vector<size_t> counts;
+    check(two_pass_multi(csr_->get(), &p, a, d_input, d_outputs, counts));
+    return counts;
   }
 
  private:
@@ -87,6 +112,19 @@ template <typename T> class Exponentiator {
   int two_pass(ll_operator* op, const ll_expo_params* p, const T& a, const T* in, T* out, int64_t* count) const {
     const std::complex<double> az(a);
     return ll_expo_two_pass(ctx_.get(), op, p, az.real(), az.imag(), in, out, count, nullptr);
+  }
+  int two_pass_multi(ll_operator* op, const ll_expo_params* p, const std::vector<T>& a, const T* in, T* const* outs,
+                     std::vector<size_t>& counts) const {
+    std::vector<double> a_reim;
+    for (const T& v : a) {
+      const std::complex<double> az(v);
+      a_reim.push_back(az.real());
+      a_reim.push_back(az.imag());
+    }
+    std::vector<int64_t> m(a.size(), 0);
+    const int rc = ll_expo_two_pass_multi(ctx_.get(), op, p, (int64_t)a.size(), a_reim.data(), in, (void* const*)outs, m.data(), nullptr);
+    counts.assign(m.begin(), m.end());
+    return rc;
   }
   int dispatch(ll_operator* op, const ll_expo_params* p, const double& a, const double* in, double* out, int64_t* count,
                bool taylor) const {

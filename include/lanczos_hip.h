@@ -64,7 +64,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_expo_two_pass (the Exponentiator without a
                              *    stored Krylov basis) and ll_recur_accum_scaled (its replayed step with a complex coefficient): two
                              *    UNTYPED entry points, the storage type comes from the operator / from an argument; ll_run_stats
-                             *    keeps its size (workspace_vectors and replay_mismatches are filled by ll_expo_two_pass too) */
+                             *    keeps its size (workspace_vectors and replay_mismatches are filled by ll_expo_two_pass too);
+                             *    also additive under minor 5, with the same note — ll_expo_two_pass_multi (several times a from one
+                             *    Krylov space) and ll_recur_accum_multi (its replayed step with several accumulators): untyped too */
 
 enum {
   LL_OK = 0,
@@ -638,6 +640,14 @@ int ll_recur_accum_z(ll_context* ctx, int64_t n_local, void* y_dev, const void* 
  * the complex product; on 'd' and 's' g_im must be 0 (LL_ERR_INVALID otherwise) and the call is ll_recur_accum_d / _s. */
 int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev,
                           double a, double b, double g_re, double g_im, void* psi_dev);
+/* ... with n_acc accumulators (1 .. LL_EXPO_MULTI_MAX) in the same sweep (the replayed step of ll_expo_two_pass_multi; an addition
+ * within minor 5, untyped): y = y - a*x - b*p once, then psi_dev[j] = psi_dev[j] + g_j*y for every j, g_j = g_reim[2j] + i g_reim[2j+1]
+ * (imaginary parts must be 0 on 'd' and 's').  Every psi_dev[j] receives the bits ll_recur_accum_scaled gives it on its own.  The
+ * accumulators must not overlap each other, y, x or p. */
+enum { LL_EXPO_MULTI_MAX = 16 };
+int ll_recur_accum_multi(ll_context* ctx, int storage, int64_t n_local, void* y_dev, const void* x_dev, const void* p_dev,
+                         double a, double b, int64_t n_acc, const double* g_reim /* host, 2*n_acc */,
+                         void* const* psi_dev /* host array of n_acc device pointers */);
 /* a5+a6+a7: orthogonalise w against nb orthonormal vectors stored row-major with leading dimension ld
  * (vector j at basis_dev + j*ld elements) and return ||w|| afterwards (LA:132-144 at LL:259-262, EX:121,145).
  * mode: LL_ORTH_CGS_DGKS (default, block classical Gram-Schmidt + a second pass when the norm drops below
@@ -845,6 +855,24 @@ int ll_expo_taylor_run_z(ll_context* ctx, ll_operator* op, const ll_expo_params*
  * Single rank only: a context with a communicator is refused with LL_ERR_INVALID. */
 int ll_expo_two_pass(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im, const void* input,
                      void* output, int64_t* itern_out, ll_run_stats* stats);
+/* ... for n_times values of a (1 .. LL_EXPO_MULTI_MAX) from ONE Krylov space (an addition within minor 5, untyped): outputs[j] =
+ * exp(a_j A) input with a_j = a_reim[2j] + i a_reim[2j+1].  The Krylov space of (A, input) does not depend on a: pass 1 runs once,
+ * with the stop rule of EX:124-158 applied to every a_j on its own; where a_j's test fires first, after m_j iterations, its
+ * coefficients exp(a_j T_{m_j}) e_1 are frozen, and pass 1 ends when the last a_j has fired (or on breakdown, or at max_iteration,
+ * which end every a_j that is still open).  Pass 2 replays max_j m_j - 1 iterations once and adds each replayed vector into the
+ * outputs whose m_j it is still below; an output past its m_j is not touched.  On a device operator outputs[j] and itern_out[j] are
+ * bit for bit what ll_expo_two_pass returns for a_j alone, for 2 max_j m_j - 1 operator applications instead of sum_j (2 m_j - 1).
+ *   outputs   : host array of n_times pointers, each to n_local values in HOST or DEVICE memory, decided per pointer; pairwise
+ *               non-overlapping (LL_ERR_INVALID otherwise); one of them may be the input's buffer; the input is otherwise never
+ *               modified.  Device memory: 3 n-sized vectors plus one per output in host memory.
+ *   itern_out : nullable; n_times values m_j.
+ *   stats     : nullable; as ll_expo_two_pass, with total_iterations = max_j m_j and workspace_vectors = 3 + host outputs.
+ * Parameters, refusals (full_orthogonalize, a communicator, an imaginary part on a real operator, a zero input) and everything
+ * else as ll_expo_two_pass. */
+int ll_expo_two_pass_multi(ll_context* ctx, ll_operator* op, const ll_expo_params* p, int64_t n_times,
+                           const double* a_reim /* host, 2*n_times */, const void* input,
+                           void* const* outputs /* host array of n_times pointers */,
+                           int64_t* itern_out /* n_times values m_j, nullable */, ll_run_stats* stats);
 
 /* ------------------------------------------------------------------ float storage types (_s float, _c complex float)
  * Same entry points as above; see the comments on the _d / _z versions. */

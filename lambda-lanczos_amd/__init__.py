@@ -40,6 +40,7 @@ from .engine import (  # noqa: F401
     orth_block,
     partition,
     recur_accum,
+    recur_accum_multi,
     scal,
     spmv,
     three_term,

@@ -18,6 +18,7 @@ SPMV_CSR_STREAM, SPMV_PB, SPMV_TILED, SPMV_SYM = 0, 1, 2, 3
 UPPER, LOWER = 0, 1
 ACCURACY_DEFAULT, ACCURACY_NORMWISE, ACCURACY_COMPONENTWISE = 0, 1, 2
 UNIQUE_ID_BYTES = 128
+EXPO_MULTI_MAX = 16
 
 
 ABI_VERSION = (0, 5)  # LL_VERSION_MAJOR, LL_VERSION_MINOR of the include/lanczos_hip.h these mirrors were written against
@@ -207,7 +208,8 @@ PROTOTYPES = {
     "ll_recur_accum_d": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
     "ll_recur_accum_z": (C.c_int, [vp, i64, vp, vp, vp, f64, f64, f64, vp]),
     "ll_recur_accum_scaled": (C.c_int, [vp, C.c_int, i64, vp, vp, vp, f64, f64, f64, f64, vp]),  # untyped: storage is an argument
-    "ll_orth_block_d": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
+    "ll_recur_accum_multi": (C.c_int, [vp, C.c_int, i64, vp, vp, vp, f64, f64, i64, P(f64), P(vp)]),  # untyped too
+    "ll_orth_block_d":(C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_orth_block_z": (C.c_int, [vp, i64, i64, vp, i64, vp, C.c_int, P(f64), vp]),
     "ll_gemv_basis_d": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, vp, i64]),
     "ll_gemv_basis_z": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, vp, i64]),
@@ -228,7 +230,8 @@ PROTOTYPES = {
     "ll_expo_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64), P(RunStats)]),
     "ll_expo_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64), P(RunStats)]),
     "ll_expo_two_pass": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64), P(RunStats)]),  # untyped: the operator's type
-    "ll_expo_taylor_run_d": (C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64)]),
+    "ll_expo_two_pass_multi": (C.c_int, [vp, vp, P(ExpoParams), i64, P(f64), vp, P(vp), P(i64), P(RunStats)]),  # untyped too
+    "ll_expo_taylor_run_d":(C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64)]),
     "ll_expo_taylor_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64)]),
 }
 

@@ -173,6 +173,40 @@ void expo_two_pass_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* 
   }
   expo_two_pass_run<T>(ctx, op, *p, a, (const T*)input, (T*)output, itern, stats);
 }
+template <typename T>
+void expo_two_pass_multi_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, int64_t n_times, const double* a_reim,
+                              const void* input, void* const* outputs, int64_t* itern, ll_run_stats* stats) {
+  typedef typename host_scalar<T>::type H;
+  H a[kRecurMultiMax];
+  for (int64_t j = 0; j < n_times; ++j) {
+    if constexpr (scalar_traits<T>::is_complex) {
+      a[j] = H(a_reim[2 * j], a_reim[2 * j + 1]);
+    } else {
+      LL_REQUIRE(a_reim[2 * j + 1] == 0.0, "a_im must be 0 with a real operator");
+      a[j] = a_reim[2 * j];
+    }
+  }
+  expo_two_pass_multi_run<T>(ctx, op, *p, n_times, a, (const T*)input, (T* const*)outputs, itern, stats);
+}
+template <typename T>
+void recur_accum_multi_impl(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, int64_t n_acc,
+                            const double* g_reim, void* const* psi) {
+  typedef typename RecurCoeff<T>::type G;
+  LL_REQUIRE(n >= 0 && y && x && g_reim && psi, "null vector");
+  RecurMultiArgs<T, G> acc = {};
+  for (int64_t j = 0; j < n_acc; ++j) {
+    LL_REQUIRE(psi[j] != nullptr, "null vector");
+    acc.psi[j] = (T*)psi[j];
+    if constexpr (scalar_traits<T>::is_complex) {
+      acc.g[j] = zc{g_reim[2 * j], g_reim[2 * j + 1]};
+    } else {
+      LL_REQUIRE(g_reim[2 * j + 1] == 0.0, "g_im must be 0 for the real storage types 'd' and 's'");
+      acc.g[j] = g_reim[2 * j];
+    }
+  }
+  acc.count = (int)n_acc;
+  launch_recur_accum_multi<T>(n, (T*)y, (const T*)x, (const T*)p, acc, nullptr, nullptr, 0, 0, a, b, nullptr, 0, nullptr, ctx->stream);
+}
 }  // namespace
 
 extern "C" {
@@ -496,6 +530,32 @@ int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n, void* y, cons
       case 'z': recur_accum_scaled_impl<zc>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
       case 's': recur_accum_scaled_impl<float>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
       case 'c': recur_accum_scaled_impl<cf>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
+      default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
+    }
+  });
+}
+int ll_expo_two_pass_multi(ll_context* ctx, ll_operator* op, const ll_expo_params* p, int64_t n_times, const double* a_reim,
+                           const void* input, void* const* outputs, int64_t* itern_out, ll_run_stats* stats) {
+  return guarded([&] {
+    LL_REQUIRE(ctx && op && p && a_reim && input && outputs, "null argument");
+    LL_REQUIRE(n_times >= 1 && n_times <= kRecurMultiMax, "n_times must be between 1 and 16");
+    const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
+    if (op->is_complex && wide) expo_two_pass_multi_impl<zc>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+    else if (op->is_complex) expo_two_pass_multi_impl<cf>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+    else if (wide) expo_two_pass_multi_impl<double>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+    else expo_two_pass_multi_impl<float>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+  });
+}
+int ll_recur_accum_multi(ll_context* ctx, int storage, int64_t n, void* y, const void* x, const void* p, double a, double b,
+                         int64_t n_acc, const double* g_reim, void* const* psi) {
+  return guarded([&] {
+    use(ctx);
+    LL_REQUIRE(n_acc >= 1 && n_acc <= kRecurMultiMax, "n_acc must be between 1 and 16");
+    switch (storage) {
+      case 'd': recur_accum_multi_impl<double>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
+      case 'z': recur_accum_multi_impl<zc>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
+      case 's': recur_accum_multi_impl<float>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
+      case 'c': recur_accum_multi_impl<cf>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
       default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
     }
   });

@@ -974,6 +974,24 @@ template <typename T>
 void launch_recur_accum_cplx(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const zc* gvec, int64_t k,
                              double a, double b, zc g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
                              hipStream_t s);
+// ... for up to kRecurMultiMax accumulators in one sweep (the multi-time Exponentiator): y is updated once, then psi[j] += g_j y for
+// j < count with the coefficient type of the storage type (double on d / s, zc on z / c) and g_j = gtab[row[j] * ldg + k + 1]
+// (gtab == nullptr: g[j]).  The argument struct travels by value; the host compacts the active accumulators into it per launch.
+constexpr int kRecurMultiMax = 16;
+constexpr int kRecurMultiBatch = 2;  // accumulators loaded before the first is stored: 1, 2 or 4 (recur.hip)
+template <typename T> struct RecurCoeff { typedef double type; };
+template <> struct RecurCoeff<zc> { typedef zc type; };
+template <> struct RecurCoeff<cf> { typedef zc type; };
+template <typename T, typename G> struct RecurMultiArgs {
+  T* psi[kRecurMultiMax];
+  G g[kRecurMultiMax];
+  int row[kRecurMultiMax];
+  int count;
+};
+template <typename T>
+void launch_recur_accum_multi(int64_t n, T* y, const T* x, const T* p, const RecurMultiArgs<T, typename RecurCoeff<T>::type>& acc,
+                              const double* rec, const typename RecurCoeff<T>::type* gtab, int64_t ldg, int64_t k, double a,
+                              double b, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s);
 // psi = g x, out of place, with the product of the accumulate above: the first term of pass 2's sum (real g: T = double, float;
 // complex g: T = zc, cf)
 template <typename T> void launch_recur_seed(int64_t n, T* psi, const T* x, double g, hipStream_t s);

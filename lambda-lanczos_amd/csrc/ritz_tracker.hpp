@@ -179,16 +179,88 @@ template <typename H> struct ExpoTracker {
     ev.resize((size_t)m);
     p.resize((size_t)m * m);
     tridiag_qr(m, alpha, beta, ev.data(), p.data());  // EX:124-126
-    o.coeff.assign((size_t)m, H(0));
+    const H overlap = advance(a, m, ev, p, expv, coeff_prev, o.coeff);
+    o.stop = std::abs(1.0 - std::abs(overlap)) < eps || beta[m - 1] < breakdown_tol;  // EX:154-158
+    o.seconds = now() - t0;
+    return o;
+  }
+
+  // coeff = exp(a T_m) e_1 from T_m's eigenpairs (ev, p); returns <coeff_prev, coeff> and moves coeff_prev on.  Shared with
+  // ExpoMultiTracker: one sequence of operations, so both trackers give the same bits for the same a.
+  static H advance(H a, int64_t m, const std::vector<double>& ev, const std::vector<double>& p, std::vector<H>& expv,
+                   std::vector<H>& coeff_prev, std::vector<H>& coeff) {
+    coeff.assign((size_t)m, H(0));
     expv.resize((size_t)m);
     for (int64_t j = 0; j < m; ++j) expv[(size_t)j] = std::exp(a * ev[(size_t)j]);  // m exponentials instead of m^2
     for (int64_t i = 0; i < m; ++i)  // EX:128-133: (exp(a T_m) e_1)_i, same product order as the reference
-      for (int64_t j = 0; j < m; ++j) o.coeff[(size_t)i] += p[(size_t)j * m + i] * expv[(size_t)j] * p[(size_t)j * m];
+      for (int64_t j = 0; j < m; ++j) coeff[(size_t)i] += p[(size_t)j * m + i] * expv[(size_t)j] * p[(size_t)j * m];
     H overlap = H(0);
-    for (size_t i = 0; i < coeff_prev.size(); ++i) overlap += conj_of(coeff_prev[i]) * o.coeff[i];  // EX:147-150
-    coeff_prev = o.coeff;                                                                          // EX:152
-    o.stop = std::abs(1.0 - std::abs(overlap)) < eps || beta[m - 1] < breakdown_tol;               // EX:154-158
-    o.seconds = now() - t0;
+    for (size_t i = 0; i < coeff_prev.size(); ++i) overlap += conj_of(coeff_prev[i]) * coeff[i];  // EX:147-150
+    coeff_prev = coeff;                                                                          // EX:152
+    return overlap;
+  }
+};
+
+// ExpoTracker for SEVERAL a on one Krylov space (ll_expo_two_pass_multi): one eigendecomposition of T_m per iteration, then the
+// stop rule of EX:124-158 for every a_j on its own.  The first m at which a_j's test fires is m_j, and exp(a_j T_{m_j}) e_1 is
+// frozen there: (m_j, coeff_j) are what an ExpoTracker with a = a_j reports at its stop, bit for bit.  The loop ends when every a_j
+// has fired or on breakdown; the a_j that have not fired by then (breakdown, or the caller's max_iteration: its last verdict)
+// carry that iteration's m and coefficients.
+template <typename H> struct ExpoMultiTracker {
+  std::vector<H> a;
+  double eps = 0.0;
+  double breakdown_tol = 0.0;
+
+  struct Out {
+    int64_t m = 0;
+    bool stop = false;  // every a_j frozen, or breakdown
+    double seconds = 0.0;
+    std::vector<int64_t> mj;             // per a_j: where it froze; this m where it has not
+    std::vector<std::vector<H>> coeff;   // per a_j: exp(a_j T_{m_j}) e_1
+  };
+
+  std::vector<std::vector<H>> coeff_prev, frozen;
+  std::vector<int64_t> frozen_m;  // 0: not yet
+  std::vector<H> expv;
+  std::vector<double> ev, p;
+
+  Out step(int64_t m, const double* alpha, const double* beta) {
+    TraceRange trace("ll::host_tridiag (exp(a_j T_k) e_1 + overlap tests)");
+    Out o;
+    o.m = m;
+    const double t0 = ExpoTracker<H>::now();
+    const size_t s = a.size();
+    coeff_prev.resize(s);
+    frozen.resize(s);
+    frozen_m.resize(s, 0);
+    o.mj.resize(s);
+    o.coeff.resize(s);
+    bool any_open = false;
+    for (size_t j = 0; j < s; ++j) any_open = any_open || frozen_m[j] == 0;
+    if (any_open) {  // (a verdict asked for after the stop repeats it)
+      ev.resize((size_t)m);
+      p.resize((size_t)m * m);
+      tridiag_qr(m, alpha, beta, ev.data(), p.data());  // EX:124-126, once for all a_j
+    }
+    const bool breakdown = beta[m - 1] < breakdown_tol;
+    bool all = true;
+    for (size_t j = 0; j < s; ++j) {
+      if (frozen_m[j] == 0) {
+        const H overlap = ExpoTracker<H>::advance(a[j], m, ev, p, expv, coeff_prev[j], o.coeff[j]);
+        o.mj[j] = m;
+        if (std::abs(1.0 - std::abs(overlap)) < eps || breakdown) {  // EX:154-158
+          frozen_m[j] = m;
+          frozen[j] = o.coeff[j];
+        } else {
+          all = false;
+        }
+      } else {
+        o.mj[j] = frozen_m[j];
+        o.coeff[j] = frozen[j];
+      }
+    }
+    o.stop = all;
+    o.seconds = ExpoTracker<H>::now() - t0;
     return o;
   }
 };

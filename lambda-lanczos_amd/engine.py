@@ -575,6 +575,18 @@ def recur_accum(ctx, y_dev, x_dev, p_dev, a, b, g, psi_dev, n=None):
              psi_dev.ptr))
 
 
+def recur_accum_multi(ctx, y_dev, x_dev, p_dev, a, b, g_list, psi_list, n=None):
+    """recur_accum with several accumulators in one sweep (ll_recur_accum_multi): y -= a x + b p once (p_dev may be None), then
+    psi_list[j] += g_list[j] y for every j.  Every accumulator receives the bits recur_accum gives it on its own."""
+    n = int(n if n is not None else y_dev.shape[-1])
+    g = np.ascontiguousarray(g_list, dtype=np.complex128).view(np.float64)
+    psi = (C.c_void_p * len(psi_list))(*[q.ptr for q in psi_list])
+    assert g.shape[0] == 2 * len(psi_list), "one coefficient per accumulator"
+    check(lib().ll_recur_accum_multi(ctx.handle, ord(_suffix(y_dev.dtype)), n, y_dev.ptr, x_dev.ptr,
+                                     None if p_dev is None else p_dev.ptr, float(a), float(b), len(psi_list),
+                                     g.ctypes.data_as(C.POINTER(C.c_double)), psi))
+
+
 def orth_block(ctx, basis_dev, nb, ld, w_dev, n, mode=capi.ORTH_CGS_DGKS, want_h=False):
     sfx = _suffix(w_dev.dtype)
     norm = C.c_double()
@@ -886,6 +898,49 @@ class Exponentiator:
         when the output is a host array), every operator application twice; full_orthogonalize must be False.  Same buffer
         conventions and return value as run(); last_stats carries workspace_vectors and replay_mismatches."""
         return self._call("ll_expo_two_pass", a, input, True, out, typed=False)
+
+    def run_two_pass_multi(self, a, input, out=None):
+        """run_two_pass for a sequence of times `a` from ONE Krylov space (ll_expo_two_pass_multi, at most 16 per call): pass 1 runs
+        once with the stop rule applied to every a[j] on its own, pass 2 once with one accumulator per output.  Returns
+        (list of outputs, list of iteration counts m_j); on a device operator each pair is bit for bit what run_two_pass(a[j], input)
+        returns, for 2 max(m_j) - 1 operator applications instead of sum(2 m_j - 1).  out: None (host arrays are returned) or a
+        sequence with one entry per time, each a DeviceArray (one of them may be `input`), a host array of the run's type, or None
+        for a new host array.  last_stats as run_two_pass: total_iterations = max(m_j), workspace_vectors = 3 + host outputs."""
+        a = [complex(v) for v in a]
+        op, owned = _as_operator(self.mv_mul, self.matrix_size, self.dtype, self.context)
+        try:
+            if isinstance(input, DeviceArray):
+                assert input.dtype == self.dtype and input.nbytes >= op.n_local * self.dtype.itemsize
+                keep_in, in_p = input, C.c_void_p(input.ptr)
+            else:
+                keep_in = np.ascontiguousarray(input, dtype=self.dtype)
+                assert keep_in.shape[0] == op.n_local, "input size differs from the (local) matrix size (EX:88)"
+                in_p = ptr(keep_in)
+            out = [None] * len(a) if out is None else list(out)
+            assert len(out) == len(a), "one output per time"
+            ptrs = []
+            for j, o in enumerate(out):
+                if o is None:
+                    o = out[j] = np.zeros(op.n_local, dtype=self.dtype)
+                if isinstance(o, DeviceArray):
+                    assert o.dtype == self.dtype and o.nbytes >= op.n_local * self.dtype.itemsize
+                    ptrs.append(o.ptr)
+                else:
+                    assert o.dtype == self.dtype and o.flags.c_contiguous and o.shape == (op.n_local,)
+                    ptrs.append(o.ctypes.data)
+            a_reim = np.array([[v.real, v.imag] for v in a], dtype=np.float64).reshape(-1)
+            its = (C.c_int64 * max(len(a), 1))()
+            p = self._params()
+            stats = capi.RunStats()
+            check(lib().ll_expo_two_pass_multi(self.context.handle, op.handle, C.byref(p), len(a),
+                                               a_reim.ctypes.data_as(C.POINTER(C.c_double)), in_p,
+                                               (C.c_void_p * max(len(a), 1))(*ptrs), its, C.byref(stats)))
+        finally:
+            if owned:
+                op.close()
+        del keep_in
+        self.last_stats = stats.as_dict()
+        return out, [int(v) for v in its[: len(a)]]
 
     def taylor_run(self, a, input, out=None):
         """Returns (output, number_of_terms) (EX:175-210)."""

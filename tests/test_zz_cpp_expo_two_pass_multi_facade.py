@@ -1,0 +1,35 @@
+"""Exponentiator<T>::run_two_pass with several times through the C++ facade (tests/cpp/expo_two_pass_multi_facade_test.cpp): compiles
+with a plain host compiler against the C ABI (CPU); the 10-site transverse-field Ising ring evolved to three times from one Krylov
+space, each output and count equal byte for byte to the facade's single-time run_two_pass, with host vectors and with device
+buffers (GPU)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "expo_two_pass_multi_facade_test.cpp")
+OUT_DIR = os.path.join(ROOT, "tests", "cpp", "_build")
+EXE = os.path.join(OUT_DIR, "expo_two_pass_multi_facade_test")
+LIB_DIR = os.path.join(ROOT, "lambda-lanczos_amd", "lib")
+
+
+def build():
+    os.makedirs(OUT_DIR, exist_ok=True)
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC, "-o", EXE,
+           "-L" + LIB_DIR, "-llanczos_hip", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def test_expo_two_pass_multi_facade_compiles_with_host_compiler():
+    build()
+    assert os.path.exists(EXE)
+
+
+@pytest.mark.gpu
+def test_expo_two_pass_multi_facade_three_times():
+    build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "PASSED" in r.stdout
