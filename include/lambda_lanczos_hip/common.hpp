@@ -307,6 +307,16 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
 
  protected:
   explicit PauliFamilyOperator(Context ctx) : DeviceOperator<T>(ctx) {}
+  // ll_pauli_expect: psi is host or device memory of local_rows() values (the library decides per pointer)
+  std::vector<double> expect(const std::vector<ll_pauli_term>& observables, const T* psi, int64_t* sweeps) const {
+    std::vector<double> out(observables.size(), 0.0);
+    check(ll_pauli_expect(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(), sweeps));
+    return out;
+  }
+  std::vector<double> expect(const std::vector<ll_pauli_term>& observables, const std::vector<T>& psi, int64_t* sweeps) const {
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
+    return expect(observables, psi.data(), sweeps);
+  }
   void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
@@ -330,6 +340,16 @@ template <typename T> class PauliOperator : public PauliFamilyOperator<T> {
     this->adopt_created(op);
   }
   // inf_norm() returns sum_t |coef_t|: an upper bound of every absolute row sum
+
+  // coef * Re <psi| P |psi> for every observable (x_mask, z_mask, coef), many per sweep over psi and with no n-sized workspace for
+  // a device psi (ll_pauli_expect); nothing is divided by <psi|psi>.  psi: a device pointer (or any host pointer) to size()
+  // values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->expect(observables, psi, sweeps);
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    return this->expect(observables, psi, sweeps);
+  }
 };
 
 // The same Hamiltonian on one magnetisation sector: vectors hold the C(n_sites, n_down) amplitudes of the states with n_down set
@@ -343,6 +363,13 @@ template <typename T> class PauliSectorOperator : public PauliFamilyOperator<T> 
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
     this->adopt_created(op);
+  }
+  // PauliOperator::expectation on the sector's basis: psi holds size() values; a partner s ^ x outside the sector contributes nothing
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->expect(observables, psi, sweeps);
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    return this->expect(observables, psi, sweeps);
   }
 };
 

@@ -66,7 +66,9 @@ extern "C" {
                              *    UNTYPED entry points, the storage type comes from the operator / from an argument; ll_run_stats
                              *    keeps its size (workspace_vectors and replay_mismatches are filled by ll_expo_two_pass too);
                              *    also additive under minor 5, with the same note — ll_expo_two_pass_multi (several times a from one
-                             *    Krylov space) and ll_recur_accum_multi (its replayed step with several accumulators): untyped too */
+                             *    Krylov space) and ll_recur_accum_multi (its replayed step with several accumulators): untyped too;
+                             *    also additive under minor 5, with the same note — ll_pauli_expect (expectation values of Pauli
+                             *    strings on a state of the basis of (6) or (7)): untyped, the storage type is the operator's */
 
 enum {
   LL_OK = 0,
@@ -459,6 +461,37 @@ int ll_op_create_pauli_symmetric_s(ll_context* ctx, int32_t n_sites, int32_t n_d
                                    int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
 int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
                                    int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
+
+/* EXPECTATION VALUES OF PAULI STRINGS on a state of the basis of (6) or (7), many per sweep over the state (an addition within
+ * minor 5, untyped: the storage type is the operator's).  The kernels read psi and write scalars: no n-sized output vector.
+ * With the conventions of (6), P|s> = i^nY (-1)^popcount(s & z) |s ^ x>, observable j = (x_j, z_j, coef_j) is answered
+ *     out[j] = coef_j * sum_s Re[ conj(psi(s ^ x_j)) i^nY_j (-1)^popcount(s & z_j) psi(s) ]  =  coef_j Re <psi| P_j |psi>,
+ * the sum over all 2^n_sites states for an operator of (6), over the states s_i of the sector whose partner s_i ^ x_j lies in the
+ * sector for one of (7) (the partner is found through the operator's rank tables).  NOTHING IS DIVIDED BY <psi|psi>: the term
+ * (0, 0, 1) returns ||psi||^2.
+ *   op        : from ll_op_create_pauli_* (6) or ll_op_create_pauli_sector_* (7).  It defines the basis and the storage type; the
+ *               Hamiltonian's own terms play no part.
+ *   obs_host  : n_obs observables (host memory).  n_obs = 0 is valid and touches nothing.  Duplicates are allowed and answered
+ *               independently.  Answered exactly +0.0 without a sweep: a string with an odd nY on a real storage type (_d, _s: it
+ *               is imaginary and antisymmetric — not refused, unlike a Hamiltonian term of (6)), and in a sector an x mask with an
+ *               odd popcount (s ^ x never stays in the sector).
+ *   psi       : n_local values of the operator's storage type, host or device memory (decided per pointer, as the two-pass
+ *               drivers do).  A device psi needs no n-sized workspace; a host psi is staged into one device vector.  Never modified.
+ *   out_host  : n_obs doubles.  The call runs on the context's stream and returns with out_host filled.
+ *   sweeps_out: nullable; the passes over psi that were launched: ceil(S / 32), S = the observables that are not identically zero
+ *               (they are sorted by x mask and cut into batches of 32 accumulators; a run of equal x masks loads the partner once).
+ * REFUSALS (LL_ERR_INVALID, each naming its cause): a null argument (ctx, op; obs_host, psi, out_host with n_obs > 0); a context
+ * with a communicator; every other operator kind, named in the message — the symmetry blocks (8) - (10) too: symmetrised
+ * observables are not built; a mask bit at or above n_sites; a coefficient that is not finite.
+ * BYTES per sweep, full space: between sizeof(T) n (every partner tile found in cache, or all observables diagonal) and
+ * (1 + G_remote) sizeof(T) n, G_remote = the x masks of the batch that touch a bit at or above the tile (2^b states, the key
+ * pauli_tile_bits of (6)); a sector: (sizeof(T) + 4) D up to (1 + G) sizeof(T) D + 4 D, G = the batch's x masks other than 0.
+ * ACCURACY: every product conj(psi(s ^ x)) psi(s) is formed in double (float inputs widened, exact for _s) and every sum is
+ * carried in double — per lane, then one block reduction per accumulator, then a fixed-order fold over the workgroups — so the
+ * error is that of a double-accumulated dot product of n terms plus one rounding for coef_j; for a given tile / block size the
+ * same bits run to run, for a host and a device psi and for every alignment of psi. */
+int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
+                    double* out_host, int64_t* sweeps_out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

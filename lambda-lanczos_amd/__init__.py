@@ -38,6 +38,7 @@ from .engine import (  # noqa: F401
     normalize,
     nrm2,
     orth_block,
+    pauli_expect,
     partition,
     recur_accum,
     recur_accum_multi,

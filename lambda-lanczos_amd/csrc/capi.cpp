@@ -560,5 +560,9 @@ int ll_recur_accum_multi(ll_context* ctx, int storage, int64_t n, void* y, const
     }
   });
 }
+int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
+                    double* out_host, int64_t* sweeps_out) {
+  return guarded([&] { pauli_expect(ctx, op, n_obs, obs_host, psi, out_host, sweeps_out); });
+}
 
 }  // extern "C"

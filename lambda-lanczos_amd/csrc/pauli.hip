@@ -26,26 +26,6 @@
 
 namespace ll {
 
-namespace {
-// r[v] <- r[v ^ m] for a wave-uniform m < V, one butterfly per bit of m (a register array indexed at run time would go to
-// scratch memory)
-template <typename T, int V> __device__ __forceinline__ void pauli_xor_permute(T (&r)[V], unsigned m) {
-#pragma unroll
-  for (int bit = 1; bit < V; bit <<= 1) {
-    if (m & bit) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        if (!(v & bit)) {
-          const T a = r[v];
-          r[v] = r[v | bit];
-          r[v | bit] = a;
-        }
-      }
-    }
-  }
-}
-}  // namespace
-
 // V: consecutive states per 16-byte access (1: element-wise, for vectors that are not 16-byte aligned and tiles shorter than one
 // access); the arithmetic per state is the same for every V.
 template <typename T, int V>

@@ -15,30 +15,9 @@
 // Bytes per apply: 2 sizeof(T) D + 4 D (x, y, states) when every gathered line is found in cache, up to
 // (G + 2) sizeof(T) D + 4 D when none is (G = groups with X_g != 0).
 #include "pauli_basis.hpp"
+#include "pauli_sector_partner.hpp"
 
 namespace ll {
-
-struct PauliSectorPartner {
-  const uint32_t* __restrict__ states;
-  const uint32_t* __restrict__ lo_rank;
-  const uint32_t* __restrict__ hi_rank;
-  int h;
-  __device__ __forceinline__ unsigned length(unsigned) const { return 0u; }  // no orbits
-  __device__ __forceinline__ unsigned dead_length() const { return 0u; }
-  template <typename T, typename A, int E>
-  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&)[E], const bool (&live)[E],
-                                            const A (&w)[E], const T (&)[E], const T* __restrict__ x, unsigned, A (&acc)[E]) const {
-    const unsigned px = __popc(X), himask = (1u << h) - 1;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      if (live[e] && 2 * __popc(s[e] & X) == px) {  // the partner has n_down set bits too
-        const unsigned p = s[e] ^ X;
-        const unsigned j = lo_rank[p & himask] + hi_rank[p >> h];
-        pauli_fma(acc[e], w[e], x[j]);
-      }
-    }
-  }
-};
 
 template <typename T>
 int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,

@@ -74,6 +74,23 @@ template <typename T, int V> __device__ __forceinline__ void pauli_store(T* __re
   if constexpr (V == 1) p[0] = r[0];
   else store_chunk<T, V>(p, r);
 }
+// r[v] <- r[v ^ m] for a wave-uniform m < V, one butterfly per bit of m (a register array indexed at run time would go to
+// scratch memory)
+template <typename T, int V> __device__ __forceinline__ void pauli_xor_permute(T (&r)[V], unsigned m) {
+#pragma unroll
+  for (int bit = 1; bit < V; bit <<= 1) {
+    if (m & bit) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (!(v & bit)) {
+          const T a = r[v];
+          r[v] = r[v | bit];
+          r[v | bit] = a;
+        }
+      }
+    }
+  }
+}
 }  // namespace
 
 }  // namespace ll

@@ -399,17 +399,45 @@ class _PauliFamily(_Operator):
     *args, n_terms, terms, out).  n is what creation counted."""
 
     def _create(self, ctx, kind, dtype, terms, *args):
-        terms = list(terms)
-        arr = (capi.PauliTerm * max(len(terms), 1))()
-        for k, (xm, zm, c) in enumerate(terms):
-            arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+        arr, n_terms = _term_array(terms)
         self.ctx, self.dtype = ctx, np.dtype(dtype)
-        self.row_begin, self.nnz = 0, len(terms)
+        self.row_begin, self.nnz = 0, n_terms
         h = C.c_void_p()
         fn = getattr(lib(), "ll_op_create_pauli" + kind + "_" + _suffix(self.dtype))
-        check(fn(ctx.handle, *args, len(terms), arr, C.byref(h)))
+        check(fn(ctx.handle, *args, n_terms, arr, C.byref(h)))
         self.handle = h
         self.n = self.n_local = self.info()[0]
+
+
+def _term_array(terms):
+    """(x_mask, z_mask, coef) tuples as an ll_pauli_term array (one spare element: ctypes has no empty array)."""
+    terms = list(terms)
+    arr = (capi.PauliTerm * max(len(terms), 1))()
+    for k, (xm, zm, c) in enumerate(terms):
+        arr[k].x_mask, arr[k].z_mask, arr[k].coef = int(xm), int(zm), float(c)
+    return arr, len(terms)
+
+
+def pauli_expect(op, psi, observables, return_sweeps=False):
+    """ll_pauli_expect: coef * Re <psi| P |psi> for every observable (x_mask, z_mask, coef) on the basis of `op`, as a float64
+    array — many observables per sweep over psi, no n-sized workspace for a device psi; nothing is divided by <psi|psi>.
+    psi: a numpy array (converted to the operator's dtype) or a DeviceArray (anything with .ptr, .dtype, .shape that names
+    device memory) of op.n_local values of that dtype.  With return_sweeps also the number of passes over psi that were
+    launched.  The library refuses every operator but PauliOperator and PauliSectorOperator."""
+    arr, n_obs = _term_array(observables)
+    if hasattr(psi, "ptr"):
+        if psi.dtype != np.dtype(op.dtype) or int(np.prod(psi.shape)) < op.n_local:
+            raise TypeError("psi must hold n_local values of the operator's dtype %s" % np.dtype(op.dtype))
+        keep, p = psi, C.c_void_p(psi.ptr)
+    else:
+        keep = np.ascontiguousarray(psi, dtype=op.dtype)
+        if keep.size != op.n_local:
+            raise ValueError("psi holds %d values, the operator's basis %d" % (keep.size, op.n_local))
+        p = ptr(keep)
+    out = np.zeros(n_obs, dtype=np.float64)
+    sweeps = C.c_int64(0)
+    check(lib().ll_pauli_expect(op.ctx.handle, op.handle, n_obs, arr, p, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sweeps)))
+    return (out, int(sweeps.value)) if return_sweeps else out
 
 
 class PauliOperator(_PauliFamily):
@@ -425,6 +453,10 @@ class PauliOperator(_PauliFamily):
         """sum_t |coef_t|: an upper bound of every absolute row sum (a safe |eigenvalue_offset|)."""
         return CsrOperator.inf_norm(self)
 
+    def expectation(self, psi, observables, return_sweeps=False):
+        """coef * Re <psi| P |psi> for every (x_mask, z_mask, coef) of `observables`, as a float64 array (pauli_expect)."""
+        return pauli_expect(self, psi, observables, return_sweeps)
+
 
 class PauliSectorOperator(_PauliFamily):
     """The same Hamiltonian on one magnetisation sector (ll_op_create_pauli_sector_*): the basis is the comb(n_sites, n_down)
@@ -437,6 +469,7 @@ class PauliSectorOperator(_PauliFamily):
         self._create(ctx, "_sector", dtype, terms, self.n_sites, self.n_down)
 
     inf_norm = PauliOperator.inf_norm
+    expectation = PauliOperator.expectation  # psi on the sector's basis; a partner outside the sector contributes nothing
 
 
 class PauliMomentumOperator(_PauliFamily):

@@ -400,6 +400,41 @@ def pauli_sector_csr(n_sites, n_down, terms, dtype=np.float64, merge=True):
     return _pauli_rows(states, terms, dtype, merge, column_of)
 
 
+def pauli_string_apply_np(n_sites, term, psi, states=None):
+    """P psi for the Pauli string P of term = (x_mask, z_mask, coef), formed exactly — a permutation, a sign and i^nY; the
+    coefficient plays no part: (P psi)(r) = i^nY (-1)^popcount((r ^ x) & z) psi(r ^ x).  states (None: psi on all 2^n_sites
+    states): psi on these states, ascending and with one popcount (sector_states); a partner r ^ x outside them contributes 0.
+    The result has psi's dtype for an even nY and the complex dtype of psi's precision for an odd one."""
+    x, z = int(term[0]), int(term[1])
+    psi = np.asarray(psi).reshape(-1)
+    if states is None:
+        r = np.arange(1 << int(n_sites), dtype=np.uint64)
+    else:
+        r = np.ascontiguousarray(states).astype(np.uint64).reshape(-1)
+    if psi.shape[0] != r.shape[0]:
+        raise ValueError("psi holds %d values for %d states" % (psi.shape[0], r.shape[0]))
+    if (x | z) >> int(n_sites):
+        raise ValueError("a mask bit at or above n_sites")
+    p = r ^ np.uint64(x)
+    if states is None:
+        src, inside = p.astype(np.int64), None
+    else:
+        src = np.minimum(np.searchsorted(r, p), max(r.shape[0] - 1, 0))
+        inside = r[src] == p if r.shape[0] else np.zeros(0, bool)
+    q = psi[src] if r.shape[0] else psi.copy()
+    q = np.where(_parity(p & np.uint64(z)) == 1, -q, q)
+    if inside is not None:
+        q = np.where(inside, q, np.zeros((), q.dtype))
+    ny = bin(x & z).count("1") & 3
+    if ny & 1:   # times i (nY = 1) or -i (nY = 3): the parts swap, exactly
+        cq = q.astype(np.result_type(q.dtype, np.complex64))
+        q = (-cq.imag + 1j * cq.real) if ny == 1 else (cq.imag - 1j * cq.real)
+        q = q.astype(cq.dtype)
+    elif ny == 2:
+        q = -q
+    return q
+
+
 # ------------------------------------------------------------------ one momentum block of an S_z sector of a ring
 # T rotates a state left by one bit (site j -> j + 1 mod L); the representative of an orbit {T^j s} is its smallest integer; block
 # m holds the representatives whose orbit length R satisfies m R = 0 (mod L), ascending (ll_op_create_pauli_momentum_*).
