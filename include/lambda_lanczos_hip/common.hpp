@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../lanczos_hip.h"
+#include "entropy.hpp"  // von_neumann_entropy of a reduced density matrix (host only)
 #include "util.hpp"  // lambda_lanczos::util::{real_t, inner_prod, norm, normalize, schmidt_orth, m_norm, sort_eigenpairs, ...}
 
 namespace lambda_lanczos_hip {
@@ -317,6 +318,18 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
     if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
     return expect(observables, psi.data(), sweeps);
   }
+  // ll_pauli_rdm: rho[a][a'] row-major, 2^m x 2^m, m = sites.size()
+  std::vector<std::complex<double>> rdm(const std::vector<int>& sites, const T* psi, int64_t* sweeps) const {
+    const std::vector<int32_t> s32(sites.begin(), sites.end());
+    const size_t dim = (size_t)1 << std::min<size_t>(s32.size(), 6);  // (a count the library refuses still gets a buffer)
+    std::vector<std::complex<double>> out(dim * dim);
+    check(ll_pauli_rdm(this->context().get(), this->get(), (int32_t)s32.size(), s32.data(), psi, reinterpret_cast<double*>(out.data()), sweeps));
+    return out;
+  }
+  std::vector<std::complex<double>> rdm(const std::vector<int>& sites, const std::vector<T>& psi, int64_t* sweeps) const {
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: psi must hold local_rows() values");
+    return rdm(sites, psi.data(), sweeps);
+  }
   void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
@@ -350,6 +363,17 @@ template <typename T> class PauliOperator : public PauliFamilyOperator<T> {
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
     return this->expect(observables, psi, sweeps);
   }
+
+  // rho_A = Tr_env |psi><psi| of up to six distinct sites in one sweep over psi (ll_pauli_rdm): row-major 2^m x 2^m with
+  // rho[a][a'] = sum_e psi(a, e) conj(psi(a', e)), bit k of a = sites[k]; exactly Hermitian, not divided by <psi|psi> (the trace
+  // is ||psi||^2).  psi as for expectation().  von_neumann_entropy (entropy.hpp) takes the result.
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->rdm(sites, psi, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& psi,
+                                                           int64_t* sweeps = nullptr) const {
+    return this->rdm(sites, psi, sweeps);
+  }
 };
 
 // The same Hamiltonian on one magnetisation sector: vectors hold the C(n_sites, n_down) amplitudes of the states with n_down set
@@ -370,6 +394,14 @@ template <typename T> class PauliSectorOperator : public PauliFamilyOperator<T> 
   }
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
     return this->expect(observables, psi, sweeps);
+  }
+  // PauliOperator::reduced_density_matrix on the sector's basis: every entry with popcount(a) != popcount(a') is exactly +0.0
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->rdm(sites, psi, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& psi,
+                                                           int64_t* sweeps = nullptr) const {
+    return this->rdm(sites, psi, sweeps);
   }
 };
 

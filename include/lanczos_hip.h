@@ -68,7 +68,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_expo_two_pass_multi (several times a from one
                              *    Krylov space) and ll_recur_accum_multi (its replayed step with several accumulators): untyped too;
                              *    also additive under minor 5, with the same note — ll_pauli_expect (expectation values of Pauli
-                             *    strings on a state of the basis of (6) or (7)): untyped, the storage type is the operator's */
+                             *    strings on a state of the basis of (6) or (7)): untyped, the storage type is the operator's;
+                             *    also additive under minor 5, with the same note — ll_pauli_rdm (the reduced density matrix of up
+                             *    to six sites of such a state, in one sweep): untyped, the storage type is the operator's */
 
 enum {
   LL_OK = 0,
@@ -492,6 +494,42 @@ int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_d
  * same bits run to run, for a host and a device psi and for every alignment of psi. */
 int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
                     double* out_host, int64_t* sweeps_out);
+
+/* REDUCED DENSITY MATRIX of up to six sites of a state of the basis of (6) or (7), in ONE sweep over the state (an addition
+ * within minor 5, untyped: the storage type is the operator's).  The kernels read psi once and write 4^m numbers.
+ *     rho[a][a'] = sum_e psi(a, e) conj(psi(a', e)),     m = n_sub, a, a' in [0, 2^m),
+ * bit k of the subsystem index a is site sites_host[k]; e runs over the configurations of the other sites (for an operator of (7):
+ * over those that leave the state in the sector).  NOTHING IS DIVIDED BY <psi|psi>: the trace is ||psi||^2, as ll_pauli_expect
+ * answers the identity.  Tomography through ll_pauli_expect needs 4^m observables = ceil(4^m / 32) sweeps for the same numbers.
+ *   op        : from ll_op_create_pauli_* (6) or ll_op_create_pauli_sector_* (7).  It defines the basis and the storage type; the
+ *               Hamiltonian's terms play no part.
+ *   sites_host: n_sub DISTINCT sites in [0, n_sites), in any order; 1 <= n_sub <= min(6, n_sites).
+ *   psi       : n_local values of the operator's storage type, host or device memory (decided per pointer).  A device psi needs
+ *               no n-sized workspace; a host psi is staged into one device vector.  Never modified.
+ *   out_host  : 2 * 4^m doubles, row-major rho[a][a'] with interleaved (re, im).  The call runs on the context's stream and returns
+ *               with out_host filled.  EXACTLY HERMITIAN: the kernels compute a <= a' and the library mirrors — out[a'][a] has the
+ *               bits of out[a][a'] in its real part and the negated imaginary part, and every zero imaginary part is +0.0 on both
+ *               sides; the diagonal's imaginary parts are +0.0; for real storage (_d, _s) every imaginary part is +0.0.  For an
+ *               operator of (7): every entry with popcount(a) != popcount(a') is +0.0 by rule, and so is every row a with
+ *               n_down - popcount(a) outside [0, n_sites - m] (no configuration of the other sites completes it).
+ *   sweeps_out: nullable; 1 when a kernel ran.  Untouched by a refused call.
+ * REFUSALS (LL_ERR_INVALID, each naming its cause, all before the device is touched): a null argument (ctx, op, sites_host, psi,
+ * out_host); a context with a communicator; every other operator kind, named in the message — the symmetry blocks (8) - (10)
+ * too; n_sub outside 1 .. 6 or above n_sites; a site outside [0, n_sites); a repeated site (the message names its index).
+ * BYTES per call, full space: sizeof(T) n — every element of psi is read from memory once, whatever the sites — plus the
+ * partials, 8 P G bytes written and read once: P = 3, 10, 40, 160, 576, 2176 doubles per workgroup for m = 1 .. 6 (twice that for
+ * complex storage) and G <= 2048 workgroups, lowered so that 8 P G <= 8 MiB (m = 5: 1820 / 910, m = 6: 481 / 240 workgroups for
+ * real / complex storage).  A sector: sizeof(T) D gathered through the operator's rank tables (two 4-byte look-ups per element,
+ * tables of 4 * 2^(n_sites / 2) bytes: cached) plus the same partials; the 2^(n_sites - m) configurations are enumerated, the
+ * empty ones skipped.  The LDS holds 2^t consecutive states times the 2^h tiles that differ in the h subsystem sites at or above t
+ * (32 KiB at most; the unstable key pauli_rdm_tile_bits forces t; a sector: 2^b configurations, key pauli_rdm_block_bits).
+ * ACCURACY: every product psi(a, e) conj(psi(a', e)) is formed in double (float inputs widened, exact for _s, _c) inside an fma
+ * and every sum is carried in double — per thread over the workgroup's rows, then a fixed-order fold inside the workgroup where
+ * one entry has several partial owners (m <= 5: 85, 25, 25, 25, 7 row slices), then a fixed-order fold over the workgroups — so
+ * each part of each entry meets the bound of a double-accumulated dot product of its two fibres psi(a, .), psi(a', .).  No
+ * atomics: for a given tile / block size the same bits run to run, for a host and a device psi and for every alignment of psi. */
+int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi,
+                 double* out_host, int64_t* sweeps_out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

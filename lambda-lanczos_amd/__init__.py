@@ -34,11 +34,13 @@ from .engine import (  # noqa: F401
     live_contexts,
     CONTEXT_CREATED_HOOKS,
     dot,
+    entanglement_entropy,
     gemv_basis,
     normalize,
     nrm2,
     orth_block,
     pauli_expect,
+    pauli_rdm,
     partition,
     recur_accum,
     recur_accum_multi,

@@ -440,6 +440,41 @@ def pauli_expect(op, psi, observables, return_sweeps=False):
     return (out, int(sweeps.value)) if return_sweeps else out
 
 
+def pauli_rdm(op, psi, sites, return_sweeps=False):
+    """ll_pauli_rdm: the reduced density matrix rho[a][a'] = sum_e psi(a, e) conj psi(a', e) of the sites `sites` (1 to 6 distinct
+    sites; bit k of a is sites[k]) of a state on the basis of `op`, as a complex128 array of shape (2^m, 2^m) — one sweep over
+    psi, no n-sized workspace for a device psi; nothing is divided by <psi|psi>: the trace is ||psi||^2.  psi as for pauli_expect:
+    a numpy array (converted to the operator's dtype) or anything with .ptr, .dtype, .shape that names device memory.  With
+    return_sweeps also the number of passes over psi (1).  The library refuses every operator but PauliOperator and
+    PauliSectorOperator."""
+    sites = [int(s) for s in sites]
+    m = len(sites)
+    arr = (C.c_int32 * max(m, 1))(*sites)
+    if hasattr(psi, "ptr"):
+        if psi.dtype != np.dtype(op.dtype) or int(np.prod(psi.shape)) < op.n_local:
+            raise TypeError("psi must hold n_local values of the operator's dtype %s" % np.dtype(op.dtype))
+        keep, p = psi, C.c_void_p(psi.ptr)
+    else:
+        keep = np.ascontiguousarray(psi, dtype=op.dtype)
+        if keep.size != op.n_local:
+            raise ValueError("psi holds %d values, the operator's basis %d" % (keep.size, op.n_local))
+        p = ptr(keep)
+    dim = 1 << min(max(m, 0), 6)   # (a count the library refuses still gets a buffer)
+    out = np.zeros((dim, dim), dtype=np.complex128)
+    sweeps = C.c_int64(0)
+    check(lib().ll_pauli_rdm(op.ctx.handle, op.handle, m, arr, p, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sweeps)))
+    return (out, int(sweeps.value)) if return_sweeps else out
+
+
+def entanglement_entropy(rho):
+    """The von Neumann entropy -sum lambda ln lambda of rho / tr rho (host numpy: numpy.linalg.eigvalsh of the Hermitian
+    matrix; eigenvalues <= 0 contribute 0)."""
+    rho = np.asarray(rho, dtype=np.complex128)
+    lam = np.linalg.eigvalsh(rho / np.trace(rho).real)
+    lam = lam[lam > 0.0]
+    return float(-np.sum(lam * np.log(lam))) + 0.0   # (never -0.0)
+
+
 class PauliOperator(_PauliFamily):
     """Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t (ll_op_create_pauli_*): `terms` is a sequence of
     (x_mask, z_mask, coef); bit j of a basis state is site j, a site carries X (x bit only), Z (z bit only) or Y (both).
@@ -457,6 +492,10 @@ class PauliOperator(_PauliFamily):
         """coef * Re <psi| P |psi> for every (x_mask, z_mask, coef) of `observables`, as a float64 array (pauli_expect)."""
         return pauli_expect(self, psi, observables, return_sweeps)
 
+    def reduced_density_matrix(self, psi, sites, return_sweeps=False):
+        """rho_A = Tr_env |psi><psi| of the sites `sites` (at most 6), complex128 of shape (2^m, 2^m), not normalised (pauli_rdm)."""
+        return pauli_rdm(self, psi, sites, return_sweeps)
+
 
 class PauliSectorOperator(_PauliFamily):
     """The same Hamiltonian on one magnetisation sector (ll_op_create_pauli_sector_*): the basis is the comb(n_sites, n_down)
@@ -470,6 +509,7 @@ class PauliSectorOperator(_PauliFamily):
 
     inf_norm = PauliOperator.inf_norm
     expectation = PauliOperator.expectation  # psi on the sector's basis; a partner outside the sector contributes nothing
+    reduced_density_matrix = PauliOperator.reduced_density_matrix  # popcount(a) != popcount(a') is exactly +0.0
 
 
 class PauliMomentumOperator(_PauliFamily):

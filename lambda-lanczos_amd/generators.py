@@ -435,6 +435,41 @@ def pauli_string_apply_np(n_sites, term, psi, states=None):
     return q
 
 
+def reduced_density_matrix_np(n_sites, sites, psi, states=None):
+    """(rho, fibres): rho[a][a'] = sum_e psi(a, e) conj psi(a', e) in complex128 — the plain host restatement of ll_pauli_rdm —
+    and fibres, the array of shape (2^m, 2^(n_sites - m)) with fibres[a][e] = psi(a, e) in psi's dtype: bit k of a is site
+    sites[k], the bits of e fill the other sites in ascending order.  states (None: psi on all 2^n_sites states): psi on these
+    states, ascending and with one popcount (sector_states); an (a, e) outside them is 0.  rho = fibres @ fibres^H, its upper triangle mirrored."""
+    sites = [int(s) for s in sites]
+    m, n_sites = len(sites), int(n_sites)
+    if not 1 <= m <= n_sites or len(set(sites)) != m or min(sites) < 0 or max(sites) >= n_sites:
+        raise ValueError("sites must be 1 to n_sites distinct sites in [0, n_sites)")
+    psi = np.asarray(psi).reshape(-1)
+    full = psi
+    if states is not None:
+        st = np.ascontiguousarray(states).astype(np.int64).reshape(-1)
+        if psi.shape[0] != st.shape[0]:
+            raise ValueError("psi holds %d values for %d states" % (psi.shape[0], st.shape[0]))
+        full = np.zeros(1 << n_sites, dtype=psi.dtype)
+        full[st] = psi
+    elif psi.shape[0] != 1 << n_sites:
+        raise ValueError("psi holds %d values for %d states" % (psi.shape[0], 1 << n_sites))
+    env = [s for s in range(n_sites) if s not in sites]
+    a = np.arange(1 << m, dtype=np.int64)
+    e = np.arange(1 << (n_sites - m), dtype=np.int64)
+    sa = np.zeros_like(a)
+    for k, s in enumerate(sites):
+        sa |= ((a >> k) & 1) << s
+    se = np.zeros_like(e)
+    for k, s in enumerate(env):
+        se |= ((e >> k) & 1) << s
+    fibres = full[sa[:, None] | se[None, :]]
+    wide = fibres.astype(np.complex128)
+    rho = wide @ wide.conj().T
+    rho = np.triu(rho, 1) + np.triu(rho, 1).conj().T + np.diag(rho.diagonal().real)   # Hermitian bit for bit
+    return rho, fibres
+
+
 # ------------------------------------------------------------------ one momentum block of an S_z sector of a ring
 # T rotates a state left by one bit (site j -> j + 1 mod L); the representative of an orbit {T^j s} is its smallest integer; block
 # m holds the representatives whose orbit length R satisfies m R = 0 (mod L), ascending (ll_op_create_pauli_momentum_*).
