@@ -318,6 +318,17 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
     if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
     return expect(observables, psi.data(), sweeps);
   }
+  // ll_pauli_expect_block: psi is host or device memory of local_rows() coefficients on a symmetry block's representatives
+  std::vector<double> expect_block(const std::vector<ll_pauli_term>& observables, const T* psi, int64_t* sweeps) const {
+    std::vector<double> out(observables.size(), 0.0);
+    check(ll_pauli_expect_block(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(),
+                                sweeps));
+    return out;
+  }
+  std::vector<double> expect_block(const std::vector<ll_pauli_term>& observables, const std::vector<T>& psi, int64_t* sweeps) const {
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
+    return expect_block(observables, psi.data(), sweeps);
+  }
   // ll_pauli_rdm: rho[a][a'] row-major, 2^m x 2^m, m = sites.size()
   std::vector<std::complex<double>> rdm(const std::vector<int>& sites, const T* psi, int64_t* sweeps) const {
     const std::vector<int32_t> s32(sites.begin(), sites.end());
@@ -420,6 +431,16 @@ template <typename T> class PauliMomentumOperator : public PauliFamilyOperator<T
                                         terms.data(), &op));
     this->adopt_created(op);
   }
+  // coef * Re <Psi| P |Psi> for every observable, Psi = B psi the state that the size() coefficients psi on the block's basis stand
+  // for — Psi is never formed: every observable is averaged over the block's group and measured with the gather of this
+  // operator's apply, up to 32 per sweep over psi (ll_pauli_expect_block); nothing is divided by <psi|psi>.  psi: a device pointer
+  // (or any host pointer) to size() values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
+  }
 };
 
 // One momentum block of the FULL 2^n_sites space of a ring: H must commute with the one-site translation and need not conserve
@@ -436,6 +457,13 @@ template <typename T> class PauliMomentumFullOperator : public PauliFamilyOperat
     check(abi<T>::create_pauli_momentum_full(ctx.get(), (int32_t)n_sites, (int32_t)momentum, (int64_t)terms.size(), terms.data(),
                                              &op));
     this->adopt_created(op);
+  }
+  // PauliMomentumOperator::expectation on this block's basis and group (ll_pauli_expect_block)
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
   }
 };
 
@@ -454,6 +482,13 @@ template <typename T> class PauliSymmetricOperator : public PauliFamilyOperator<
     check(abi<T>::create_pauli_symmetric(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int32_t)parity,
                                          (int32_t)inversion, (int64_t)terms.size(), terms.data(), &op));
     this->adopt_created(op);
+  }
+  // PauliMomentumOperator::expectation on this block's basis and group (ll_pauli_expect_block)
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    return this->expect_block(observables, psi, sweeps);
   }
 };
 

@@ -70,7 +70,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_pauli_expect (expectation values of Pauli
                              *    strings on a state of the basis of (6) or (7)): untyped, the storage type is the operator's;
                              *    also additive under minor 5, with the same note — ll_pauli_rdm (the reduced density matrix of up
-                             *    to six sites of such a state, in one sweep): untyped, the storage type is the operator's */
+                             *    to six sites of such a state, in one sweep): untyped, the storage type is the operator's;
+                             *    also additive under minor 5, with the same note — ll_pauli_expect_block (expectation values of
+                             *    Pauli strings on a state of a symmetry block (8) - (10)): untyped, the storage type is the operator's */
 
 enum {
   LL_OK = 0,
@@ -483,8 +485,8 @@ int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_d
  *   sweeps_out: nullable; the passes over psi that were launched: ceil(S / 32), S = the observables that are not identically zero
  *               (they are sorted by x mask and cut into batches of 32 accumulators; a run of equal x masks loads the partner once).
  * REFUSALS (LL_ERR_INVALID, each naming its cause): a null argument (ctx, op; obs_host, psi, out_host with n_obs > 0); a context
- * with a communicator; every other operator kind, named in the message — the symmetry blocks (8) - (10) too: symmetrised
- * observables are not built; a mask bit at or above n_sites; a coefficient that is not finite.
+ * with a communicator; every other operator kind, named in the message — the symmetry blocks (8) - (10) too: they are measured
+ * by ll_pauli_expect_block below; a mask bit at or above n_sites; a coefficient that is not finite.
  * BYTES per sweep, full space: between sizeof(T) n (every partner tile found in cache, or all observables diagonal) and
  * (1 + G_remote) sizeof(T) n, G_remote = the x masks of the batch that touch a bit at or above the tile (2^b states, the key
  * pauli_tile_bits of (6)); a sector: (sizeof(T) + 4) D up to (1 + G) sizeof(T) D + 4 D, G = the batch's x masks other than 0.
@@ -494,6 +496,29 @@ int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_d
  * same bits run to run, for a host and a device psi and for every alignment of psi. */
 int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
                     double* out_host, int64_t* sweeps_out);
+
+/* ... ON A RING'S SYMMETRY BLOCK: the state is given by its n_local coefficients c on the representatives of a block operator of
+ * (8) - (10) (an addition within minor 5, untyped: the storage type is the operator's).  With B the block's isometry and Psi = B c,
+ *     out[j] = coef_j Re <Psi| P_j |Psi>          (NOTHING IS DIVIDED BY <c|c> = <Psi|Psi>: the term (0, 0, 1) returns ||c||^2)
+ * without Psi ever being formed: Psi transforms by a one-dimensional character of the block's group G (the one-site shift; the
+ * reflection iff parity != 0; the global flip iff inversion != 0), so P_j is replaced by its average over G,
+ * Pbar_j = (1 / |G|) sum_h h P_j h^-1 — images: both masks rotated / bit-reversed / the sign (-1)^popcount(z) — which commutes
+ * with G; the kernel forms sum_a Re[conj(c_a) (Pbar_j c)(a)] with the gather of the operator's own apply, in registers: no n-sized
+ * workspace for a device psi, up to 32 observables per sweep over c.
+ *   op        : from ll_op_create_pauli_momentum_* (8), _momentum_full_* (9) or _symmetric_* (10).  It defines the basis, the
+ *               group and the storage type; the Hamiltonian's own terms play no part.
+ *   obs_host, psi, out_host: as ll_pauli_expect.  Answered exactly +0.0 without a sweep: an observable all of whose images cancel
+ *               (the flip is in use and popcount(z) is odd), an odd nY on a real storage type, and with a fixed S_z sector an x
+ *               mask with an odd popcount.  A string that leaves the sector or the block needs no special case.
+ *   sweeps_out: nullable; ceil(S / 32), S = the observables that are not identically zero, in the caller's order.
+ * REFUSALS (LL_ERR_INVALID, each naming its cause): those of ll_pauli_expect; every operator kind but (8) - (10), named in the
+ * message — for (6) and (7) the message points to ll_pauli_expect.
+ * ACCURACY: all arithmetic in double (float inputs widened): per state one fma per distinct image string and group, then
+ * Re[conj(c_a) .], summed per wave, workgroup and grid in an order that depends on the block size (the tuning key of the
+ * operator's apply) and the grid alone: the same bits run to run, for a host and a device psi, for every alignment of psi and
+ * wherever an observable stands in the call. */
+int ll_pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
+                          double* out_host, int64_t* sweeps_out);
 
 /* REDUCED DENSITY MATRIX of up to six sites of a state of the basis of (6) or (7), in ONE sweep over the state (an addition
  * within minor 5, untyped: the storage type is the operator's).  The kernels read psi once and write 4^m numbers.

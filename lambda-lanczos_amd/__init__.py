@@ -40,6 +40,7 @@ from .engine import (  # noqa: F401
     nrm2,
     orth_block,
     pauli_expect,
+    pauli_expect_block,
     pauli_rdm,
     partition,
     recur_accum,

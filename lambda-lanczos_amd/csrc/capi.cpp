@@ -564,6 +564,10 @@ int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const
                     double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_expect(ctx, op, n_obs, obs_host, psi, out_host, sweeps_out); });
 }
+int ll_pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
+                          double* out_host, int64_t* sweeps_out) {
+  return guarded([&] { pauli_expect_block(ctx, op, n_obs, obs_host, psi, out_host, sweeps_out); });
+}
 int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi,
                  double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_rdm(ctx, op, n_sub, sites_host, psi, out_host, sweeps_out); });

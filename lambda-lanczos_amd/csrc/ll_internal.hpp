@@ -672,7 +672,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_rdm.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_rdm.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -790,6 +790,11 @@ int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, doub
 // ll_pauli_expect (pauli_expect.hip; planned by pauli_expect_plan.hpp): every check, then the sweeps on the operator's storage type
 void pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi, double* out,
                   int64_t* sweeps_out);
+const char* pauli_expect_kind_name(int kind);  // "a CSR operator", ...: what the measuring entry points' refusals call an operator
+// ll_pauli_expect_block (pauli_expect_block.hip; planned by pauli_expect_block_plan.hpp): the same on a ring's symmetry block,
+// psi = the coefficients on the block's representatives
+void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi, double* out,
+                        int64_t* sweeps_out);
 // ll_pauli_rdm (pauli_rdm.hip; planned by pauli_rdm_plan.hpp): every check, then the one sweep on the operator's storage type
 void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, double* out,
                int64_t* sweeps_out);

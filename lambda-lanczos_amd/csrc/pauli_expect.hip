@@ -249,9 +249,12 @@ int launch_pauli_expect_sector(const ll_operator& op, int count, const uint32_t*
   LL_HIP(hipGetLastError());
   return grid;
 }
+}  // namespace
 
-const char* expect_kind_name(int kind) {
+const char* pauli_expect_kind_name(int kind) {
   switch (kind) {
+    case ll_operator::PAULI: return "a full-space sum of Pauli strings";
+    case ll_operator::PAULI_SECTOR: return "a sum of Pauli strings on an S_z sector";
     case ll_operator::CSR: return "a CSR operator";
     case ll_operator::HOST_CB: return "a host-callback operator";
     case ll_operator::DEV_CB: return "a device-callback operator";
@@ -263,7 +266,6 @@ const char* expect_kind_name(int kind) {
     default: return "an operator of an unknown kind";
   }
 }
-}  // namespace
 
 template <typename T>
 void pauli_expect_run(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi,
@@ -327,11 +329,11 @@ void pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const l
   LL_REQUIRE(op->ctx == ctx, "the operator belongs to another context");
   LL_REQUIRE(ctx->comm == nullptr, "expectation values are not built for sharded contexts (a context with a communicator)");
   if (op->kind == ll_operator::PAULI_MOMENTUM || op->kind == ll_operator::PAULI_MOMENTUM_FULL || op->kind == ll_operator::PAULI_SYMMETRIC)
-    LL_REQUIRE(false, std::string("the operator is ") + expect_kind_name(op->kind) +
+    LL_REQUIRE(false, std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
                           ": symmetrised observables are not built (an observable must be summed over the block's group first); "
                           "measure on a full-space or S_z-sector operator");
   LL_REQUIRE(op->kind == ll_operator::PAULI || op->kind == ll_operator::PAULI_SECTOR,
-             std::string("the operator is ") + expect_kind_name(op->kind) +
+             std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
                  ": expectation values of Pauli strings need an operator that defines a spin basis (full-space or S_z-sector "
                  "sum of Pauli strings)");
   if (sweeps_out) *sweeps_out = 0;

@@ -22,53 +22,15 @@
 // Bytes per apply: (2 sizeof(T) + 5) D_m (x, y, reps, orbit_len) when every gather is found in cache, up to
 // (2 sizeof(T) + 5) D_m + G (sizeof(T) + 4) D_m when none is (G = groups with X_g != 0: one orbit entry and one element each).
 #include "pauli_basis.hpp"
+#include "pauli_momentum_partner.hpp"  // PauliMomentumPartner: shared with the measuring kernel
 
 namespace ll {
-
-struct PauliMomentumPartner {
-  const uint32_t* __restrict__ states;  // reps
-  const uint8_t* __restrict__ orbit_len;
-  const uint32_t* __restrict__ orbit;
-  const uint32_t* __restrict__ lo_rank;
-  const uint32_t* __restrict__ hi_rank;
-  const double* __restrict__ ratio;
-  const double* __restrict__ phase;
-  int n_sites, h, momentum, nshort;
-  int short_shift[3];
-  __device__ __forceinline__ unsigned length(unsigned i) const { return (unsigned)orbit_len[i]; }
-  __device__ __forceinline__ unsigned dead_length() const { return (unsigned)n_sites; }
-  template <typename T, typename A, int E>
-  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&ra)[E], const bool (&live)[E],
-                                            const A (&w)[E], const T (&)[E], const T* __restrict__ x, unsigned, A (&acc)[E]) const {
-    const unsigned px = __popc(X), himask = (1u << h) - 1;
-    const unsigned L = (unsigned)n_sites, smask = (L >= 32u ? 0u : (1u << L)) - 1u;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      if (live[e] && 2 * __popc(s[e] & X) == px) {  // the partner has n_down set bits too
-        const unsigned p = s[e] ^ X;
-        const unsigned o = orbit[lo_rank[p & himask] + hi_rank[p >> h]];
-        if (o != kPauliOrbitExcluded) {  // the partner's orbit is in the block
-          const unsigned j = o >> kPauliOrbitShiftBits, l = o & ((1u << kPauliOrbitShiftBits) - 1);
-          bool is_short = false;  // T^(L / q) p == p for a prime q of L: the orbit is shorter than L
-          for (int q = 0; q < nshort; ++q) is_short = is_short || pauli_rotl(p, (unsigned)short_shift[q], L, smask) == p;
-          const unsigned rb = is_short ? (unsigned)orbit_len[j] : L;
-          A wg = w[e];
-          if (rb != ra[e]) wg = momentum_scale(wg, ratio[ra[e] * 32u + rb]);
-          if (momentum != 0) wg = momentum_phase(wg, phase[2 * l], phase[2 * l + 1]);
-          pauli_fma(acc[e], wg, x[j]);
-        }
-      }
-    }
-  }
-};
 
 template <typename T>
 int launch_pauli_momentum(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                           const ScaleIn<T>* scp) {
   const PauliMomentumImage& im = op.pauli_momentum;
-  const PauliMomentumPartner pt{im.reps.get(),  im.orbit_len.get(), im.orbit.get(), im.lo_rank.get(),
-                                im.hi_rank.get(), im.ratio.get(),   im.phase.get(), im.n_sites,
-                                im.h,             im.momentum,      im.nshort,      {im.short_shift[0], im.short_shift[1], im.short_shift[2]}};
+  const PauliMomentumPartner pt = pauli_momentum_partner(im);
   return launch_pauli_basis(pauli_block_bits(op, &Tuning::pauli_momentum_block_bits, kPauliMomentumBlockBits), im.dim, im.terms, pt,
                             x, y, offset, dot_partials, s, scp);
 }

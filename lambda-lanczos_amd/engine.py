@@ -418,12 +418,7 @@ def _term_array(terms):
     return arr, len(terms)
 
 
-def pauli_expect(op, psi, observables, return_sweeps=False):
-    """ll_pauli_expect: coef * Re <psi| P |psi> for every observable (x_mask, z_mask, coef) on the basis of `op`, as a float64
-    array — many observables per sweep over psi, no n-sized workspace for a device psi; nothing is divided by <psi|psi>.
-    psi: a numpy array (converted to the operator's dtype) or a DeviceArray (anything with .ptr, .dtype, .shape that names
-    device memory) of op.n_local values of that dtype.  With return_sweeps also the number of passes over psi that were
-    launched.  The library refuses every operator but PauliOperator and PauliSectorOperator."""
+def _pauli_expect_call(entry, op, psi, observables, return_sweeps):
     arr, n_obs = _term_array(observables)
     if hasattr(psi, "ptr"):
         if psi.dtype != np.dtype(op.dtype) or int(np.prod(psi.shape)) < op.n_local:
@@ -436,8 +431,27 @@ def pauli_expect(op, psi, observables, return_sweeps=False):
         p = ptr(keep)
     out = np.zeros(n_obs, dtype=np.float64)
     sweeps = C.c_int64(0)
-    check(lib().ll_pauli_expect(op.ctx.handle, op.handle, n_obs, arr, p, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sweeps)))
+    check(getattr(lib(), entry)(op.ctx.handle, op.handle, n_obs, arr, p, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sweeps)))
     return (out, int(sweeps.value)) if return_sweeps else out
+
+
+def pauli_expect(op, psi, observables, return_sweeps=False):
+    """ll_pauli_expect: coef * Re <psi| P |psi> for every observable (x_mask, z_mask, coef) on the basis of `op`, as a float64
+    array — many observables per sweep over psi, no n-sized workspace for a device psi; nothing is divided by <psi|psi>.
+    psi: a numpy array (converted to the operator's dtype) or a DeviceArray (anything with .ptr, .dtype, .shape that names
+    device memory) of op.n_local values of that dtype.  With return_sweeps also the number of passes over psi that were
+    launched.  The library refuses every operator but PauliOperator and PauliSectorOperator."""
+    return _pauli_expect_call("ll_pauli_expect", op, psi, observables, return_sweeps)
+
+
+def pauli_expect_block(op, psi, observables, return_sweeps=False):
+    """ll_pauli_expect_block: coef * Re <Psi| P |Psi> for every observable (x_mask, z_mask, coef), Psi = B psi the state that the
+    op.n_local coefficients `psi` on the representatives of a symmetry block stand for (B: generators.momentum_embedding,
+    full_momentum_embedding or symmetric_embedding) — Psi is never formed: every observable is averaged over the block's group
+    (generators.symmetrised_strings) and measured with the gather of the operator's own apply, up to 32 per sweep over psi;
+    nothing is divided by <psi|psi>.  psi and return_sweeps as pauli_expect.  The library refuses every operator but
+    PauliMomentumOperator, PauliMomentumFullOperator and PauliSymmetricOperator."""
+    return _pauli_expect_call("ll_pauli_expect_block", op, psi, observables, return_sweeps)
 
 
 def pauli_rdm(op, psi, sites, return_sweeps=False):
@@ -527,6 +541,11 @@ class PauliMomentumOperator(_PauliFamily):
         """sum_t |coef_t|: an upper bound of every |eigenvalue| of the block (a safe |eigenvalue_offset|)."""
         return CsrOperator.inf_norm(self)
 
+    def expectation(self, psi, observables, return_sweeps=False):
+        """coef * Re <B psi| P |B psi> for every (x_mask, z_mask, coef) of `observables`, psi the coefficients on the block's
+        representatives, as a float64 array (pauli_expect_block)."""
+        return pauli_expect_block(self, psi, observables, return_sweeps)
+
 
 class PauliMomentumFullOperator(_PauliFamily):
     """One momentum block of the full 2^n_sites space of a ring (ll_op_create_pauli_momentum_full_*): the operator B^H H B with
@@ -541,6 +560,7 @@ class PauliMomentumFullOperator(_PauliFamily):
         self._create(ctx, "_momentum_full", dtype, terms, self.n_sites, self.momentum)  # n = D_m
 
     inf_norm = PauliMomentumOperator.inf_norm
+    expectation = PauliMomentumOperator.expectation
 
 
 class PauliSymmetricOperator(_PauliFamily):
@@ -559,6 +579,7 @@ class PauliSymmetricOperator(_PauliFamily):
                      self.parity, self.inversion)  # n = D
 
     inf_norm = PauliMomentumOperator.inf_norm
+    expectation = PauliMomentumOperator.expectation
 
 
 class HostOperator(_Operator):

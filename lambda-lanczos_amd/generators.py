@@ -797,6 +797,35 @@ def inversion_fault(n_sites, terms):
     return None
 
 
+def symmetrised_strings(n_sites, term, parity=0, inversion=0):
+    """The average of the string `term` = (x_mask, z_mask[, coef]) over the group G of a ring's symmetry block — the one-site shift
+    always, the reflection iff parity != 0, the global flip iff inversion != 0 — as a list of (x_mask, z_mask, weight): the numpy
+    mirror of csrc/pauli_expect_block_plan.hpp.  The |G| images (both masks rotated left / bit-reversed; the flip keeps the masks
+    and gives the sign (-1)^popcount(z)) are merged by (x, z) with their signed multiplicities added as integers, cancelled
+    strings dropped, the others weighted multiplicity / |G| and sorted by x mask, then z mask.  The coefficient of `term` is
+    not in the weights; an empty list means the observable is identically zero on every state of such a block.  For a state
+    Psi = B c of the block, <Psi| P |Psi> = c^H M c with M = pauli_symmetric_csr(..., symmetrised_strings(...), ...)."""
+    L, x, z = int(n_sites), int(term[0]), int(term[1])
+    mask = (1 << L) - 1
+    if not 1 <= L <= 30 or (x | z) & ~mask:
+        raise ValueError("need 1 <= n_sites <= 30 and masks below 2^n_sites")
+
+    def rev(v):
+        return int(format(v, "0%db" % L)[::-1], 2)
+
+    def rot(v, j):
+        return ((v << j) | (v >> (L - j))) & mask
+
+    flip_sign = -1 if bin(z).count("1") & 1 else 1
+    mult, order = {}, 0
+    for bx, bz in (((x, z), (rev(x), rev(z))) if parity else ((x, z),)):
+        for j in range(L):
+            key = (rot(bx, j), rot(bz, j))
+            mult[key] = mult.get(key, 0) + 1 + (flip_sign if inversion else 0)
+            order += 2 if inversion else 1
+    return [(kx, kz, mult[(kx, kz)] / order) for kx, kz in sorted(mult) if mult[(kx, kz)] != 0]
+
+
 def pauli_symmetric_csr(n_sites, m, parity, inversion, terms, dtype=np.float64, n_down=None, merge=True):
     """The block B^H H B (B = symmetric_embedding; H = pauli_csr, or pauli_sector_csr with n_down) as CSR over symmetric_basis,
     from the gather form, in double: row a holds, per x mask X whose partner a ^ X = g b has b in the block,
