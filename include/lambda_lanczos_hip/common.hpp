@@ -341,6 +341,46 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
     if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: psi must hold local_rows() values");
     return rdm(sites, psi.data(), sweeps);
   }
+  // ll_pauli_block_expand / ll_pauli_block_project: this operator is the block; c holds local_rows() values, psi target.local_rows()
+  void block_expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const {
+    check(ll_pauli_block_expand(this->context().get(), this->get(), target.get(), c, psi_out));
+  }
+  std::vector<T> block_expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const {
+    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expand: c must hold local_rows() values");
+    std::vector<T> psi((size_t)target.local_rows());
+    block_expand(target, c.data(), psi.data());
+    return psi;
+  }
+  void block_project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const {
+    check(ll_pauli_block_project(this->context().get(), this->get(), target.get(), psi, c_out));
+  }
+  std::vector<T> block_project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const {
+    if ((int64_t)psi.size() != target.local_rows()) throw Error(LL_ERR_INVALID, "project: psi must hold target.local_rows() values");
+    std::vector<T> c((size_t)this->local_rows());
+    block_project(target, psi.data(), c.data());
+    return c;
+  }
+  // rho_A of Psi = B c: expanded into a device buffer of the context, measured by ll_pauli_rdm on the target, the buffer freed
+  std::vector<std::complex<double>> block_rdm(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
+                                              int64_t* sweeps) const {
+    void* buf = nullptr;
+    check(ll_malloc(this->context().get(), (size_t)std::max<int64_t>(target.local_rows(), 1) * sizeof(T), &buf));
+    std::vector<std::complex<double>> rho;
+    try {
+      block_expand(target, c, static_cast<T*>(buf));
+      rho = target.rdm(sites, static_cast<const T*>(buf), sweeps);
+    } catch (...) {
+      (void)ll_free(this->context().get(), buf);
+      throw;
+    }
+    check(ll_free(this->context().get(), buf));
+    return rho;
+  }
+  std::vector<std::complex<double>> block_rdm(const std::vector<int>& sites, const std::vector<T>& c,
+                                              const PauliFamilyOperator<T>& target, int64_t* sweeps) const {
+    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: c must hold local_rows() values");
+    return block_rdm(sites, c.data(), target, sweeps);
+  }
   void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
@@ -441,6 +481,23 @@ template <typename T> class PauliMomentumOperator : public PauliFamilyOperator<T
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
     return this->expect_block(observables, psi, sweeps);
   }
+
+  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
+  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
+  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
+  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
+  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
+  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
+  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
+  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
+                                                           int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
+                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
+  }
 };
 
 // One momentum block of the FULL 2^n_sites space of a ring: H must commute with the one-site translation and need not conserve
@@ -464,6 +521,23 @@ template <typename T> class PauliMomentumFullOperator : public PauliFamilyOperat
   }
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
     return this->expect_block(observables, psi, sweeps);
+  }
+
+  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
+  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
+  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
+  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
+  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
+  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
+  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
+  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
+                                                           int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
+                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
   }
 };
 
@@ -489,6 +563,23 @@ template <typename T> class PauliSymmetricOperator : public PauliFamilyOperator<
   }
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
     return this->expect_block(observables, psi, sweeps);
+  }
+
+  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
+  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
+  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
+  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
+  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
+  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
+  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
+  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
+                                                           int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
+                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
+    return this->block_rdm(sites, c, target, sweeps);
   }
 };
 

@@ -72,7 +72,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_pauli_rdm (the reduced density matrix of up
                              *    to six sites of such a state, in one sweep): untyped, the storage type is the operator's;
                              *    also additive under minor 5, with the same note — ll_pauli_expect_block (expectation values of
-                             *    Pauli strings on a state of a symmetry block (8) - (10)): untyped, the storage type is the operator's */
+                             *    Pauli strings on a state of a symmetry block (8) - (10)): untyped, the storage type is the operator's;
+                             *    also additive under minor 5, with the same note — ll_pauli_block_expand and ll_pauli_block_project
+                             *    (a state between a symmetry block (8) - (10) and the basis of (6) or (7)): untyped */
 
 enum {
   LL_OK = 0,
@@ -519,6 +521,51 @@ int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const
  * wherever an observable stands in the call. */
 int ll_pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,
                           double* out_host, int64_t* sweeps_out);
+
+/* A STATE BETWEEN A RING'S SYMMETRY BLOCK AND THE FULL SPACE (an addition within minor 5, untyped: the storage type is the
+ * operators').  B is the isometry of a block operator of (8) - (10): the row of the state t = g b — b a representative of the
+ * block with an orbit of R_b states, g an element of the block's group G — holds val(t) = chi(g) / sqrt(R_b) in the column of b
+ * (chi(T^j P^rho Z^zeta) = e^(-2 pi i momentum j / n_sites) parity^rho inversion^zeta); the row of a state whose orbit the block
+ * excludes is empty.
+ *     ll_pauli_block_expand :  psi_out[t] = val(t) c[col(t)]                                            Psi = B c
+ *     ll_pauli_block_project:  c_out[a]   = sum over the orbit of representative a of conj(val(t)) psi[t]     c = B^H Psi
+ * project is B^H Psi for ANY Psi, in the block or not: ||c_out||^2 is the weight of Psi in the block, and project(expand(c)) = c.
+ * With expand every facility of the full space applies to a block state (ll_pauli_rdm, ll_pauli_expect, an operator that breaks
+ * the symmetry); with project a symmetric state of the full space is taken into the block.
+ *   block  : from ll_op_create_pauli_momentum_* (8), _momentum_full_* (9) or _symmetric_* (10): the representatives, the group,
+ *            the character and the storage type.  Its Hamiltonian's terms play no part.
+ *   target : from ll_op_create_pauli_* (6) or ll_op_create_pauli_sector_* (7): the basis of Psi — all 2^n_sites states, or the
+ *            states of the sector ascending (its states[] and rank tables are used).  Its terms play no part.
+ *            Same context, n_sites and storage type as block.  A sector target needs a block of that n_down ((8), or (10) with
+ *            n_down >= 0).  A full-space target takes every block: for a sector block every state outside the sector is written
+ *            +0.0 by expand and is not read by project.
+ *   c, c_out     : block->n_local values;   psi, psi_out : target->n_local values.  Host or device memory, decided per pointer; a
+ *            host buffer is staged through one device vector.  Inputs are never modified.  Every element of the output is written
+ *            (a state whose orbit the block excludes: exactly +0.0).  The call returns with the output filled.
+ * REFUSALS (LL_ERR_INVALID, each naming its cause, before the device is touched): a null argument; a context with a communicator;
+ * a wrong kind for block or target, named in the message; differing contexts, n_sites or storage types; a full-space block ((9),
+ * or (10) with n_down < 0) with a sector target; differing n_down; input and output that overlap.
+ * ACCURACY: all arithmetic in double (float inputs widened, exact), one rounding to the storage type at the end.
+ *   expand : c[col] times the host-formed double 1.0 / sqrt((double)R) (one rounding per component), then times the phase where
+ *            momentum != 0 (table entries cos, -sin of the host, exact on the axes), then the sign (exact).  REAL CHARACTER
+ *            (2 momentum = 0 mod n_sites: the phases are exactly +-1): one double product, bit for bit (double)c * (+-1 / sqrt(R))
+ *            rounded to T.  COMPLEX PHASES: per element |error| <= 16 eps_d |val c| plus the storage rounding, independent of
+ *            n_sites — per component the factor (sqrt and division: 2 u, u = eps_d / 2), the scaling (u), the table entry (2 u),
+ *            the product (u) and the sum of two (u) make 7 u |val c|, sqrt(2) times that for the modulus: 10 u; a reference that
+ *            forms val = phase / sqrt(R) and the complex product in double carries 9 u of its own: 19 u < 32 u = 16 eps_d.
+ *   project: the |G| = n_sites (x 2 with parity, x 2 with inversion) terms conj(chi(g)) psi[g a] are formed (a complex phase: two
+ *            products and a sum) and summed in double in the order rho, zeta, j of g = T^j P^rho Z^zeta, then multiplied by the
+ *            host-formed double sqrt((double)R_a) / (double)|G|: the error of a double-accumulated sum of |G| terms
+ *            (2 (|G| + 8) eps_d sum |terms| covers it) plus 4 eps_d for the factor and its product, plus the storage rounding.  With
+ *            a real character and a psi of integers the sum S is an exact integer and the result is bit for bit
+ *            (double)S * (sqrt((double)R_a) / (double)|G|) rounded to T.
+ * No atomics; the same bits run to run, for host and device buffers, for every alignment and for every block size and grid.
+ * BYTES: expand writes sizeof(T) N and reads c through a cached gather (plus 4 N of states for a sector target, 4 N of orbit table
+ * for (8), about search_trips representatives per state for (9), (10)); project reads sizeof(T) N gathered and writes sizeof(T) D.
+ * TIMES: DESIGN.md 3.7 (measured: expand is bound by its integer search, not by bytes).  Block sizes: the unstable tuning keys pauli_block_expand_block_bits (2^b output indices
+ * per workgroup block, default 10) and pauli_block_project_block_bits (2^b representatives, default 8). */
+int ll_pauli_block_expand(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* c, void* psi_out);
+int ll_pauli_block_project(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* psi, void* c_out);
 
 /* REDUCED DENSITY MATRIX of up to six sites of a state of the basis of (6) or (7), in ONE sweep over the state (an addition
  * within minor 5, untyped: the storage type is the operator's).  The kernels read psi once and write 4^m numbers.

@@ -39,6 +39,8 @@ from .engine import (  # noqa: F401
     normalize,
     nrm2,
     orth_block,
+    pauli_block_expand,
+    pauli_block_project,
     pauli_expect,
     pauli_expect_block,
     pauli_rdm,

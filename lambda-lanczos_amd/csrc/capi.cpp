@@ -568,6 +568,12 @@ int ll_pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs,
                           double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_expect_block(ctx, op, n_obs, obs_host, psi, out_host, sweeps_out); });
 }
+int ll_pauli_block_expand(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* c, void* psi_out) {
+  return guarded([&] { pauli_block_embed(ctx, block, target, true, c, psi_out); });
+}
+int ll_pauli_block_project(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* psi, void* c_out) {
+  return guarded([&] { pauli_block_embed(ctx, block, target, false, psi, c_out); });
+}
 int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi,
                  double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_rdm(ctx, op, n_sub, sites_host, psi, out_host, sweeps_out); });

@@ -258,6 +258,8 @@ struct Tuning {
   int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
   int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
   int pauli_symmetric_block_bits = -1;  // key pauli_symmetric_block_bits = b: the same for the momentum / reflection / spin-inversion kernel (-1: kPauliSymmetricBlockBits)
+  int pauli_block_expand_block_bits = -1;   // key pauli_block_expand_block_bits = b: ll_pauli_block_expand's workgroups take blocks of 2^b output indices (-1: kPauliBlockExpandBlockBits, pauli_block_embed_plan.hpp); tests force several trips of the grid-stride loop
+  int pauli_block_project_block_bits = -1;  // key pauli_block_project_block_bits = b: ll_pauli_block_project's take blocks of 2^b representatives (-1: kPauliBlockProjectBlockBits)
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   int pauli_rdm_tile_bits = -1;    // key pauli_rdm_tile_bits = t: the reduced-density-matrix kernel's tiles hold 2^t states (-1: what fills kPauliTileBytes of LDS with the super-tile); tests force subsystem sites above the tile on small problems
   int pauli_rdm_block_bits = -1;   // key pauli_rdm_block_bits = b: its sector form gathers 2^b environment configurations per LDS batch (-1: what fills kPauliTileBytes)
@@ -672,7 +674,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_rdm.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_rdm.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -795,6 +797,9 @@ const char* pauli_expect_kind_name(int kind);  // "a CSR operator", ...: what th
 // psi = the coefficients on the block's representatives
 void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi, double* out,
                         int64_t* sweeps_out);
+// ll_pauli_block_expand / ll_pauli_block_project (pauli_block_embed.hip; planned by pauli_block_embed_plan.hpp): every check, then
+// Psi = B c (expand) or c = B^H Psi (project) on the operators' storage type
+void pauli_block_embed(ll_context* ctx, const ll_operator* block, const ll_operator* target, bool expand, const void* in, void* out);
 // ll_pauli_rdm (pauli_rdm.hip; planned by pauli_rdm_plan.hpp): every check, then the one sweep on the operator's storage type
 void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, double* out,
                int64_t* sweeps_out);

@@ -16,19 +16,13 @@ struct PauliMomentumFullPartner {
   unsigned in_block;  // bit R set: orbits of length R are in the block (m R = 0 mod n_sites)
   __device__ __forceinline__ unsigned length(unsigned i) const { return (unsigned)orbit_len[i]; }
   __device__ __forceinline__ unsigned dead_length() const { return 1u; }
-  template <typename T, typename A, int E>
-  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&ra)[E], const bool (&live)[E],
-                                            const A (&w)[E], const T (&xi)[E], const T* __restrict__ x, unsigned dim,
-                                            A (&acc)[E]) const {
-    if (X == 0u) {  // the diagonal: the partner is the representative itself (R_b = R_a, l = 0)
-#pragma unroll
-      for (int e = 0; e < E; ++e)
-        if (live[e]) pauli_fma(acc[e], w[e], xi[e]);
-      return;
-    }
-    const unsigned L = (unsigned)n_sites, smask = (1u << L) - 1u, m = (unsigned)momentum;  // L <= 30
-    // the partners' representatives: the smallest of the L rotations, the first shift that reaches it, the period
-    unsigned cur[E], rep[E], first[E], rb[E];
+  // The representatives of the states p = s ^ X: the smallest of the L rotations, the first shift that reaches it, the period.  The ONE
+  // definition of that rule: add_group below and the expanding kernel (pauli_block_embed.hip) call it.
+  template <int E>
+  __device__ __forceinline__ void locate(const unsigned (&s)[E], unsigned X, unsigned (&rep)[E], unsigned (&first)[E],
+                                         unsigned (&rb)[E]) const {
+    const unsigned L = (unsigned)n_sites, smask = (1u << L) - 1u;  // L <= 30
+    unsigned cur[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       cur[e] = rep[e] = s[e] ^ X;
@@ -46,6 +40,20 @@ struct PauliMomentumFullPartner {
         first[e] = less ? j : first[e];
       }
     }
+  }
+  template <typename T, typename A, int E>
+  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&ra)[E], const bool (&live)[E],
+                                            const A (&w)[E], const T (&xi)[E], const T* __restrict__ x, unsigned dim,
+                                            A (&acc)[E]) const {
+    if (X == 0u) {  // the diagonal: the partner is the representative itself (R_b = R_a, l = 0)
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        if (live[e]) pauli_fma(acc[e], w[e], xi[e]);
+      return;
+    }
+    const unsigned m = (unsigned)momentum;
+    unsigned rep[E], first[E], rb[E];
+    locate(s, X, rep, first, rb);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       if (live[e] && ((in_block >> rb[e]) & 1u) != 0u) {  // the partner's orbit is in the block: reps[] holds b

@@ -26,20 +26,15 @@ struct PauliSymmetricPartner {
     who = less ? code : who;
     rep = less ? c : rep;
   }
-  template <typename T, typename A, int E>
-  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&ra)[E], const bool (&live)[E],
-                                            const A (&w)[E], const T (&xi)[E], const T* __restrict__ x, unsigned dim,
-                                            A (&acc)[E]) const {
-    if (X == 0u) {  // the diagonal: the partner is the representative itself (R_b = R_a, the identity element)
-#pragma unroll
-      for (int e = 0; e < E; ++e)
-        if (live[e]) pauli_fma(acc[e], w[e], xi[e]);
-      return;
-    }
-    const unsigned L = (unsigned)n_sites, smask = (1u << L) - 1u, m = (unsigned)momentum;  // 1 <= L <= 30
+  // The representatives of the states p = s ^ X: the smallest of the |G| images, the element that reaches it first (its code), how many
+  // reach it (the stabiliser's size).  The ONE definition of that rule: add_group below and the expanding kernel
+  // (pauli_block_embed.hip) call it.
+  template <int E>
+  __device__ __forceinline__ void locate(const unsigned (&s)[E], unsigned X, unsigned (&rep)[E], unsigned (&who)[E],
+                                         unsigned (&cnt)[E]) const {
+    const unsigned L = (unsigned)n_sites, smask = (1u << L) - 1u;  // 1 <= L <= 30
     const bool use_p = use_parity != 0u, use_z = use_inversion != 0u;
-    // the partners' representatives: the smallest of the |G| images, the element that reaches it first, how many reach it
-    unsigned cur[E], rev[E], rep[E], who[E], cnt[E];
+    unsigned cur[E], rev[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       cur[e] = s[e] ^ X;
@@ -61,6 +56,21 @@ struct PauliSymmetricPartner {
         cur[e] = pauli_rotl(cur[e], 1u, L, smask);
       }
     }
+  }
+  template <typename T, typename A, int E>
+  __device__ __forceinline__ void add_group(unsigned X, const unsigned (&s)[E], const unsigned (&ra)[E], const bool (&live)[E],
+                                            const A (&w)[E], const T (&xi)[E], const T* __restrict__ x, unsigned dim,
+                                            A (&acc)[E]) const {
+    if (X == 0u) {  // the diagonal: the partner is the representative itself (R_b = R_a, the identity element)
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        if (live[e]) pauli_fma(acc[e], w[e], xi[e]);
+      return;
+    }
+    const unsigned L = (unsigned)n_sites, m = (unsigned)momentum;  // 1 <= L <= 30
+    const bool use_p = use_parity != 0u, use_z = use_inversion != 0u;
+    unsigned rep[E], who[E], cnt[E];
+    locate(s, X, rep, who, cnt);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       if (live[e]) {

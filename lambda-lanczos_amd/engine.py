@@ -454,6 +454,60 @@ def pauli_expect_block(op, psi, observables, return_sweeps=False):
     return _pauli_expect_call("ll_pauli_expect_block", op, psi, observables, return_sweeps)
 
 
+def _pauli_embed_call(entry, block, target, vec, n_in, n_out, out):
+    dtype = np.dtype(block.dtype)
+    if hasattr(vec, "ptr"):
+        if vec.dtype != dtype or int(np.prod(vec.shape)) < n_in:
+            raise TypeError("the input must hold %d values of the operators' dtype %s" % (n_in, dtype))
+        keep, p = vec, C.c_void_p(vec.ptr)
+    else:
+        keep = np.ascontiguousarray(vec, dtype=dtype)
+        if keep.size != n_in:
+            raise ValueError("the input holds %d values, its basis %d" % (keep.size, n_in))
+        p = ptr(keep)
+    if out is None:
+        out = np.empty(n_out, dtype=dtype)
+    if hasattr(out, "ptr"):
+        if out.dtype != dtype or int(np.prod(out.shape)) < n_out:
+            raise TypeError("out must hold %d values of the operators' dtype %s" % (n_out, dtype))
+        q = C.c_void_p(out.ptr)
+    else:
+        if not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size == n_out and out.flags.c_contiguous and
+                out.flags.writeable):
+            raise TypeError("out must be a contiguous writeable numpy array of %d values of dtype %s" % (n_out, dtype))
+        q = ptr(out)
+    check(getattr(lib(), entry)(block.ctx.handle, block.handle, target.handle, p, q))
+    del keep
+    return out
+
+
+def pauli_block_expand(block, c, target, out=None):
+    """ll_pauli_block_expand: Psi = B c — the block.n_local coefficients c on the representatives of a symmetry block
+    (PauliMomentumOperator, PauliMomentumFullOperator, PauliSymmetricOperator) as the target.n_local amplitudes on the basis of
+    `target` (a PauliOperator, or the PauliSectorOperator of the block's n_down), B = generators.momentum_embedding,
+    full_momentum_embedding or symmetric_embedding.  States whose orbit the block excludes, and for a sector block in the full
+    space the states outside the sector, come back exactly +0.0.  c: a numpy array (converted to the operators' dtype) or a
+    DeviceArray (anything with .ptr, .dtype, .shape); out: None (a new numpy array), a numpy array or a DeviceArray of the
+    operators' dtype — returned filled."""
+    return _pauli_embed_call("ll_pauli_block_expand", block, target, c, block.n_local, target.n_local, out)
+
+
+def pauli_block_project(block, psi, target, out=None):
+    """ll_pauli_block_project: c = B^H Psi for ANY Psi on the basis of `target` — the block.n_local coefficients of its part in the
+    block; ||c||^2 is the weight of Psi in the block and pauli_block_project(block, pauli_block_expand(block, c, t), t) = c.
+    Arguments as pauli_block_expand."""
+    return _pauli_embed_call("ll_pauli_block_project", block, target, psi, target.n_local, block.n_local, out)
+
+
+def _block_rdm(block, c, sites, target, return_sweeps=False):
+    buf = block.ctx.empty(target.n_local, block.dtype)   # the expanded state: a context-owned device buffer, freed below
+    try:
+        pauli_block_expand(block, c, target, out=buf)
+        return pauli_rdm(target, buf, sites, return_sweeps)
+    finally:
+        buf.free()
+
+
 def pauli_rdm(op, psi, sites, return_sweeps=False):
     """ll_pauli_rdm: the reduced density matrix rho[a][a'] = sum_e psi(a, e) conj psi(a', e) of the sites `sites` (1 to 6 distinct
     sites; bit k of a is sites[k]) of a state on the basis of `op`, as a complex128 array of shape (2^m, 2^m) — one sweep over
@@ -546,6 +600,20 @@ class PauliMomentumOperator(_PauliFamily):
         representatives, as a float64 array (pauli_expect_block)."""
         return pauli_expect_block(self, psi, observables, return_sweeps)
 
+    def expand(self, c, target, out=None):
+        """Psi = B c on the basis of `target`: the PauliOperator of the ring, or the PauliSectorOperator of this block's n_down
+        (pauli_block_expand)."""
+        return pauli_block_expand(self, c, target, out)
+
+    def project(self, psi, target, out=None):
+        """c = B^H Psi, the part of ANY state on the basis of `target` that lies in this block (pauli_block_project)."""
+        return pauli_block_project(self, psi, target, out)
+
+    def reduced_density_matrix(self, c, sites, target, return_sweeps=False):
+        """rho_A = Tr_env |Psi><Psi| of Psi = B c: c is expanded into a device buffer of target.n_local values, measured with
+        target.reduced_density_matrix (pauli_rdm) and the buffer freed.  entanglement_entropy takes the result."""
+        return _block_rdm(self, c, sites, target, return_sweeps)
+
 
 class PauliMomentumFullOperator(_PauliFamily):
     """One momentum block of the full 2^n_sites space of a ring (ll_op_create_pauli_momentum_full_*): the operator B^H H B with
@@ -561,6 +629,9 @@ class PauliMomentumFullOperator(_PauliFamily):
 
     inf_norm = PauliMomentumOperator.inf_norm
     expectation = PauliMomentumOperator.expectation
+    expand = PauliMomentumOperator.expand
+    project = PauliMomentumOperator.project
+    reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
 
 
 class PauliSymmetricOperator(_PauliFamily):
@@ -580,6 +651,9 @@ class PauliSymmetricOperator(_PauliFamily):
 
     inf_norm = PauliMomentumOperator.inf_norm
     expectation = PauliMomentumOperator.expectation
+    expand = PauliMomentumOperator.expand
+    project = PauliMomentumOperator.project
+    reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
 
 
 class HostOperator(_Operator):
