@@ -297,7 +297,7 @@ template <typename T> class LatticeOperator : public DeviceOperator<T> {
 };
 
 // What the five Pauli-sum operators below share: size() and local_rows() are read from the created operator (ll_op_info), and
-// device_bytes().
+// device_bytes().  PauliSpinBasisOperator and PauliRingBlockOperator add the measurements of the two kinds of basis.
 template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
  public:
   int64_t device_bytes() const {
@@ -308,78 +308,15 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
 
  protected:
   explicit PauliFamilyOperator(Context ctx) : DeviceOperator<T>(ctx) {}
-  // ll_pauli_expect: psi is host or device memory of local_rows() values (the library decides per pointer)
-  std::vector<double> expect(const std::vector<ll_pauli_term>& observables, const T* psi, int64_t* sweeps) const {
-    std::vector<double> out(observables.size(), 0.0);
-    check(ll_pauli_expect(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(), sweeps));
-    return out;
-  }
-  std::vector<double> expect(const std::vector<ll_pauli_term>& observables, const std::vector<T>& psi, int64_t* sweeps) const {
-    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
-    return expect(observables, psi.data(), sweeps);
-  }
-  // ll_pauli_expect_block: psi is host or device memory of local_rows() coefficients on a symmetry block's representatives
-  std::vector<double> expect_block(const std::vector<ll_pauli_term>& observables, const T* psi, int64_t* sweeps) const {
-    std::vector<double> out(observables.size(), 0.0);
-    check(ll_pauli_expect_block(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(),
-                                sweeps));
-    return out;
-  }
-  std::vector<double> expect_block(const std::vector<ll_pauli_term>& observables, const std::vector<T>& psi, int64_t* sweeps) const {
-    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
-    return expect_block(observables, psi.data(), sweeps);
-  }
-  // ll_pauli_rdm: rho[a][a'] row-major, 2^m x 2^m, m = sites.size()
-  std::vector<std::complex<double>> rdm(const std::vector<int>& sites, const T* psi, int64_t* sweeps) const {
+  // ll_pauli_rdm on `op`, for both kinds of basis (a ring block measures on its target): rho[a][a'] row-major, 2^m x 2^m,
+  // m = sites.size(); psi is host or device memory of op.local_rows() values (the library decides per pointer)
+  static std::vector<std::complex<double>> rdm(const PauliFamilyOperator<T>& op, const std::vector<int>& sites, const T* psi,
+                                               int64_t* sweeps) {
     const std::vector<int32_t> s32(sites.begin(), sites.end());
     const size_t dim = (size_t)1 << std::min<size_t>(s32.size(), 6);  // (a count the library refuses still gets a buffer)
     std::vector<std::complex<double>> out(dim * dim);
-    check(ll_pauli_rdm(this->context().get(), this->get(), (int32_t)s32.size(), s32.data(), psi, reinterpret_cast<double*>(out.data()), sweeps));
+    check(ll_pauli_rdm(op.context().get(), op.get(), (int32_t)s32.size(), s32.data(), psi, reinterpret_cast<double*>(out.data()), sweeps));
     return out;
-  }
-  std::vector<std::complex<double>> rdm(const std::vector<int>& sites, const std::vector<T>& psi, int64_t* sweeps) const {
-    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: psi must hold local_rows() values");
-    return rdm(sites, psi.data(), sweeps);
-  }
-  // ll_pauli_block_expand / ll_pauli_block_project: this operator is the block; c holds local_rows() values, psi target.local_rows()
-  void block_expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const {
-    check(ll_pauli_block_expand(this->context().get(), this->get(), target.get(), c, psi_out));
-  }
-  std::vector<T> block_expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const {
-    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expand: c must hold local_rows() values");
-    std::vector<T> psi((size_t)target.local_rows());
-    block_expand(target, c.data(), psi.data());
-    return psi;
-  }
-  void block_project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const {
-    check(ll_pauli_block_project(this->context().get(), this->get(), target.get(), psi, c_out));
-  }
-  std::vector<T> block_project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const {
-    if ((int64_t)psi.size() != target.local_rows()) throw Error(LL_ERR_INVALID, "project: psi must hold target.local_rows() values");
-    std::vector<T> c((size_t)this->local_rows());
-    block_project(target, psi.data(), c.data());
-    return c;
-  }
-  // rho_A of Psi = B c: expanded into a device buffer of the context, measured by ll_pauli_rdm on the target, the buffer freed
-  std::vector<std::complex<double>> block_rdm(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
-                                              int64_t* sweeps) const {
-    void* buf = nullptr;
-    check(ll_malloc(this->context().get(), (size_t)std::max<int64_t>(target.local_rows(), 1) * sizeof(T), &buf));
-    std::vector<std::complex<double>> rho;
-    try {
-      block_expand(target, c, static_cast<T*>(buf));
-      rho = target.rdm(sites, static_cast<const T*>(buf), sweeps);
-    } catch (...) {
-      (void)ll_free(this->context().get(), buf);
-      throw;
-    }
-    check(ll_free(this->context().get(), buf));
-    return rho;
-  }
-  std::vector<std::complex<double>> block_rdm(const std::vector<int>& sites, const std::vector<T>& c,
-                                              const PauliFamilyOperator<T>& target, int64_t* sweeps) const {
-    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: c must hold local_rows() values");
-    return block_rdm(sites, c.data(), target, sweeps);
   }
   void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
@@ -390,40 +327,123 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
   }
 };
 
-// Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t on n_sites spins (n = 2^n_sites): what a many-body user writes as an
-// mv_mul plugin, applied on the device from its list of Pauli strings.  Bit j of a basis state is site j; a term's site j
-// carries X (x_mask bit only), Z (z_mask bit only), Y (both).  A Heisenberg bond J S_j.S_k is {m, 0, J/4}, {m, m, J/4},
-// {0, m, J/4} with m = 2^j | 2^k.  Real T: an even number of Y per term.  Single-rank contexts only (ll_op_create_pauli_*).
 using PauliTerm = ll_pauli_term;
-template <typename T> class PauliOperator : public PauliFamilyOperator<T> {
- public:
-  PauliOperator(int n_sites, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : PauliFamilyOperator<T>(ctx) {
-    ll_operator* op = nullptr;
-    check(abi<T>::create_pauli(ctx.get(), (int32_t)n_sites, (int64_t)terms.size(), terms.data(), &op));
-    this->adopt_created(op);
-  }
-  // inf_norm() returns sum_t |coef_t|: an upper bound of every absolute row sum
 
+// The operators whose basis is a spin basis — PauliOperator (all 2^n_sites states) and PauliSectorOperator (one S_z sector): a
+// site is a tensor factor, so Pauli strings and subsystems are measured on psi itself.
+template <typename T> class PauliSpinBasisOperator : public PauliFamilyOperator<T> {
+ public:
   // coef * Re <psi| P |psi> for every observable (x_mask, z_mask, coef), many per sweep over psi and with no n-sized workspace for
   // a device psi (ll_pauli_expect); nothing is divided by <psi|psi>.  psi: a device pointer (or any host pointer) to size()
-  // values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.
+  // values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.  On a sector a partner s ^ x outside
+  // the sector contributes nothing.
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->expect(observables, psi, sweeps);
+    std::vector<double> out(observables.size(), 0.0);
+    check(ll_pauli_expect(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(), sweeps));
+    return out;
   }
   std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
-    return this->expect(observables, psi, sweeps);
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
+    return expectation(observables, psi.data(), sweeps);
   }
 
   // rho_A = Tr_env |psi><psi| of up to six distinct sites in one sweep over psi (ll_pauli_rdm): row-major 2^m x 2^m with
   // rho[a][a'] = sum_e psi(a, e) conj(psi(a', e)), bit k of a = sites[k]; exactly Hermitian, not divided by <psi|psi> (the trace
-  // is ||psi||^2).  psi as for expectation().  von_neumann_entropy (entropy.hpp) takes the result.
+  // is ||psi||^2).  psi as for expectation().  On a sector every entry with popcount(a) != popcount(a') is exactly +0.0.
+  // von_neumann_entropy (entropy.hpp) takes the result.
   std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->rdm(sites, psi, sweeps);
+    return this->rdm(*this, sites, psi, sweeps);
   }
   std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& psi,
                                                            int64_t* sweeps = nullptr) const {
-    return this->rdm(sites, psi, sweeps);
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: psi must hold local_rows() values");
+    return reduced_density_matrix(sites, psi.data(), sweeps);
+  }
+
+ protected:
+  explicit PauliSpinBasisOperator(Context ctx) : PauliFamilyOperator<T>(ctx) {}
+};
+
+// The operators whose basis is a symmetry block of a ring — PauliMomentumOperator, PauliMomentumFullOperator and
+// PauliSymmetricOperator: vectors hold coefficients on the block's representatives, Psi = B c with B the block's isometry.
+template <typename T> class PauliRingBlockOperator : public PauliFamilyOperator<T> {
+ public:
+  // coef * Re <Psi| P |Psi> for every observable, Psi = B psi the state that the size() coefficients psi on the block's basis stand
+  // for — Psi is never formed: every observable is averaged over the block's group and measured with the gather of this
+  // operator's apply, up to 32 per sweep over psi (ll_pauli_expect_block); nothing is divided by <psi|psi>.  psi: a device pointer
+  // (or any host pointer) to size() values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
+    std::vector<double> out(observables.size(), 0.0);
+    check(ll_pauli_expect_block(this->context().get(), this->get(), (int64_t)observables.size(), observables.data(), psi, out.data(),
+                                sweeps));
+    return out;
+  }
+  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expectation: psi must hold local_rows() values");
+    return expectation(observables, psi.data(), sweeps);
+  }
+
+  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
+  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
+  // host or device memory, or std::vector<T>; c holds local_rows() values, psi target.local_rows().
+  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const {
+    check(ll_pauli_block_expand(this->context().get(), this->get(), target.get(), c, psi_out));
+  }
+  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const {
+    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "expand: c must hold local_rows() values");
+    std::vector<T> psi((size_t)target.local_rows());
+    expand(target, c.data(), psi.data());
+    return psi;
+  }
+  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const {
+    check(ll_pauli_block_project(this->context().get(), this->get(), target.get(), psi, c_out));
+  }
+  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const {
+    if ((int64_t)psi.size() != target.local_rows()) throw Error(LL_ERR_INVALID, "project: psi must hold target.local_rows() values");
+    std::vector<T> c((size_t)this->local_rows());
+    project(target, psi.data(), c.data());
+    return c;
+  }
+
+  // rho_A of Psi = B c: c is expanded into a device buffer of the context, measured by the target's reduced_density_matrix
+  // (ll_pauli_rdm) and the buffer freed; von_neumann_entropy (entropy.hpp) takes the result.
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
+                                                           int64_t* sweeps = nullptr) const {
+    void* buf = nullptr;
+    check(ll_malloc(this->context().get(), (size_t)std::max<int64_t>(target.local_rows(), 1) * sizeof(T), &buf));
+    std::vector<std::complex<double>> rho;
+    try {
+      expand(target, c, static_cast<T*>(buf));
+      rho = this->rdm(target, sites, static_cast<const T*>(buf), sweeps);
+    } catch (...) {
+      (void)ll_free(this->context().get(), buf);
+      throw;
+    }
+    check(ll_free(this->context().get(), buf));
+    return rho;
+  }
+  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
+                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
+    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: c must hold local_rows() values");
+    return reduced_density_matrix(sites, c.data(), target, sweeps);
+  }
+
+ protected:
+  explicit PauliRingBlockOperator(Context ctx) : PauliFamilyOperator<T>(ctx) {}
+};
+
+// Matrix-free spin-1/2 Hamiltonian H = sum_t coef_t P_t on n_sites spins (n = 2^n_sites): what a many-body user writes as an
+// mv_mul plugin, applied on the device from its list of Pauli strings.  Bit j of a basis state is site j; a term's site j
+// carries X (x_mask bit only), Z (z_mask bit only), Y (both).  A Heisenberg bond J S_j.S_k is {m, 0, J/4}, {m, m, J/4},
+// {0, m, J/4} with m = 2^j | 2^k.  Real T: an even number of Y per term.  Single-rank contexts only (ll_op_create_pauli_*).
+// inf_norm() returns sum_t |coef_t|: an upper bound of every absolute row sum.
+template <typename T> class PauliOperator : public PauliSpinBasisOperator<T> {
+ public:
+  PauliOperator(int n_sites, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
+      : PauliSpinBasisOperator<T>(ctx) {
+    ll_operator* op = nullptr;
+    check(abi<T>::create_pauli(ctx.get(), (int32_t)n_sites, (int64_t)terms.size(), terms.data(), &op));
+    this->adopt_created(op);
   }
 };
 
@@ -431,28 +451,13 @@ template <typename T> class PauliOperator : public PauliFamilyOperator<T> {
 // bits (a set bit is sigma_z = -1), in ascending integer order; size() returns that number.  H must conserve total S_z
 // (Heisenberg, XXZ, J1-J2, Dzyaloshinskii-Moriya, z fields): one that does not is refused with an Error that names the x mask
 // at fault (ll_op_create_pauli_sector_*).
-template <typename T> class PauliSectorOperator : public PauliFamilyOperator<T> {
+template <typename T> class PauliSectorOperator : public PauliSpinBasisOperator<T> {
  public:
   PauliSectorOperator(int n_sites, int n_down, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : PauliFamilyOperator<T>(ctx) {
+      : PauliSpinBasisOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_sector(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int64_t)terms.size(), terms.data(), &op));
     this->adopt_created(op);
-  }
-  // PauliOperator::expectation on the sector's basis: psi holds size() values; a partner s ^ x outside the sector contributes nothing
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->expect(observables, psi, sweeps);
-  }
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
-    return this->expect(observables, psi, sweeps);
-  }
-  // PauliOperator::reduced_density_matrix on the sector's basis: every entry with popcount(a) != popcount(a') is exactly +0.0
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->rdm(sites, psi, sweeps);
-  }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& psi,
-                                                           int64_t* sweeps = nullptr) const {
-    return this->rdm(sites, psi, sweeps);
   }
 };
 
@@ -461,42 +466,15 @@ template <typename T> class PauliSectorOperator : public PauliFamilyOperator<T> 
 // orbit representatives (smallest member) whose orbit length R satisfies m R = 0 (mod n_sites), ascending; size() returns D_m.
 // 0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image holds 4 C(n_sites, n_down) bytes of look-up
 // table (device_bytes()); inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue| (ll_op_create_pauli_momentum_*).
-template <typename T> class PauliMomentumOperator : public PauliFamilyOperator<T> {
+template <typename T> class PauliMomentumOperator : public PauliRingBlockOperator<T> {
  public:
   PauliMomentumOperator(int n_sites, int n_down, int momentum, const std::vector<PauliTerm>& terms,
                         Context ctx = Context::default_context())
-      : PauliFamilyOperator<T>(ctx) {
+      : PauliRingBlockOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int64_t)terms.size(),
                                         terms.data(), &op));
     this->adopt_created(op);
-  }
-  // coef * Re <Psi| P |Psi> for every observable, Psi = B psi the state that the size() coefficients psi on the block's basis stand
-  // for — Psi is never formed: every observable is averaged over the block's group and measured with the gather of this
-  // operator's apply, up to 32 per sweep over psi (ll_pauli_expect_block); nothing is divided by <psi|psi>.  psi: a device pointer
-  // (or any host pointer) to size() values, or a std::vector<T>.  sweeps (nullable): the passes over psi that were launched.
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-
-  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
-  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
-  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
-  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
-  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
-  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
-  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
-  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
-                                                           int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
-  }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
-                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
   }
 };
 
@@ -506,38 +484,14 @@ template <typename T> class PauliMomentumOperator : public PauliFamilyOperator<T
 // 2^n_sites / n_sites).  0 <= momentum < n_sites; real T takes momentum 0 and n_sites / 2 only.  The image is O(D_m) — no table
 // over the 2^n_sites states: device_bytes() <= 8 D_m + 64 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
 // (ll_op_create_pauli_momentum_full_*).
-template <typename T> class PauliMomentumFullOperator : public PauliFamilyOperator<T> {
+template <typename T> class PauliMomentumFullOperator : public PauliRingBlockOperator<T> {
  public:
   PauliMomentumFullOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, Context ctx = Context::default_context())
-      : PauliFamilyOperator<T>(ctx) {
+      : PauliRingBlockOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_momentum_full(ctx.get(), (int32_t)n_sites, (int32_t)momentum, (int64_t)terms.size(), terms.data(),
                                              &op));
     this->adopt_created(op);
-  }
-  // PauliMomentumOperator::expectation on this block's basis and group (ll_pauli_expect_block)
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-
-  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
-  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
-  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
-  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
-  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
-  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
-  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
-  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
-                                                           int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
-  }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
-                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
   }
 };
 
@@ -547,39 +501,15 @@ template <typename T> class PauliMomentumFullOperator : public PauliFamilyOperat
 // returns D.  parity != 0 and real T take momentum 0 and n_sites / 2 only; an empty block is refused.  The image is O(D):
 // device_bytes() <= 8 D + 192 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|
 // (ll_op_create_pauli_symmetric_*).
-template <typename T> class PauliSymmetricOperator : public PauliFamilyOperator<T> {
+template <typename T> class PauliSymmetricOperator : public PauliRingBlockOperator<T> {
  public:
   PauliSymmetricOperator(int n_sites, int momentum, const std::vector<PauliTerm>& terms, int parity = 0, int inversion = 0,
                          int n_down = -1, Context ctx = Context::default_context())
-      : PauliFamilyOperator<T>(ctx) {
+      : PauliRingBlockOperator<T>(ctx) {
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_symmetric(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int32_t)parity,
                                          (int32_t)inversion, (int64_t)terms.size(), terms.data(), &op));
     this->adopt_created(op);
-  }
-  // PauliMomentumOperator::expectation on this block's basis and group (ll_pauli_expect_block)
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const T* psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-  std::vector<double> expectation(const std::vector<PauliTerm>& observables, const std::vector<T>& psi, int64_t* sweeps = nullptr) const {
-    return this->expect_block(observables, psi, sweeps);
-  }
-
-  // Psi = B c on the basis of `target` — the PauliOperator of the ring or the PauliSectorOperator of this block's n_down — and
-  // c = B^H Psi, the part of ANY state of that basis in this block (ll_pauli_block_expand / ll_pauli_block_project): pointers to
-  // host or device memory, or std::vector<T>.  reduced_density_matrix expands c into a device buffer, measures it with the
-  // target's reduced_density_matrix and frees the buffer; von_neumann_entropy (entropy.hpp) takes the result.
-  void expand(const PauliFamilyOperator<T>& target, const T* c, T* psi_out) const { this->block_expand(target, c, psi_out); }
-  std::vector<T> expand(const PauliFamilyOperator<T>& target, const std::vector<T>& c) const { return this->block_expand(target, c); }
-  void project(const PauliFamilyOperator<T>& target, const T* psi, T* c_out) const { this->block_project(target, psi, c_out); }
-  std::vector<T> project(const PauliFamilyOperator<T>& target, const std::vector<T>& psi) const { return this->block_project(target, psi); }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const T* c, const PauliFamilyOperator<T>& target,
-                                                           int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
-  }
-  std::vector<std::complex<double>> reduced_density_matrix(const std::vector<int>& sites, const std::vector<T>& c,
-                                                           const PauliFamilyOperator<T>& target, int64_t* sweeps = nullptr) const {
-    return this->block_rdm(sites, c, target, sweeps);
   }
 };
 

@@ -514,11 +514,7 @@ int ll_expo_two_pass(ll_context* ctx, ll_operator* op, const ll_expo_params* p, 
                      void* output, int64_t* itern_out, ll_run_stats* stats) {
   return guarded([&] {
     LL_REQUIRE(ctx && op && p && input && output && itern_out, "null argument");
-    const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-    if (op->is_complex && wide) expo_two_pass_impl<zc>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
-    else if (op->is_complex) expo_two_pass_impl<cf>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
-    else if (wide) expo_two_pass_impl<double>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
-    else expo_two_pass_impl<float>(ctx, op, p, a_re, a_im, input, output, itern_out, stats);
+    for_storage_type(*op, [&](auto t) { expo_two_pass_impl<decltype(t)>(ctx, op, p, a_re, a_im, input, output, itern_out, stats); });
   });
 }
 int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n, void* y, const void* x, const void* p, double a, double b,
@@ -539,11 +535,9 @@ int ll_expo_two_pass_multi(ll_context* ctx, ll_operator* op, const ll_expo_param
   return guarded([&] {
     LL_REQUIRE(ctx && op && p && a_reim && input && outputs, "null argument");
     LL_REQUIRE(n_times >= 1 && n_times <= kRecurMultiMax, "n_times must be between 1 and 16");
-    const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-    if (op->is_complex && wide) expo_two_pass_multi_impl<zc>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
-    else if (op->is_complex) expo_two_pass_multi_impl<cf>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
-    else if (wide) expo_two_pass_multi_impl<double>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
-    else expo_two_pass_multi_impl<float>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+    for_storage_type(*op, [&](auto t) {
+      expo_two_pass_multi_impl<decltype(t)>(ctx, op, p, n_times, a_reim, input, outputs, itern_out, stats);
+    });
   });
 }
 int ll_recur_accum_multi(ll_context* ctx, int storage, int64_t n, void* y, const void* x, const void* p, double a, double b,

@@ -623,6 +623,16 @@ struct ll_operator {
 
 namespace ll {
 
+// f(T{}) with T = the operator's storage type: the one place that turns is_complex / elem_bytes into a template argument
+template <typename F> void for_storage_type(const ll_operator& op, F&& f) {
+  const bool wide = op.elem_bytes == (op.is_complex ? (int)sizeof(zc) : (int)sizeof(double));
+  if (op.is_complex && wide) f(zc{});
+  else if (op.is_complex) f(cf{});
+  else if (wide) f(double{});
+  else f(float{});
+}
+const char* operator_kind_name(int kind);  // "a CSR operator", ...: what a refusal calls an operator (operators.cpp)
+
 // ---------------------------------------------------------------- operator construction (operators.cpp, pauli_operators.cpp)
 // What the extern "C" entry points (capi.cpp) call.  create_csr takes resolved options: csr_options_default(false) for the plain
 // entry points, csr_options_default(true) for the _dev_ ones, the caller's for the _opt_ ones.
@@ -789,10 +799,12 @@ int launch_pauli_symmetric(const ll_operator& op, const T* x, T* y, double offse
                            const ScaleIn<T>* sc = nullptr);
 template <typename T>  // whichever of the five op.kind names (pauli_operators.cpp): what Engine::apply calls
 int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s, const ScaleIn<T>* sc);
+// string j of a list of terms or observables (`what`): its masks below n_sites, its coefficient finite (pauli_operators.cpp)
+void check_pauli_string(const char* what, int64_t j, const ll_pauli_term& q, int n_sites);
+// The host side that the four measuring entry points below share: pauli_measure.hpp.
 // ll_pauli_expect (pauli_expect.hip; planned by pauli_expect_plan.hpp): every check, then the sweeps on the operator's storage type
 void pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi, double* out,
                   int64_t* sweeps_out);
-const char* pauli_expect_kind_name(int kind);  // "a CSR operator", ...: what the measuring entry points' refusals call an operator
 // ll_pauli_expect_block (pauli_expect_block.hip; planned by pauli_expect_block_plan.hpp): the same on a ring's symmetry block,
 // psi = the coefficients on the block's representatives
 void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi, double* out,

@@ -332,6 +332,22 @@ template <typename Image, typename Build> bool build_optional_image(ll_context* 
 
 }  // namespace
 
+const char* operator_kind_name(int kind) {
+  switch (kind) {
+    case ll_operator::PAULI: return "a full-space sum of Pauli strings";
+    case ll_operator::PAULI_SECTOR: return "a sum of Pauli strings on an S_z sector";
+    case ll_operator::CSR: return "a CSR operator";
+    case ll_operator::HOST_CB: return "a host-callback operator";
+    case ll_operator::DEV_CB: return "a device-callback operator";
+    case ll_operator::DENSE: return "a dense operator";
+    case ll_operator::STENCIL: return "a lattice operator";
+    case ll_operator::PAULI_MOMENTUM: return "a momentum block of an S_z sector";
+    case ll_operator::PAULI_MOMENTUM_FULL: return "a momentum block of the full space";
+    case ll_operator::PAULI_SYMMETRIC: return "a momentum / reflection / spin-inversion block";
+    default: return "an operator of an unknown kind";
+  }
+}
+
 // The header of every operator: kind, storage type, context and row range.  Sharded operators must use the ll_partition()
 // row ranges (equal shard strides); a single-GPU operator is whole.
 template <typename T>

@@ -111,23 +111,12 @@ __global__ __launch_bounds__(kBlock) void pauli_kernel(int b, unsigned ntiles, i
   }
 }
 
-template <typename T> int pauli_default_tile_bits() {
-  int b = 0;
-  while (((size_t)sizeof(T) << (b + 1)) <= (size_t)kPauliTileBytes) ++b;
-  return b;
-}
-
 template <typename T>
 int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s, const ScaleIn<T>* scp) {
   const ScaleIn<T> sc = scp ? *scp : ScaleIn<T>{};
   const PauliImage& im = op.pauli;
   const PauliTermImage& tm = im.terms;
-  // states per tile: the context's pauli_tile_bits, else what fills kPauliTileBytes of LDS; never more than the vector, and at
-  // most kPauliMaxTileBytes (the LDS a launch may ask for without raising the kernel's limit)
-  const int forced = op.ctx ? op.ctx->tune.pauli_tile_bits : -1;
-  int b = forced >= 0 ? forced : pauli_default_tile_bits<T>();
-  while (b > 0 && ((size_t)sizeof(T) << b) > (size_t)kPauliMaxTileBytes) --b;
-  b = std::min(b, im.n_sites);
+  const int b = pauli_tile_bits<T>(op);  // states per tile
   const unsigned ntiles = 1u << (im.n_sites - b);
   const int grid = (int)std::min<unsigned>(ntiles, (unsigned)kMaxGrid);
   const size_t lds = std::max<size_t>((size_t)sizeof(T) << b, 16);

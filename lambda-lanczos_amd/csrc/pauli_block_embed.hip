@@ -31,6 +31,7 @@
 #include "ll_internal.hpp"
 #include "loop_support.hpp"
 #include "pauli_block_embed_plan.hpp"
+#include "pauli_measure.hpp"
 #include "pauli_momentum_full_partner.hpp"
 #include "pauli_shared.hpp"
 #include "pauli_symmetric_partner.hpp"
@@ -271,16 +272,16 @@ PauliEmbedSide embed_side(const ll_operator& op) {
       sd.n_down = op.pauli_sector.n_down;
       break;
     case ll_operator::PAULI_MOMENTUM:
-      sd.role = kPauliEmbedBlockMomentum;
-      sd.n_sites = op.pauli_momentum.n_sites;
-      sd.n_down = op.pauli_momentum.n_down;
-      break;
     case ll_operator::PAULI_MOMENTUM_FULL:
-    case ll_operator::PAULI_SYMMETRIC:
-      sd.role = op.kind == ll_operator::PAULI_SYMMETRIC ? kPauliEmbedBlockSymmetric : kPauliEmbedBlockMomentumFull;
-      sd.n_sites = op.pauli_block.n_sites;
-      sd.n_down = op.pauli_block.n_down;
+    case ll_operator::PAULI_SYMMETRIC: {
+      const PauliBlockView bv = pauli_block_view(op);
+      sd.role = op.kind == ll_operator::PAULI_MOMENTUM    ? kPauliEmbedBlockMomentum
+                : op.kind == ll_operator::PAULI_SYMMETRIC ? kPauliEmbedBlockSymmetric
+                                                          : kPauliEmbedBlockMomentumFull;
+      sd.n_sites = bv.n_sites;
+      sd.n_down = bv.n_down;
       break;
+    }
     default: break;
   }
   return sd;
@@ -290,54 +291,41 @@ template <typename T>
 void pauli_block_embed_run(ll_context* ctx, const ll_operator* block, const ll_operator* target, bool expand, const void* in, void* out) {
   LL_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const bool momentum = block->kind == ll_operator::PAULI_MOMENTUM;
+  const PauliBlockView bv = pauli_block_view(*block);
   const bool sector_target = target->kind == ll_operator::PAULI_SECTOR;
   const int64_t dim = block->n_local, n = target->n_local;
   const int64_t n_in = expand ? dim : n, n_out = expand ? n : dim;
-  const int L = momentum ? block->pauli_momentum.n_sites : block->pauli_block.n_sites;
-  const int parity = momentum ? 0 : block->pauli_block.parity, inversion = momentum ? 0 : block->pauli_block.inversion;
-  const unsigned m = (unsigned)(momentum ? block->pauli_momentum.momentum : block->pauli_block.momentum);
-  const double* const phase = momentum ? block->pauli_momentum.phase.get() : block->pauli_block.phase.get();
+  const unsigned m = (unsigned)bv.momentum;
 
-  DevBuf<T> staged_in, staged_out;  // a host buffer: one device vector each
-  const T* x = (const T*)in;
-  if (!is_device_ptr(in)) {
-    staged_in.alloc(ctx, (size_t)n_in);
-    LL_HIP(hipMemcpyAsync(staged_in.p, in, (size_t)n_in * sizeof(T), hipMemcpyHostToDevice, s));
-    x = staged_in.p;
-  }
-  T* y = (T*)out;
-  const bool host_out = !is_device_ptr(out);
-  if (host_out) {
-    staged_out.alloc(ctx, (size_t)n_out);
-    y = staged_out.p;
-  }
-  const std::vector<double> fac =
-      expand ? pauli_block_expand_factors() : pauli_block_project_factors(pauli_block_group_size(L, parity != 0, inversion != 0));
+  DevBuf<T> staged_in, staged_out;
+  const T* const x = stage_in(ctx, staged_in, in, n_in);
+  T* const y = stage_out(ctx, staged_out, out, n_out);
+  const std::vector<double> fac = expand ? pauli_block_expand_factors()
+                                         : pauli_block_project_factors(pauli_block_group_size(bv.n_sites, bv.parity != 0, bv.inversion != 0));
   DevBuf<double> dfac;
   dfac.alloc(ctx, fac.size());
   LL_HIP(hipMemcpyAsync(dfac.p, fac.data(), fac.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  const EmbedTables tb{m, phase, dfac.p};
+  const EmbedTables tb{m, bv.phase, dfac.p};
   if (expand) {
     const PauliEmbedLaunch g = pauli_block_embed_launch(n, ctx->tune.pauli_block_expand_block_bits, kPauliBlockExpandBlockBits, kMaxGrid);
     if (sector_target) launch_expand_kind<T, true>(*block, g, n, target->pauli_sector.states.get(), tb, x, y, s);
     else launch_expand_kind<T, false>(*block, g, n, nullptr, tb, x, y, s);
   } else {
     const PauliEmbedLaunch g = pauli_block_embed_launch(dim, ctx->tune.pauli_block_project_block_bits, kPauliBlockProjectBlockBits, kMaxGrid);
-    const uint32_t* const reps = momentum ? block->pauli_momentum.reps.get() : block->pauli_block.basis.reps.get();
-    const uint8_t* const olen = momentum ? block->pauli_momentum.orbit_len.get() : block->pauli_block.basis.orbit_len.get();
     const PauliSectorImage& ts = target->pauli_sector;
+    const unsigned use_p = bv.parity != 0 ? 1u : 0u, use_z = bv.inversion != 0 ? 1u : 0u;
+    const unsigned neg_p = bv.parity < 0 ? 1u : 0u, neg_z = bv.inversion < 0 ? 1u : 0u;
     if (sector_target)
       hipLaunchKernelGGL((pauli_block_project_kernel<T, true>), dim3(g.grid), dim3(kBlock), 0, s, g.bits, (unsigned)g.units, (unsigned)dim,
-                         reps, olen, ts.lo_rank.get(), ts.hi_rank.get(), ts.h, L, m, parity != 0 ? 1u : 0u, inversion != 0 ? 1u : 0u,
-                         parity < 0 ? 1u : 0u, inversion < 0 ? 1u : 0u, phase, tb.factor, x, y);
+                         bv.reps, bv.orbit_len, ts.lo_rank.get(), ts.hi_rank.get(), ts.h, bv.n_sites, m, use_p, use_z, neg_p, neg_z,
+                         bv.phase, tb.factor, x, y);
     else
       hipLaunchKernelGGL((pauli_block_project_kernel<T, false>), dim3(g.grid), dim3(kBlock), 0, s, g.bits, (unsigned)g.units, (unsigned)dim,
-                         reps, olen, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, L, m, parity != 0 ? 1u : 0u,
-                         inversion != 0 ? 1u : 0u, parity < 0 ? 1u : 0u, inversion < 0 ? 1u : 0u, phase, tb.factor, x, y);
+                         bv.reps, bv.orbit_len, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, bv.n_sites, m, use_p, use_z, neg_p,
+                         neg_z, bv.phase, tb.factor, x, y);
     LL_HIP(hipGetLastError());
   }
-  if (host_out) LL_HIP(hipMemcpyAsync(out, staged_out.p, (size_t)n_out * sizeof(T), hipMemcpyDeviceToHost, s));
+  stage_out_finish(ctx, staged_out, out, n_out);
   LL_HIP(hipStreamSynchronize(s));  // the factor table, the staged buffers and a pageable host buffer are no longer in use
 }
 }  // namespace
@@ -346,29 +334,24 @@ void pauli_block_embed_run(ll_context* ctx, const ll_operator* block, const ll_o
 void pauli_block_embed(ll_context* ctx, const ll_operator* block, const ll_operator* target, bool expand, const void* in, void* out) {
   const char* const who = expand ? "ll_pauli_block_expand" : "ll_pauli_block_project";
   LL_REQUIRE(ctx != nullptr && block != nullptr && target != nullptr && in != nullptr && out != nullptr, std::string(who) + ": null argument");
-  LL_REQUIRE(block->ctx == ctx, "the block operator belongs to another context");
-  LL_REQUIRE(target->ctx == ctx, "the target operator belongs to another context");
-  LL_REQUIRE(ctx->comm == nullptr, "block embeddings are not built for sharded contexts (a context with a communicator)");
+  pauli_measure_prologue(ctx, "block embeddings", {{block, "the block operator"}, {target, "the target operator"}});
   const PauliEmbedSide bs = embed_side(*block), ts = embed_side(*target);
   LL_REQUIRE(pauli_embed_is_block(bs.role),
-             std::string("the block operator is ") + pauli_expect_kind_name(block->kind) +
+             std::string("the block operator is ") + operator_kind_name(block->kind) +
                  ": it must be a momentum, full-momentum or momentum / reflection / spin-inversion block of a sum of Pauli strings");
   LL_REQUIRE(pauli_embed_is_target(ts.role),
-             std::string("the target operator is ") + pauli_expect_kind_name(target->kind) +
+             std::string("the target operator is ") + operator_kind_name(target->kind) +
                  ": it must be a full-space or S_z-sector sum of Pauli strings, which names the basis of the expanded state");
   if (const char* fault = pauli_block_embed_fault(bs, ts))
-    LL_REQUIRE(false, std::string(fault) + " (block: " + pauli_expect_kind_name(block->kind) + ", n_sites " + std::to_string(bs.n_sites) +
-                          ", n_down " + std::to_string(bs.n_down) + "; target: " + pauli_expect_kind_name(target->kind) + ", n_sites " +
+    LL_REQUIRE(false, std::string(fault) + " (block: " + operator_kind_name(block->kind) + ", n_sites " + std::to_string(bs.n_sites) +
+                          ", n_down " + std::to_string(bs.n_down) + "; target: " + operator_kind_name(target->kind) + ", n_sites " +
                           std::to_string(ts.n_sites) + ", n_down " + std::to_string(ts.n_down) + ")");
   const size_t eb = (size_t)block->elem_bytes;
   const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)(expand ? block->n_local : target->n_local) * eb;
   const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)(expand ? target->n_local : block->n_local) * eb;
   LL_REQUIRE(a1 <= b0 || b1 <= a0, "input and output overlap");
-  const bool wide = block->elem_bytes == (block->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-  if (block->is_complex && wide) pauli_block_embed_run<zc>(ctx, block, target, expand, in, out);
-  else if (block->is_complex) pauli_block_embed_run<cf>(ctx, block, target, expand, in, out);
-  else if (wide) pauli_block_embed_run<double>(ctx, block, target, expand, in, out);
-  else pauli_block_embed_run<float>(ctx, block, target, expand, in, out);
+  for_storage_type(*block, [&](auto t) { pauli_block_embed_run<decltype(t)>(ctx, block, target, expand, in, out); });
 }
 
 }  // namespace ll
+

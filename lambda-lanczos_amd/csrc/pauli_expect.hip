@@ -32,6 +32,7 @@
 #include "ll_internal.hpp"
 #include "loop_support.hpp"
 #include "pauli_expect_plan.hpp"
+#include "pauli_measure.hpp"
 #include "pauli_sector_partner.hpp"
 #include "pauli_shared.hpp"
 
@@ -215,15 +216,8 @@ template <typename T>
 int launch_pauli_expect(const ll_operator& op, int count, const uint32_t* sx, const uint32_t* sz, const uint32_t* sf, const T* x,
                         double* partials, hipStream_t s) {
   constexpr int B = kPauliExpectBatch;
-  const PauliImage& im = op.pauli;
-  // the tile of launch_pauli (pauli.hip): the context's pauli_tile_bits, else what fills kPauliTileBytes; at most the vector
-  const int forced = op.ctx ? op.ctx->tune.pauli_tile_bits : -1;
-  int b = forced;
-  if (b < 0)
-    for (b = 0; ((size_t)sizeof(T) << (b + 1)) <= (size_t)kPauliTileBytes;) ++b;
-  while (b > 0 && ((size_t)sizeof(T) << b) > (size_t)kPauliMaxTileBytes) --b;
-  b = std::min(b, im.n_sites);
-  const unsigned ntiles = 1u << (im.n_sites - b);
+  const int b = pauli_tile_bits<T>(op);  // the tile of launch_pauli (pauli.hip)
+  const unsigned ntiles = 1u << (op.pauli.n_sites - b);
   const int grid = (int)std::min<unsigned>(ntiles, (unsigned)kMaxGrid);
   const size_t lds = std::max<size_t>((size_t)sizeof(T) << b, 16);
   constexpr int VM = (int)(16 / sizeof(T));
@@ -240,84 +234,47 @@ int launch_pauli_expect_sector(const ll_operator& op, int count, const uint32_t*
                                const T* x, double* partials, hipStream_t s) {
   constexpr int B = kPauliExpectBatch;
   const PauliSectorImage& im = op.pauli_sector;
-  const PauliSectorPartner pt{im.states.get(), im.lo_rank.get(), im.hi_rank.get(), im.h};
   const int b = pauli_block_bits(op, &Tuning::pauli_sector_block_bits, kPauliSectorBlockBits);
   const unsigned nblocks = (unsigned)((im.dim + ((int64_t)1 << b) - 1) >> b);
   const int grid = (int)std::min<unsigned>(nblocks, (unsigned)kMaxGrid);
   hipLaunchKernelGGL((pauli_expect_sector_kernel<T, B>), dim3(grid), dim3(kBlock), 0, s, b, nblocks, (unsigned)im.dim, count, sx, sz,
-                     sf, pt, x, partials);
+                     sf, pauli_sector_partner(im), x, partials);
   LL_HIP(hipGetLastError());
   return grid;
 }
 }  // namespace
-
-const char* pauli_expect_kind_name(int kind) {
-  switch (kind) {
-    case ll_operator::PAULI: return "a full-space sum of Pauli strings";
-    case ll_operator::PAULI_SECTOR: return "a sum of Pauli strings on an S_z sector";
-    case ll_operator::CSR: return "a CSR operator";
-    case ll_operator::HOST_CB: return "a host-callback operator";
-    case ll_operator::DEV_CB: return "a device-callback operator";
-    case ll_operator::DENSE: return "a dense operator";
-    case ll_operator::STENCIL: return "a lattice operator";
-    case ll_operator::PAULI_MOMENTUM: return "a momentum block of an S_z sector";
-    case ll_operator::PAULI_MOMENTUM_FULL: return "a momentum block of the full space";
-    case ll_operator::PAULI_SYMMETRIC: return "a momentum / reflection / spin-inversion block";
-    default: return "an operator of an unknown kind";
-  }
-}
 
 template <typename T>
 void pauli_expect_run(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi,
                       double* out, int64_t* sweeps_out) {
   constexpr int B = kPauliExpectBatch;
   const bool sector = op->kind == ll_operator::PAULI_SECTOR;
-  const int n_sites = sector ? op->pauli_sector.n_sites : op->pauli.n_sites;
-  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
-  for (int64_t j = 0; j < n_obs; ++j) {
-    LL_REQUIRE(((obs[j].x_mask | obs[j].z_mask) & ~site_mask) == 0, "observable " + std::to_string(j) + ": a mask bit at or above n_sites");
-    LL_REQUIRE(std::isfinite(obs[j].coef), "observable " + std::to_string(j) + ": the coefficient is not finite");
-  }
+  check_observables(sector ? op->pauli_sector.n_sites : op->pauli.n_sites, n_obs, obs);
   const PauliExpectPlan plan = pauli_expect_plan(scalar_traits<T>::is_complex, sector, n_obs, obs, B);
   for (int64_t j = 0; j < n_obs; ++j) out[j] = 0.0;  // what the identically zero observables keep: +0.0
-  const int64_t nslots = plan.nslots(), nbatches = plan.nbatches();
-  if (sweeps_out) *sweeps_out = nbatches;
-  if (nslots == 0) return;
+  const int64_t nslots = plan.nslots();
+  if (sweeps_out) *sweeps_out = plan.nbatches();
+  if (nslots == 0) return;  // nothing has touched the device
 
   LL_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int64_t nl = op->n_local;
-  DevBuf<T> staged;  // a host psi: one device vector
-  const T* x = (const T*)psi;
-  if (!is_device_ptr(psi)) {
-    staged.alloc(ctx, (size_t)std::max<int64_t>(nl, 1));
-    LL_HIP(hipMemcpyAsync(staged.p, psi, (size_t)nl * sizeof(T), hipMemcpyHostToDevice, s));
-    x = staged.p;
-  }
-  // the slot tables [x | z | flags] and the folded sums of every batch
+  DevBuf<T> staged;
+  const T* const x = stage_in(ctx, staged, psi, op->n_local);
+  // the slot tables [x | z | flags]
   std::vector<uint32_t> tab((size_t)3 * nslots);
   std::copy(plan.x.begin(), plan.x.end(), tab.begin());
   std::copy(plan.z.begin(), plan.z.end(), tab.begin() + nslots);
   std::copy(plan.flags.begin(), plan.flags.end(), tab.begin() + 2 * nslots);
   DevBuf<uint32_t> dtab;
-  DevBuf<double> sums;
   dtab.alloc(ctx, tab.size());
-  sums.alloc(ctx, (size_t)nslots);
   LL_HIP(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  ctx->ensure_partials((size_t)kMaxGrid * B);
-  double* const partials = ctx->partials.get();
-  for (int64_t k = 0; k < nbatches; ++k) {
-    const int64_t i0 = plan.batch_begin(k);
+  const std::vector<double> sums = pauli_measure_sweeps(ctx, plan, (size_t)kMaxGrid * B, [&](int64_t k, double* partials) {
     const int count = (int)plan.batch_count(k);
-    const uint32_t *sx = dtab.p + i0, *sz = sx + nslots, *sf = sz + nslots;
-    const int grid = sector ? launch_pauli_expect_sector<T>(*op, count, sx, sz, sf, x, partials, s)
-                            : launch_pauli_expect<T>(*op, count, sx, sz, sf, x, partials, s);
-    launch_reduce_cols(partials, grid, count, sums.p + i0, nullptr, s);  // fixed order over the workgroups
-  }
-  std::vector<double> host((size_t)nslots);
-  LL_HIP(hipMemcpyAsync(host.data(), sums.p, (size_t)nslots * sizeof(double), hipMemcpyDeviceToHost, s));
-  LL_HIP(hipStreamSynchronize(s));  // (also: tab and a pageable psi are no longer read)
-  for (int64_t i = 0; i < nslots; ++i) out[plan.obs[(size_t)i]] = plan.coef[(size_t)i] * host[(size_t)i];
+    const uint32_t *sx = dtab.p + plan.batch_begin(k), *sz = sx + nslots, *sf = sz + nslots;
+    return sector ? launch_pauli_expect_sector<T>(*op, count, sx, sz, sf, x, partials, s)
+                  : launch_pauli_expect<T>(*op, count, sx, sz, sf, x, partials, s);
+  });
+  for (int64_t i = 0; i < nslots; ++i) out[plan.obs[(size_t)i]] = plan.coef[(size_t)i] * sums[(size_t)i];
 }
 
 // what capi.cpp calls: the checks that do not depend on the storage type, then the operator's type
@@ -326,23 +283,18 @@ void pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const l
   LL_REQUIRE(ctx != nullptr && op != nullptr, "null argument");
   LL_REQUIRE(n_obs >= 0, "n_obs is negative");
   LL_REQUIRE(n_obs == 0 || (obs != nullptr && psi != nullptr && out != nullptr), "null argument");
-  LL_REQUIRE(op->ctx == ctx, "the operator belongs to another context");
-  LL_REQUIRE(ctx->comm == nullptr, "expectation values are not built for sharded contexts (a context with a communicator)");
+  pauli_measure_prologue(ctx, "expectation values", {{op, "the operator"}});
   if (op->kind == ll_operator::PAULI_MOMENTUM || op->kind == ll_operator::PAULI_MOMENTUM_FULL || op->kind == ll_operator::PAULI_SYMMETRIC)
-    LL_REQUIRE(false, std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
+    LL_REQUIRE(false, std::string("the operator is ") + operator_kind_name(op->kind) +
                           ": symmetrised observables are not built (an observable must be summed over the block's group first); "
                           "measure on a full-space or S_z-sector operator");
   LL_REQUIRE(op->kind == ll_operator::PAULI || op->kind == ll_operator::PAULI_SECTOR,
-             std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
+             std::string("the operator is ") + operator_kind_name(op->kind) +
                  ": expectation values of Pauli strings need an operator that defines a spin basis (full-space or S_z-sector "
                  "sum of Pauli strings)");
   if (sweeps_out) *sweeps_out = 0;
   if (n_obs == 0) return;
-  const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-  if (op->is_complex && wide) pauli_expect_run<zc>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else if (op->is_complex) pauli_expect_run<cf>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else if (wide) pauli_expect_run<double>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else pauli_expect_run<float>(ctx, op, n_obs, obs, psi, out, sweeps_out);
+  for_storage_type(*op, [&](auto t) { pauli_expect_run<decltype(t)>(ctx, op, n_obs, obs, psi, out, sweeps_out); });
 }
 
 }  // namespace ll

@@ -31,6 +31,7 @@
 #include "ll_internal.hpp"
 #include "loop_support.hpp"
 #include "pauli_expect_block_plan.hpp"
+#include "pauli_measure.hpp"
 #include "pauli_momentum_full_partner.hpp"
 #include "pauli_momentum_partner.hpp"
 #include "pauli_shared.hpp"
@@ -156,33 +157,22 @@ template <typename T>
 void pauli_expect_block_run(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs, const void* psi,
                             double* out, int64_t* sweeps_out) {
   constexpr int B = kPauliExpectBlockBatch;
-  const bool momentum = op->kind == ll_operator::PAULI_MOMENTUM;
+  const PauliBlockView bv = pauli_block_view(*op);
   PauliBlockGroup grp;
-  grp.n_sites = momentum ? op->pauli_momentum.n_sites : op->pauli_block.n_sites;
-  grp.reflection = !momentum && op->pauli_block.parity != 0;
-  grp.flip = !momentum && op->pauli_block.inversion != 0;
-  const bool sector = momentum || op->pauli_block.n_down >= 0;
-  const uint64_t site_mask = ((uint64_t)1 << grp.n_sites) - 1;
-  for (int64_t j = 0; j < n_obs; ++j) {
-    LL_REQUIRE(((obs[j].x_mask | obs[j].z_mask) & ~site_mask) == 0, "observable " + std::to_string(j) + ": a mask bit at or above n_sites");
-    LL_REQUIRE(std::isfinite(obs[j].coef), "observable " + std::to_string(j) + ": the coefficient is not finite");
-  }
-  const PauliExpectBlockPlan plan = pauli_expect_block_plan(grp, scalar_traits<T>::is_complex, sector, n_obs, obs, B);
+  grp.n_sites = bv.n_sites;
+  grp.reflection = bv.parity != 0;
+  grp.flip = bv.inversion != 0;
+  check_observables(bv.n_sites, n_obs, obs);
+  const PauliExpectBlockPlan plan = pauli_expect_block_plan(grp, scalar_traits<T>::is_complex, bv.n_down >= 0, n_obs, obs, B);
   for (int64_t j = 0; j < n_obs; ++j) out[j] = 0.0;  // what the identically zero observables keep: +0.0
-  const int64_t nslots = plan.nslots(), nbatches = plan.nbatches();
-  if (sweeps_out) *sweeps_out = nbatches;
-  if (nslots == 0) return;
+  const int64_t nslots = plan.nslots();
+  if (sweeps_out) *sweeps_out = plan.nbatches();
+  if (nslots == 0) return;  // nothing has touched the device
 
   LL_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int64_t nl = op->n_local;
-  DevBuf<T> staged;  // a host psi: one device vector
-  const T* x = (const T*)psi;
-  if (!is_device_ptr(psi)) {
-    staged.alloc(ctx, (size_t)std::max<int64_t>(nl, 1));
-    LL_HIP(hipMemcpyAsync(staged.p, psi, (size_t)nl * sizeof(T), hipMemcpyHostToDevice, s));
-    x = staged.p;
-  }
+  DevBuf<T> staged;
+  const T* const x = stage_in(ctx, staged, psi, op->n_local);
   // the slots' tables, one after the other: sg[slot] = its first group, gptr[] counts the strings from the call's first
   std::vector<int32_t> sg, gptr;
   std::vector<uint32_t> gx, tz;
@@ -199,26 +189,17 @@ void pauli_expect_block_run(ll_context* ctx, const ll_operator* op, int64_t n_ob
   gptr.push_back((int32_t)tz.size());
   DevBuf<int32_t> dsg, dgptr;
   DevBuf<uint32_t> dgx, dtz;
-  DevBuf<double> dtc, sums;
+  DevBuf<double> dtc;
   expect_block_upload(ctx, dsg, sg, s);
   expect_block_upload(ctx, dgptr, gptr, s);
   expect_block_upload(ctx, dgx, gx, s);
   expect_block_upload(ctx, dtz, tz, s);
   expect_block_upload(ctx, dtc, tc, s);
-  sums.alloc(ctx, (size_t)nslots);
-  ctx->ensure_partials((size_t)kMaxGrid * B);
-  double* const partials = ctx->partials.get();
-  for (int64_t k = 0; k < nbatches; ++k) {
-    const int64_t i0 = plan.batch_begin(k);
-    const int count = (int)plan.batch_count(k);
-    const ExpectBlockTables tb{dsg.p + i0, dgx.p, dgptr.p, dtz.p, dtc.p};
-    const int grid = launch_pauli_expect_block_op<T>(*op, count, tb, x, partials, s);
-    launch_reduce_cols(partials, grid, count, sums.p + i0, nullptr, s);  // fixed order over the workgroups
-  }
-  std::vector<double> host((size_t)nslots);
-  LL_HIP(hipMemcpyAsync(host.data(), sums.p, (size_t)nslots * sizeof(double), hipMemcpyDeviceToHost, s));
-  LL_HIP(hipStreamSynchronize(s));  // (also: the tables and a pageable psi are no longer read)
-  for (int64_t i = 0; i < nslots; ++i) out[plan.slots[(size_t)i].obs] = plan.slots[(size_t)i].coef * host[(size_t)i];
+  const std::vector<double> sums = pauli_measure_sweeps(ctx, plan, (size_t)kMaxGrid * B, [&](int64_t k, double* partials) {
+    const ExpectBlockTables tb{dsg.p + plan.batch_begin(k), dgx.p, dgptr.p, dtz.p, dtc.p};
+    return launch_pauli_expect_block_op<T>(*op, (int)plan.batch_count(k), tb, x, partials, s);
+  });
+  for (int64_t i = 0; i < nslots; ++i) out[plan.slots[(size_t)i].obs] = plan.slots[(size_t)i].coef * sums[(size_t)i];
 }
 
 // what capi.cpp calls: the checks that do not depend on the storage type, then the operator's type
@@ -227,23 +208,18 @@ void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, c
   LL_REQUIRE(ctx != nullptr && op != nullptr, "null argument");
   LL_REQUIRE(n_obs >= 0, "n_obs is negative");
   LL_REQUIRE(n_obs == 0 || (obs != nullptr && psi != nullptr && out != nullptr), "null argument");
-  LL_REQUIRE(op->ctx == ctx, "the operator belongs to another context");
-  LL_REQUIRE(ctx->comm == nullptr, "expectation values are not built for sharded contexts (a context with a communicator)");
+  pauli_measure_prologue(ctx, "expectation values", {{op, "the operator"}});
   if (op->kind == ll_operator::PAULI || op->kind == ll_operator::PAULI_SECTOR)
-    LL_REQUIRE(false, std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
+    LL_REQUIRE(false, std::string("the operator is ") + operator_kind_name(op->kind) +
                           ": its basis is not a symmetry block; measure with ll_pauli_expect");
   LL_REQUIRE(op->kind == ll_operator::PAULI_MOMENTUM || op->kind == ll_operator::PAULI_MOMENTUM_FULL ||
                  op->kind == ll_operator::PAULI_SYMMETRIC,
-             std::string("the operator is ") + pauli_expect_kind_name(op->kind) +
+             std::string("the operator is ") + operator_kind_name(op->kind) +
                  ": expectation values on a symmetry block need a momentum, full-momentum or momentum / reflection / "
                  "spin-inversion block of a sum of Pauli strings");
   if (sweeps_out) *sweeps_out = 0;
   if (n_obs == 0) return;
-  const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-  if (op->is_complex && wide) pauli_expect_block_run<zc>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else if (op->is_complex) pauli_expect_block_run<cf>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else if (wide) pauli_expect_block_run<double>(ctx, op, n_obs, obs, psi, out, sweeps_out);
-  else pauli_expect_block_run<float>(ctx, op, n_obs, obs, psi, out, sweeps_out);
+  for_storage_type(*op, [&](auto t) { pauli_expect_block_run<decltype(t)>(ctx, op, n_obs, obs, psi, out, sweeps_out); });
 }
 
 }  // namespace ll

@@ -25,8 +25,18 @@ namespace ll {
 constexpr uint32_t kExpectSlotNewGroup = 1u;  // the slot's x mask differs from the slot before it in the batch: load the partner
 constexpr uint32_t kExpectSlotImag = 2u;      // the slot sums Im v (complex storage, nY odd), else Re v
 
-struct PauliExpectPlan {
+// The slots of a measuring call cut into batches of at most `batch`, one sweep each: what both plans (this one and
+// pauli_expect_block_plan.hpp) derive from; the planning function counts the slots when it has made them.
+struct PauliBatches {
+  int64_t slot_count = 0;
   int batch = 0;                       // B: slots per sweep at most
+  int64_t nslots() const { return slot_count; }
+  int64_t nbatches() const { return batch > 0 ? (slot_count + batch - 1) / batch : 0; }
+  int64_t batch_begin(int64_t k) const { return k * batch; }
+  int64_t batch_count(int64_t k) const { return std::min<int64_t>(batch, slot_count - k * batch); }
+};
+
+struct PauliExpectPlan : PauliBatches {
   int64_t n_obs = 0;
   // per slot, in kernel order
   std::vector<uint32_t> x, z, flags;
@@ -34,10 +44,6 @@ struct PauliExpectPlan {
   std::vector<int64_t> obs;            // the caller's index of the slot's observable
   // per observable of the caller
   std::vector<int64_t> slot;           // its slot, -1: identically zero
-  int64_t nslots() const { return (int64_t)x.size(); }
-  int64_t nbatches() const { return batch > 0 ? (nslots() + batch - 1) / batch : 0; }
-  int64_t batch_begin(int64_t k) const { return k * batch; }
-  int64_t batch_count(int64_t k) const { return std::min<int64_t>(batch, nslots() - k * batch); }
 };
 
 inline bool pauli_expect_is_zero(uint64_t x_mask, uint64_t z_mask, bool complex_storage, bool sector) {
@@ -66,6 +72,7 @@ PauliExpectPlan pauli_expect_plan(bool complex_storage, bool sector, int64_t n_o
     if (!pauli_expect_is_zero(terms[j].x_mask, terms[j].z_mask, complex_storage, sector)) order.push_back(j);
   std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return terms[a].x_mask < terms[b].x_mask; });
   const size_t ns = order.size();
+  p.slot_count = (int64_t)ns;
   p.x.resize(ns);
   p.z.resize(ns);
   p.flags.resize(ns);

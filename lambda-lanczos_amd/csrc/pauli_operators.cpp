@@ -6,6 +6,12 @@
 #include "ll_internal.hpp"
 
 namespace ll {
+void check_pauli_string(const char* what, int64_t j, const ll_pauli_term& q, int n_sites) {
+  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
+  LL_REQUIRE(((q.x_mask | q.z_mask) & ~site_mask) == 0, what + (" " + std::to_string(j)) + ": a mask bit at or above n_sites");
+  LL_REQUIRE(std::isfinite(q.coef), what + (" " + std::to_string(j)) + ": the coefficient is not finite");
+}
+
 namespace {
 // Validate, fold i^nY into the coefficient (a sign for the real types, one of {1, i, -1, -i} for the complex ones), group the
 // terms by x mask — groups by ascending mask, the terms of a group in the caller's order.
@@ -28,13 +34,11 @@ PauliTables pauli_tables(ll_context* ctx, int32_t n_sites, int64_t n_terms, cons
              "exchanges between them, which are not built): use a single-GPU context");
   LL_REQUIRE(n_terms < (int64_t)0x7fffffff, "too many terms");
   constexpr bool cplx = scalar_traits<T>::is_complex;
-  const uint64_t site_mask = ((uint64_t)1 << n_sites) - 1;
   std::vector<int64_t> order((size_t)n_terms);
   PauliTables pt;
   for (int64_t t = 0; t < n_terms; ++t) {
     const ll_pauli_term& q = terms[t];
-    LL_REQUIRE(((q.x_mask | q.z_mask) & ~site_mask) == 0, "term " + std::to_string(t) + ": a mask bit at or above n_sites");
-    LL_REQUIRE(std::isfinite(q.coef), "term " + std::to_string(t) + ": the coefficient is not finite");
+    check_pauli_string("term", t, q, n_sites);
     LL_REQUIRE(cplx || (__builtin_popcountll(q.x_mask & q.z_mask) & 1) == 0,
                "term " + std::to_string(t) + ": an odd number of Y factors makes the matrix complex; use a complex storage type");
     order[(size_t)t] = t;

@@ -33,6 +33,7 @@
 #include "engine.hpp"
 #include "ll_internal.hpp"
 #include "loop_support.hpp"
+#include "pauli_measure.hpp"
 #include "pauli_rdm_plan.hpp"
 #include "pauli_sector_partner.hpp"
 #include "pauli_shared.hpp"
@@ -241,7 +242,6 @@ int launch_pauli_rdm(const ll_operator& op, const int32_t* sites, const T* x, do
 template <typename T, int M>
 int launch_pauli_rdm_sector(const ll_operator& op, const int32_t* sites, const T* x, double* partials, hipStream_t s) {
   const PauliSectorImage& im = op.pauli_sector;
-  const PauliSectorPartner pt{im.states.get(), im.lo_rank.get(), im.hi_rank.get(), im.h};
   const int forced = op.ctx ? op.ctx->tune.pauli_rdm_block_bits : -1;
   const int b = pauli_rdm_block_bits(im.n_sites, M, (int)sizeof(T), forced, kPauliRdmLdsBytes);
   const PauliRdmGeom g = pauli_rdm_geom(im.n_sites, M, sites, 0);
@@ -250,7 +250,7 @@ int launch_pauli_rdm_sector(const ll_operator& op, const int32_t* sites, const T
   const int grid = rdm_grid(nbatches, pauli_rdm_partials(M, kRdmComplex<T>));
   const size_t lds = std::max<size_t>((size_t)sizeof(T) << (b + M), 16);
   hipLaunchKernelGGL((pauli_rdm_sector_kernel<T, M>), dim3(grid), dim3(kBlock), lds, s, g, b, (unsigned)nbatches, (unsigned)nenv,
-                     (int)im.n_down, pt, x, partials);
+                     (int)im.n_down, pauli_sector_partner(im), x, partials);
   LL_HIP(hipGetLastError());
   return grid;
 }
@@ -258,20 +258,6 @@ template <typename T, int M>
 int launch_pauli_rdm_any(const ll_operator& op, const int32_t* sites, const T* x, double* partials, hipStream_t s) {
   return op.kind == ll_operator::PAULI_SECTOR ? launch_pauli_rdm_sector<T, M>(op, sites, x, partials, s)
                                               : launch_pauli_rdm<T, M>(op, sites, x, partials, s);
-}
-
-const char* rdm_kind_name(int kind) {
-  switch (kind) {
-    case ll_operator::CSR: return "a CSR operator";
-    case ll_operator::HOST_CB: return "a host-callback operator";
-    case ll_operator::DEV_CB: return "a device-callback operator";
-    case ll_operator::DENSE: return "a dense operator";
-    case ll_operator::STENCIL: return "a lattice operator";
-    case ll_operator::PAULI_MOMENTUM: return "a momentum block of an S_z sector";
-    case ll_operator::PAULI_MOMENTUM_FULL: return "a momentum block of the full space";
-    case ll_operator::PAULI_SYMMETRIC: return "a momentum / reflection / spin-inversion block";
-    default: return "an operator of an unknown kind";
-  }
 }
 }  // namespace
 
@@ -282,32 +268,21 @@ void pauli_rdm_run(ll_context* ctx, const ll_operator* op, int m, const int32_t*
   const bool sector = op->kind == ll_operator::PAULI_SECTOR;
   LL_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int64_t nl = op->n_local;
-  DevBuf<T> staged;  // a host psi: one device vector
-  const T* x = (const T*)psi;
-  if (!is_device_ptr(psi)) {
-    staged.alloc(ctx, (size_t)std::max<int64_t>(nl, 1));
-    LL_HIP(hipMemcpyAsync(staged.p, psi, (size_t)nl * sizeof(T), hipMemcpyHostToDevice, s));
-    x = staged.p;
-  }
+  DevBuf<T> staged;
+  const T* const x = stage_in(ctx, staged, psi, op->n_local);
+  // one batch: the 4^m numbers of the upper triangle are its slots
   const int count = pauli_rdm_partials(m, cplx);
-  ctx->ensure_partials((size_t)rdm_grid(kMaxGrid, count) * count);
-  double* const partials = ctx->partials.get();
-  DevBuf<double> sums;
-  sums.alloc(ctx, (size_t)count);
-  int grid = 0;
-  switch (m) {
-    case 1: grid = launch_pauli_rdm_any<T, 1>(*op, sites, x, partials, s); break;
-    case 2: grid = launch_pauli_rdm_any<T, 2>(*op, sites, x, partials, s); break;
-    case 3: grid = launch_pauli_rdm_any<T, 3>(*op, sites, x, partials, s); break;
-    case 4: grid = launch_pauli_rdm_any<T, 4>(*op, sites, x, partials, s); break;
-    case 5: grid = launch_pauli_rdm_any<T, 5>(*op, sites, x, partials, s); break;
-    default: grid = launch_pauli_rdm_any<T, 6>(*op, sites, x, partials, s); break;
-  }
-  launch_reduce_cols(partials, grid, count, sums.p, nullptr, s);  // fixed order over the workgroups
-  std::vector<double> host((size_t)count);
-  LL_HIP(hipMemcpyAsync(host.data(), sums.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
-  LL_HIP(hipStreamSynchronize(s));  // (also: a pageable psi is no longer read)
+  const std::vector<double> host =
+      pauli_measure_sweeps(ctx, PauliBatches{count, count}, (size_t)rdm_grid(kMaxGrid, count) * count, [&](int64_t, double* partials) {
+        switch (m) {
+          case 1: return launch_pauli_rdm_any<T, 1>(*op, sites, x, partials, s);
+          case 2: return launch_pauli_rdm_any<T, 2>(*op, sites, x, partials, s);
+          case 3: return launch_pauli_rdm_any<T, 3>(*op, sites, x, partials, s);
+          case 4: return launch_pauli_rdm_any<T, 4>(*op, sites, x, partials, s);
+          case 5: return launch_pauli_rdm_any<T, 5>(*op, sites, x, partials, s);
+          default: return launch_pauli_rdm_any<T, 6>(*op, sites, x, partials, s);
+        }
+      });
   if (sweeps_out) *sweeps_out = 1;
   // the upper triangle, mirrored: out[a'][a] = conj(out[a][a']) with every zero imaginary part +0.0
   const int dim = 1 << m;
@@ -330,14 +305,13 @@ void pauli_rdm_run(ll_context* ctx, const ll_operator* op, int m, const int32_t*
 void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, double* out,
                int64_t* sweeps_out) {
   LL_REQUIRE(ctx != nullptr && op != nullptr && sites != nullptr && psi != nullptr && out != nullptr, "null argument");
-  LL_REQUIRE(op->ctx == ctx, "the operator belongs to another context");
-  LL_REQUIRE(ctx->comm == nullptr, "reduced density matrices are not built for sharded contexts (a context with a communicator)");
+  pauli_measure_prologue(ctx, "reduced density matrices", {{op, "the operator"}});
   if (op->kind == ll_operator::PAULI_MOMENTUM || op->kind == ll_operator::PAULI_MOMENTUM_FULL || op->kind == ll_operator::PAULI_SYMMETRIC)
-    LL_REQUIRE(false, std::string("the operator is ") + rdm_kind_name(op->kind) +
+    LL_REQUIRE(false, std::string("the operator is ") + operator_kind_name(op->kind) +
                           ": reduced density matrices of symmetry blocks are not built (a site is not a tensor factor of the "
                           "block's basis); measure on a full-space or S_z-sector operator");
   LL_REQUIRE(op->kind == ll_operator::PAULI || op->kind == ll_operator::PAULI_SECTOR,
-             std::string("the operator is ") + rdm_kind_name(op->kind) +
+             std::string("the operator is ") + operator_kind_name(op->kind) +
                  ": a reduced density matrix needs an operator that defines a spin basis (full-space or S_z-sector sum of Pauli "
                  "strings)");
   const int n_sites = op->kind == ll_operator::PAULI_SECTOR ? op->pauli_sector.n_sites : op->pauli.n_sites;
@@ -350,11 +324,7 @@ void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int3
                                             std::to_string(n_sites) + ")");
   LL_REQUIRE(err != kRdmSiteRepeated, "site " + std::to_string(which) + " of the list (" +
                                           std::to_string(which >= 0 ? sites[which] : 0) + ") is repeated");
-  const bool wide = op->elem_bytes == (op->is_complex ? (int)sizeof(zc) : (int)sizeof(double));
-  if (op->is_complex && wide) pauli_rdm_run<zc>(ctx, op, n_sub, sites, psi, out, sweeps_out);
-  else if (op->is_complex) pauli_rdm_run<cf>(ctx, op, n_sub, sites, psi, out, sweeps_out);
-  else if (wide) pauli_rdm_run<double>(ctx, op, n_sub, sites, psi, out, sweeps_out);
-  else pauli_rdm_run<float>(ctx, op, n_sub, sites, psi, out, sweeps_out);
+  for_storage_type(*op, [&](auto t) { pauli_rdm_run<decltype(t)>(ctx, op, n_sub, sites, psi, out, sweeps_out); });
 }
 
 }  // namespace ll

@@ -23,9 +23,8 @@ template <typename T>
 int launch_pauli_sector(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                         const ScaleIn<T>* scp) {
   const PauliSectorImage& im = op.pauli_sector;
-  const PauliSectorPartner pt{im.states.get(), im.lo_rank.get(), im.hi_rank.get(), im.h};
-  return launch_pauli_basis(pauli_block_bits(op, &Tuning::pauli_sector_block_bits, kPauliSectorBlockBits), im.dim, im.terms, pt, x,
-                            y, offset, dot_partials, s, scp);
+  return launch_pauli_basis(pauli_block_bits(op, &Tuning::pauli_sector_block_bits, kPauliSectorBlockBits), im.dim, im.terms,
+                            pauli_sector_partner(im), x, y, offset, dot_partials, s, scp);
 }
 #define LL_INST_PAULI_SECTOR(T) \
   template int launch_pauli_sector<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const ScaleIn<T>*);

@@ -28,4 +28,8 @@ struct PauliSectorPartner {
   }
 };
 
+inline PauliSectorPartner pauli_sector_partner(const PauliSectorImage& im) {
+  return PauliSectorPartner{im.states.get(), im.lo_rank.get(), im.hi_rank.get(), im.h};
+}
+
 }  // namespace ll

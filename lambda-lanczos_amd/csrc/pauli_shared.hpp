@@ -9,6 +9,17 @@
 
 namespace ll {
 
+// The full-space kernels (pauli.hip, pauli_expect.hip) stage tiles of 2^b states of T in LDS: the context's pauli_tile_bits, else
+// what fills kPauliTileBytes; at most kPauliMaxTileBytes (the LDS a launch may ask for without raising the kernel's limit) and
+// never more than the vector
+template <typename T> int pauli_tile_bits(const ll_operator& op) {
+  int b = op.ctx ? op.ctx->tune.pauli_tile_bits : -1;
+  if (b < 0)
+    for (b = 0; ((size_t)sizeof(T) << (b + 1)) <= (size_t)kPauliTileBytes;) ++b;
+  while (b > 0 && ((size_t)sizeof(T) << b) > (size_t)kPauliMaxTileBytes) --b;
+  return std::min(b, op.pauli.n_sites);
+}
+
 namespace {
 constexpr int kPauliLaneStates = 4;  // states a lane carries through the term loop at a time (accumulators in registers)
 

@@ -418,17 +418,28 @@ def _term_array(terms):
     return arr, len(terms)
 
 
+def _vector_arg(vec, n, dtype, type_error, value_error):
+    """(keep_alive, void*) of a vector argument of n values of `dtype`: a numpy array (converted to dtype; ValueError unless it
+    holds exactly n) or anything with .ptr, .dtype, .shape that names device memory (TypeError unless it holds at least n values
+    of dtype).  The two texts are formats of n, dtype and size (what the array holds), filled in only when raised.  The caller
+    keeps keep_alive until the library returns."""
+    if hasattr(vec, "ptr"):
+        if vec.dtype != dtype or int(np.prod(vec.shape)) < n:
+            raise TypeError(type_error % {"n": n, "dtype": np.dtype(dtype)})
+        return vec, C.c_void_p(vec.ptr)
+    keep = np.ascontiguousarray(vec, dtype=dtype)
+    if keep.size != n:
+        raise ValueError(value_error % {"n": n, "size": keep.size})
+    return keep, ptr(keep)
+
+
+_PSI_ERRORS = ("psi must hold n_local values of the operator's dtype %(dtype)s", "psi holds %(size)d values, the operator's basis %(n)d")
+_INPUT_ERRORS = ("the input must hold %(n)d values of the operators' dtype %(dtype)s", "the input holds %(size)d values, its basis %(n)d")
+
+
 def _pauli_expect_call(entry, op, psi, observables, return_sweeps):
     arr, n_obs = _term_array(observables)
-    if hasattr(psi, "ptr"):
-        if psi.dtype != np.dtype(op.dtype) or int(np.prod(psi.shape)) < op.n_local:
-            raise TypeError("psi must hold n_local values of the operator's dtype %s" % np.dtype(op.dtype))
-        keep, p = psi, C.c_void_p(psi.ptr)
-    else:
-        keep = np.ascontiguousarray(psi, dtype=op.dtype)
-        if keep.size != op.n_local:
-            raise ValueError("psi holds %d values, the operator's basis %d" % (keep.size, op.n_local))
-        p = ptr(keep)
+    keep, p = _vector_arg(psi, op.n_local, op.dtype, *_PSI_ERRORS)
     out = np.zeros(n_obs, dtype=np.float64)
     sweeps = C.c_int64(0)
     check(getattr(lib(), entry)(op.ctx.handle, op.handle, n_obs, arr, p, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sweeps)))
@@ -456,15 +467,7 @@ def pauli_expect_block(op, psi, observables, return_sweeps=False):
 
 def _pauli_embed_call(entry, block, target, vec, n_in, n_out, out):
     dtype = np.dtype(block.dtype)
-    if hasattr(vec, "ptr"):
-        if vec.dtype != dtype or int(np.prod(vec.shape)) < n_in:
-            raise TypeError("the input must hold %d values of the operators' dtype %s" % (n_in, dtype))
-        keep, p = vec, C.c_void_p(vec.ptr)
-    else:
-        keep = np.ascontiguousarray(vec, dtype=dtype)
-        if keep.size != n_in:
-            raise ValueError("the input holds %d values, its basis %d" % (keep.size, n_in))
-        p = ptr(keep)
+    keep, p = _vector_arg(vec, n_in, dtype, *_INPUT_ERRORS)
     if out is None:
         out = np.empty(n_out, dtype=dtype)
     if hasattr(out, "ptr"):
@@ -518,15 +521,7 @@ def pauli_rdm(op, psi, sites, return_sweeps=False):
     sites = [int(s) for s in sites]
     m = len(sites)
     arr = (C.c_int32 * max(m, 1))(*sites)
-    if hasattr(psi, "ptr"):
-        if psi.dtype != np.dtype(op.dtype) or int(np.prod(psi.shape)) < op.n_local:
-            raise TypeError("psi must hold n_local values of the operator's dtype %s" % np.dtype(op.dtype))
-        keep, p = psi, C.c_void_p(psi.ptr)
-    else:
-        keep = np.ascontiguousarray(psi, dtype=op.dtype)
-        if keep.size != op.n_local:
-            raise ValueError("psi holds %d values, the operator's basis %d" % (keep.size, op.n_local))
-        p = ptr(keep)
+    keep, p = _vector_arg(psi, op.n_local, op.dtype, *_PSI_ERRORS)
     dim = 1 << min(max(m, 0), 6)   # (a count the library refuses still gets a buffer)
     out = np.zeros((dim, dim), dtype=np.complex128)
     sweeps = C.c_int64(0)

@@ -167,6 +167,25 @@ int main() {
     const PauliExpectPlan p = pauli_expect_plan<Term>(true, false, 0, nullptr, 32);
     REQUIRE(p.nslots() == 0 && p.nbatches() == 0, "empty plan");
   }
+  // PauliBatches, which both plans and the measuring driver count with: the batches tile [0, nslots) exactly, in order, none empty
+  // and none above the batch size; no slots: no batches; a non-positive batch size: no batches
+  for (int64_t ns = 0; ns <= 70; ++ns) {
+    for (int B : {1, 2, 31, 32, 33}) {
+      const PauliBatches bt{ns, B};
+      REQUIRE(bt.nslots() == ns && bt.nbatches() == (ns + B - 1) / B, "batches: %lld slots by %d: %lld batches", (long long)ns, B,
+              (long long)bt.nbatches());
+      REQUIRE(ns != 0 || bt.nbatches() == 0, "batches: no slots, %lld batches", (long long)bt.nbatches());
+      int64_t at = 0;
+      for (int64_t k = 0; k < bt.nbatches(); ++k) {
+        REQUIRE(bt.batch_begin(k) == at && bt.batch_count(k) >= 1 && bt.batch_count(k) <= B,
+                "batches: %lld slots by %d: batch %lld begins at %lld with %lld, after %lld", (long long)ns, B, (long long)k,
+                (long long)bt.batch_begin(k), (long long)bt.batch_count(k), (long long)at);
+        at += bt.batch_count(k);
+      }
+      REQUIRE(at == ns, "batches: %lld slots by %d: the batches hold %lld", (long long)ns, B, (long long)at);
+    }
+    for (int B : {0, -1, -32}) REQUIRE((PauliBatches{ns, B}).nbatches() == 0, "batches: %lld slots by %d", (long long)ns, B);
+  }
   std::printf("%lld checks, %lld failures\n", checks, fails);
   return fails == 0 ? 0 : 1;
 }
