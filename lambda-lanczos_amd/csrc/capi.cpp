@@ -74,7 +74,7 @@ template <typename T>
 void recur_accum_impl(ll_context* ctx, int64_t n, T* y, const T* x, const T* p, double a, double b, double g, T* psi) {
   use(ctx);
   LL_REQUIRE(n >= 0 && y && x && psi, "null vector");
-  launch_recur_accum<T>(n, y, x, p, psi, nullptr, nullptr, 0, a, b, g, nullptr, 0, nullptr, ctx->stream);
+  launch_recur_accum<T, double>(n, y, x, p, psi, nullptr, nullptr, 0, a, b, g, nullptr, 0, nullptr, ctx->stream);
 }
 template <typename T>
 void orth_impl(ll_context* ctx, int64_t n, int64_t nb, const T* basis, int64_t ld, T* w, int mode, double* norm_out,
@@ -147,45 +147,36 @@ void taylor_run_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, 
   LL_REQUIRE(ctx && p && input && output && nterms, "null argument");
   taylor_run<T>(ctx, op, *p, a, input, output, nterms);
 }
+// (re, im) as the host scalar of T's runs; a non-zero imaginary part on real storage is refused with the caller's text
+template <typename T> typename host_scalar<T>::type host_scalar_of(double re, double im, const char* refusal) {
+  if constexpr (scalar_traits<T>::is_complex) {
+    return std::complex<double>(re, im);
+  } else {
+    LL_REQUIRE(im == 0.0, refusal);
+    return re;
+  }
+}
+constexpr const char* kRealTime = "a_im must be 0 with a real operator";
+constexpr const char* kRealCoeff = "g_im must be 0 for the real storage types 'd' and 's'";
 template <typename T>
 void recur_accum_scaled_impl(ll_context* ctx, int64_t n, void* y, const void* x, const void* p, double a, double b, double g_re,
                              double g_im, void* psi) {
+  typedef typename RecurCoeff<T>::type G;
   LL_REQUIRE(n >= 0 && y && x && psi, "null vector");
-  if constexpr (scalar_traits<T>::is_complex) {
-    launch_recur_accum_cplx<T>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, zc{g_re, g_im}, nullptr, 0,
-                               nullptr, ctx->stream);
-  } else {
-    LL_REQUIRE(g_im == 0.0, "g_im must be 0 for the real storage types 'd' and 's'");
-    launch_recur_accum<T>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, g_re, nullptr, 0, nullptr, ctx->stream);
-  }
+  const G g = RecurCoeff<T>::of(host_scalar_of<T>(g_re, g_im, kRealCoeff));
+  launch_recur_accum<T, G>(n, (T*)y, (const T*)x, (const T*)p, (T*)psi, nullptr, nullptr, 0, a, b, g, nullptr, 0, nullptr, ctx->stream);
 }
 // the storage type is the operator's
 template <typename T>
 void expo_two_pass_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, double a_re, double a_im, const void* input,
                         void* output, int64_t* itern, ll_run_stats* stats) {
-  typedef typename host_scalar<T>::type H;
-  H a;
-  if constexpr (scalar_traits<T>::is_complex) {
-    a = H(a_re, a_im);
-  } else {
-    LL_REQUIRE(a_im == 0.0, "a_im must be 0 with a real operator");
-    a = a_re;
-  }
-  expo_two_pass_run<T>(ctx, op, *p, a, (const T*)input, (T*)output, itern, stats);
+  expo_two_pass_run<T>(ctx, op, *p, host_scalar_of<T>(a_re, a_im, kRealTime), (const T*)input, (T*)output, itern, stats);
 }
 template <typename T>
 void expo_two_pass_multi_impl(ll_context* ctx, ll_operator* op, const ll_expo_params* p, int64_t n_times, const double* a_reim,
                               const void* input, void* const* outputs, int64_t* itern, ll_run_stats* stats) {
-  typedef typename host_scalar<T>::type H;
-  H a[kRecurMultiMax];
-  for (int64_t j = 0; j < n_times; ++j) {
-    if constexpr (scalar_traits<T>::is_complex) {
-      a[j] = H(a_reim[2 * j], a_reim[2 * j + 1]);
-    } else {
-      LL_REQUIRE(a_reim[2 * j + 1] == 0.0, "a_im must be 0 with a real operator");
-      a[j] = a_reim[2 * j];
-    }
-  }
+  typename host_scalar<T>::type a[kRecurMultiMax];
+  for (int64_t j = 0; j < n_times; ++j) a[j] = host_scalar_of<T>(a_reim[2 * j], a_reim[2 * j + 1], kRealTime);
   expo_two_pass_multi_run<T>(ctx, op, *p, n_times, a, (const T*)input, (T* const*)outputs, itern, stats);
 }
 template <typename T>
@@ -197,12 +188,7 @@ void recur_accum_multi_impl(ll_context* ctx, int64_t n, void* y, const void* x, 
   for (int64_t j = 0; j < n_acc; ++j) {
     LL_REQUIRE(psi[j] != nullptr, "null vector");
     acc.psi[j] = (T*)psi[j];
-    if constexpr (scalar_traits<T>::is_complex) {
-      acc.g[j] = zc{g_reim[2 * j], g_reim[2 * j + 1]};
-    } else {
-      LL_REQUIRE(g_reim[2 * j + 1] == 0.0, "g_im must be 0 for the real storage types 'd' and 's'");
-      acc.g[j] = g_reim[2 * j];
-    }
+    acc.g[j] = RecurCoeff<T>::of(host_scalar_of<T>(g_reim[2 * j], g_reim[2 * j + 1], kRealCoeff));
   }
   acc.count = (int)n_acc;
   launch_recur_accum_multi<T>(n, (T*)y, (const T*)x, (const T*)p, acc, nullptr, nullptr, 0, 0, a, b, nullptr, 0, nullptr, ctx->stream);
@@ -521,13 +507,7 @@ int ll_recur_accum_scaled(ll_context* ctx, int storage, int64_t n, void* y, cons
                           double g_re, double g_im, void* psi) {
   return guarded([&] {
     use(ctx);
-    switch (storage) {
-      case 'd': recur_accum_scaled_impl<double>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
-      case 'z': recur_accum_scaled_impl<zc>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
-      case 's': recur_accum_scaled_impl<float>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
-      case 'c': recur_accum_scaled_impl<cf>(ctx, n, y, x, p, a, b, g_re, g_im, psi); break;
-      default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
-    }
+    for_storage_char(storage, [&](auto t) { recur_accum_scaled_impl<decltype(t)>(ctx, n, y, x, p, a, b, g_re, g_im, psi); });
   });
 }
 int ll_expo_two_pass_multi(ll_context* ctx, ll_operator* op, const ll_expo_params* p, int64_t n_times, const double* a_reim,
@@ -545,13 +525,7 @@ int ll_recur_accum_multi(ll_context* ctx, int storage, int64_t n, void* y, const
   return guarded([&] {
     use(ctx);
     LL_REQUIRE(n_acc >= 1 && n_acc <= kRecurMultiMax, "n_acc must be between 1 and 16");
-    switch (storage) {
-      case 'd': recur_accum_multi_impl<double>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
-      case 'z': recur_accum_multi_impl<zc>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
-      case 's': recur_accum_multi_impl<float>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
-      case 'c': recur_accum_multi_impl<cf>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); break;
-      default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
-    }
+    for_storage_char(storage, [&](auto t) { recur_accum_multi_impl<decltype(t)>(ctx, n, y, x, p, a, b, n_acc, g_reim, psi); });
   });
 }
 int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const ll_pauli_term* obs_host, const void* psi,

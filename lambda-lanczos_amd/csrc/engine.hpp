@@ -1,5 +1,5 @@
 // Host drivers of the device-resident Lanczos loop (templated on the scalar type; Engine, Basis and RunList are instantiated
-// in engine.cpp, the whole-loop drivers in lanczos_run.cpp, expo_run.cpp, two_pass_run.cpp and expo_two_pass_run.cpp).  See
+// in engine.cpp, the whole-loop drivers in lanczos_run.cpp, expo_run.cpp, two_pass_run.cpp and expo_two_pass_multi_run.cpp).  See
 // DESIGN.md for the data flow.
 #pragma once
 
@@ -255,7 +255,7 @@ template <typename T> struct IterationSpec {
 int64_t pick_chunk_vecs(int64_t initial_vector_size, int64_t max_iteration, int64_t vec_bytes, int64_t cap_bytes);
 int64_t default_slab_bytes(int64_t n, int64_t n_local, int64_t n_shard, int elem_bytes, const Tuning& tune);
 
-// Whole-loop drivers (lanczos_run.cpp; expo_run.cpp; two_pass_run.cpp; expo_two_pass_run.cpp; expo_two_pass_multi_run.cpp)
+// Whole-loop drivers (lanczos_run.cpp; expo_run.cpp; two_pass_run.cpp; expo_two_pass_multi_run.cpp)
 template <typename T>
 void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P, double* eigvals, T* eigvecs,
                  int64_t* n_found, int64_t* iter_counts, int64_t iter_cap, double* alpha_out, double* beta_out,
@@ -268,12 +268,13 @@ void two_pass_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P, 
 template <typename T>
 void expo_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P, typename host_scalar<T>::type a,
               const T* input, T* output, int64_t* itern_out, ll_run_stats* stats);
-// expo_run without a stored basis (expo_two_pass_run.cpp): three n-sized work vectors whatever the iteration count, four when the
-// output is host memory; the plain recurrence only (full_orthogonalize is refused), every operator application twice.
+// expo_run without a stored basis (expo_two_pass_multi_run.cpp, as a list of one time): three n-sized work vectors whatever the
+// iteration count, four when the output is host memory; the plain recurrence only (full_orthogonalize is refused), every operator
+// application twice.
 template <typename T>
 void expo_two_pass_run(ll_context* ctx, ll_operator* op, const ll_expo_params& P, typename host_scalar<T>::type a,
                        const T* input, T* output, int64_t* itern_out, ll_run_stats* stats);
-// ... for n_times values of a on ONE Krylov space (expo_two_pass_multi_run.cpp): pass 1 once with a stop test per a_j, pass 2 once
+// ... for n_times values of a on ONE Krylov space: pass 1 once with a stop test per a_j, pass 2 once
 // with one accumulator per output; outputs[j] (host or device memory, decided per pointer) and itern_out[j] (nullable array) are
 // what expo_two_pass_run gives for a[j]; three work vectors plus one per output in host memory.
 template <typename T>

@@ -4,7 +4,8 @@
 // the device already executes iteration k+1 (lag-1 speculation: a speculative iteration only writes basis slots
 // the results never read, so stopping one iteration "late" on the device is harmless).
 // This header is the loop machinery both drivers share (lanczos_run.cpp, expo_run.cpp; the basis-free drivers — recurrence.hpp,
-// two_pass_run.cpp, expo_two_pass_run.cpp — take the argument checks and the speculation policy at its end).  Run-scoped resources: loop_support.hpp; the host algebra of the raw-basis forms: raw_basis.hpp.
+// two_pass_run.cpp, expo_two_pass_multi_run.cpp — take the argument checks, the default start vector and the speculation policy at
+// its end).  Run-scoped resources: loop_support.hpp; the host algebra of the raw-basis forms: raw_basis.hpp.
 #pragma once
 
 #include "engine.hpp"
@@ -16,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <random>
 #include <string>
 #include <variant>
 
@@ -1034,6 +1036,16 @@ template <typename T, typename Params> void check_run(ll_context* ctx, ll_operat
              "operator scalar type mismatch");
   LL_REQUIRE(P.matrix_size == op->n, "matrix_size differs from the operator dimension");
   LL_REQUIRE(P.max_iteration >= 1, "max_iteration must be >= 1");
+}
+
+// The default start vector (LL:70-104): std::random_device-seeded mt19937, uniform [-1,1]; complex: real part, then imaginary part
+template <typename T> void random_start(T* v, int64_t n) {
+  typedef typename scalar_traits<T>::real Real;
+  std::random_device dev;
+  std::mt19937 mt(dev());
+  std::uniform_real_distribution<Real> r((Real)-1, (Real)1);
+  Real* f = reinterpret_cast<Real*>(v);
+  for (int64_t i = 0; i < n * scalar_traits<T>::reals; ++i) f[i] = r(mt);
 }
 
 // The ll_run_stats fields both runs fill (n_passes, seconds_setup and seconds_finish are the eigen-solver's own).

@@ -2,45 +2,7 @@
 // EigenPairManager bookkeeping, on the loop machinery of lanczos_loop.hpp.
 #include "lanczos_loop.hpp"
 
-#include <random>
-
 namespace ll {
-namespace {
-
-template <typename T> void default_init(T* v, int64_t n);
-// LL:70-104: std::random_device-seeded mt19937, uniform [-1,1]; complex: both parts.
-template <> void default_init<double>(double* v, int64_t n) {
-  std::random_device dev;
-  std::mt19937 mt(dev());
-  std::uniform_real_distribution<double> r(-1.0, 1.0);
-  for (int64_t i = 0; i < n; ++i) v[i] = r(mt);
-}
-template <> void default_init<float>(float* v, int64_t n) {
-  std::random_device dev;
-  std::mt19937 mt(dev());
-  std::uniform_real_distribution<float> r(-1.0f, 1.0f);
-  for (int64_t i = 0; i < n; ++i) v[i] = r(mt);
-}
-template <> void default_init<cf>(cf* v, int64_t n) {
-  std::random_device dev;
-  std::mt19937 mt(dev());
-  std::uniform_real_distribution<float> r(-1.0f, 1.0f);
-  for (int64_t i = 0; i < n; ++i) {
-    v[i].re = r(mt);
-    v[i].im = r(mt);
-  }
-}
-template <> void default_init<zc>(zc* v, int64_t n) {
-  std::random_device dev;
-  std::mt19937 mt(dev());
-  std::uniform_real_distribution<double> r(-1.0, 1.0);
-  for (int64_t i = 0; i < n; ++i) {
-    v[i].re = r(mt);
-    v[i].im = r(mt);
-  }
-}
-
-}  // namespace
 
 // ================================================================= LambdaLanczos<T>::run
 template <typename T>
@@ -118,7 +80,7 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
       LL_HIP(hipMemcpyAsync(U.vec(0), P.init_vector_dev, (size_t)nl * sizeof(T), hipMemcpyDeviceToDevice, s));
     } else {
       if (P.init_vector) P.init_vector(stage, nl, op->row_begin, P.init_user);
-      else default_init<T>(stage, nl);
+      else random_start<T>(stage, nl);
       LL_HIP(hipMemcpyAsync(U.vec(0), stage, (size_t)nl * sizeof(T), hipMemcpyHostToDevice, s));
     }
     const int64_t L = spec ? spec->n_orth : (int64_t)kept.size();

@@ -631,6 +631,16 @@ template <typename F> void for_storage_type(const ll_operator& op, F&& f) {
   else if (wide) f(double{});
   else f(float{});
 }
+// f(T{}) with T = the storage type a character names (the untyped primitives of capi.cpp)
+template <typename F> void for_storage_char(int storage, F&& f) {
+  switch (storage) {
+    case 'd': f(double{}); break;
+    case 'z': f(zc{}); break;
+    case 's': f(float{}); break;
+    case 'c': f(cf{}); break;
+    default: LL_REQUIRE(false, "storage must be one of 'd', 'z', 's', 'c'");
+  }
+}
 const char* operator_kind_name(int kind);  // "a CSR operator", ...: what a refusal calls an operator (operators.cpp)
 
 // ---------------------------------------------------------------- operator construction (operators.cpp, pauli_operators.cpp)
@@ -980,8 +990,8 @@ int launch_scale_publish(int64_t n, T* v, const double* partials, int nparts, do
 // Plain three-term update with host scalars (primitive API).
 template <typename T>
 void launch_three_term(int64_t n, T* w, const T* u_prev, const T* u_cur, double beta, double alpha, hipStream_t s);
-// The two-pass recurrence without a stored basis (recur.hip; two_pass_run.cpp).  rec: one record of kRecurRec doubles per
-// iteration k on the device — alpha_k, a_k, b_k, c_k = ||r_k||^2.
+// The two-pass recurrence without a stored basis (recur.hip; recurrence.hpp and its two drivers).  rec: one record of kRecurRec
+// doubles per iteration k on the device — alpha_k, a_k, b_k, c_k = ||r_k||^2.
 constexpr int kRecurRec = 4;
 // pass 1: y <- y - a x - b p (p nullable) with alpha folded from the operator kernel's partials, a = alpha / sqrt(c_k),
 // b = sqrt(c_k / c_{k-1}) (normalised: x and p were scaled to unit norm in place: a = alpha, b = sqrt(c_k)); (alpha, a, b) ->
@@ -991,27 +1001,30 @@ int launch_recur_step(int64_t n, T* y, const T* x, const T* p, const double* alp
                       int64_t k, bool normalised, double* partials, hipStream_t s);
 // ... folded by one workgroup: rec[k + 1].c = sum; host_mapped[0..4) = {alpha_k, sum, 0, sum}
 void launch_recur_fold(const double* partials, int nparts, double* rec, int64_t k, double* host_mapped, hipStream_t s);
+// The coefficient of pass 2's accumulate: a double on real vectors (the Ritz vector's s_k, a real exp(a T_m) e_1), zc on complex
+// ones.  of(): from the host scalar.
+template <typename T> struct RecurCoeff {
+  typedef double type;
+  static double of(double g) { return g; }
+};
+template <> struct RecurCoeff<zc> {
+  typedef zc type;
+  static zc of(std::complex<double> g) { return zc{g.real(), g.imag()}; }
+};
+template <> struct RecurCoeff<cf> : RecurCoeff<zc> {};
 // pass 2: the same update with (a, b) read from rec[k] (rec == nullptr: the values a, b), then psi += g y with g = gvec[k + 1]
 // (gvec == nullptr: the value g).  alpha_partials (nullable, needs rec): workgroup 0 folds them and adds 1 to *mismatches
-// when the sum differs as bits from rec[k].alpha.
-template <typename T>
-void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const double* gvec, int64_t k,
-                        double a, double b, double g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
-                        hipStream_t s);
-// ... with a complex g (T = zc, cf only): gvec holds (re, im) pairs, g is rounded to T and the product g y is the complex one.  The
-// update of y is the same code, so a replay with either coefficient type reproduces pass 1's vectors.
-template <typename T>
-void launch_recur_accum_cplx(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const zc* gvec, int64_t k,
-                             double a, double b, zc g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
-                             hipStream_t s);
+// when the sum differs as bits from rec[k].alpha.  G = double (every T), or zc (T = zc, cf only): gvec then holds (re, im) pairs, g
+// is rounded to T and the product g y is the complex one.  The update of y is the same code, so a replay with either coefficient
+// type reproduces pass 1's vectors.
+template <typename T, typename G>
+void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const G* gvec, int64_t k, double a,
+                        double b, G g, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s);
 // ... for up to kRecurMultiMax accumulators in one sweep (the multi-time Exponentiator): y is updated once, then psi[j] += g_j y for
 // j < count with the coefficient type of the storage type (double on d / s, zc on z / c) and g_j = gtab[row[j] * ldg + k + 1]
 // (gtab == nullptr: g[j]).  The argument struct travels by value; the host compacts the active accumulators into it per launch.
 constexpr int kRecurMultiMax = 16;
 constexpr int kRecurMultiBatch = 2;  // accumulators loaded before the first is stored: 1, 2 or 4 (recur.hip)
-template <typename T> struct RecurCoeff { typedef double type; };
-template <> struct RecurCoeff<zc> { typedef zc type; };
-template <> struct RecurCoeff<cf> { typedef zc type; };
 template <typename T, typename G> struct RecurMultiArgs {
   T* psi[kRecurMultiMax];
   G g[kRecurMultiMax];
@@ -1022,10 +1035,8 @@ template <typename T>
 void launch_recur_accum_multi(int64_t n, T* y, const T* x, const T* p, const RecurMultiArgs<T, typename RecurCoeff<T>::type>& acc,
                               const double* rec, const typename RecurCoeff<T>::type* gtab, int64_t ldg, int64_t k, double a,
                               double b, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s);
-// psi = g x, out of place, with the product of the accumulate above: the first term of pass 2's sum (real g: T = double, float;
-// complex g: T = zc, cf)
-template <typename T> void launch_recur_seed(int64_t n, T* psi, const T* x, double g, hipStream_t s);
-template <typename T> void launch_recur_seed_cplx(int64_t n, T* psi, const T* x, zc g, hipStream_t s);
+// psi = g x, out of place, with the product of the accumulate above: the first term of pass 2's sum (G = RecurCoeff<T>::type)
+template <typename T, typename G> void launch_recur_seed(int64_t n, T* psi, const T* x, G g, hipStream_t s);
 // partials of <a,b> (reals per workgroup). Returns grid.
 template <typename T> int launch_dot(int64_t n, const T* a, const T* b, double* partials, hipStream_t s);
 // out_r = sum_{k=m-1..0} coeff[r*m+k] * u_k, r < nout; coeff on device, type acc_t<T>; the sums are carried in acc_t<T> and

@@ -1,4 +1,4 @@
-// The two-pass Lanczos recurrence without a stored basis (two_pass_run.cpp, expo_two_pass_run.cpp): the plain
+// The two-pass Lanczos recurrence without a stored basis (two_pass_run.cpp, expo_two_pass_multi_run.cpp): the plain
 // three-term update on UNNORMALISED vectors, once with its coefficient record and norm (pass 1) and once replayed from the record
 // while the result — the Ritz vector, or exp(a A) v — is accumulated (pass 2).  Streaming strip kernels in the geometry of
 // kernels.hip (strip<T>, 16 KiB strips, balanced persistent grid); both passes go through ONE element update (recur_update), so
@@ -251,31 +251,13 @@ void launch_recur_fold(const double* partials, int nparts, double* rec, int64_t 
   hipLaunchKernelGGL(recur_fold_kernel, dim3(1), dim3(kBlock), 0, s, partials, nparts, rec, k, host_mapped);
   LL_HIP(hipGetLastError());
 }
-namespace {
 template <typename T, typename G>
-void launch_recur_accum_g(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const G* gvec, int64_t k, double a,
-                          double b, G g, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s) {
+void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const G* gvec, int64_t k, double a,
+                        double b, G g, const double* alpha_partials, int alpha_nparts, long long* mismatches, hipStream_t s) {
+  static_assert(std::is_same<G, double>::value || scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
   hipLaunchKernelGGL((recur_accum_kernel<T, G>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, y, x, p, psi, rec,
                      gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches);
   LL_HIP(hipGetLastError());
-}
-template <typename T, typename G> void launch_recur_seed_g(int64_t n, T* psi, const T* x, G g, hipStream_t s) {
-  hipLaunchKernelGGL((recur_seed_kernel<T, G>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, psi, x, g);
-  LL_HIP(hipGetLastError());
-}
-}  // namespace
-template <typename T>
-void launch_recur_accum(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const double* gvec, int64_t k,
-                        double a, double b, double g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
-                        hipStream_t s) {
-  launch_recur_accum_g<T, double>(n, y, x, p, psi, rec, gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches, s);
-}
-template <typename T>
-void launch_recur_accum_cplx(int64_t n, T* y, const T* x, const T* p, T* psi, const double* rec, const zc* gvec, int64_t k,
-                             double a, double b, zc g, const double* alpha_partials, int alpha_nparts, long long* mismatches,
-                             hipStream_t s) {
-  static_assert(scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
-  launch_recur_accum_g<T, zc>(n, y, x, p, psi, rec, gvec, k, a, b, g, alpha_partials, alpha_nparts, mismatches, s);
 }
 template <typename T>
 void launch_recur_accum_multi(int64_t n, T* y, const T* x, const T* p, const RecurMultiArgs<T, typename RecurCoeff<T>::type>& acc,
@@ -286,33 +268,33 @@ void launch_recur_accum_multi(int64_t n, T* y, const T* x, const T* p, const Rec
                      y, x, p, acc, rec, gtab, ldg, k, a, b, alpha_partials, alpha_nparts, mismatches);
   LL_HIP(hipGetLastError());
 }
-template <typename T> void launch_recur_seed(int64_t n, T* psi, const T* x, double g, hipStream_t s) {
-  launch_recur_seed_g<T, double>(n, psi, x, g, s);
-}
-template <typename T> void launch_recur_seed_cplx(int64_t n, T* psi, const T* x, zc g, hipStream_t s) {
-  static_assert(scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
-  launch_recur_seed_g<T, zc>(n, psi, x, g, s);
+template <typename T, typename G> void launch_recur_seed(int64_t n, T* psi, const T* x, G g, hipStream_t s) {
+  static_assert(std::is_same<G, double>::value || scalar_traits<T>::is_complex, "a complex coefficient needs complex vectors");
+  hipLaunchKernelGGL((recur_seed_kernel<T, G>), dim3(strip_grid(n, strip<T>::ELEMS)), dim3(kBlock), 0, s, n, psi, x, g);
+  LL_HIP(hipGetLastError());
 }
 
+// accumulate: a real coefficient on every storage type (the eigen-solver's Ritz vector; the primitive ll_recur_accum_*), a complex
+// one on the complex types; seed: the Exponentiator's coefficient type only (RecurCoeff<T>)
+#define LL_INST_RECUR_ACCUM(T, G)                                                                                                \
+  template void launch_recur_accum<T, G>(int64_t, T*, const T*, const T*, T*, const double*, const G*, int64_t, double, double, \
+                                         G, const double*, int, long long*, hipStream_t);
+#define LL_INST_RECUR_SEED(T, G) template void launch_recur_seed<T, G>(int64_t, T*, const T*, G, hipStream_t);
 #define LL_INST_RECUR(T)                                                                                                       \
   template int launch_recur_step<T>(int64_t, T*, const T*, const T*, const double*, int, double*, int64_t, bool, double*,      \
                                     hipStream_t);                                                                              \
-  template void launch_recur_accum<T>(int64_t, T*, const T*, const T*, T*, const double*, const double*, int64_t, double,      \
-                                      double, double, const double*, int, long long*, hipStream_t);
+  LL_INST_RECUR_ACCUM(T, double)
 LL_FOR_EACH_SCALAR(LL_INST_RECUR)
 #define LL_INST_RECUR_MULTI(T)                                                                                                   \
   template void launch_recur_accum_multi<T>(int64_t, T*, const T*, const T*, const RecurMultiArgs<T, RecurCoeff<T>::type>&,      \
                                             const double*, const RecurCoeff<T>::type*, int64_t, int64_t, double, double,         \
                                             const double*, int, long long*, hipStream_t);
 LL_FOR_EACH_SCALAR(LL_INST_RECUR_MULTI)
-// the Exponentiator's coefficients: real on real vectors, complex on complex ones
-template void launch_recur_seed<double>(int64_t, double*, const double*, double, hipStream_t);
-template void launch_recur_seed<float>(int64_t, float*, const float*, double, hipStream_t);
-#define LL_INST_RECUR_CPLX(T)                                                                                                  \
-  template void launch_recur_accum_cplx<T>(int64_t, T*, const T*, const T*, T*, const double*, const zc*, int64_t, double,     \
-                                           double, zc, const double*, int, long long*, hipStream_t);                           \
-  template void launch_recur_seed_cplx<T>(int64_t, T*, const T*, zc, hipStream_t);
-LL_INST_RECUR_CPLX(zc)
-LL_INST_RECUR_CPLX(cf)
+LL_INST_RECUR_SEED(double, double)
+LL_INST_RECUR_SEED(float, double)
+LL_INST_RECUR_ACCUM(zc, zc)
+LL_INST_RECUR_SEED(zc, zc)
+LL_INST_RECUR_ACCUM(cf, zc)
+LL_INST_RECUR_SEED(cf, zc)
 
 }  // namespace ll

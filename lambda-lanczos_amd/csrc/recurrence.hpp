@@ -1,10 +1,14 @@
 // The plain three-term recurrence on three rotating, UNNORMALISED vectors that both basis-free drivers run:
-// two_pass_run.cpp (the extreme eigenpair) and expo_two_pass_run.cpp (exp(a A) v).  Here: the buffers and the operator call of one
-// iteration (Recurrence), and the host side of pass 1 (recur_pass1: enqueue, collect the scalars, hand T_k to the tracker's worker).
-// What differs between the two drivers is the tracker (RitzTracker / ExpoTracker) and what pass 2 accumulates.  Kernels: recur.hip.
+// two_pass_run.cpp (the extreme eigenpair) and expo_two_pass_multi_run.cpp (exp(a_j A) v).  Here: the buffers and the operator call
+// of one iteration (Recurrence), the host side of pass 1 (recur_pass1: enqueue, collect the scalars, hand T_k to the tracker's
+// worker), and the run both drivers are written on (TwoPass: set-up, c_0, pass 1, the replay loop, host outputs, statistics).
+// What differs between the two drivers is the tracker (RitzTracker / ExpoMultiTracker), where r_0 comes from and what pass 2
+// accumulates.  Kernels: recur.hip.
 #pragma once
 
 #include "lanczos_loop.hpp"
+
+#include <optional>
 
 namespace ll {
 
@@ -110,5 +114,107 @@ void recur_pass1(Recurrence<T>& rc, StepWorker<Tracker>& worker, EventRing& ring
   typename Tracker::Out r;
   while (!stopped && worker.wait_pop(r)) stopped = absorb(r);  // the first stop verdict wins; else the last iteration's values
 }
+
+// One run of the two passes: what every basis-free driver owns, and the steps they share, in the order they take them.
+//   TwoPass tp(ctx, op, offset);  tp.own_vector(b) per output kept in a workspace vector;  tp.prepare(max_iteration);
+//   r_0 -> tp.rc.vec(0);  tp.start(t0, noun);  last = tp.pass1(tracker, max_iteration);
+//   tp.replay(g, gdev, seed, step);  tp.read_mismatches();  tp.to_host(dst, src) per host output;  sync;  tp.finish(stats)
+template <typename T> struct TwoPass {
+  ll_context* const ctx;
+  ll_operator* const op;
+  const double t_start;
+  const hipStream_t s;
+  const int64_t nl, ld;
+  const size_t vbytes;
+  Engine<T> E;
+  Recurrence<T> rc;
+  std::optional<EventRing> ring;
+  std::vector<double> alpha, beta, csq;  // of pass 1; csq[k] = c_k = ||r_k||^2
+  RecurPassTimes pt;                     // (a driver adds its own host steps to pt.tridiag)
+  double t_setup = 0.0, t_fin0 = 0.0;
+  int64_t m = 0;  // iterations kept
+  int64_t workspace_vectors = 3;
+  DevBuf<long long> mism;
+  long long mismatches = 0;
+
+  static double begin(ll_context* ctx) {
+    LL_HIP(hipSetDevice(ctx->device));
+    return now_s();
+  }
+  TwoPass(ll_context* ctx_, ll_operator* op_, double offset)
+      : ctx(ctx_), op(op_), t_start(begin(ctx_)), s(ctx_->stream), nl(op_->n_local),
+        ld(round_up(std::max<int64_t>(std::max(nl, op_->n_shard), 1), 256)), vbytes((size_t)nl * sizeof(T)), E(ctx_, op_, nl),
+        rc{E, s, nl, offset, E.can_scale_input(), {}, {}, 0} {
+    for (auto& b : rc.buf) b.alloc(ctx, (size_t)ld);
+  }
+  void own_vector(DevBuf<T>& b) {
+    b.alloc(ctx, (size_t)ld);
+    ++workspace_vectors;
+  }
+  void prepare(int64_t max_iteration) {
+    ctx->ensure_pinned(kPinnedScalars);
+    ctx->ensure_partials((size_t)kMaxGrid * Engine<T>::R);
+    ctx->ensure_h(4);
+    ring.emplace();
+    rc.ensure_rec(std::min<int64_t>(max_iteration, 4095));
+  }
+  // r_0 is in rc.vec(0): c_0 = ||r_0||^2 to the record and the host; t0: when the driver began to bring r_0 there
+  void start(double t0, const char* refusal) {
+    E.norm2_dev(rc.vec(0), rc.c(0));
+    csq.resize(1);
+    E.fetch(rc.c(0), csq.data(), 1);
+    LL_REQUIRE(csq[0] > 0.0 && std::isfinite(csq[0]), refusal);
+    t_setup = now_s() - t0;
+  }
+  template <typename Tracker> typename Tracker::Out pass1(const Tracker& cfg, int64_t max_iteration) {
+    typename Tracker::Out last;
+    {
+      StepWorker<Tracker> worker(cfg, threaded_verdicts(ctx, op), ctx->tune.tridiag_test_jitter_us);
+      recur_pass1(rc, worker, *ring, max_iteration, alpha, beta, csq, last, pt);
+    }
+    m = last.m;  // iterations the device ran ahead of the verdict are dropped
+    LL_HIP(hipStreamSynchronize(s));
+    t_fin0 = now_s();
+    return last;
+  }
+  // Pass 2: the coefficient table to the device; seed() brings r_0 back to rc.vec(0) and enqueues the first term of the sum; then
+  // m - 1 replayed iterations, each the operator and step(k, y = r_{k+1}, x = r_k, p = r_{k-1} or nullptr, da, mism), which
+  // launches the update with its accumulate
+  template <typename G, typename Seed, typename Step> void replay(const std::vector<G>& g, DevBuf<G>& gdev, Seed&& seed, Step&& step) {
+    gdev.alloc(ctx, g.size());
+    mism.alloc(ctx, 2);
+    LL_HIP(hipMemcpyAsync(gdev.p, g.data(), g.size() * sizeof(G), hipMemcpyHostToDevice, s));
+    LL_HIP(hipMemsetAsync(mism.p, 0, 2 * sizeof(long long), s));
+    seed();
+    for (int64_t k = 0; k + 1 < m; ++k) {
+      const typename Engine<T>::DeferredAlpha da = rc.operate(k);
+      step(k, rc.vec(k + 1), rc.vec(k), k > 0 ? rc.vec(k + 2) : nullptr, da, mism.p);
+    }
+  }
+  void read_mismatches() { LL_HIP(hipMemcpyAsync(&mismatches, mism.p, sizeof(long long), hipMemcpyDeviceToHost, s)); }
+  void to_host(T* dst, const T* src) {
+    T* const stage = (T*)ctx->ensure_stage(std::max<size_t>(vbytes, sizeof(T)));
+    LL_HIP(hipMemcpyAsync(stage, src, vbytes, hipMemcpyDeviceToHost, s));
+    LL_HIP(hipStreamSynchronize(s));
+    host_copy(dst, stage, vbytes);
+  }
+  void finish(ll_run_stats* stats) {
+    if (stats) {
+      std::memset(stats, 0, sizeof(*stats));
+      stats->n_passes = 1;
+      stats->total_iterations = m;
+      stats->last_alpha_len = m;
+      stats->seconds_host_tridiag = pt.tridiag;
+      stats->seconds_host_enqueue = pt.enqueue;
+      stats->seconds_host_wait = pt.wait;
+      stats->seconds_setup = t_setup;
+      stats->seconds_finish = now_s() - t_fin0;
+      stats->workspace_vectors = workspace_vectors;
+      stats->replay_mismatches = (int64_t)mismatches;
+      stats->seconds_total = now_s() - t_start;
+    }
+    ctx->drain_comm_events(nullptr, nullptr);
+  }
+};
 
 }  // namespace ll

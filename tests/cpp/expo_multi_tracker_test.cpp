@@ -5,7 +5,10 @@
 //   where it never stops); `stop` is false before max_j m_j and true at it;
 //   breakdown (beta = 0 at m = 3) ends every time there: all m_j = 3;
 //   a max_iteration cut (prefixes end before the last time has fired) gives the unfrozen times that m and that coefficient vector;
-//   through StepWorker, threaded and unthreaded, consumed the way recur_pass1 does, the last verdict is the inline one.
+//   through StepWorker, threaded and unthreaded, consumed the way recur_pass1 does, the last verdict is the inline one;
+//   with ONE time the multi tracker IS the single one (ll_expo_two_pass runs on it): at every prefix up to and including the stop,
+//   m, stop and the coefficient bytes are the ExpoTracker's, inline and through StepWorker, for a run that stops by overlap, one
+//   that breaks down at m = 1 and one cut by the prefixes ending.
 // A clean run prints "<checks> checks, 0 failures".
 #include <cmath>
 #include <complex>
@@ -57,7 +60,7 @@ template <typename H> struct Single {
   bool stopped = false;
   std::vector<H> coeff;
 };
-// what expo_two_pass_run keeps of an ExpoTracker fed the prefixes 1 .. K: the first stop verdict, else the last one
+// what a single-time run keeps of an ExpoTracker fed the prefixes 1 .. K: the first stop verdict, else the last one
 template <typename H>
 Single<H> run_single(H a, double eps, double tol, const std::vector<double>& A, const std::vector<double>& B, int64_t K) {
   ll::ExpoTracker<H> t;
@@ -117,18 +120,18 @@ typename ll::ExpoMultiTracker<H>::Out compare(const char* what, const std::vecto
   return last;
 }
 
-// the consumption of recur_pass1 (recurrence.hpp): submit prefix `col`, absorb whatever is there, the first stop verdict wins
-template <typename H>
-typename ll::ExpoMultiTracker<H>::Out through_worker(const ll::ExpoMultiTracker<H>& cfg, bool threaded, const std::vector<double>& A,
-                                                     const std::vector<double>& B, int64_t K) {
-  typedef ll::ExpoMultiTracker<H> Tracker;
+// the consumption of recur_pass1 (recurrence.hpp): submit prefix `col`, absorb whatever is there, the first stop verdict wins.
+// Returns every verdict absorbed, in order: the prefixes 1 .. stop (or 1 .. K)
+template <typename Tracker>
+std::vector<typename Tracker::Out> worker_verdicts(const Tracker& cfg, bool threaded, const std::vector<double>& A,
+                                                   const std::vector<double>& B, int64_t K) {
   ll::StepWorker<Tracker> worker(cfg, threaded);
-  typename Tracker::Out last;
+  std::vector<typename Tracker::Out> seen;
   std::vector<double> alpha, beta;
   bool stopped = false;
   auto absorb = [&](typename Tracker::Out& o) {
-    last = std::move(o);
-    return last.stop;
+    seen.push_back(std::move(o));
+    return seen.back().stop;
   };
   for (int64_t col = 0; !stopped && col < K;) {
     alpha.push_back(A[(size_t)col]);
@@ -139,13 +142,63 @@ typename ll::ExpoMultiTracker<H>::Out through_worker(const ll::ExpoMultiTracker<
   }
   typename Tracker::Out r;
   while (!stopped && worker.wait_pop(r)) stopped = absorb(r);
-  return last;
+  return seen;
+}
+template <typename H>
+typename ll::ExpoMultiTracker<H>::Out through_worker(const ll::ExpoMultiTracker<H>& cfg, bool threaded, const std::vector<double>& A,
+                                                     const std::vector<double>& B, int64_t K) {
+  return worker_verdicts(cfg, threaded, A, B, K).back();
 }
 
 template <typename H>
 void same_verdict(const typename ll::ExpoMultiTracker<H>::Out& x, const typename ll::ExpoMultiTracker<H>::Out& y) {
   CHECK(x.m == y.m && x.stop == y.stop && x.mj == y.mj && x.coeff.size() == y.coeff.size());
   for (size_t j = 0; j < x.coeff.size() && j < y.coeff.size(); ++j) CHECK(same_bytes(x.coeff[j], y.coeff[j]));
+}
+
+// ---- one time: the multi tracker's verdict against the single tracker's for the same prefix
+template <typename H> void same_as_single(const typename ll::ExpoTracker<H>::Out& s, const typename ll::ExpoMultiTracker<H>::Out& t) {
+  CHECK(t.m == s.m);
+  CHECK(t.stop == s.stop);
+  CHECK(t.mj.size() == 1 && t.mj[0] == s.m);
+  CHECK(t.coeff.size() == 1 && same_bytes(t.coeff[0], s.coeff));
+}
+// both trackers over the prefixes 1 .. K; the run must end at want_m, by a stop verdict or (want_stop == false) by the prefixes ending
+template <typename H>
+void one_time(const char* what, H a, double eps, double tol, const std::vector<double>& A, const std::vector<double>& B, int64_t K,
+              int64_t want_m, bool want_stop) {
+  ll::ExpoTracker<H> single;
+  single.a = a;
+  single.eps = eps;
+  single.breakdown_tol = tol;
+  const ll::ExpoMultiTracker<H> multi = config<H>({a}, eps, tol);
+  {
+    ll::ExpoTracker<H> s = single;
+    ll::ExpoMultiTracker<H> t = multi;
+    int64_t last_m = 0;
+    bool stopped = false;
+    for (int64_t m = 1; m <= K && !stopped; ++m) {
+      const typename ll::ExpoTracker<H>::Out os = s.step(m, A.data(), B.data());
+      same_as_single<H>(os, t.step(m, A.data(), B.data()));
+      CHECK(os.m == m);
+      last_m = m;
+      stopped = os.stop;
+    }
+    CHECK(last_m == want_m);
+    CHECK(stopped == want_stop);
+    std::printf("%s, one time: m = %lld%s\n", what, (long long)last_m, stopped ? "" : ", never stopped");
+  }
+  for (bool threaded : {false, true}) {
+    const std::vector<typename ll::ExpoTracker<H>::Out> vs = worker_verdicts(single, threaded, A, B, K);
+    const std::vector<typename ll::ExpoMultiTracker<H>::Out> vt = worker_verdicts(multi, threaded, A, B, K);
+    CHECK((int64_t)vs.size() == want_m);
+    CHECK(vt.size() == vs.size());
+    for (size_t i = 0; i < vs.size() && i < vt.size(); ++i) {
+      CHECK(vs[i].m == (int64_t)i + 1);
+      CHECK(vs[i].stop == (want_stop && (int64_t)i + 1 == want_m));
+      same_as_single<H>(vs[i], vt[i]);
+    }
+  }
 }
 }  // namespace
 
@@ -193,6 +246,16 @@ int main() {
     const ll::ExpoMultiTracker<Z>::Out again = t.step(full.m + 1, A.data(), B.data());
     CHECK(again.stop && again.mj == full.mj);
     for (size_t j = 0; j < again.coeff.size(); ++j) CHECK(same_bytes(again.coeff[j], full.coeff[j]));
+  }
+  // ---- one time: ExpoMultiTracker against ExpoTracker at every prefix, with the three ways a run ends
+  {
+    const std::vector<double> a1 = {1.0, 2.0, 3.0}, b1 = {0.0, 0.7, 0.9};  // r_1 = 0: breakdown at m = 1
+    one_time<Z>("complex, overlap", Z(0, -2.0), eps, tol, A, B, K, full.mj[0], true);
+    one_time<Z>("complex, breakdown", Z(0, -2.0), eps, tol, a1, b1, 3, 1, true);
+    one_time<Z>("complex, cut", Z(0, -6.0), eps, tol, A, B, cut, cut, false);
+    one_time<double>("real, overlap", 0.0, eps, tol, A, B, K, 2, true);  // exp(0 T) e_1 = e_1 at every m: the test fires at m = 2
+    one_time<double>("real, breakdown", -0.5, eps, tol, a1, b1, 3, 1, true);
+    one_time<double>("real, cut", -0.5, eps, tol, A, B, 40, 40, false);
   }
   std::printf("%d checks, %d failures\n", checks, failures);
   return failures == 0 ? 0 : 1;

@@ -1,4 +1,4 @@
-"""The Exponentiator without a stored Krylov basis (ll_expo_two_pass, csrc/expo_two_pass_run.cpp, csrc/recur.hip): the replayed step
+"""The Exponentiator without a stored Krylov basis (ll_expo_two_pass, csrc/expo_two_pass_multi_run.cpp, csrc/recur.hip): the replayed step
 with a complex coefficient against exact arithmetic, the solver against the oracle's plain recurrence (EX:87-173 with
 full_orthogonalize = false) and against this library's stored-basis run, the buffer conventions and the constant work-space, the
 edges, and the refusals."""
