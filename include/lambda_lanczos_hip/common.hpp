@@ -16,6 +16,7 @@
 
 #include "../lanczos_hip.h"
 #include "entropy.hpp"  // von_neumann_entropy of a reduced density matrix (host only)
+#include "spectral.hpp"  // continued_fraction, spectral_function of the coefficients of a Lanczos run (host only)
 #include "util.hpp"  // lambda_lanczos::util::{real_t, inner_prod, norm, normalize, schmidt_orth, m_norm, sort_eigenpairs, ...}
 
 namespace lambda_lanczos_hip {
@@ -403,6 +404,23 @@ template <typename T> class PauliRingBlockOperator : public PauliFamilyOperator<
     std::vector<T> c((size_t)this->local_rows());
     project(target, psi.data(), c.data());
     return c;
+  }
+
+  // out = B_t^H (sum of `terms`) B c: the strings applied to the state c of this block, taken on the momentum block `target` of the
+  // same kind, n_sites and n_down, without a vector of the full space (ll_pauli_block_transfer) — the strings need not commute
+  // with the translation, the target selects their component of momentum m_t - m.  c holds local_rows() values, out
+  // target.local_rows(); norm2 (nullable): sum |out|^2 as the kernel sums it.  For PauliMomentumOperator and
+  // PauliMomentumFullOperator; the library refuses a PauliSymmetricOperator (that needs semi-momentum states).
+  void transfer(const PauliRingBlockOperator<T>& target, const std::vector<PauliTerm>& terms, const T* c, T* out,
+                double* norm2 = nullptr) const {
+    check(ll_pauli_block_transfer(this->context().get(), this->get(), target.get(), (int64_t)terms.size(), terms.data(), c, out, norm2));
+  }
+  std::vector<T> transfer(const PauliRingBlockOperator<T>& target, const std::vector<PauliTerm>& terms, const std::vector<T>& c,
+                          double* norm2 = nullptr) const {
+    if ((int64_t)c.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "transfer: c must hold local_rows() values");
+    std::vector<T> out((size_t)target.local_rows());
+    transfer(target, terms, c.data(), out.data(), norm2);
+    return out;
   }
 
   // rho_A of Psi = B c: c is expanded into a device buffer of the context, measured by the target's reduced_density_matrix

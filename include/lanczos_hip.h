@@ -74,7 +74,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_pauli_expect_block (expectation values of
                              *    Pauli strings on a state of a symmetry block (8) - (10)): untyped, the storage type is the operator's;
                              *    also additive under minor 5, with the same note — ll_pauli_block_expand and ll_pauli_block_project
-                             *    (a state between a symmetry block (8) - (10) and the basis of (6) or (7)): untyped */
+                             *    (a state between a symmetry block (8) - (10) and the basis of (6) or (7)): untyped;
+                             *    also additive under minor 5, with the same note — ll_pauli_block_transfer (a sum of Pauli strings
+                             *    applied between two momentum blocks (8) or (9)): untyped */
 
 enum {
   LL_OK = 0,
@@ -566,6 +568,37 @@ int ll_pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs,
  * per workgroup block, default 10) and pauli_block_project_block_bits (2^b representatives, default 8). */
 int ll_pauli_block_expand(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* c, void* psi_out);
 int ll_pauli_block_project(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* psi, void* c_out);
+
+/* A SUM OF PAULI STRINGS BETWEEN TWO MOMENTUM BLOCKS OF A RING (an addition within minor 5, untyped: the storage type is the
+ * operators').  With B_s, B_t the isometries of two block operators of (8), or of (9) (see ll_pauli_block_expand),
+ *     out = B_t^H (sum_j coef_j P_j) B_s c
+ * without a vector of the full space: phi = O psi for an operator O that carries momentum q = m_t - m_s (mod n_sites) — the
+ * start of a dynamical correlation function (ll_lanczos_two_pass_* with eigvec = NULL, init_vector_dev = phi, eps = 0 and
+ * max_iteration = M returns the M-step tridiagonal of (H_target, phi); lambda_lanczos_hip/spectral.hpp holds the continued
+ * fraction) and, by its norm, a static structure factor.  THE STRINGS NEED NOT COMMUTE WITH THE TRANSLATION: projecting onto the
+ * target block selects their momentum-q component, Z_0 stands for (1 / n_sites) sum_r e^(-2 pi i q r / n_sites) Z_r.
+ *   source, target : both from ll_op_create_pauli_momentum_* (8) with equal n_sites and n_down, or both from
+ *            ll_op_create_pauli_momentum_full_* (9) with equal n_sites; same context and storage type; source == target is allowed
+ *            (q = 0).  Their Hamiltonians' terms play no part.
+ *   terms_host : n_terms strings (x_mask, z_mask, real coef), as at creation.  n_terms == 0: out is exactly +0.0, nothing is
+ *            launched.  In a sector (8) a string with an odd popcount(x_mask) contributes nothing (no partner stays in the sector).
+ *   c : source->n_local values, never modified;  out : target->n_local values, every element written.  Host or device memory,
+ *            decided per pointer; a host buffer is staged through one device vector.
+ *   norm2_out : nullable; sum |out|^2 of the rounded output in double, formed in the kernel's epilogue (one partial per workgroup,
+ *            folded in a fixed order).
+ * REFUSALS (LL_ERR_INVALID, each naming its cause, before the device is touched): a null argument; n_terms < 0; a context with a
+ * communicator; a block of (10) (a momentum-q operator does not commute with the reflection: that needs semi-momentum states);
+ * every other kind; mixed kinds; differing contexts, n_sites, n_down or storage types; a mask bit at or above n_sites or a
+ * coefficient that is not finite; a real storage type with a string of an odd number of Y; out overlapping c.
+ * ACCURACY: the host merges the images of the strings into weights (the phase e^(2 pi i q j / n_sites), exact on the axes, times
+ * coef / period: two roundings per component, and one per merged addition); the kernel forms per x mask the signed sum of the
+ * weights, times sqrt(R_a / R_b) where the lengths differ, times the source's phase where m_s != 0, one double fma per x mask in
+ * ascending mask order, one rounding to the storage type.  The same bits run to run, for host and device buffers and for every
+ * alignment; norm2_out depends on the block size and the grid alone.
+ * BYTES and TIMES: DESIGN.md 3.8.  Block sizes: the keys of the target's own apply (pauli_momentum_block_bits,
+ * pauli_momentum_full_block_bits). */
+int ll_pauli_block_transfer(ll_context* ctx, const ll_operator* source, const ll_operator* target, int64_t n_terms,
+                            const ll_pauli_term* terms_host, const void* c, void* out, double* norm2_out);
 
 /* REDUCED DENSITY MATRIX of up to six sites of a state of the basis of (6) or (7), in ONE sweep over the state (an addition
  * within minor 5, untyped: the storage type is the operator's).  The kernels read psi once and write 4^m numbers.

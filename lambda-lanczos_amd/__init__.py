@@ -30,7 +30,9 @@ from .engine import (  # noqa: F401
     PauliSymmetricOperator,
     StencilOperator,
     LambdaLanczos,
+    continued_fraction,
     default_context,
+    lanczos_coefficients,
     live_contexts,
     CONTEXT_CREATED_HOOKS,
     dot,
@@ -41,6 +43,7 @@ from .engine import (  # noqa: F401
     orth_block,
     pauli_block_expand,
     pauli_block_project,
+    pauli_block_transfer,
     pauli_expect,
     pauli_expect_block,
     pauli_rdm,
@@ -48,6 +51,7 @@ from .engine import (  # noqa: F401
     recur_accum,
     recur_accum_multi,
     scal,
+    spectral_function,
     spmv,
     three_term,
     tridiag_bisect,

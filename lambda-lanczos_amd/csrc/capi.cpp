@@ -542,6 +542,10 @@ int ll_pauli_block_expand(ll_context* ctx, const ll_operator* block, const ll_op
 int ll_pauli_block_project(ll_context* ctx, const ll_operator* block, const ll_operator* target, const void* psi, void* c_out) {
   return guarded([&] { pauli_block_embed(ctx, block, target, false, psi, c_out); });
 }
+int ll_pauli_block_transfer(ll_context* ctx, const ll_operator* source, const ll_operator* target, int64_t n_terms,
+                            const ll_pauli_term* terms_host, const void* c, void* out, double* norm2_out) {
+  return guarded([&] { pauli_block_transfer(ctx, source, target, n_terms, terms_host, c, out, norm2_out); });
+}
 int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi,
                  double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_rdm(ctx, op, n_sub, sites_host, psi, out_host, sweeps_out); });

@@ -694,7 +694,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_rdm.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_block_transfer.hip, pauli_rdm.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -822,6 +822,10 @@ void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, c
 // ll_pauli_block_expand / ll_pauli_block_project (pauli_block_embed.hip; planned by pauli_block_embed_plan.hpp): every check, then
 // Psi = B c (expand) or c = B^H Psi (project) on the operators' storage type
 void pauli_block_embed(ll_context* ctx, const ll_operator* block, const ll_operator* target, bool expand, const void* in, void* out);
+// ll_pauli_block_transfer (pauli_block_transfer.hip; planned by pauli_block_transfer_plan.hpp): every check, then
+// out = B_t^H (sum of the strings) B_s c on the operators' storage type
+void pauli_block_transfer(ll_context* ctx, const ll_operator* source, const ll_operator* target, int64_t n_terms,
+                          const ll_pauli_term* terms, const void* c, void* out, double* norm2_out);
 // ll_pauli_rdm (pauli_rdm.hip; planned by pauli_rdm_plan.hpp): every check, then the one sweep on the operator's storage type
 void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, double* out,
                int64_t* sweeps_out);

@@ -146,11 +146,6 @@ int launch_pauli_expect_block_op(const ll_operator& op, int count, const ExpectB
                                        op.pauli_block.dim, count, tb, pauli_symmetric_partner(op.pauli_block), x, partials, s);
   }
 }
-
-template <typename V> void expect_block_upload(ll_context* ctx, DevBuf<V>& dst, const std::vector<V>& src, hipStream_t s) {
-  dst.alloc(ctx, std::max<size_t>(src.size(), 1));
-  if (!src.empty()) LL_HIP(hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice, s));
-}
 }  // namespace
 
 template <typename T>
@@ -190,11 +185,11 @@ void pauli_expect_block_run(ll_context* ctx, const ll_operator* op, int64_t n_ob
   DevBuf<int32_t> dsg, dgptr;
   DevBuf<uint32_t> dgx, dtz;
   DevBuf<double> dtc;
-  expect_block_upload(ctx, dsg, sg, s);
-  expect_block_upload(ctx, dgptr, gptr, s);
-  expect_block_upload(ctx, dgx, gx, s);
-  expect_block_upload(ctx, dtz, tz, s);
-  expect_block_upload(ctx, dtc, tc, s);
+  stage_table(ctx, dsg, sg);
+  stage_table(ctx, dgptr, gptr);
+  stage_table(ctx, dgx, gx);
+  stage_table(ctx, dtz, tz);
+  stage_table(ctx, dtc, tc);
   const std::vector<double> sums = pauli_measure_sweeps(ctx, plan, (size_t)kMaxGrid * B, [&](int64_t k, double* partials) {
     const ExpectBlockTables tb{dsg.p + plan.batch_begin(k), dgx.p, dgptr.p, dtz.p, dtc.p};
     return launch_pauli_expect_block_op<T>(*op, (int)plan.batch_count(k), tb, x, partials, s);

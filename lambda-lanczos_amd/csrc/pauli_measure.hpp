@@ -1,5 +1,5 @@
 // The host side that the measuring entry points on the Pauli-sum operators share (pauli_expect.hip, pauli_expect_block.hip,
-// pauli_rdm.hip, pauli_block_embed.hip): the checks they begin with, a host vector staged on the device, the sweeps over the
+// pauli_rdm.hip, pauli_block_embed.hip, pauli_block_transfer.hip): the checks they begin with, a host vector staged on the device, the sweeps over the
 // batches of a plan with their fold, and one view of the three kinds of symmetry block.  The kernels, their launch wrappers and
 // the per-kind switches stay in the .hip files; the storage-type dispatch is for_storage_type (ll_internal.hpp).
 #pragma once
@@ -43,6 +43,12 @@ template <typename T> T* stage_out(ll_context* ctx, DevBuf<T>& staged, void* dst
 }
 template <typename T> void stage_out_finish(ll_context* ctx, const DevBuf<T>& staged, void* dst, int64_t n) {
   if (staged.p) LL_HIP(hipMemcpyAsync(dst, staged.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+}
+
+// A host table of a call on the device, enqueued on the stream (the caller keeps `src` until it has synchronised)
+template <typename V> void stage_table(ll_context* ctx, DevBuf<V>& dst, const std::vector<V>& src) {
+  dst.alloc(ctx, std::max<size_t>(src.size(), 1));
+  if (!src.empty()) LL_HIP(hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice, ctx->stream));
 }
 
 // One sweep per batch: launch(k, partials) enqueues batch k — bt.batch_count(k) columns of partials, one row per workgroup — and

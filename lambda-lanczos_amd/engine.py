@@ -465,20 +465,25 @@ def pauli_expect_block(op, psi, observables, return_sweeps=False):
     return _pauli_expect_call("ll_pauli_expect_block", op, psi, observables, return_sweeps)
 
 
-def _pauli_embed_call(entry, block, target, vec, n_in, n_out, out):
-    dtype = np.dtype(block.dtype)
-    keep, p = _vector_arg(vec, n_in, dtype, *_INPUT_ERRORS)
+def _out_arg(out, n_out, dtype):
+    """(out, void*) of an output of n_out values of `dtype`: None (a new numpy array), a contiguous writeable numpy array of
+    exactly that, or anything with .ptr, .dtype, .shape that names device memory of at least that (TypeError otherwise)."""
     if out is None:
         out = np.empty(n_out, dtype=dtype)
     if hasattr(out, "ptr"):
         if out.dtype != dtype or int(np.prod(out.shape)) < n_out:
             raise TypeError("out must hold %d values of the operators' dtype %s" % (n_out, dtype))
-        q = C.c_void_p(out.ptr)
-    else:
-        if not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size == n_out and out.flags.c_contiguous and
-                out.flags.writeable):
-            raise TypeError("out must be a contiguous writeable numpy array of %d values of dtype %s" % (n_out, dtype))
-        q = ptr(out)
+        return out, C.c_void_p(out.ptr)
+    if not (isinstance(out, np.ndarray) and out.dtype == dtype and out.size == n_out and out.flags.c_contiguous and
+            out.flags.writeable):
+        raise TypeError("out must be a contiguous writeable numpy array of %d values of dtype %s" % (n_out, dtype))
+    return out, ptr(out)
+
+
+def _pauli_embed_call(entry, block, target, vec, n_in, n_out, out):
+    dtype = np.dtype(block.dtype)
+    keep, p = _vector_arg(vec, n_in, dtype, *_INPUT_ERRORS)
+    out, q = _out_arg(out, n_out, dtype)
     check(getattr(lib(), entry)(block.ctx.handle, block.handle, target.handle, p, q))
     del keep
     return out
@@ -500,6 +505,67 @@ def pauli_block_project(block, psi, target, out=None):
     block; ||c||^2 is the weight of Psi in the block and pauli_block_project(block, pauli_block_expand(block, c, t), t) = c.
     Arguments as pauli_block_expand."""
     return _pauli_embed_call("ll_pauli_block_project", block, target, psi, target.n_local, block.n_local, out)
+
+
+def pauli_block_transfer(source, target, terms, c, out=None, return_norm2=False):
+    """ll_pauli_block_transfer: out = B_t^H (sum_j coef_j P_j) B_s c — a sum of Pauli strings (x_mask, z_mask, coef) applied to
+    the source.n_local coefficients c of a state of one momentum block, the result taken as the target.n_local coefficients on
+    another (both PauliMomentumOperator of one n_sites and n_down, or both PauliMomentumFullOperator of one n_sites; B =
+    generators.momentum_embedding / full_momentum_embedding), without a vector of the full space
+    (generators.pauli_block_transfer_np).  The strings need not commute with the translation: the target block selects their
+    component of momentum target.momentum - source.momentum.  c: a numpy array (converted to the operators' dtype) or a
+    DeviceArray (anything with .ptr, .dtype, .shape); out: None (a new numpy array), a numpy array or a DeviceArray of the
+    operators' dtype — returned filled; with return_norm2 also sum |out|^2 as the kernel sums it."""
+    dtype = np.dtype(source.dtype)
+    arr, n_terms = _term_array(terms)
+    keep, p = _vector_arg(c, source.n_local, dtype, *_INPUT_ERRORS)
+    out, q = _out_arg(out, target.n_local, dtype)
+    norm2 = C.c_double(0.0)
+    check(lib().ll_pauli_block_transfer(source.ctx.handle, source.handle, target.handle, n_terms, arr, p, q, C.byref(norm2)))
+    del keep
+    return (out, float(norm2.value)) if return_norm2 else out
+
+
+def lanczos_coefficients(op, start, m):
+    """(alpha, beta, iterations): the Lanczos tridiagonal of (op, start) after at most m steps without a stored basis — a thin
+    wrapper over LambdaLanczos.run_two_pass(want_vector=False) with eps = 0 (the stop test cannot fire; breakdown still ends
+    the run) and max_iteration = m.  start: a DeviceArray of op.n_local values of op.dtype, read and never modified; it need not
+    be normalised.  alpha and beta hold `iterations` entries each, indexed as ll_lanczos_two_pass_* writes them: beta[k] couples
+    alpha[k] and alpha[k + 1], and the last entry, beta[iterations - 1], is the norm of the residual that ended the run — not
+    an element of the tridiagonal (continued_fraction leaves it out)."""
+    if not isinstance(start, DeviceArray):
+        raise TypeError("start must be a DeviceArray of op.n_local values")
+    eng = LambdaLanczos(op, op.n, False, 1, dtype=op.dtype, context=op.ctx)
+    eng.init_vector = start
+    eng.eps = 0.0
+    eng.max_iteration = int(m)
+    _, _, info = eng.run_two_pass(want_vector=False)
+    return eng.last_alpha, eng.last_beta, info["iterations"]
+
+
+def continued_fraction(alpha, beta, z, norm2=1.0):
+    """norm2 / (z - alpha[0] - beta[0]^2 / (z - alpha[1] - beta[1]^2 / (... - alpha[m - 1]))) = norm2 e_1^T (z - T)^-1 e_1 for the
+    m x m tridiagonal T of a Lanczos run, vectorised over complex z and evaluated bottom-up (m divisions per z).  Indexing as
+    ll_lanczos_two_pass_* writes it (lanczos_coefficients): m = len(alpha), beta[k] couples alpha[k] and alpha[k + 1]; only
+    beta[0 .. m - 2] enter, so beta may hold m - 1 entries or m (the residual norm in the last one is not read)."""
+    alpha = np.asarray(alpha, dtype=np.float64).reshape(-1)
+    beta = np.asarray(beta, dtype=np.float64).reshape(-1)
+    m = alpha.shape[0]
+    if m < 1 or beta.shape[0] < m - 1:
+        raise ValueError("need at least one alpha and len(alpha) - 1 betas")
+    z = np.asarray(z, dtype=np.complex128)
+    d = z - alpha[m - 1]
+    for k in range(m - 2, -1, -1):
+        d = z - alpha[k] - (beta[k] * beta[k]) / d
+    return float(norm2) / d
+
+
+def spectral_function(alpha, beta, omega, eta, e0=0.0, norm2=1.0):
+    """-Im G(omega + e0 + i eta) / pi with G = continued_fraction(alpha, beta, ., norm2): the spectral function of the start
+    vector of the Lanczos run, Lorentz-broadened by eta > 0, on the real frequencies omega measured from e0 (the ground-state
+    energy).  It integrates to norm2 over omega."""
+    z = np.asarray(omega, dtype=np.float64) + float(e0) + 1j * float(eta)
+    return -continued_fraction(alpha, beta, z, norm2).imag / np.pi
 
 
 def _block_rdm(block, c, sites, target, return_sweeps=False):
@@ -604,6 +670,12 @@ class PauliMomentumOperator(_PauliFamily):
         """c = B^H Psi, the part of ANY state on the basis of `target` that lies in this block (pauli_block_project)."""
         return pauli_block_project(self, psi, target, out)
 
+    def transfer(self, terms, c, target, out=None, return_norm2=False):
+        """B_t^H (sum of `terms`) B c: the strings applied to the state c of this block, taken on the momentum block `target` of
+        the same kind, n_sites and n_down (pauli_block_transfer).  The library refuses a momentum / reflection / spin-inversion
+        block."""
+        return pauli_block_transfer(self, target, terms, c, out, return_norm2)
+
     def reduced_density_matrix(self, c, sites, target, return_sweeps=False):
         """rho_A = Tr_env |Psi><Psi| of Psi = B c: c is expanded into a device buffer of target.n_local values, measured with
         target.reduced_density_matrix (pauli_rdm) and the buffer freed.  entanglement_entropy takes the result."""
@@ -626,6 +698,7 @@ class PauliMomentumFullOperator(_PauliFamily):
     expectation = PauliMomentumOperator.expectation
     expand = PauliMomentumOperator.expand
     project = PauliMomentumOperator.project
+    transfer = PauliMomentumOperator.transfer
     reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
 
 
@@ -648,6 +721,7 @@ class PauliSymmetricOperator(_PauliFamily):
     expectation = PauliMomentumOperator.expectation
     expand = PauliMomentumOperator.expand
     project = PauliMomentumOperator.project
+    transfer = PauliMomentumOperator.transfer  # exists to surface the library's refusal: semi-momentum states are not built
     reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
 
 

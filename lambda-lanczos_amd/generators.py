@@ -859,6 +859,121 @@ def pauli_symmetric_csr(n_sites, m, parity, inversion, terms, dtype=np.float64, 
 
     return _pauli_rows(reps, terms, dtype, merge, column_of)
 
+
+# ------------------------------------------------------------------ a sum of Pauli strings between two momentum blocks of a ring
+# out = B_t^H (sum_j coef_j P_j) B_s c (ll_pauli_block_transfer): B_s, B_t the embeddings of two blocks of one kind,
+#   kind "momentum"       shape = (n_sites, n_down, m)    momentum_embedding
+#   kind "momentum_full"  shape = (n_sites, m)            full_momentum_embedding
+def transferred_strings(n_sites, term, q):
+    """The momentum-q component of the string `term` = (x_mask, z_mask[, coef]) on a ring,
+        Pbar_q = (1 / L) sum_{j < L} e^(+2 pi i q j / L) [(x, z) both rotated RIGHT by j sites],
+    as a list of (x_mask, z_mask, weight) with complex weights, sorted by x mask, then z mask: the numpy mirror of
+    csrc/pauli_block_transfer_plan.hpp.  B_t^H P B_s = B_t^H Pbar_q B_s for q = m_t - m_s (mod L).  A string whose masks come
+    back after r sites has r distinct images; they survive iff q r = 0 (mod L) — decided in integers — with the weight
+    e^(2 pi i q j / L) / r, exact where the phase lies on an axis.  The coefficient of `term` is not in the weights; an empty
+    list means the string has no momentum-q component."""
+    L, x, z, q = int(n_sites), int(term[0]), int(term[1]), int(q)
+    mask = (1 << L) - 1
+    if not 1 <= L <= 30 or (x | z) & ~mask or not 0 <= q < L:
+        raise ValueError("need 1 <= n_sites <= 30, masks below 2^n_sites and 0 <= q < n_sites")
+
+    def rotr(v, j):
+        return ((v >> j) | (v << (L - j))) & mask
+
+    r = next(d for d in range(1, L + 1) if L % d == 0 and rotr(x, d) == x and rotr(z, d) == z)
+    if (q * r) % L:
+        return []
+    ph = np.conj(_momentum_phases(L, q))   # e^(+2 pi i q j / L)
+    return sorted((rotr(x, j), rotr(z, j), complex(ph[j]) / r) for j in range(r))
+
+
+def _transfer_block(kind, shape):
+    """(n_sites, n_down or None, m, states of the embedding's rows or None, (col, val) of the embedding, (reps, periods))."""
+    if kind == "momentum":
+        n_sites, n_down, m = (int(v) for v in shape)
+        return (n_sites, n_down, m, sector_states(n_sites, n_down), momentum_embedding(n_sites, n_down, m, dense=False),
+                momentum_basis(n_sites, n_down, m))
+    if kind == "momentum_full":
+        n_sites, m = (int(v) for v in shape)
+        return n_sites, None, m, None, full_momentum_embedding(n_sites, m, dense=False), full_momentum_basis(n_sites, m)
+    raise ValueError("kind must be 'momentum' or 'momentum_full'")
+
+
+def pauli_block_transfer_np(kind, shape_s, shape_t, terms, c, return_magnitude=False):
+    """out = B_t^H (sum_j coef_j P_j) B_s c in complex128 by its definition — expand with the source's one-entry-per-row
+    embedding, pauli_string_apply_np per term, project with the target's — the plain host restatement of
+    ll_pauli_block_transfer.  kind and the shapes as in the comment above; `terms` holds (x_mask, z_mask, coef); c holds the
+    source block's coefficients.  In a sector a partner outside it contributes nothing.  With return_magnitude also
+    |B_t|^T (sum_j |coef_j| |P_j|) |B_s| |c| per row: the sum of the absolute values of everything the row gathers, which bounds
+    the same sum over the merged strings of the gather form (pauli_block_transfer_rows_np)."""
+    L, nd, _, states, (col_s, val_s), _ = _transfer_block(kind, shape_s)
+    L_t, nd_t, _, _, (col_t, val_t), (reps_t, _) = _transfer_block(kind, shape_t)
+    if L != L_t or nd != nd_t:
+        raise ValueError("the two blocks differ in n_sites or n_down")
+    c = np.asarray(c, dtype=np.complex128).reshape(-1)
+    psi = np.where(col_s >= 0, val_s * c[np.maximum(col_s, 0)], 0.0)
+    phi = np.zeros_like(psi)
+    for term in terms:
+        phi = phi + float(term[2]) * pauli_string_apply_np(L, term, psi, states)
+    out = np.zeros(reps_t.shape[0], np.complex128)
+    rows = np.flatnonzero(col_t >= 0)
+    np.add.at(out, col_t[rows], np.conj(val_t[rows]) * phi[rows])
+    if not return_magnitude:
+        return out
+    apsi, aphi = np.abs(psi), np.zeros(psi.shape[0])
+    for term in terms:
+        aphi = aphi + abs(float(term[2])) * pauli_string_apply_np(L, (term[0], 0, 1.0), apsi, states)
+    mag = np.bincount(col_t[rows], weights=np.abs(val_t[rows]) * aphi[rows], minlength=reps_t.shape[0])
+    return out, mag
+
+
+def pauli_block_transfer_rows_np(kind, shape_s, shape_t, terms, c, rows=None):
+    """(values, magnitudes) of the rows `rows` (None: all) of pauli_block_transfer_np's result from the GATHER form that the kernel
+    evaluates, in complex128 / float64:
+        out(a) = sum over the strings (X', z', weight) of transferred_strings(term, m_t - m_s), over the terms
+                 coef weight i^nY (-1)^popcount((a ^ X') & z') sqrt(R_a / R_b) e^(-2 pi i m_s l / L) c_b,     a ^ X' = T^l b
+    with a, R_a of the target block and b, l, R_b of the source block; a partner outside the source block (or outside the sector)
+    contributes nothing.  magnitudes[a] = the sum of the absolute values of those contributions: what an error bound of the row
+    multiplies.  Cost O(rows x strings x n_sites): rows of a 20-site block stay cheap."""
+    L, nd, m_s, (reps_s, _) = _transfer_reps(kind, shape_s)
+    L_t, nd_t, m_t, (reps_t, per_t) = _transfer_reps(kind, shape_t)
+    if L != L_t or nd != nd_t:
+        raise ValueError("the two blocks differ in n_sites or n_down")
+    c = np.asarray(c, dtype=np.complex128).reshape(-1)
+    rows = np.arange(reps_t.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64)
+    a = reps_t[rows].astype(np.uint64)
+    ra = per_t[rows].astype(np.float64)
+    phases = _momentum_phases(L, m_s)
+    val, mag = np.zeros(a.shape[0], np.complex128), np.zeros(a.shape[0], np.float64)
+    q = (m_t - m_s) % L
+    reps_s64 = reps_s.astype(np.uint64)
+    for term in terms:
+        for x, z, wt in transferred_strings(L, term, q):
+            p = a ^ np.uint64(x)
+            _, b, l, rb = _orbits_of(L, p)
+            inb = (m_s * rb) % L == 0
+            if nd is not None:
+                inb &= _popcount(p) == nd
+            j = np.minimum(np.searchsorted(reps_s64, b), reps_s64.shape[0] - 1)
+            inb &= reps_s64[j] == b
+            sign = np.where(_parity(p & np.uint64(z)) == 1, -1.0, 1.0)
+            t = (float(term[2]) * wt * (1j ** (bin(x & z).count("1") & 3))) * sign * np.sqrt(ra / rb) * phases[l] * c[j]
+            t = np.where(inb, t, 0.0)
+            val += t
+            mag += np.abs(t)
+    return val, mag
+
+
+def _transfer_reps(kind, shape):
+    """(n_sites, n_down or None, m, (reps, periods)): _transfer_block without the embedding over all states."""
+    if kind == "momentum":
+        n_sites, n_down, m = (int(v) for v in shape)
+        return n_sites, n_down, m, momentum_basis(n_sites, n_down, m)
+    if kind == "momentum_full":
+        n_sites, m = (int(v) for v in shape)
+        return n_sites, None, m, full_momentum_basis(n_sites, m)
+    raise ValueError("kind must be 'momentum' or 'momentum_full'")
+
 # ------------------------------------------------------------------ C++ versions (BASELINE sizes)
 _gen = None
 
