@@ -931,10 +931,12 @@ typedef struct ll_run_stats {
   int64_t replay_mismatches;     /* ll_lanczos_two_pass_*: replayed iterations whose alpha differed, as bits, from the recorded
                                   * one: 0 unless the operator is not reproducible from call to call */
   int64_t reserved[4];           /* later statistics are taken from here, so the struct size stays what it is.  In use, unnamed:
-                                  * [0] block_iterations: iterations that ran in the raw-basis block form (up to four per sweep,
+                                  * [0] block_iterations: iterations that ran in the raw-basis block form (up to eight per sweep,
                                   * DESIGN.md 3.2; pair_iterations counts those of them that shared a sweep),
                                   * [1] block_flushed_vectors: raw vectors completed in place when a pass left that form (one
-                                  * multi-axpy over the basis each; 0 in ordinary runs).  The rest is zero. */
+                                  * multi-axpy over the basis each; 0 in ordinary runs),
+                                  * [2] block8_iterations: ... of block_iterations, those that ran eight to a sweep (real double, where the guard
+                                  * of DESIGN.md 3.2 admitted them; 0 in complex double and with the tuning key block_gs_max = 4).  The rest is zero. */
 } ll_run_stats;
 int ll_ctx_set_profiling(ll_context* ctx, int enabled);
 

@@ -118,6 +118,7 @@ class RunStats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["block_iterations"] = int(self.reserved[0])        # (unnamed in the C struct: taken from the reserved tail)
         d["block_flushed_vectors"] = int(self.reserved[1])
+        d["block8_iterations"] = int(self.reserved[2])
         return d
 
 

@@ -54,7 +54,11 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "sharded_norm") t.sharded_norm_measured = v == "measured";
   else if (key == "pair_gs") t.pair_gs = e ? d.pair_gs : to_flag(v);
   else if (key == "block_gs") t.block_gs = e ? d.block_gs : to_flag(v);
-  else if (key == "pb_diag") t.pb_diag = e ? d.pb_diag : to_flag(v);
+  else if (key == "block_gs_max") {
+    const long long m = e ? d.block_gs_max : to_ll(v);
+    if (m != 4 && m != 8) return false;  // (ll_ctx_set_tuning: LL_ERR_INVALID)
+    t.block_gs_max = (int)m;
+  } else if (key == "pb_diag") t.pb_diag = e ? d.pb_diag : to_flag(v);
   else if (key == "fuse_launches") {
     const long long level = e ? 2 : to_ll(v);
     t.fuse_launches = level >= 1;

@@ -14,13 +14,13 @@
 
 namespace ll {
 
-// Device scalar area (ctx->scal, 64 doubles):
-//   [0..8)    alpha ring (slot = k % 8: kRingSlots, loop_support.hpp)
-//   [8..32)   norm triples (c0,c1,c2) ring, slot s at 8 + 3*s
-//   [32..35)  scratch triple for one-off orthogonalisations (start vector, primitives)
-//   [40]      spare scalar (dot results)
-//   [63]      constant 0
-constexpr int kScalAlpha = 0, kScalNorms = 8, kScalScratch = 32, kScalSpare = 40, kScalZero = 63, kScalCount = 64;
+// Device scalar area (ctx->scal, 128 doubles):
+//   [0..16)   alpha ring (slot = k % 16: kRingSlots, loop_support.hpp)
+//   [16..64)  norm triples (c0,c1,c2) ring, slot s at 16 + 3*s
+//   [64..67)  scratch triple for one-off orthogonalisations (start vector, primitives)
+//   [72]      spare scalar (dot results)
+//   [127]     constant 0
+constexpr int kScalAlpha = 0, kScalNorms = 16, kScalScratch = 64, kScalSpare = 72, kScalZero = 127, kScalCount = 128;
 
 // ---------------------------------------------------------------- host helpers shared by Engine and the whole-loop drivers
 inline double now_s() {

@@ -1,4 +1,4 @@
-// UP TO FOUR Lanczos iterations per sweep over a RAW basis (the "block" form), streaming geometry: the prediction through the
+// UP TO EIGHT Lanczos iterations per sweep over a RAW basis (the "block" form), streaming geometry: the prediction through the
 // recorded tridiagonal, the software-pipelined sweep and the fold.  Executable specification, launch by launch, with the
 // derivation and the numbers: tools/block_gs_model.py (profiles/block_gs_model.txt).  The raw three-term update between the
 // operator applications is pair_three_term_kernel (gs_pair.hip).
@@ -8,7 +8,7 @@
 // measured, eps-sized coefficients C_j[l] = <u_l, a_j>, l < j (rows of a packed triangle, row j at reals * j (j - 1) / 2).  The
 // orthonormal u_j = (a_j - sum_l C_j[l] u_l) / rho_j exist only implicitly; consumers transform their coefficient vectors to
 // first order in C (LoopState::ritz_basis, LoopState::block_flush).  State between blocks: a_0 .. a_k stored, alpha_0 ..
-// alpha_{k-1}, beta_j = rho_{j+1} recorded.  One block of m <= 4 iterations:
+// alpha_{k-1}, beta_j = rho_{j+1} recorded.  One block of m <= 8 iterations (eight: real double only, behind the host's guard, kBlock8Tau):
 //   m x (operator kernel on x / |x|, fused dot e_s; pair_three_term_kernel: b_s = y - e_s x - |x| x_prev, |b_s|^2)
 //   block_predict_kernel   alpha_k from e_0; p_s = predicted components of b_s along u_0 .. u_k; the compensation coefficients
 //   block_sweep_kernel     ONE pass over a_0 .. a_k: <a_j, b_s> for all j, s; b_{m-1} and b_{m-2} (BOTH operands of the next block's
@@ -143,6 +143,85 @@ void launch_block_predict(int k, int m, int reals, const BlockScalars& sc, const
   LL_HIP(hipGetLastError());
 }
 
+// wave_sum_transposed<8> (dev_helpers.hpp) without the LDS crossbar and with fewer instructions: the exchanges across 32 and 16
+// lanes are gfx950's v_permlane32_swap / v_permlane16_swap (the upper rows of x change places with the lower rows of y: x + y is
+// then the sum of x in the lower rows and of y in the upper rows), those inside a row of 16 are DPP moves.  The trips of the sweep
+// of eight are bound by their instruction count, and 20 shuffle-adds through ds_bpermute with their selects were half of it
+// (2.2 TB/s with them, 5.3 TB/s without: DESIGN_EXPERIMENTS E23).  On return a[0] of lane L is the full sum of accumulator L / 8, in a fixed order.
+template <int CTRL> __device__ __forceinline__ double dpp_move(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ void swap_add32(double& x, double y) {
+  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+  x = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void swap_add16(double& x, double y) {
+  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+  x = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void wave_sum_transposed8(double (&a)[8], int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) swap_add32(a[i], a[i + 4]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) swap_add16(a[i], a[i + 2]);
+  const bool upper = (lane & 8) != 0;
+  const double keep = upper ? a[1] : a[0], send = upper ? a[0] : a[1];
+  double v = keep + dpp_move<0x128>(send);  // row_ror:8: lane ^ 8
+  v += dpp_move<0x141>(v);                  // row_half_mirror: lane i of eight <-> 7 - i
+  v += dpp_move<0x4e>(v);                   // quad_perm [2, 3, 0, 1]: lane ^ 2
+  v += dpp_move<0xb1>(v);                   // quad_perm [1, 0, 3, 2]: lane ^ 1
+  a[0] = v;
+}
+
+// The same trip for EIGHT new vectors, two pieces per lane, REAL double only (the complex sweep of eight needs 264 registers — one
+// wave per SIMD — and complex passes keep blocks of four: LoopState::enqueue_block_f64).  The compensations first; then the column sets in two halves of four, the
+// 4 NV sums of a half in ONE transposing reduction (4 NV - 1 + log2(64 / (4 NV)) shuffle-adds against 6 x 4 for a reduction per set:
+// with two pieces per lane a trip has half the elements to spread them over) — all eight at once do not fit the registers beside the
+// strips.  Accumulator v * 4 + i of a half ends up in lanes 64 / (4 NV) * (v * 4 + i) ..
+template <typename T, int NV, int PC>
+__device__ __forceinline__ void block_trip_compute8(const T (&ur)[NV][strip<T, PC>::EPT], int nv, const T (&b)[8][strip<T, PC>::EPT],
+                                                    T (&cA)[strip<T, PC>::EPT], T (&cB)[strip<T, PC>::EPT],
+                                                    const double* __restrict__ prAc, const double* __restrict__ prBc, double* mine,
+                                                    int setstride, int lane) {
+  constexpr int EPT = strip<T, PC>::EPT;
+  constexpr int H = 4, NF = H * NV, LPF = 64 / NF;
+  static_assert(!scalar_traits<T>::is_complex && NF == 8, "the sweep of eight: real double, two stored vectors per trip");
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int vv = v < nv ? v : nv - 1;
+    const bool real = v < nv;  // (uniform: scalar selects)
+    const double xa = ld_const(prAc, vv), xb = ld_const(prBc, vv);
+    const double ca = real ? xa : 0.0, cb = real ? xb : 0.0;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+      fnma_acc(cA[e], ca, ur[v][e]);
+      fnma_acc(cB[e], cb, ur[v][e]);
+    }
+  }
+  const int f = lane / LPF, fv = f / H, fi = f % H;
+#pragma unroll
+  for (int h = 0; h < 8 / H; ++h) {
+    double fs[NF];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+      for (int i = 0; i < H; ++i) {
+        double sm = 0.0;
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) cfma_acc(sm, ur[v][e], b[h * H + i][e]);
+        fs[v * H + i] = sm;
+      }
+    }
+    wave_sum_transposed8(fs, lane);
+    if ((lane & (LPF - 1)) == 0 && fv < nv) mine[(h * H + fi) * setstride + fv] += fs[0];
+    __builtin_amdgcn_sched_barrier(0);  // (the halves one after the other: their accumulators share registers)
+  }
+}
+
 // One trip of the block sweep: NV stored strips; M measured column sets (against the RAW new vectors), two compensations.
 // nv <= NV of the strips are real (a prefix), like in pair_trip_compute.
 template <typename T, int NV, int PC, int M>
@@ -151,6 +230,10 @@ __device__ __forceinline__ void block_trip_compute(const T (&ur)[NV][strip<T, PC
                                                    const double* __restrict__ prAc, const double* __restrict__ prBc, double* mine,
                                                    int setstride, int lane) {
   constexpr int EPT = strip<T, PC>::EPT;
+  if constexpr (M == 8) {
+    block_trip_compute8<T, NV, PC>(ur, nv, b, cA, cB, prAc, prBc, mine, setstride, lane);
+    return;
+  }
   double sre[M][NV], sim[M][NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -286,6 +369,58 @@ __global__ __launch_bounds__(kBlock) void block_sweep_kernel(int64_t n, const T*
       b[M - 1][e] = cA[e];
       if constexpr (M >= 2) b[M - 2][e] = cB[e];
     }
+    if constexpr (M == 8) {
+      // 28 products and 8 norms per strip (real double only): two transposing reductions of 16 and four wave sums instead of 36 wave
+      // sums.  The products (pair (i, ip) at i (i - 1) / 2 + ip) 0 .. 15; then the products 16 .. 27 followed by |v_0|^2 .. |v_3|^2
+      // (one of 32 does not fit the registers beside the eight strips); |v_4|^2 .. |v_7|^2 by themselves.
+      constexpr int NP = M * (M - 1) / 2;
+      static_assert(NP + 4 == 32 && !scalar_traits<T>::is_complex, "the Gram triangle of eight and four norms fill two reductions of 16");
+      const int f = lane >> 2;  // the accumulator of a reduction of 16 whose sum this lane holds
+      auto half = [&](auto first_c) {
+        constexpr int FIRST = decltype(first_c)::value;
+        double ga[16];
+        int a = 0;
+#pragma unroll
+        for (int i = 1; i < M; ++i) {
+#pragma unroll
+          for (int ip = 0; ip < i; ++ip) {
+            if (a >= FIRST && a < FIRST + 16) {
+              double g = 0.0;
+#pragma unroll
+              for (int e = 0; e < EPT; ++e) cfma_acc(g, b[ip][e], b[i][e]);
+              ga[a - FIRST] = g;
+            }
+            ++a;
+          }
+        }
+        if constexpr (FIRST == 16) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            double n0 = 0.0;
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) n0 += abs2(b[i][e]);
+            ga[NP - 16 + i] = n0;
+          }
+        }
+        wave_sum_transposed<16>(ga, lane);
+        if ((lane & 3) == 0) tail[FIRST + f] += ga[0];  // (28 .. 31: |v_0|^2 .. |v_3|^2, which follow the products)
+        if constexpr (FIRST == 16) {
+#pragma unroll
+          for (int i = 4; i < M; ++i) {
+            double nn = 0.0;
+#pragma unroll
+            for (int e = 0; e < EPT; ++e) nn += abs2(b[i][e]);
+            nn = wave_sum(nn);
+            if (lane == 0) tail[NP + i] += nn;
+          }
+        }
+      };
+      __builtin_amdgcn_sched_barrier(0);
+      half(std::integral_constant<int, 0>{});
+      __builtin_amdgcn_sched_barrier(0);  // (the halves one after the other: their accumulators share registers)
+      half(std::integral_constant<int, 16>{});
+      return;
+    }
     int at = 0;
 #pragma unroll
     for (int i = 1; i < M; ++i) {
@@ -346,10 +481,13 @@ template <typename T>
 int launch_block_sweep(int64_t n, const T* const* vtab, int W, int m, const BlockVecs<T>& bv, const double* prA, const double* prB,
                        double* partials, int pieces, int per_launch, hipStream_t s) {
   constexpr int R = scalar_traits<T>::reals;
-  LL_REQUIRE(m == 1 || m == 2 || m == 4, "internal: block sweep of 1, 2 or 4 iterations");
+  LL_REQUIRE(m == 1 || m == 2 || m == 4 || m == 8, "internal: block sweep of 1, 2, 4 or 8 iterations");
   const int64_t strips16k = (n * (int64_t)sizeof(T) + 16383) / 16384;
   int pc = strips16k >= kLaggedFullStrips ? 4 : 2;
   if (pieces == 2 || pieces == 4) pc = pieces;
+  // Eight new strips of four pieces are 64 VGPRs more than the 228 of <double, 4, 4, 2>: beyond the 256 that two waves per SIMD
+  // leave.  Eight always run with two pieces per lane (8 KiB strips; profiles/block_gs_registers.txt).
+  if (m == 8) pc = 2;
   const int grid = pc == 4 ? strip_grid(n, strip<T, 4>::ELEMS) : strip_grid(n, strip<T, 2>::ELEMS);
   const int ng = R * m * (m - 1) / 2 + m;
   per_launch = std::max(1, std::min(per_launch, block_sweep_max_vecs<T>(m)));
@@ -363,7 +501,10 @@ int launch_block_sweep(int64_t n, const T* const* vtab, int W, int m, const Bloc
       else if (m == 2) LL_BLOCK_SWEEP(4, 2);
       else LL_BLOCK_SWEEP(4, 1);
     } else {
-      if (m == 4) LL_BLOCK_SWEEP(2, 4);
+      if (m == 8) {
+        if constexpr (scalar_traits<T>::is_complex) LL_REQUIRE(false, "internal: the block sweep of eight is built for real double only");
+        else LL_BLOCK_SWEEP(2, 8);
+      } else if (m == 4) LL_BLOCK_SWEEP(2, 4);
       else if (m == 2) LL_BLOCK_SWEEP(2, 2);
       else LL_BLOCK_SWEEP(2, 1);
     }

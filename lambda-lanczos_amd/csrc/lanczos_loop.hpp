@@ -123,8 +123,10 @@ template <typename T> struct LoopState {
     static constexpr size_t kDoubles = 10 * kPairRec + 64;
   } pb;
   bool slot_pair[kRingSlots] = {};                    // the scalars of this ring slot came from a pair or block fold (its gate is valid)
-  int ev_of_slot[kRingSlots] = {0, 1, 2, 3, 4, 5, 6, 7};  // the event that covers a ring slot's scalars (the slots of a pair or block share one)
-  // Block form (gs_block.hip; tools/block_gs_model.py): UP TO FOUR iterations per sweep over a basis that is never rewritten.  The
+  static_assert(kRingSlots == 16 && kScalNorms >= kScalAlpha + kRingSlots && kScalScratch >= kScalNorms + 3 * kRingSlots,
+                "the rings of the device scalar area follow kRingSlots");
+  int ev_of_slot[kRingSlots] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};  // the event that covers a ring slot's scalars (the slots of a pair or block share one)
+  // Block form (gs_block.hip; tools/block_gs_model.py): UP TO EIGHT iterations per sweep over a basis that is never rewritten.  The
   // slots U.vec(j), j >= blk_k0, hold the RAW three-term vectors a_j; bb.rho2[j] and row j of the packed triangle bb.cpk (at
   // R j (j - 1) / 2) hold rho_j^2 and the measured coefficients C_j[l] = <u_l, a_j>, and the orthonormal u_j = (a_j - sum_l C_j[l] u_l)
   // / rho_j exist only implicitly: the Ritz GEMV takes transformed coefficients (ritz_basis), and leaving the form completes the raw
@@ -137,16 +139,19 @@ template <typename T> struct LoopState {
   int64_t blk_k0 = 0;          // first raw vector of the pass (the vectors in front of it are complete: rho = 1, zero rows)
   int64_t n_block = 0;         // iterations enqueued in the block form (statistics)
   int64_t n_block_flushed = 0; // raw vectors completed by block_flush (statistics: multi-axpys over the basis)
+  int64_t n_block8 = 0;        // ... of n_block: iterations enqueued eight to a sweep (statistics)
+  int blk_quiet = 0;           // this pass: collected block iterations in a row whose gate value stayed <= kBlock8Tau (the guard of
+                               // the blocks of eight, ll_internal.hpp; collect counts, enqueue_block_f64 asks for kBlock8Quiet)
   DevBuf<double> bbuf;
   DevBuf<T> bsplit[2];         // hand-over vectors of a split block sweep
   struct BlockBuf {            // the regions of bbuf (enable_block)
     double* rho2 = nullptr;    // cap entries
     double* cpk = nullptr;     // packed rows 0 .. cap - 1
     double* dk = nullptr;      // predict scratch, a record
-    double* p = nullptr;       // predictions, four records
+    double* p = nullptr;       // predictions, kBlockMaxM records
     double *prA = nullptr, *prB = nullptr;    // compensation coefficients, a record each
     double *raw0 = nullptr, *raw1 = nullptr;  // fold scratch, a record each
-    double* cols = nullptr;    // folded columns: four records and the Gram tail
+    double* cols = nullptr;    // folded columns: kBlockMaxM records and the Gram tail
     double* nsq = nullptr;     // |b_s|^2 (and <x_prev, b_s>) of the block's three-term updates, 4 doubles apart
     int64_t cap = 0;           // vectors the records are sized for
     size_t rec = 0;            // doubles per record
@@ -158,18 +163,19 @@ template <typename T> struct LoopState {
     bb.cap = std::min<int64_t>(max_k_hint, (int64_t)kBlockMaxVecs) + 8;
     bb.rec = R * (size_t)(bb.cap + 8);
     const size_t tri = block_row_at(bb.cap) + R * (size_t)bb.cap;
-    bbuf.alloc(E.ctx, (size_t)bb.cap + tri + 13 * bb.rec + 64);
+    constexpr size_t kTail = R * (size_t)(kBlockMaxM * (kBlockMaxM - 1) / 2) + (size_t)kBlockMaxM;  // Gram triangle and norms
+    bbuf.alloc(E.ctx, (size_t)bb.cap + tri + (5 + 2 * (size_t)kBlockMaxM) * bb.rec + kTail + 4 * (size_t)kBlockMaxM + 32);
     double* b = bbuf.p;
     bb.rho2 = carve(b, (size_t)bb.cap);
     bb.cpk = carve(b, tri);
     bb.dk = carve(b, bb.rec);
-    bb.p = carve(b, 4 * bb.rec);
+    bb.p = carve(b, (size_t)kBlockMaxM * bb.rec);
     bb.prA = carve(b, bb.rec);
     bb.prB = carve(b, bb.rec);
     bb.raw0 = carve(b, bb.rec);
     bb.raw1 = carve(b, bb.rec);
-    bb.cols = carve(b, 4 * bb.rec + 32);
-    bb.nsq = carve(b, 16);
+    bb.cols = carve(b, (size_t)kBlockMaxM * bb.rec + kTail);
+    bb.nsq = carve(b, 4 * (size_t)kBlockMaxM);
   }
   // the gate of the pair form: what is neglected is the SQUARE of a relative coefficient, which must stay below the rounding of the
   // storage type (float vectors carry coefficients of ~1e-6 by rounding alone)
@@ -216,7 +222,7 @@ template <typename T> struct LoopState {
     if (lagged) bind_buffers();
     // two iterations per sweep (device operators, streaming vectors; enqueue_pair decides per iteration)
     if (lagged && tune.pair_gs && vec_bytes() >= pair_min_bytes()) enable_pair();
-    // up to four per sweep over a raw basis: where the pipelined pair sweep runs (pointer table, streaming vectors: enqueue_block
+    // up to eight per sweep over a raw basis: where the pipelined pair sweep runs (pointer table, streaming vectors: enqueue_block
     // decides), double precision, one rank, and only for passes that cannot outgrow the form's bound
     if (pair_enabled && tune.block_gs && vtab.p && sizeof(typename scalar_traits<T>::real) == 8 && E.ctx->comm == nullptr &&
         max_iteration >= 1 && max_iteration <= (int64_t)kBlockMaxVecs)
@@ -305,6 +311,7 @@ template <typename T> struct LoopState {
     pair_allowed = true;
     block_allowed = true;
     blk_k0 = 0;
+    blk_quiet = 0;
     for (auto& b : slot_pair) b = false;
     // (lambda_shifted == nullptr with locked vectors — a caller's orthogonalizeTo list, run_iteration LL:216-220,259: their Rayleigh
     // quotients theta_i = <z_i, (A + offset) z_i> are MEASURED below and take the eigenvalues' place; the residual gate then decides
@@ -321,7 +328,7 @@ template <typename T> struct LoopState {
       // against 0.62 s for the second call.
       constexpr size_t R = (size_t)Engine<T>::R;
       const size_t reach = (size_t)std::max<int64_t>(0, std::min<int64_t>(max_k_hint, (int64_t)kLaggedMaxCols)) + (size_t)n_lock + 2;
-      const size_t cols = std::min<size_t>(kPresizeCols, (block_enabled ? 4 : 2) * R * reach + 6 * R + 4);  // (longer runs: powers of two, enqueue_pair)
+      const size_t cols = std::min<size_t>(kPresizeCols, (block_enabled ? (size_t)E.ctx->tune.block_gs_max : 2) * R * reach + 6 * R + 4);  // (longer runs: powers of two, enqueue_pair)
       E.ctx->ensure_partials((size_t)kMaxGrid * cols);
     }
     if (!lag_ok || n_lock == 0) return;
@@ -533,7 +540,8 @@ template <typename T> struct LoopState {
     if (tail.nvec == 2) basis.add(tail.pair.r[1], 1);
     return basis;
   }
-  // Iterations kk .. kk + m - 1 in the block form, m = 4, or 2 or 1 where fewer remain before max_iteration.  Entered from the
+  // Iterations kk .. kk + m - 1 in the block form: m = 8 in real double where the guard admits it (blk_quiet; key block_gs_max = 4: never), else 4,
+  // and 4, 2 or 1 where fewer remain before max_iteration.  Entered from the
   // one-sweep state (iteration kk - 1 pending with its measured coefficients, u_0 .. u_{kk-2} complete) or continued from a block.
   // Returns m; 0: not taken.
   int64_t enqueue_block(int64_t kk, double offset) {
@@ -557,7 +565,9 @@ template <typename T> struct LoopState {
     }
     const int64_t remaining = max_k_hint - (kk - 1);  // never beyond the loop's max_iteration
     if (remaining < 1) return 0;
-    const int m = remaining >= 4 ? 4 : (remaining >= 2 ? 2 : 1);
+    // (complex double keeps blocks of four: its sweep of eight needs 264 registers, one wave per SIMD, and no rate of it has been measured)
+    const bool eight = !scalar_traits<T>::is_complex && tune.block_gs_max >= 8 && remaining >= 8 && blk_quiet >= kBlock8Quiet;
+    const int m = eight ? 8 : (remaining >= 4 ? 4 : (remaining >= 2 ? 2 : 1));
     // the streaming geometry of the pipelined pair sweep (launch_pair_sweep), within the records
     const int64_t strips16k = (nl * (int64_t)sizeof(T) + 16383) / 16384;
     const bool streaming = tune.sweep_pipeline >= 2 || strips16k > 2 * kCUs + kCUs / 4;
@@ -584,8 +594,8 @@ template <typename T> struct LoopState {
     const T* const* vt = vtab_sync();
     BlockScalars sc{};
     BlockHost host{};
-    int slots[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) {
+    int slots[kBlockMaxM] = {};
+    for (int i = 0; i < kBlockMaxM; ++i) {
       const int ii = std::min(i, m - 1);
       slots[i] = (int)((kk + ii) % kRingSlots);
       sc.e[i] = E.S(kScalAlpha + slots[i]);
@@ -624,6 +634,7 @@ template <typename T> struct LoopState {
     }
     pending = BlockIter{k + m};
     n_block += m;
+    if (m == 8) n_block8 += m;
     if (m >= 2) n_pair += m;  // (iterations that shared a sweep with a neighbour)
     n_lagged += m;
     t_enqueue += now_s() - te0;
@@ -903,6 +914,8 @@ template <typename T> struct LoopState {
     t_wait += now_s() - tw0;
     const volatile double* hp = pinned_slot(slot);
     Scalars r{hp[0], hp[1], hp[2], hp[3], false};
+    // the guard of the blocks of eight: how many block iterations in a row, up to this one, published a quiet gate value
+    blk_quiet = block_enabled && slot_pair[slot] && *pinned_gate(slot) <= kBlock8Tau ? std::min(blk_quiet + 1, (int)kBlock8Quiet) : 0;
     double* const beta2_dev = E.S(kScalNorms + 3 * slot) + 1;  // what the next three-term update reads as beta_j^2
     if (dgks && r.c1 < E.ctx->tune.dgks_threshold * r.c0) {
       // DGKS "twice is enough", decided here from the published norms: the first pass removed more than half of
@@ -1066,6 +1079,7 @@ void fill_stats(ll_run_stats* stats, LoopState<T>& loop, int64_t total_iteration
     stats->pair_gate_trips = loop.n_gate_trips;
     stats->reserved[0] = loop.n_block;          // block_iterations
     stats->reserved[1] = loop.n_block_flushed;  // block_flushed_vectors
+    stats->reserved[2] = loop.n_block8;         // block8_iterations
     loop.timer.collect(stats->seconds_spmv, stats->seconds_orth);
     ctx->drain_comm_events(&stats->seconds_comm_gather, &stats->seconds_comm_allreduce);
     stats->seconds_total = now_s() - t_start;

@@ -245,7 +245,8 @@ struct Tuning {
   bool event_in_launch = true;     // key event_in_launch = 0: iteration events as marker packets behind the publishing kernel (A/B)
   bool ritz_tail = true;           // key ritz_tail = 0: a pair pending at the end of a pass is completed by sweeps of its own instead of entering the Ritz GEMV through its raw vectors (A/B)
   int sweep_pipeline = 1;          // key sweep_pipeline: 1 (default) the software-pipelined pair sweep on streaming vectors (> ~9 MiB), 0 never (A/B: same bits), 2 on every length (parity tests on small cases)
-  bool block_gs = true;            // key block_gs = 0: never the raw-basis block form (up to four iterations per sweep); the pair form where it applies (A/B)
+  bool block_gs = true;            // key block_gs = 0: never the raw-basis block form (up to eight iterations per sweep); the pair form where it applies (A/B)
+  int block_gs_max = 8;            // key block_gs_max = 4|8: the largest block the form takes (eight: real double only); 4: never eight iterations per sweep (the form as it was before blocks of eight, A/B)
   bool pair_gs = true;             // LL_PAIR_GS=0: never two iterations per sweep (the one-sweep form throughout; A/B and parity hunts)
   // --- test hooks (not for users)
   bool force_rp64 = false;         // key force_rp64 = 1: 64-bit row offsets on small matrices
@@ -892,6 +893,16 @@ int launch_lagged(int64_t n, T* w, const BasisSegs<T>& segs, const Lagged<T>& lg
 // Streaming geometry only; 2 * reals * K + 5 * reals + 1 <= kLaggedMaxCols columns per workgroup (K stored columns).
 constexpr double kPairGate = 1e-8;  // largest relative coefficient the pair form accepts in double precision (second-order terms
                                     // stay below 1e-16; float storage: 2e-4, lanczos_loop.hpp)
+// The guard of the block form's blocks of EIGHT.  Fresh rounding along a converged Ritz direction grows by r = (theta - alpha) / beta
+// per operator application and is measured only by the next sweep: a block of m reaches about eps r^(m-1), so a gate value g
+// published by blocks of four predicts g (g / eps)^(4/3) at eight — a factor 10 under kPairGate for g <= 1.6e-13, IF r is stationary.
+// While a Ritz value is still converging it is not (an outlier: 5e-16, 1e-13, 1e-12 in the first three blocks of four), so eight are
+// taken only after kBlock8Quiet consecutive collected iterations published a gate value <= kBlock8Tau; kBlock8Tau lies between what
+// blocks of four publish without a converged outlier (<= 2.3e-14) and with one (1e-13 .. 5e-12).  tools/block_gs_model.py
+// (run_guarded; TAU, QUIET) and profiles/block8_model.txt: no block of eight in 24 outlier runs, where ONE block <= 1.6e-13 admitted
+// one in every run.  kPairGate stays the safety net behind it.
+constexpr double kBlock8Tau = 5e-14;
+constexpr int kBlock8Quiet = 12;
 template <typename T>
 int launch_pair_three_term(int64_t n, T* y, const T* x, const T* p, double* e, const double* e_partials, int e_nparts,
                            const double* cx2, const double* cp2, double* partials, bool colmajor,
@@ -931,21 +942,22 @@ void launch_pair_fold(const double* m, int P, int L, int reals, const double* la
                       const double* rho2sq, const double* n3sq, const double* e1, const double* e2, double* rec3, double* rec4,
                       double* nxt, double* hist_alpha, double* hist_beta, double* scratch, double* host_a, double* host_b,
                       double* gate_a, double* gate_b, hipStream_t s, hipEvent_t stop = nullptr);
-// The block form (up to four iterations per sweep over a RAW basis; gs_block.hip; tools/block_gs_model.py is the executable
+// The block form (up to eight iterations per sweep over a RAW basis; gs_block.hip; tools/block_gs_model.py is the executable
 // specification).  Streaming geometry, double and complex double, no locked columns.  The form keeps reals * K^2 / 2 coefficients
 // for a pass of K vectors and leaving it costs one multi-axpy per raw vector, so it is bounded by a vector count and only taken by
 // passes that cannot outgrow it (LoopState::enqueue_block).
 constexpr int kBlockMaxVecs = 1024;
+constexpr int kBlockMaxM = 8;  // iterations per block at most (eight: real double only, behind the guard, kBlock8Tau)
 struct BlockScalars {
-  const double* e[4];    // <x, A x> of the block's operator applications
-  const double* nsq[4];  // |b_s|^2 of the raw three-term vectors
+  const double* e[kBlockMaxM];    // <x, A x> of the block's operator applications
+  const double* nsq[kBlockMaxM];  // |b_s|^2 of the raw three-term vectors
 };
 struct BlockHost {
-  double* slot[4];  // host slots of the block's iterations (alpha, beta^2, ||w||^2 before, after)
-  double* gate[4];  // ... and their gate values
+  double* slot[kBlockMaxM];  // host slots of the block's iterations (alpha, beta^2, ||w||^2 before, after)
+  double* gate[kBlockMaxM];  // ... and their gate values
 };
 template <typename T> struct BlockVecs {
-  T* b[4];     // the new vectors in their basis slots; the sweep rewrites the last two
+  T* b[kBlockMaxM];  // the new vectors in their basis slots; the sweep rewrites the last two
   T* part[2];  // hand-over vectors of a split sweep (touched only when there is more than one launch)
 };
 template <typename T> constexpr int block_sweep_max_vecs(int m) {  // stored vectors per launch: 4 x (m reals Wl + Gram) doubles of LDS

@@ -36,10 +36,10 @@ template <typename T> struct DevBuf {
 };
 
 // The host's read-back area (ctx->pinned, pinned and device-mapped): iteration k publishes its four scalars (alpha, beta^2, c0, c1)
-// into ring slot k % kRingSlots; the gate values of the pair and block forms follow the slots, one per slot.  Eight slots: a
-// block of four iterations is enqueued while the four of the block before it are still being collected.
-constexpr int kRingSlots = 8, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
-constexpr size_t kPinnedScalars = 48;  // (kGateAt + kRingSlots used)
+// into ring slot k % kRingSlots; the gate values of the pair and block forms follow the slots, one per slot.  Sixteen slots: a
+// block of eight iterations is enqueued while the eight of the block before it are still being collected.
+constexpr int kRingSlots = 16, kSlotScalars = 4, kGateAt = kRingSlots * kSlotScalars;
+constexpr size_t kPinnedScalars = 96;  // (kGateAt + kRingSlots used)
 
 struct EventRing {
   hipEvent_t ev[kRingSlots];

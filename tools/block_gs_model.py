@@ -1,5 +1,5 @@
-"""Executable specification (numpy) of the RAW-BASIS BLOCK form of the Gram-Schmidt step: m <= 4 Lanczos iterations per sweep over
-the basis and NO late update, written launch by launch the way csrc/gs_block.hip and csrc/lanczos_loop.hpp implement it (block_*
+"""Executable specification (numpy) of the RAW-BASIS BLOCK form of the Gram-Schmidt step: m <= 8 Lanczos iterations per sweep over
+the basis (eight only behind the measured guard of run_guarded, below) and NO late update, written launch by launch the way csrc/gs_block.hip and csrc/lanczos_loop.hpp implement it (block_*
 kernels, LoopState::enqueue_block, block_flush, ritz_basis).  Successor of tools/pair_gs_model.py (the pair form, csrc/gs_pair.hip).
 
 The stored vectors are never rewritten.  The basis in memory is a_0, a_1, ...: every a_j is the raw three-term vector of its
@@ -26,12 +26,14 @@ for j <= k, alpha_0 .. alpha_{k-1}, beta_j = rho_{j+1} for j < k.  One block of 
 alpha of the last vector of a block comes from e_1 of the NEXT block (or of the single iteration that follows the form).
 
     python tools/block_gs_model.py        -> profiles/block_gs_model.txt
+    python tools/block_gs_model.py --block8   -> profiles/block8_model.txt  (blocks of eight behind the guard: run_guarded)
 """
 import importlib.util
 import os
 import sys
 
 import numpy as np
+import scipy.sparse as sp
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _spec = importlib.util.spec_from_file_location("pair_gs_model", os.path.join(_HERE, "pair_gs_model.py"))
@@ -236,6 +238,132 @@ def run_loop(A, v0, K, m, both_seeds=True, plant=None, gate=GATE, mutate=None):
     return L
 
 
+# ---- blocks of EIGHT behind a measured guard (csrc/lanczos_loop.hpp: LoopState::collect, enqueue_block_f64)
+# Fresh rounding along a converged Ritz direction grows by r = (theta - alpha) / beta per operator application and is measured only
+# by the next sweep: a block of m reaches about eps r^(m-1).  From a gate value g measured with blocks of four the value at eight is
+# predicted as g (g / eps)^(4/3); a factor 10 under the gate (1e-8) asks for g <= 1.6e-13.  That prediction assumes a STATIONARY r.
+# While a Ritz value is still converging r grows from block to block (the outlier matrix below: 5e-16, 1e-13, 1e-12 in the first three
+# blocks of four), so one quiet block is no evidence: the guard asks for kBlock8Quiet CONSECUTIVE collected iterations at or below
+# kBlock8Tau, and kBlock8Tau sits between what blocks of four publish on matrices without converged outliers (<= 2.3e-14 over the
+# problems below, 300 iterations) and what they publish once an outlier has converged (1e-13 .. 5e-12).  The host enqueues a block
+# while the block before it is still running, so the guard sees the gate values up to the block BEFORE the previous one (lag = 1).
+TAU = 5e-14     # kBlock8Tau
+QUIET = 12      # kBlock8Quiet
+
+
+def run_guarded(A, v0, K, mmax=8, tau=TAU, quiet_need=QUIET, lag=1, plant=None, gate=GATE, mutate=None):
+    """K recorded iterations in blocks of 8 (where the guard admits them and eight remain), else 4, 2, 1: never past K.  The gate
+    works as in run_loop.  Leaves L.sizes (the block sizes taken) and L.n8 (iterations run in eights)."""
+    L = BlockLoop(A, v0, K, True, plant, mutate)
+    L.start()
+    L.gate_trips, L.n8, L.sizes = 0, 0, []
+    blocks = []                                          # the gate values of every block, in order
+    while len(L.al) < K and not L.gate_trips:
+        rem = K - len(L.al)
+        quiet = 0
+        for blk in blocks[:len(blocks) - lag]:           # what the host has collected when it enqueues this block
+            for g in blk:
+                quiet = quiet + 1 if g <= tau else 0
+        m = 8 if (mmax >= 8 and rem >= 8 and quiet >= quiet_need) else 4 if rem >= 4 else 2 if rem >= 2 else 1
+        k0 = L.k
+        L.block(m)
+        L.sizes.append(m)
+        L.n8 += m if m == 8 else 0
+        blocks.append([L.gates[j] for j in range(k0 + 1, L.k + 1)])
+        for j in range(k0 + 1, L.k + 1):
+            if not L.gates[j] <= gate:
+                L.gate_trips = 1
+                L.flush(j)
+                break
+    if len(L.al) < K:
+        L.flush()
+        while len(L.al) < K:
+            L.clean_iteration()
+    return L
+
+
+def _random_rows(n, per_row, lo, complex_, seed, imag=1.0):
+    rng = np.random.default_rng(seed)
+    rows, cols = np.repeat(np.arange(n), per_row), rng.integers(0, n, per_row * n)
+    vals = rng.uniform(lo, 1, per_row * n) + (1j * imag * rng.uniform(-1, 1, per_row * n) if complex_ else 0)
+    v0 = rng.uniform(-1, 1, n) + (1j * rng.uniform(-1, 1, n) if complex_ else 0)
+    return sp.csr_matrix((vals, (rows, cols)), shape=(n, n)), v0 / np.linalg.norm(v0)
+
+
+def config3_problem(n, complex_, seed=5):
+    """The flagship's type: B + B^H + 7 I, seven entries per row of B in (-1, 1)."""
+    B, v0 = _random_rows(n, 7, -1, complex_, seed)
+    return (B + B.conj().T + 7 * sp.eye(n)).tocsr(), v0
+
+
+def outlier_problem(n, complex_, seed=7):
+    """Symmetric with a dominant outlier: fifteen entries per row in (0, 1), symmetrised.  The largest Ritz value converges within
+    the first blocks and r = (theta - alpha) / beta is about 13 from then on."""
+    B, v0 = _random_rows(n, 15, 0, complex_, seed, imag=0.1)
+    return ((B + B.conj().T) * 0.5).tocsr(), v0
+
+
+def norm_inf(A):
+    return abs(A).sum(axis=1).max()
+
+
+def measure8(A, v0, K, ref=None, **kw):
+    ra, rb, _ = ref if ref is not None else reference(A, v0, K)
+    with np.errstate(all="ignore"):
+        L = run_guarded(A, v0, K, **kw)
+    a, b = np.array(L.al), np.array(L.be)
+    return dict(dalpha=np.abs(a - ra[:K]).max(), dbeta=np.abs(b - rb[:K]).max(), tol=1e-10 * norm_inf(A), maxcoef=L.maxcoef,
+                gate_trips=L.gate_trips, n8=L.n8, sizes=L.sizes, alpha=a, beta=b)
+
+
+def main8():
+    out = ["blocks of eight behind the guard (tools/block_gs_model.py --block8): eight only after %d consecutive collected iterations" % QUIET,
+           "with a gate value <= %.1e, guard one block late (the host's view); against full re-orthogonalisation; gate 1e-08" % TAU, ""]
+    problems = (("the model's problem, n = 3000", lambda c: make_problem(3000, c)),
+                ("config-3 type, n = 20000", lambda c: config3_problem(20000, c)))
+    for name, mk in problems:
+        for cplx in (False, True):
+            A, v0 = mk(cplx)
+            ref = reference(A, v0, 1024)
+            for K in (100, 300, 1024):
+                r = measure8(A, v0, K, ref)
+                out.append("  %s, %s, K = %4d: max|dalpha| %.1e  max|dbeta| %.1e  (1e-10 ||A|| = %.1e)  largest relative coefficient %.1e  "
+                           "gate trips %d  in eights %d (%.0f %%)" % (name, "complex" if cplx else "real", K, r["dalpha"], r["dbeta"], r["tol"],
+                                                                   r["maxcoef"], r["gate_trips"], r["n8"], 100.0 * r["n8"] / K))
+    out += ["", "the outlier matrix (n = 4000, K = 100), seeds 0 .. 11: runs in which the guard admitted a block of eight, and the"
+            " largest coefficient;", "a guard on ONE quiet block (at or below 1.6e-13) for comparison:"]
+    for label, kw in (("%d iterations <= %.1e" % (QUIET, TAU), {}), ("one block <= 1.6e-13", dict(tau=1.6e-13, quiet_need=1))):
+        for cplx in (False, True):
+            admitted, worst, trips = 0, 0.0, 0
+            for seed in range(12):
+                A, v0 = outlier_problem(4000, cplx, seed)
+                with np.errstate(all="ignore"):
+                    L = run_guarded(A, v0, 100, **kw)
+                admitted += L.n8 > 0
+                worst = max(worst, L.maxcoef)
+                trips += L.gate_trips
+            out.append("  %-26s %s: %2d of 12 runs took a block of eight; largest relative coefficient %.1e; gate trips %d" % (
+                label, "complex" if cplx else "real   ", admitted, worst, trips))
+    A, v0 = outlier_problem(4000, False)
+    with np.errstate(all="ignore"):
+        L8, L4 = run_guarded(A, v0, 100), run_loop(A, v0, 100, 4)
+    out.append("  seed 7, real: in eights %d; alpha and beta equal to the m = 4 run bit for bit: %s" % (
+        L8.n8, np.array_equal(L8.al, L4.al) and np.array_equal(L8.be, L4.be)))
+    out += ["", "a component of 1e-6 planted in each position of a block of eight (config-3 type, n = 6000, K = 120; the block starts at",
+            "vector 27 with the guard's default warm-up):"]
+    A, v0 = config3_problem(6000, False)
+    ref = reference(A, v0, 120)
+    for pos in range(8):
+        r = measure8(A, v0, 120, ref, plant=(1e-6, 27, pos))
+        out.append("  position %d: gate trips %d  largest relative coefficient %.1e  max|dalpha| %.1e  max|dbeta| %.1e" % (
+            pos + 1, r["gate_trips"], r["maxcoef"], r["dalpha"], r["dbeta"]))
+    text = "\n".join(out) + "\n"
+    print(text)
+    if "--no-write" not in sys.argv:
+        with open(os.path.join(os.path.dirname(_HERE), "profiles", "block8_model.txt"), "w") as f:
+            f.write(text)
+
+
 def from_pair(P):
     """The block state from a PairLoop's state between sweeps (P complete vectors, r1 and r2 pending with their measured
     coefficients): the stored vectors are used as they are, the two pending ones become a_P and a_{P+1}."""
@@ -363,4 +491,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main8() if "--block8" in sys.argv else main()
