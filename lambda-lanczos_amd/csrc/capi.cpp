@@ -87,11 +87,10 @@ void orth_impl(ll_context* ctx, int64_t n, int64_t nb, const T* basis, int64_t l
   RunList<T> runs;
   runs.ld = ld;
   runs.add(basis, nb);
-  const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
   double* d_htot = nullptr;
   if (h_out && nb > 0) LL_HIP(hipMalloc((void**)&d_htot, (size_t)R * nb * sizeof(double)));
   const DevArray<double> htot(d_htot);
-  const NormRefs refs = E.orth(w, runs, mode, no_tt, E.S(kScalScratch), d_htot);
+  const NormRefs refs = E.orth(w, runs, mode, ThreeTerm<T>::none(), E.S(kScalScratch), d_htot);
   ctx->ensure_pinned(16);
   launch_publish(ctx->pinned.get() + 8, nullptr, refs, ctx->stream);
   ctx->sync();

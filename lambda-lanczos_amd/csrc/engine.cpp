@@ -343,81 +343,68 @@ template <typename T> void Engine<T>::dot_dev(const T* a, const T* b, double* d_
   all_reduce(d_out, R);
 }
 
+// ================================================================= Gram-Schmidt in two sweeps
+// How a pass ends, given where the partial sums of ||w||^2 lie (c0: what is published as the norm before the pass, nullable)
+// and what the loop asked for: a single GPU can leave the fold to the caller's normalisation kernel or publish from the fold;
+// a communicator, or no request, takes the plain fold and the all-reduce.
 template <typename T>
-NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c, double* h_total,
-                         bool first_pass_only, Publish* publish) {
-  TraceRange trace("ll::orth (three-term + Gram-Schmidt + norm)");
+typename Engine<T>::PassEnding Engine<T>::close_pass(const double* partials, int nparts, const double* c0, double* c, const PassRequest* req) {
+  const bool publishes = req && ctx->comm == nullptr;
+  if (publishes && req->caller_normalises) return PartialsPending{partials, nparts, c0, c + 1};
+  if (publishes) {
+    launch_reduce_publish(partials, nparts, c + 1, req->alpha, c0, req->host, ctx->stream);
+    return Published{};
+  }
+  launch_reduce_cols(partials, nparts, 1, c + 1, nullptr, ctx->stream);
+  all_reduce(c + 1, 1);
+  return Folded{};
+}
+
+// three-term update (if any) + ||w||^2 only
+template <typename T>
+typename Engine<T>::PassEnd Engine<T>::three_term_only(T* w, int64_t ld, const ThreeTerm<T>& tt, double* c, const PassRequest* req) {
+  ctx->ensure_partials(kMaxGrid);
+  const int grid = launch_mdot<T>(n_local, w, no_segs<T>(ld), tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, ctx->stream);
+  return PassEnd{plain_norm(c + 1), close_pass(ctx->partials.get(), grid, nullptr, c, req)};
+}
+
+// The reference's operation order (LA:132-144): for every basis vector h = <u,w>; w -= h u, strictly sequential.
+template <typename T> NormRefs Engine<T>::mgs_sweep(T* w, const RunList<T>& runs, const ThreeTerm<T>& tt, double* c, double* h_total) {
   hipStream_t s = ctx->stream;
-  const int nb = runs.total();
-  const bool sharded = ctx->comm != nullptr;
-  const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
-  ctx->ensure_h((size_t)2 * (R * nb + 2));
   double* h1 = ctx->h.get();
-  double* h2 = ctx->h.get() + (R * nb + 2);
-
-  if (nb == 0) {  // three-term update (if any) + ||w||^2 only
-    const BasisSegs<T> none = no_segs<T>(runs.ld);
-    ctx->ensure_partials(kMaxGrid);
-    const int grid = launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-    if (publish && !sharded && publish->can_defer) {
-      *publish = Publish{publish->host, publish->alpha, true, true, true, ctx->partials.get(), grid, c + 1, nullptr};
-    } else if (publish && !sharded) {
-      launch_reduce_publish(ctx->partials.get(), grid, c + 1, publish->alpha, nullptr, publish->host, s);
-      publish->done = true;
-    } else {
-      launch_reduce_cols(ctx->partials.get(), grid, 1, c + 1, nullptr, s);
-      all_reduce(c + 1, 1);
-    }
-    return plain_norm(c + 1);
-  }
-
-  if (mode == LL_ORTH_MGS) {
-    // The reference's operation order (LA:132-144): for every basis vector h = <u,w>; w -= h u, strictly sequential.
-    ctx->ensure_partials((size_t)kMaxGrid * (R + 1));
-    if (tt.u_cur) {
-      const BasisSegs<T> none = no_segs<T>(runs.ld);
-      launch_mdot<T>(n_local, w, none, tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-    }
-    int j = 0, grid = 0;
-    for (auto& r : runs.runs)
-      for (int i = 0; i < r.second; ++i, ++j) {
-        BasisSegs<T> one;
-        one.nseg = 1;
-        one.ld = runs.ld;
-        one.base[0] = r.first + (int64_t)i * runs.ld;
-        one.count[0] = 1;
-        grid = launch_mdot<T>(n_local, w, one, no_tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-        launch_reduce_cols(ctx->partials.get(), grid, R + 1, h1 + R * j, S(kScalSpare), s);
-        all_reduce(h1 + R * j, R);
-        grid = launch_maxpy<T>(n_local, w, one, h1 + R * j, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-      }
-    launch_reduce_cols(ctx->partials.get(), grid, 1, c + 1, nullptr, s);
-    all_reduce(c + 1, 1);
-    if (h_total) LL_HIP(hipMemcpyAsync(h_total, h1, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return plain_norm(c + 1);
-  }
-
-  const std::vector<BasisSegs<T>> groups = runs.groups(max_vecs_per_launch<T>());
-  const NormRefs refs{c, c + 1, c + 2, mode == LL_ORTH_CGS2 ? 1 : 0, ctx->tune.dgks_threshold};
-  const NormRefs* pred = mode == LL_ORTH_CGS2 ? nullptr : &refs;
-  auto count_of = [](const BasisSegs<T>& g) {
-    int t = 0;
-    for (int i = 0; i < g.nseg; ++i) t += g.count[i];
-    return t;
-  };
-  size_t max_cols = 1;
-  for (auto& g : groups) max_cols = std::max(max_cols, (size_t)R * count_of(g) + 1);
-  ctx->ensure_partials((size_t)kMaxGrid * max_cols);
-
-  // ---- pass 1: h = U^H w (+ fused three-term update and ||w||^2), then w -= U h (+ fused ||w||^2)
-  int off = 0;
+  ctx->ensure_partials((size_t)kMaxGrid * (R + 1));
+  if (tt.u_cur) launch_mdot<T>(n_local, w, no_segs<T>(runs.ld), tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
   int grid = 0;
+  for (const BasisSegs<T>& one : runs.groups(1)) {  // one vector per launch
+    grid = launch_mdot<T>(n_local, w, one, ThreeTerm<T>::none(), nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    launch_reduce_cols(ctx->partials.get(), grid, R + 1, h1, S(kScalSpare), s);
+    all_reduce(h1, R);
+    grid = launch_maxpy<T>(n_local, w, one, h1, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    h1 += R;
+  }
+  launch_reduce_cols(ctx->partials.get(), grid, 1, c + 1, nullptr, s);
+  all_reduce(c + 1, 1);
+  if (h_total) LL_HIP(hipMemcpyAsync(h_total, ctx->h.get(), (size_t)R * runs.total() * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return plain_norm(c + 1);
+}
+
+// pass 1: h = U^H w (+ fused three-term update and ||w||^2), then w -= U h (+ fused ||w||^2)
+template <typename T>
+typename Engine<T>::PassEnd Engine<T>::cgs_first_pass(T* w, const std::vector<BasisSegs<T>>& groups, int nb, const ThreeTerm<T>& tt,
+                                                      double* c, bool derive, const PassRequest* req) {
+  hipStream_t s = ctx->stream;
+  const bool sharded = ctx->comm != nullptr;
+  double* h1 = ctx->h.get();
+  size_t max_cols = 1;
+  for (auto& g : groups) max_cols = std::max(max_cols, (size_t)R * g.total() + 1);
+  ctx->ensure_partials((size_t)kMaxGrid * max_cols);
+  int off = 0, grid = 0;
   double* norm_partials = ctx->partials.get();  // where the multi-axpy leaves the partial sums of ||w'||^2
   bool folded_in_maxpy = false;
   for (size_t g = 0; g < groups.size(); ++g) {
-    const int nbg = count_of(groups[g]);
-    const bool last = g + 1 == groups.size();
-    const int mgrid = launch_mdot<T>(n_local, w, groups[g], g == 0 ? tt : no_tt, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    const int nbg = groups[g].total();
+    const int mgrid = launch_mdot<T>(n_local, w, groups[g], g == 0 ? tt : ThreeTerm<T>::none(), nullptr, ctx->partials.get(),
+                                     ctx->tune.blas_small_bytes, s);
     if (groups.size() == 1 && !sharded && ctx->tune.fuse_launches) {
       // small vectors, small grids: the multi-axpy folds the coefficients itself (one launch less per iteration)
       if (!ctx->norm_partials) ctx->norm_partials = ctx->dev_alloc<double>((size_t)kMaxGrid, "norm partials");
@@ -426,15 +413,9 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
       if (folded_in_maxpy) norm_partials = ctx->norm_partials.get();
     }
     if (!folded_in_maxpy)
-      launch_reduce_cols(ctx->partials.get(), mgrid, R * nbg + 1, h1 + R * off, (last && !sharded) ? c : nullptr, s);
+      launch_reduce_cols(ctx->partials.get(), mgrid, R * nbg + 1, h1 + R * off, (g + 1 == groups.size() && !sharded) ? c : nullptr, s);
     off += nbg;
   }
-  // Sharded whole-loop passes: the norm after the pass follows from what the one all-reduce below delivers
-  // (||w'||^2 = ||w||^2 - sum |h_j|^2 for an orthonormal basis) — one all-reduce per iteration less.  Its relative error
-  // is eps * ||w||^2 / ||w'||^2, i.e. a few eps whenever the DGKS test (evaluated on these two numbers) does not ask
-  // for a second pass anyway.  LL_SHARDED_NORM=measured restores the reduced-and-all-reduced partial norms of maxpy.
-  const bool derive_norm = !ctx->tune.sharded_norm_measured;
-  const bool derive = sharded && first_pass_only && mode == LL_ORTH_CGS_DGKS && derive_norm;
   if (sharded) {  // one all-reduce for all coefficients and the norm (latency-sized)
     all_reduce(h1, (size_t)R * nb + 1);
     if (!derive) launch_copy_scalar(c, h1 + R * nb, s);  // (derive: copied by the derive kernel after the update)
@@ -442,58 +423,74 @@ NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm
   off = 0;
   for (size_t g = 0; g < groups.size() && !folded_in_maxpy; ++g) {
     grid = launch_maxpy<T>(n_local, w, groups[g], h1 + R * off, nullptr, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-    off += count_of(groups[g]);
+    off += groups[g].total();
   }
-  if (derive && publish && publish->can_defer) {  // ... inside the caller's normalisation kernel (launch_scale_derive)
-    publish->derive = true;
-    publish->derive_c0 = h1 + R * nb;
-    publish->derive_h = h1;
-    publish->derive_count = R * nb;
-    publish->c0_out = c;
-    publish->c1 = c + 1;
-  } else if (derive) {  // norm + copy of ||w||^2 + (whole-loop drivers) the publish step in one small launch
-    launch_derive_norm(h1 + R * nb, h1, R * nb, c, c + 1, publish ? publish->alpha : nullptr, publish ? publish->host : nullptr, s);
-    if (publish) publish->done = true;
-  } else if (publish && !sharded && first_pass_only && mode == LL_ORTH_CGS_DGKS && publish->can_defer) {
-    *publish = Publish{publish->host, publish->alpha, true, true, true, norm_partials, grid, c + 1, c};
-  } else if (publish && !sharded && first_pass_only && mode == LL_ORTH_CGS_DGKS) {
-    launch_reduce_publish(norm_partials, grid, c + 1, publish->alpha, c, publish->host, s);
-    publish->done = true;
-  } else {
-    launch_reduce_cols(norm_partials, grid, 1, c + 1, nullptr, s);
-    all_reduce(c + 1, 1);
-  }
-  if (first_pass_only && mode == LL_ORTH_CGS_DGKS) {
-    if (h_total) LL_HIP(hipMemcpyAsync(h_total, h1, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return NormRefs{c, c + 1, c + 1, 0};  // final norm = c1; (c0, c1) go to the host through publish
-  }
+  const NormRefs refs{c, c + 1, c + 1, 0};  // final norm = c1
+  if (!derive) return PassEnd{refs, close_pass(norm_partials, grid, c, c, req)};
+  // ... inside the caller's normalisation kernel (launch_scale_derive), or in one small launch: norm + copy of ||w||^2 + (with a
+  // request) the publish step
+  if (req && req->caller_normalises) return PassEnd{refs, DerivePending{h1 + R * nb, h1, R * nb, c, c + 1}};
+  launch_derive_norm(h1 + R * nb, h1, R * nb, c, c + 1, req ? req->alpha : nullptr, req ? req->host : nullptr, s);
+  return PassEnd{refs, req ? PassEnding(Published{}) : PassEnding(Folded{})};
+}
 
-  // ---- pass 2: always (CGS2) or only when ||w|| dropped below ||w_before||/sqrt(2) (DGKS); decided on the device
-  off = 0;
-  for (size_t g = 0; g < groups.size(); ++g) {
-    const int nbg = count_of(groups[g]);
-    const int g2 = launch_mdot<T>(n_local, w, groups[g], no_tt, pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-    launch_reduce_cols(ctx->partials.get(), g2, R * nbg + 1, h2 + R * off, S(kScalSpare), s);
-    off += nbg;
+// pass 2: always (CGS2: pred null) or only when ||w|| dropped below ||w_before||/sqrt(2) (DGKS); decided on the device
+template <typename T>
+void Engine<T>::cgs_second_pass(T* w, const std::vector<BasisSegs<T>>& groups, int nb, const NormRefs* pred, double* c) {
+  hipStream_t s = ctx->stream;
+  double* h2 = ctx->h.get() + (R * nb + 2);
+  int off = 0, grid = 0;
+  for (auto& g : groups) {
+    const int g2 = launch_mdot<T>(n_local, w, g, ThreeTerm<T>::none(), pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    launch_reduce_cols(ctx->partials.get(), g2, R * g.total() + 1, h2 + R * off, S(kScalSpare), s);
+    off += g.total();
   }
-  if (sharded) all_reduce(h2, (size_t)R * nb);
+  if (ctx->comm != nullptr) all_reduce(h2, (size_t)R * nb);
   off = 0;
-  for (size_t g = 0; g < groups.size(); ++g) {
-    grid = launch_maxpy<T>(n_local, w, groups[g], h2 + R * off, pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
-    off += count_of(groups[g]);
+  for (auto& g : groups) {
+    grid = launch_maxpy<T>(n_local, w, g, h2 + R * off, pred, ctx->partials.get(), ctx->tune.blas_small_bytes, s);
+    off += g.total();
   }
   launch_reduce_cols(ctx->partials.get(), grid, 1, c + 2, nullptr, s);
   all_reduce(c + 2, 1);
+}
+
+template <typename T>
+NormRefs Engine<T>::orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c, double* h_total) {
+  TraceRange trace("ll::orth (three-term + Gram-Schmidt + norm)");
+  const int nb = runs.total();
+  ctx->ensure_h((size_t)2 * (R * nb + 2));  // the coefficients of pass 1, then those of pass 2
+  if (nb == 0) return three_term_only(w, runs.ld, tt, c, nullptr).refs;
+  if (mode == LL_ORTH_MGS) return mgs_sweep(w, runs, tt, c, h_total);
+  const std::vector<BasisSegs<T>> groups = runs.groups(max_vecs_per_launch<T>());
+  const NormRefs refs{c, c + 1, c + 2, mode == LL_ORTH_CGS2 ? 1 : 0, ctx->tune.dgks_threshold};
+  const NormRefs* pred = mode == LL_ORTH_CGS2 ? nullptr : &refs;
+  cgs_first_pass(w, groups, nb, tt, c, /* derive: never, the device's test of pass 2 compares measured norms */ false, nullptr);
+  cgs_second_pass(w, groups, nb, pred, c);
   if (h_total) {
-    LL_HIP(hipMemcpyAsync(h_total, h1, (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, s));
-    launch_accumulate_h(h_total, h2, R * nb, pred, s);
+    LL_HIP(hipMemcpyAsync(h_total, ctx->h.get(), (size_t)R * nb * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    launch_accumulate_h(h_total, ctx->h.get() + (R * nb + 2), R * nb, pred, ctx->stream);
   }
   return refs;
 }
 
+template <typename T>
+typename Engine<T>::PassEnd Engine<T>::orth_pass(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c,
+                                                 const PassRequest* req) {
+  const int nb = runs.total();
+  if (nb > 0 && mode != LL_ORTH_CGS_DGKS) return PassEnd{orth(w, runs, mode, tt, c, nullptr), Folded{}};
+  TraceRange trace("ll::orth (three-term + Gram-Schmidt + norm)");
+  ctx->ensure_h((size_t)2 * (R * nb + 2));
+  if (nb == 0) return three_term_only(w, runs.ld, tt, c, req);
+  // Sharded whole-loop passes: the norm after the pass follows from what the one all-reduce of the pass delivers
+  // (||w'||^2 = ||w||^2 - sum |h_j|^2 for an orthonormal basis) — one all-reduce per iteration less.  Its relative error
+  // is eps * ||w||^2 / ||w'||^2, i.e. a few eps whenever the DGKS test (evaluated on these two numbers) does not ask
+  // for a second pass anyway.  LL_SHARDED_NORM=measured restores the reduced-and-all-reduced partial norms of maxpy.
+  return cgs_first_pass(w, runs.groups(max_vecs_per_launch<T>()), nb, tt, c, ctx->comm != nullptr && !ctx->tune.sharded_norm_measured, req);
+}
+
 template <typename T> double Engine<T>::second_pass(T* u, const RunList<T>& runs) {
-  const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
-  const NormRefs r = orth(u, runs, LL_ORTH_CGS_DGKS, no_tt, S(kScalScratch), nullptr, true);
+  const NormRefs r = orth_pass(u, runs, LL_ORTH_CGS_DGKS, ThreeTerm<T>::none(), S(kScalScratch), nullptr).refs;
   launch_scale<T>(n_local, u, 0.0, &r, ctx->stream);
   double shrink = 0.0;
   fetch(r.c1, &shrink, 1);

@@ -9,6 +9,7 @@
 #include <map>
 #include <system_error>
 #include <thread>
+#include <variant>
 
 #include "ll_internal.hpp"
 
@@ -187,38 +188,56 @@ template <typename T> struct Engine {
   int apply_pb(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2);
   int apply_tiled(const T* x, bool x_padded, T* y, double offset, double* dotp, const double* xnorm2);
   int apply_callback(const T* x, T* y, double offset, double* dotp);
-  // Orthogonalise w against the runs with an optional fused three-term update; c = device triple for the norms.
-  // Returns the NormRefs every consumer must use for ||w|| afterwards.  h_total (device, nullable): R*nb doubles.
-  // first_pass_only (whole-loop drivers, LL_ORTH_CGS_DGKS): enqueue pass 1 only and return refs whose final norm is
-  // c1; the driver evaluates the DGKS test on the host from the published (c0, c1) one iteration later and runs the
-  // rare second pass itself (second_pass below) — no predicated no-op launches or collectives per iteration.
-  // publish (nullable; single-GPU loops): where the iteration's four scalars go; when the final norm fold of this
-  // call can carry them (first_pass_only, no communicator) it does and sets publish->done.
-  struct Publish {
-    double* host;         // pinned, device-mapped slot of 4 doubles
-    const double* alpha;  // device scalar
-    bool done;
-    // can_defer (set by the caller): the caller scales w right after orth() and can fold + publish in that kernel
-    // (launch_scale_publish); orth then launches no fold of its own and describes it here (deferred = true).
-    bool can_defer = false;
-    bool deferred = false;
-    const double* partials = nullptr;
-    int nparts = 0;
-    double* c1 = nullptr;
-    const double* c0 = nullptr;
-    // sharded contexts with the derived norm: the caller's normalisation kernel forms ||w'||^2 = *derive_c0 - sum h_i^2
-    // itself and publishes (launch_scale_derive); c0_out / c1 receive the two norms.
-    bool derive = false;
-    const double* derive_c0 = nullptr;
-    const double* derive_h = nullptr;
-    int derive_count = 0;
-    double* c0_out = nullptr;
+  // ---- Gram-Schmidt in two sweeps (multi-dot, multi-axpy) with an optional fused three-term update; c = device triple for the norms
+  // The complete call (the primitive ll_orth_block_*, a restart pass's start vector): orthogonalise w against the runs in `mode`,
+  // the second pass of the CGS modes decided on the device.  Returns the NormRefs every consumer must use for ||w|| afterwards.
+  // h_total (device, nullable): R*nb doubles.
+  NormRefs orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c, double* h_total);
+  // What a whole-loop iteration asks of its pass: where the iteration's four scalars go.
+  struct PassRequest {
+    double* host = nullptr;         // pinned, device-mapped slot of 4 doubles
+    const double* alpha = nullptr;  // device scalar
+    bool caller_normalises = false; // the caller scales w right after the pass and can carry the norm's fold + the publish step there
   };
-  NormRefs orth(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c, double* h_total,
-                bool first_pass_only = false, Publish* publish = nullptr);
+  // How a pass ended: exactly one of four.
+  struct Published {};        // c[1] holds the norm, the four scalars are on their way to the host
+  struct Folded {};           // c[1] holds the all-reduced norm; the caller publishes
+  struct PartialsPending {    // no fold launched: the caller's normalisation kernel folds and publishes (launch_scale_publish, ScaleIn)
+    const double* partials;
+    int nparts;
+    const double* c0;  // ||w||^2 before the pass (null: a pass without Gram-Schmidt has none)
+    double* c1;
+  };
+  struct DerivePending {  // sharded: the caller's normalisation kernel forms ||w'||^2 = *c0_src - sum h_i^2 and publishes (launch_scale_derive)
+    const double* c0_src;
+    const double* h;
+    int count;
+    double* c0_out;  // c0_out / c1 receive the two norms
+    double* c1;
+  };
+  typedef std::variant<Published, Folded, PartialsPending, DerivePending> PassEnding;
+  struct PassEnd {
+    NormRefs refs;
+    PassEnding how;
+  };
+  // The loop's pass (LoopState::enqueue; req nullable: second_pass).  LL_ORTH_CGS_DGKS, and any mode without basis vectors: pass 1
+  // only, ending in whichever of the four ways the request and the context allow; the final norm of refs is c1, and the driver
+  // evaluates the DGKS test on the host from the published (c0, c1) one iteration later and runs the rare second pass itself
+  // (second_pass below) — no predicated no-op launches or collectives per iteration.  LL_ORTH_MGS and LL_ORTH_CGS2 against basis
+  // vectors: the complete call, which ends Folded.
+  PassEnd orth_pass(T* w, const RunList<T>& runs, int mode, const ThreeTerm<T>& tt, double* c, const PassRequest* req);
   // The deferred second pass on the already normalised vector u = w1/||w1||: orthogonalise against `runs` once more,
   // renormalise, and return ||u'||^2 (the factor by which beta^2 shrinks).  Synchronises the stream.
   double second_pass(T* u, const RunList<T>& runs);
+  // the pieces of orth / orth_pass: the three-term update alone (no basis vectors), the sequential sweep of LL_ORTH_MGS, the two
+  // passes of the CGS modes (derive: the norm after pass 1 follows from the all-reduced coefficients, loop passes on sharded
+  // contexts), and how a pass ends given the partial sums of its norm and what the caller asked for
+  PassEnd three_term_only(T* w, int64_t ld, const ThreeTerm<T>& tt, double* c, const PassRequest* req);
+  NormRefs mgs_sweep(T* w, const RunList<T>& runs, const ThreeTerm<T>& tt, double* c, double* h_total);
+  PassEnd cgs_first_pass(T* w, const std::vector<BasisSegs<T>>& groups, int nb, const ThreeTerm<T>& tt, double* c, bool derive,
+                         const PassRequest* req);
+  void cgs_second_pass(T* w, const std::vector<BasisSegs<T>>& groups, int nb, const NormRefs* pred, double* c);
+  PassEnding close_pass(const double* partials, int nparts, const double* c0, double* c, const PassRequest* req);
   // ||v||^2 -> *d_out (device, all-reduced)
   void norm2_dev(const T* v, double* d_out);
   // <a,b> -> d_out[0..R) (device, all-reduced)

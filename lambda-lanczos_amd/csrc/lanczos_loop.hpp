@@ -52,9 +52,15 @@ template <typename T> struct LoopState {
   // What is pending between two enqueues — at most ONE of the three, hence one value:
   struct None {};
   struct DeferredIter {  // iteration k ended without its normalisation / publish: they ride in the next operator kernel
-    typename Engine<T>::Publish pub;
+    typename Engine<T>::PartialsPending sums;
+    double* host;
+    const double* alpha;
     int slot;
     int64_t k;
+    // what the kernel that normalises w_k into u_out folds and publishes (the next operator kernel, or flush's launch_scale_publish);
+    // in ScaleIn's field order: partials, nparts, c1_out, alpha, c0, host, u_out (a field added there must be added here)
+    static_assert(sizeof(ScaleIn<T>) == 7 * sizeof(void*), "ScaleIn has changed: revisit scale_in");
+    ScaleIn<T> scale_in(T* u_out) const { return ScaleIn<T>{sums.partials, sums.nparts, sums.c1, alpha, sums.c0, host, u_out}; }
   };
   struct LaggedIter {  // iteration k ended with the raw w_k: its late update rides in the next sweep (see below)
     int64_t k;
@@ -398,7 +404,7 @@ template <typename T> struct LoopState {
     int off = 0;
     for (auto& grp : runs.groups(max_vecs_per_launch<T>())) {
       launch_maxpy<T>(nl, dst, grp, c + Engine<T>::R * off, nullptr, E.ctx->partials.get(), small_bytes, s);
-      for (int i = 0; i < grp.nseg; ++i) off += grp.count[i];
+      off += grp.total();
     }
   }
   // u_j = (raw - [locked, u_0 .. u_{j-1}] g) / rho in its basis slot, with the two-sweep kernels: a raw vector completed with its
@@ -819,20 +825,11 @@ template <typename T> struct LoopState {
     const double te0 = now_s();
     const int slot = (int)(k % kRingSlots);
     slot_pair[slot] = false;
-    const T* x = U.vec(k - 1);
-    T* y = defer ? work[k & 1].p : U.vec(k);
-    ScaleIn<T> sc;
     const DeferredIter* const prev = pending_as<DeferredIter>();  // iteration k - 1, if its normalisation is pending
-    if (prev) {  // u_{k-1} is still w_{k-1} in its work buffer: this operator kernel normalises it on the fly
-      x = work[(k - 1) & 1].p;
-      sc.partials = prev->pub.partials;
-      sc.nparts = prev->pub.nparts;
-      sc.c1_out = prev->pub.c1;
-      sc.alpha = prev->pub.alpha;
-      sc.c0 = prev->pub.c0;
-      sc.host = prev->pub.host;
-      sc.u_out = U.vec(k - 1);
-    }
+    // (then u_{k-1} is still w_{k-1} in its work buffer: this operator kernel normalises it on the fly)
+    const T* x = prev ? work[(k - 1) & 1].p : U.vec(k - 1);
+    T* y = defer ? work[k & 1].p : U.vec(k);
+    const ScaleIn<T> sc = prev ? prev->scale_in(U.vec(k - 1)) : ScaleIn<T>{};
     timer.mark();
     typename Engine<T>::DeferredAlpha da;
     // the operator kernel that publishes iteration k-1's scalars completes that iteration's event itself where its launcher can
@@ -850,33 +847,36 @@ template <typename T> struct LoopState {
     }
     timer.mark();
     const ThreeTerm<T> tt = three_term(k, slot, da);  // P4
-    typename Engine<T>::Publish pub{pinned_slot(slot), E.S(kScalAlpha + slot), false};
-    pub.can_defer = fuse_launches;
-    const NormRefs refs = E.orth(y, runs, mode, tt, E.S(kScalNorms + 3 * slot), nullptr, true, &pub);  // P5-P7
-    if (pub.deferred && defer) {  // P8 rides in the next operator kernel
-      pending = DeferredIter{pub, slot, k};
-    } else if (pub.deferred) {  // norm fold + publish + normalisation in one launch (P8)
-      launch_scale_publish<T>(nl, y, pub.partials, pub.nparts, pub.c1, pub.alpha, pub.c0, pub.host, s);
+    typename Engine<T>::PassRequest req;
+    req.host = pinned_slot(slot);
+    req.alpha = E.S(kScalAlpha + slot);
+    req.caller_normalises = fuse_launches;
+    const typename Engine<T>::PassEnd end = E.orth_pass(y, runs, mode, tt, E.S(kScalNorms + 3 * slot), &req);  // P5-P7
+    const auto* const sums = std::get_if<typename Engine<T>::PartialsPending>(&end.how);
+    if (sums && defer) {  // P8 rides in the next operator kernel
+      pending = DeferredIter{*sums, req.host, req.alpha, slot, k};
+    } else if (sums) {  // norm fold + publish + normalisation in one launch (P8)
+      launch_scale_publish<T>(nl, y, sums->partials, sums->nparts, sums->c1, req.alpha, sums->c0, req.host, s);
       slot_event(slot);
-    } else if (pub.derive) {  // sharded: derived norm + publish + normalisation in one launch
-      launch_scale_derive<T>(nl, y, pub.derive_c0, pub.derive_h, pub.derive_count, pub.c0_out, pub.c1, pub.alpha, pub.host, s);
+    } else if (const auto* dv = std::get_if<typename Engine<T>::DerivePending>(&end.how)) {  // sharded: derived norm + publish + normalisation in one launch
+      launch_scale_derive<T>(nl, y, dv->c0_src, dv->h, dv->count, dv->c0_out, dv->c1, req.alpha, req.host, s);
       slot_event(slot);
-    } else {
+    } else {  // folded: w is in its basis slot already
       LL_REQUIRE(!defer, "internal: deferred normalisation needs the fused norm fold");
-      if (!pub.done) launch_publish(pub.host, pub.alpha, refs, s);
+      if (std::holds_alternative<typename Engine<T>::Folded>(end.how)) launch_publish(req.host, req.alpha, end.refs, s);
       slot_event(slot);
-      launch_scale<T>(nl, y, 0.0, &refs, s);  // P8
+      launch_scale<T>(nl, y, 0.0, &end.refs, s);  // P8
     }
     timer.mark();
-    refs_prev = refs;
+    refs_prev = end.refs;
     t_enqueue += now_s() - te0;
   }
   // the pending iteration is the last one: normalise it into its basis slot and publish its scalars now
   void flush() {
     const DeferredIter* const d = pending_as<DeferredIter>();
     if (!d) return;
-    launch_scale_publish<T>(nl, U.vec(d->k), d->pub.partials, d->pub.nparts, d->pub.c1, d->pub.alpha, d->pub.c0, d->pub.host, s,
-                            work[d->k & 1].p);
+    const ScaleIn<T> sc = d->scale_in(U.vec(d->k));
+    launch_scale_publish<T>(nl, sc.u_out, sc.partials, sc.nparts, sc.c1_out, sc.alpha, sc.c0, sc.host, s, work[d->k & 1].p);
     slot_event(d->slot);
     pending = None{};
   }

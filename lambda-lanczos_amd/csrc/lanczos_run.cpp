@@ -94,13 +94,12 @@ void lanczos_run(ll_context* ctx, ll_operator* op, const ll_lanczos_params& P_in
         ++j;
       }
     }
-    const ThreeTerm<T> no_tt{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}};
     NormRefs refs0;
     if (L > 0) {
       RunList<T> lk;
       lk.ld = ld;
       lk.add(d_locked.p, L);
-      refs0 = E.orth(U.vec(0), lk, mode, no_tt, E.S(kScalScratch), nullptr);  // LL:233
+      refs0 = E.orth(U.vec(0), lk, mode, ThreeTerm<T>::none(), E.S(kScalScratch), nullptr);  // LL:233
     } else {
       E.norm2_dev(U.vec(0), E.S(kScalScratch) + 1);
       refs0 = E.plain_norm(E.S(kScalScratch) + 1);

@@ -172,6 +172,11 @@ template <typename T> struct BasisSegs {
   int count[kMaxSegs];
   int nseg;
   long long ld;
+  int total() const {  // vectors in all runs
+    int t = 0;
+    for (int i = 0; i < nseg; ++i) t += count[i];
+    return t;
+  }
 };
 
 // The three squared norms of one Gram-Schmidt call, as device scalars:
@@ -864,6 +869,7 @@ template <typename T> struct ThreeTerm {
   const double* alpha_partials = nullptr;
   int alpha_nparts = 0;
   double* alpha_out = nullptr;
+  static ThreeTerm none() { return ThreeTerm{nullptr, nullptr, nullptr, NormRefs{nullptr, nullptr, nullptr, 0}}; }  // no update
 };
 // small_bytes: vectors shorter than this many bytes take the small-vector geometry (Tuning::blas_small_bytes).
 template <typename T>
