@@ -319,6 +319,15 @@ template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
     check(ll_pauli_rdm(op.context().get(), op.get(), (int32_t)s32.size(), s32.data(), psi, reinterpret_cast<double*>(out.data()), sweeps));
     return out;
   }
+  // ll_pauli_rdm_tiled on `op`: the same layout for 4 to 13 sites
+  static std::vector<std::complex<double>> rdm_tiled(const PauliFamilyOperator<T>& op, const std::vector<int>& sites, const T* psi,
+                                                     int64_t* sweeps) {
+    const std::vector<int32_t> s32(sites.begin(), sites.end());
+    const size_t dim = (size_t)1 << (s32.size() >= 4 && s32.size() <= 13 ? s32.size() : 4);  // (a refused count: a small buffer)
+    std::vector<std::complex<double>> out(dim * dim);
+    check(ll_pauli_rdm_tiled(op.context().get(), op.get(), (int32_t)s32.size(), s32.data(), psi, out.data(), sweeps));
+    return out;
+  }
   void adopt_created(ll_operator* op) {
     int64_t n = 0, n_local = 0, n_terms = 0;
     const int rc = ll_op_info(op, &n, &n_local, &n_terms);
@@ -359,6 +368,18 @@ template <typename T> class PauliSpinBasisOperator : public PauliFamilyOperator<
                                                            int64_t* sweeps = nullptr) const {
     if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix: psi must hold local_rows() values");
     return reduced_density_matrix(sites, psi.data(), sweeps);
+  }
+
+  // The same rho_A for 4 to 13 distinct sites — the half chain of a ring of 20 to 26 sites — formed as a rank-K update on the f64
+  // matrix cores (ll_pauli_rdm_tiled): the same layout and the same Hermitian contract, 4^m values (1 GiB at 13 sites).
+  // von_neumann_entropy (entropy.hpp) keeps its limit of 64 x 64: a larger rho goes to an eigen-solver of the caller's.
+  std::vector<std::complex<double>> reduced_density_matrix_tiled(const std::vector<int>& sites, const T* psi, int64_t* sweeps = nullptr) const {
+    return this->rdm_tiled(*this, sites, psi, sweeps);
+  }
+  std::vector<std::complex<double>> reduced_density_matrix_tiled(const std::vector<int>& sites, const std::vector<T>& psi,
+                                                                 int64_t* sweeps = nullptr) const {
+    if ((int64_t)psi.size() != this->local_rows()) throw Error(LL_ERR_INVALID, "reduced_density_matrix_tiled: psi must hold local_rows() values");
+    return reduced_density_matrix_tiled(sites, psi.data(), sweeps);
   }
 
  protected:

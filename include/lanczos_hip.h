@@ -76,7 +76,9 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_pauli_block_expand and ll_pauli_block_project
                              *    (a state between a symmetry block (8) - (10) and the basis of (6) or (7)): untyped;
                              *    also additive under minor 5, with the same note — ll_pauli_block_transfer (a sum of Pauli strings
-                             *    applied between two momentum blocks (8) or (9)): untyped */
+                             *    applied between two momentum blocks (8) or (9)): untyped;
+                             *    also additive under minor 5, with the same note — ll_pauli_rdm_tiled (the reduced density matrix of
+                             *    4 to 13 sites as a rank-K update on the f64 matrix cores, into host or device memory): untyped */
 
 enum {
   LL_OK = 0,
@@ -635,6 +637,46 @@ int ll_pauli_block_transfer(ll_context* ctx, const ll_operator* source, const ll
  * atomics: for a given tile / block size the same bits run to run, for a host and a device psi and for every alignment of psi. */
 int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi,
                  double* out_host, int64_t* sweeps_out);
+
+/* REDUCED DENSITY MATRIX of 4 to 13 sites — the half chain of a ring of 20 to 26 sites — as a Hermitian rank-K update on the f64
+ * matrix cores (an addition within minor 5, untyped: the storage type is the operator's).  The same numbers as ll_pauli_rdm,
+ *     rho[a][a'] = sum_e psi(a, e) conj(psi(a', e)),     m = n_sub, a, a' in [0, 2^m),  bit k of a = site sites_host[k],
+ * formed as rho = F F^H with F the 2^m x 2^(n_sites - m) matrix of fibres: rho is cut into macro-tiles of 64 x 64, one workgroup
+ * per tile of the upper triangle and slice of K stages KC environment configurations at a time in LDS and multiplies them with
+ * v_mfma_f64_16x16x4_f64; a finishing kernel folds the slices and writes both triangles.  NOTHING IS DIVIDED BY <psi|psi>.
+ *   op        : from ll_op_create_pauli_* (6) or ll_op_create_pauli_sector_* (7), as for ll_pauli_rdm.
+ *   sites_host: n_sub DISTINCT sites in [0, n_sites), in any order; 4 <= n_sub <= min(13, n_sites) — from 4 sites on 2^m is a multiple
+ *               of the 16-row MFMA tile (m = 4, 5, 6 overlap ll_pauli_rdm on purpose: a cross-check; one macro-tile, zero-padded at
+ *               m = 4, 5).  WHY 13: out is 1 GiB there, and above it the eigen-decomposition of rho (O(8^m) on the host) limits the
+ *               workflow, not this kernel; half chains of 28 to 30 sites need the singular values of F instead.
+ *   psi       : n_local values of the operator's storage type, host or device memory (decided per pointer).  Never modified.
+ *   out       : 2 * 4^m doubles, row-major rho[a][a'] with interleaved (re, im), HOST OR DEVICE memory (decided per pointer; a host
+ *               out is staged in a device buffer of the same size).  The call returns with out filled.  EXACTLY HERMITIAN, as
+ *               ll_pauli_rdm: only a <= a' is computed, out[a'][a] has the bits of out[a][a'] in its real part and the negated
+ *               imaginary part, every zero is +0.0; the diagonal's imaginary parts and, for real storage, all of them are +0.0.
+ *               For an operator of (7): every entry with popcount(a) != popcount(a') is +0.0 by rule, and so is every row a with
+ *               n_down - popcount(a) outside [0, n_sites - m].
+ *   sweeps_out: nullable; 1 when the kernels ran.  Untouched by a refused call.
+ * REFUSALS (LL_ERR_INVALID, each naming its cause, all before the device is touched): a null argument (ctx, op, sites_host, psi,
+ * out); a context with a communicator; every other operator kind, named in the message — the symmetry blocks (8) - (10) with the
+ * advice to expand the state (ll_pauli_block_expand) and measure on the target; n_sub outside 4 .. 13 or above n_sites; a site
+ * outside [0, n_sites); a repeated site (the message names its index).
+ * BYTES per call, full space: psi is read once per macro-tile row and column it enters, nb + 1 times with nb = 2^max(0, m - 6)
+ * blocks per side (mostly from the caches: a K-step of a block is read by its nb + 1 tiles at about the same time), plus the
+ * partials, 8 P T S bytes written and read once — P = 4096 doubles per macro-tile (8192 for complex storage), T = nb (nb + 1) / 2
+ * macro-tiles, S = ksplit slices — plus 32 * 4^m bytes of out.  WORKSPACE: the partials, allocated for the call from the context's
+ * buffer cache: S is the smallest power of two with T S >= 512 (twice the CUs) that the K-steps allow and that keeps 8 P T S
+ * within 64 MiB (the unstable key pauli_rdm_tiled_ksplit forces S); with S = 1 the partials are the upper triangle of rho, up to
+ * 516 MiB at m = 13 in complex storage.  A host psi or out adds its staged copy.  LDS: 4 planes (2 for real storage) of KC x 80
+ * doubles, 40 KiB at the default KC = 16 (key pauli_rdm_tiled_kc: 4, 8 or 16).  A sector gathers through the operator's rank
+ * tables; the 2^(n_sites - m) configurations are enumerated and the states outside the sector multiplied as zeros.
+ * ACCURACY: float inputs are widened to double (exact); every product and sum is formed in double by the matrix core, four
+ * environment configurations per instruction, KC per K-step, the K-steps of a slice in ascending order, and the slices are folded
+ * in slice order — each part of each entry is held to the bound of a double-accumulated dot product of its two fibres psi(a, .),
+ * psi(a', .) by tests/test_gpu_pauli_rdm_tiled.py.  No atomics: for a given (KC, ksplit) the same bits run to run, for a host and
+ * a device psi, for a host and a device out and for every alignment of psi. */
+int ll_pauli_rdm_tiled(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi, void* out,
+                       int64_t* sweeps_out);
 
 /* Which SpMV kernel a CSR operator uses (both are bit-reproducible run to run; their results agree to rounding IN THE
  * NORM-WISE SENSE stated below):

@@ -47,6 +47,7 @@ from .engine import (  # noqa: F401
     pauli_expect,
     pauli_expect_block,
     pauli_rdm,
+    pauli_rdm_tiled,
     partition,
     recur_accum,
     recur_accum_multi,

@@ -238,6 +238,7 @@ PROTOTYPES = {
     "ll_pauli_block_project": (C.c_int, [vp, vp, vp, vp, vp]),
     "ll_pauli_block_transfer": (C.c_int, [vp, vp, vp, i64, P(PauliTerm), vp, vp, P(f64)]),   # untyped: the operators' type
     "ll_pauli_rdm": (C.c_int, [vp, vp, C.c_int32, P(C.c_int32), vp, P(f64), P(i64)]),  # untyped: the operator's type
+    "ll_pauli_rdm_tiled": (C.c_int, [vp, vp, C.c_int32, P(C.c_int32), vp, vp, P(i64)]),  # out: host or device memory
     "ll_expo_taylor_run_d":(C.c_int, [vp, vp, P(ExpoParams), f64, vp, vp, P(i64)]),
     "ll_expo_taylor_run_z": (C.c_int, [vp, vp, P(ExpoParams), f64, f64, vp, vp, P(i64)]),
 }

@@ -549,5 +549,9 @@ int ll_pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const in
                  double* out_host, int64_t* sweeps_out) {
   return guarded([&] { pauli_rdm(ctx, op, n_sub, sites_host, psi, out_host, sweeps_out); });
 }
+int ll_pauli_rdm_tiled(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites_host, const void* psi, void* out,
+                       int64_t* sweeps_out) {
+  return guarded([&] { pauli_rdm_tiled(ctx, op, n_sub, sites_host, psi, out, sweeps_out); });
+}
 
 }  // extern "C"

@@ -83,6 +83,8 @@ bool tuning_apply(Tuning& t, const std::string& key, const std::string& v) {
   else if (key == "force_rp64") t.force_rp64 = e ? false : to_flag(v);
   else if (key == "spmv_tile_balance") t.spmv_tile_balance = e ? d.spmv_tile_balance : to_flag(v);
   else if (int Tuning::*bits = pauli_bits_key(key)) t.*bits = e ? d.*bits : (int)std::max<long long>(0, std::min<long long>(30, to_ll(v)));
+  else if (key == "pauli_rdm_tiled_kc") t.pauli_rdm_tiled_kc = e ? d.pauli_rdm_tiled_kc : (int)std::max<long long>(0, std::min<long long>(1 << 20, to_ll(v)));
+  else if (key == "pauli_rdm_tiled_ksplit") t.pauli_rdm_tiled_ksplit = e ? d.pauli_rdm_tiled_ksplit : (int)std::max<long long>(0, std::min<long long>(1 << 20, to_ll(v)));
   else if (key == "stencil_vec") t.stencil_vec = e ? d.stencil_vec : to_flag(v);
   else if (key == "tl_force") t.tl_force = e ? false : to_flag(v);
   else if (key == "tl_xcd") t.tl_xcd_order = e ? d.tl_xcd_order : to_flag(v);

@@ -269,6 +269,8 @@ struct Tuning {
   int pauli_sector_block_bits = -1;  // key pauli_sector_block_bits = b: the S_z-sector kernel's workgroups take blocks of 2^b indices (-1: kPauliSectorBlockBits); tests force many blocks on small sectors
   int pauli_rdm_tile_bits = -1;    // key pauli_rdm_tile_bits = t: the reduced-density-matrix kernel's tiles hold 2^t states (-1: what fills kPauliTileBytes of LDS with the super-tile); tests force subsystem sites above the tile on small problems
   int pauli_rdm_block_bits = -1;   // key pauli_rdm_block_bits = b: its sector form gathers 2^b environment configurations per LDS batch (-1: what fills kPauliTileBytes)
+  int pauli_rdm_tiled_kc = 0;      // key pauli_rdm_tiled_kc = KC: the tiled reduced-density-matrix kernel stages KC environment configurations per K-step (0: 16; a power of two in 4 .. 16, others are lowered to one); tests force many K-steps on small problems
+  int pauli_rdm_tiled_ksplit = 0;  // key pauli_rdm_tiled_ksplit = s: its K-steps are dealt to s slices (0: what fills twice the CUs within 64 MiB of partials; lowered to a power of two that the K-steps allow)
   int test_workspace_fill = -1;    // key test_workspace_fill = 0..255: every device buffer of floating-point element type that the context hands out (dev_alloc<T>, Krylov slabs, DevBuf<T>; new or from the slab cache) is filled with that byte before use (-1, unset: not touched); tests poison the workspace with it
   bool stencil_vec = true;         // key stencil_vec = 0: scalar lattice kernel on shapes the vector kernel would take
   double stall_trace_ms = -1.0;    // key stall_trace = ms: print where a whole-loop call longer than this spent its time
@@ -700,7 +702,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_block_transfer.hip, pauli_rdm.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_block_transfer.hip, pauli_rdm.hip, pauli_rdm_tiled.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -835,6 +837,10 @@ void pauli_block_transfer(ll_context* ctx, const ll_operator* source, const ll_o
 // ll_pauli_rdm (pauli_rdm.hip; planned by pauli_rdm_plan.hpp): every check, then the one sweep on the operator's storage type
 void pauli_rdm(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, double* out,
                int64_t* sweeps_out);
+// ll_pauli_rdm_tiled (pauli_rdm_tiled.hip; planned by pauli_rdm_tiled_plan.hpp): every check, then the rank-K update on the f64
+// matrix cores and its finishing kernel on the operator's storage type; out is host or device memory
+void pauli_rdm_tiled(ll_context* ctx, const ll_operator* op, int32_t n_sub, const int32_t* sites, const void* psi, void* out,
+                     int64_t* sweeps_out);
 // y += offset * x ; partials of Re<x,y> (post-pass for callback operators).
 template <typename T>
 int launch_offset_dot(int64_t n, const T* x, T* y, double offset, double* dot_partials, hipStream_t s);

@@ -595,6 +595,36 @@ def pauli_rdm(op, psi, sites, return_sweeps=False):
     return (out, int(sweeps.value)) if return_sweeps else out
 
 
+def pauli_rdm_tiled(op, psi, sites, out=None, return_sweeps=False):
+    """ll_pauli_rdm_tiled: the reduced density matrix of pauli_rdm for 4 to 13 distinct sites (bit k of a is sites[k]), formed as
+    the rank-K update rho = F F^H on the f64 matrix cores — the half chain of a ring of 20 to 26 sites.  Returns a complex128
+    array of shape (2^m, 2^m); or fills `out`, a DeviceArray (anything with .ptr, .dtype, .shape that names device memory) of
+    4^m complex128 values or a contiguous writeable complex128 numpy array of that size, and returns it.  Exactly Hermitian, not
+    divided by <psi|psi>.  psi as for pauli_rdm.  With return_sweeps also the number of passes (1).  The library refuses every
+    operator but PauliOperator and PauliSectorOperator, and a count outside 4 .. 13."""
+    sites = [int(s) for s in sites]
+    m = len(sites)
+    arr = (C.c_int32 * max(m, 1))(*sites)
+    keep, p = _vector_arg(psi, op.n_local, op.dtype, *_PSI_ERRORS)
+    dim = 1 << (m if 4 <= m <= 13 else 4)   # (a count the library refuses still gets a buffer, a small one)
+    if out is None:
+        out = np.zeros((dim, dim), dtype=np.complex128)
+    out, q = _out_arg(out, dim * dim, np.dtype(np.complex128))
+    sweeps = C.c_int64(0)
+    check(lib().ll_pauli_rdm_tiled(op.ctx.handle, op.handle, m, arr, p, q, C.byref(sweeps)))
+    del keep
+    return (out, int(sweeps.value)) if return_sweeps else out
+
+
+def _block_rdm_tiled(block, c, sites, target, return_sweeps=False):
+    buf = block.ctx.empty(target.n_local, block.dtype)   # the expanded state: a context-owned device buffer, freed below
+    try:
+        pauli_block_expand(block, c, target, out=buf)
+        return pauli_rdm_tiled(target, buf, sites, None, return_sweeps)
+    finally:
+        buf.free()
+
+
 def entanglement_entropy(rho):
     """The von Neumann entropy -sum lambda ln lambda of rho / tr rho (host numpy: numpy.linalg.eigvalsh of the Hermitian
     matrix; eigenvalues <= 0 contribute 0)."""
@@ -625,6 +655,10 @@ class PauliOperator(_PauliFamily):
         """rho_A = Tr_env |psi><psi| of the sites `sites` (at most 6), complex128 of shape (2^m, 2^m), not normalised (pauli_rdm)."""
         return pauli_rdm(self, psi, sites, return_sweeps)
 
+    def reduced_density_matrix_tiled(self, psi, sites, out=None, return_sweeps=False):
+        """rho_A of 4 to 13 sites on the f64 matrix cores, complex128 of shape (2^m, 2^m) or `out` filled (pauli_rdm_tiled)."""
+        return pauli_rdm_tiled(self, psi, sites, out, return_sweeps)
+
 
 class PauliSectorOperator(_PauliFamily):
     """The same Hamiltonian on one magnetisation sector (ll_op_create_pauli_sector_*): the basis is the comb(n_sites, n_down)
@@ -639,6 +673,7 @@ class PauliSectorOperator(_PauliFamily):
     inf_norm = PauliOperator.inf_norm
     expectation = PauliOperator.expectation  # psi on the sector's basis; a partner outside the sector contributes nothing
     reduced_density_matrix = PauliOperator.reduced_density_matrix  # popcount(a) != popcount(a') is exactly +0.0
+    reduced_density_matrix_tiled = PauliOperator.reduced_density_matrix_tiled
 
 
 class PauliMomentumOperator(_PauliFamily):
@@ -681,6 +716,10 @@ class PauliMomentumOperator(_PauliFamily):
         target.reduced_density_matrix (pauli_rdm) and the buffer freed.  entanglement_entropy takes the result."""
         return _block_rdm(self, c, sites, target, return_sweeps)
 
+    def reduced_density_matrix_tiled(self, c, sites, target, return_sweeps=False):
+        """The same for 4 to 13 sites: expand, target.reduced_density_matrix_tiled (pauli_rdm_tiled), free."""
+        return _block_rdm_tiled(self, c, sites, target, return_sweeps)
+
 
 class PauliMomentumFullOperator(_PauliFamily):
     """One momentum block of the full 2^n_sites space of a ring (ll_op_create_pauli_momentum_full_*): the operator B^H H B with
@@ -700,6 +739,7 @@ class PauliMomentumFullOperator(_PauliFamily):
     project = PauliMomentumOperator.project
     transfer = PauliMomentumOperator.transfer
     reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
+    reduced_density_matrix_tiled = PauliMomentumOperator.reduced_density_matrix_tiled
 
 
 class PauliSymmetricOperator(_PauliFamily):
@@ -723,6 +763,7 @@ class PauliSymmetricOperator(_PauliFamily):
     project = PauliMomentumOperator.project
     transfer = PauliMomentumOperator.transfer  # exists to surface the library's refusal: semi-momentum states are not built
     reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
+    reduced_density_matrix_tiled = PauliMomentumOperator.reduced_density_matrix_tiled
 
 
 class HostOperator(_Operator):
