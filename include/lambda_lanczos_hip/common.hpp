@@ -297,7 +297,7 @@ template <typename T> class LatticeOperator : public DeviceOperator<T> {
   }
 };
 
-// What the five Pauli-sum operators below share: size() and local_rows() are read from the created operator (ll_op_info), and
+// What the six Pauli-sum operators below share: size() and local_rows() are read from the created operator (ll_op_info), and
 // device_bytes().  PauliSpinBasisOperator and PauliRingBlockOperator add the measurements of the two kinds of basis.
 template <typename T> class PauliFamilyOperator : public DeviceOperator<T> {
  public:
@@ -387,7 +387,8 @@ template <typename T> class PauliSpinBasisOperator : public PauliFamilyOperator<
 };
 
 // The operators whose basis is a symmetry block of a ring — PauliMomentumOperator, PauliMomentumFullOperator and
-// PauliSymmetricOperator: vectors hold coefficients on the block's representatives, Psi = B c with B the block's isometry.
+// PauliSymmetricOperator — or of a torus, PauliTorusOperator (expectation() only: the library refuses the rest for that kind):
+// vectors hold coefficients on the block's representatives, Psi = B c with B the block's isometry.
 template <typename T> class PauliRingBlockOperator : public PauliFamilyOperator<T> {
  public:
   // coef * Re <Psi| P |Psi> for every observable, Psi = B psi the state that the size() coefficients psi on the block's basis stand
@@ -548,6 +549,29 @@ template <typename T> class PauliSymmetricOperator : public PauliRingBlockOperat
     ll_operator* op = nullptr;
     check(abi<T>::create_pauli_symmetric(ctx.get(), (int32_t)n_sites, (int32_t)n_down, (int32_t)momentum, (int32_t)parity,
                                          (int32_t)inversion, (int64_t)terms.size(), terms.data(), &op));
+    this->adopt_created(op);
+  }
+};
+
+// One translation block (mx, my) of an lx x ly torus: site (x, y) is bit x + lx y, 0 <= mx < lx, 0 <= my < ly; n_down = -1 is the
+// full space, else the S_z sector.  H must commute with both one-site translations (creation names the direction and the term at
+// fault).  Vectors hold the D amplitudes of |r; mx my>, r running over the admitted representatives of the translation orbits,
+// ascending; size() returns D.  Real T takes mx = 0 or lx / 2 and my = 0 or ly / 2 only; an empty block is refused.  The image
+// is O(D): device_bytes() <= 8 D + 192 KiB; inf_norm() returns sum_t |coef_t|, a bound of every |eigenvalue|; expectation()
+// measures on the block; the library refuses expand, project, transfer and the density matrices for this kind
+// (ll_op_create_pauli_torus: one untyped entry point, the storage type goes as a character).
+template <typename T> class PauliTorusOperator : public PauliRingBlockOperator<T> {
+ public:
+  PauliTorusOperator(int lx, int ly, int mx, int my, const std::vector<PauliTerm>& terms, int n_down = -1,
+                     Context ctx = Context::default_context())
+      : PauliRingBlockOperator<T>(ctx) {
+    constexpr int32_t storage = std::is_same<T, double>::value                 ? 'd'
+                                : std::is_same<T, std::complex<double>>::value ? 'z'
+                                : std::is_same<T, float>::value                ? 's'
+                                                                               : 'c';
+    ll_operator* op = nullptr;
+    check(ll_op_create_pauli_torus(ctx.get(), storage, (int32_t)lx, (int32_t)ly, (int32_t)n_down, (int32_t)mx, (int32_t)my,
+                                   (int64_t)terms.size(), terms.data(), &op));
     this->adopt_created(op);
   }
 };

@@ -78,7 +78,10 @@ extern "C" {
                              *    also additive under minor 5, with the same note — ll_pauli_block_transfer (a sum of Pauli strings
                              *    applied between two momentum blocks (8) or (9)): untyped;
                              *    also additive under minor 5, with the same note — ll_pauli_rdm_tiled (the reduced density matrix of
-                             *    4 to 13 sites as a rank-K update on the f64 matrix cores, into host or device memory): untyped */
+                             *    4 to 13 sites as a rank-K update on the f64 matrix cores, into host or device memory): untyped;
+                             *    also additive under minor 5, with the same note — ll_op_create_pauli_torus (the translation blocks
+                             *    of an Lx x Ly torus, kind (11)): ONE untyped entry point, the storage type is an argument;
+                             *    ll_pauli_expect_block accepts its operators */
 
 enum {
   LL_OK = 0,
@@ -472,6 +475,55 @@ int ll_op_create_pauli_symmetric_s(ll_context* ctx, int32_t n_sites, int32_t n_d
 int ll_op_create_pauli_symmetric_c(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity,
                                    int32_t inversion, int64_t n_terms, const ll_pauli_term* terms_host, ll_operator** out);
 
+/* (11) the same sum on ONE TRANSLATION BLOCK OF AN Lx x Ly TORUS — the first block outside the ring: square-lattice Heisenberg
+ *     and J1-J2 clusters (4 x 4, 6 x 4, 6 x 5), the transverse-field Ising model on a torus — of the full 2^n space (n_down = -1)
+ *     or of one S_z sector (0 <= n_down <= n), n = Lx Ly.  UNTYPED: storage is 'd', 'z', 's' or 'c' (the character codes of
+ *     ll_recur_accum_scaled), with the meaning of the typed suffixes.  Conventions: site (x, y) is bit x + Lx y.  T_x rotates each
+ *     of the Ly fields of Lx bits LEFT by one, site (x, y) -> ((x + 1) mod Lx, y); T_y rotates the n-bit word LEFT by Lx bits,
+ *     site (x, y) -> (x, (y + 1) mod Ly).  The group is G = {T_x^a T_y^b}, |G| = n elements, with the character
+ *         chi(T_x^a T_y^b) = e^(-2 pi i (mx a / Lx + my b / Ly)),        0 <= mx < Lx, 0 <= my < Ly.
+ *     The representative of a G-orbit is its smallest integer; it is admitted iff chi(g) = 1 for every g of its stabiliser and, for
+ *     n_down >= 0, iff its popcount is n_down — on a torus the orbit's length alone does not decide that (a stabiliser generated
+ *     by a diagonal translation).  The basis is the admitted representatives r in ASCENDING order, D of them (about 2^n / n), each
+ *     standing for |r; mx my> = N_r^(-1/2) sum_{g in G} chi(g) g |r>.  With B the matrix of these vectors — an isometry — THE
+ *     OPERATOR IS B^H H B, H the operator of (6) (of (7) for n_down >= 0).  Equivalent gather form, which the kernel evaluates:
+ *     for representative a (number i) and every group of terms with x mask X_g write a ^ X_g = h b with b the representative; if
+ *     b is in the basis,
+ *         y(i) += w_g(a) sqrt(R_a / R_b) chi(h) v(number of b),
+ *     R = |G| / |stabiliser| the orbit length (at most 30), w_g the weight of (6), groups in ascending mask order.  With Ly = 1
+ *     (or Lx = 1) the torus is the ring of (10): the result has the same bits as (10) with parity = inversion = 0, the same
+ *     n_down and momentum = mx (my).
+ *     LIMITS: lx, ly >= 1 and lx ly <= 30; D < 2^27 - 1.  The real types ('d', 's') need 2 mx mod Lx = 0 and 2 my mod Ly = 0,
+ *     besides the even-nY rule; 'z' / 'c' take every (mx, my).
+ *     REFUSALS (LL_ERR_INVALID, each naming its cause): those of (6); a storage code other than the four; lx or ly below 1, or
+ *     lx ly above 30; mx outside [0, lx) or my outside [0, ly); a real type with 2 mx mod Lx != 0 or 2 my mod Ly != 0; n_down
+ *     outside [-1, n]; n_down >= 0 with an H that does not conserve S_z (the rule and the message of (7)); an H that does not
+ *     commute with T_x, or with T_y (with equal masks merged, moving every term's masks by one site must map the term set onto
+ *     itself with exactly equal coefficients: the direction and the (x_mask, z_mask) of the first term at fault are named; open
+ *     boundaries in either direction — an open cylinder — and a ring's Hamiltonian given as a torus are refused this way); an
+ *     EMPTY block; a context of more than one rank.
+ *     The image is O(D), with no table over the 2^n states nor over the sector: the term tables, the D representatives (4 D
+ *     bytes), their orbit lengths (D bytes), the bucket table of (9) (at most D / 2 bytes), sqrt(R_a / R_b) for every pair (32^2
+ *     doubles) and the n phases.  ll_op_device_bytes counts all of it and stays below 8 D + 192 KiB.  Creation visits the states
+ *     of the space (or of the sector) on the host, on at most 16 threads, leaving each at the first image below it: O(2^n) steps.
+ *     The kernel finds a partner's representative in registers — n steps, b outer and a inner, one masked two-shift rotation
+ *     each, about 9 integer operations per image and partner —, counts the elements that reach it (the stabiliser's size, hence
+ *     R_b, without a load), finds its number by the bounded search of (9) and takes it iff the entry found equals it.
+ *     First apply and creation times (6 x 4 and 6 x 5 at half filling): DESIGN.md section 3.1; UNMEASURED: the block size of the
+ *     kernel (key pauli_torus_block_bits).
+ *     ACCURACY: that of (8) - (10) — component-wise against the exact block; w_g summed in double as in (6), times
+ *     sqrt(R_a / R_b) where the orbit lengths differ, times the phase where (mx, my) != (0, 0) (one table entry e^(-2 pi i k / n),
+ *     k = (mx a Ly + my b Lx) mod n, exact on the axes), one double fma per group, one rounding to T; the single-type
+ *     storage-product contract is not claimed; the same bits run to run and for every block size, grid and buffer alignment.
+ *     Queries: as (10) — ll_op_info reports n = n_local = D and the number of TERMS as nnz_local; ll_op_inf_norm returns
+ *     sum_t |coef_t|, a bound of EVERY |EIGENVALUE| of the block; ll_op_set_accuracy / ll_op_select_spmv answer LL_ERR_INVALID,
+ *     ll_op_accuracy the component-wise class.  ll_pauli_expect_block measures on the block; ll_pauli_block_expand,
+ *     ll_pauli_block_project, ll_pauli_block_transfer and the density-matrix entry points answer LL_ERR_INVALID naming this kind
+ *     (not built).  Point-group symmetries of the torus, spin inversion on top of it and tilted clusters are not built. */
+int ll_op_create_pauli_torus(ll_context* ctx, int32_t storage /* 'd','z','s','c' */, int32_t lx, int32_t ly,
+                             int32_t n_down /* -1: full space */, int32_t mx, int32_t my, int64_t n_terms,
+                             const ll_pauli_term* terms_host, ll_operator** out);
+
 /* EXPECTATION VALUES OF PAULI STRINGS on a state of the basis of (6) or (7), many per sweep over the state (an addition within
  * minor 5, untyped: the storage type is the operator's).  The kernels read psi and write scalars: no n-sized output vector.
  * With the conventions of (6), P|s> = i^nY (-1)^popcount(s & z) |s ^ x>, observable j = (x_j, z_j, coef_j) is answered
@@ -511,13 +563,14 @@ int ll_pauli_expect(ll_context* ctx, const ll_operator* op, int64_t n_obs, const
  * Pbar_j = (1 / |G|) sum_h h P_j h^-1 — images: both masks rotated / bit-reversed / the sign (-1)^popcount(z) — which commutes
  * with G; the kernel forms sum_a Re[conj(c_a) (Pbar_j c)(a)] with the gather of the operator's own apply, in registers: no n-sized
  * workspace for a device psi, up to 32 observables per sweep over c.
- *   op        : from ll_op_create_pauli_momentum_* (8), _momentum_full_* (9) or _symmetric_* (10).  It defines the basis, the
- *               group and the storage type; the Hamiltonian's own terms play no part.
+ *   op        : from ll_op_create_pauli_momentum_* (8), _momentum_full_* (9), _symmetric_* (10) or ll_op_create_pauli_torus (11).  It
+ *               defines the basis, the group and the storage type; the Hamiltonian's own terms play no part.  For (11) G is the
+ *               Lx Ly translations of the torus: both masks moved by the same T_x^a T_y^b, no signs, nothing cancels.
  *   obs_host, psi, out_host: as ll_pauli_expect.  Answered exactly +0.0 without a sweep: an observable all of whose images cancel
  *               (the flip is in use and popcount(z) is odd), an odd nY on a real storage type, and with a fixed S_z sector an x
  *               mask with an odd popcount.  A string that leaves the sector or the block needs no special case.
  *   sweeps_out: nullable; ceil(S / 32), S = the observables that are not identically zero, in the caller's order.
- * REFUSALS (LL_ERR_INVALID, each naming its cause): those of ll_pauli_expect; every operator kind but (8) - (10), named in the
+ * REFUSALS (LL_ERR_INVALID, each naming its cause): those of ll_pauli_expect; every operator kind but (8) - (11), named in the
  * message — for (6) and (7) the message points to ll_pauli_expect.
  * ACCURACY: all arithmetic in double (float inputs widened): per state one fma per distinct image string and group, then
  * Re[conj(c_a) .], summed per wave, workgroup and grid in an order that depends on the block size (the tuning key of the

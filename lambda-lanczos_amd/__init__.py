@@ -28,6 +28,7 @@ from .engine import (  # noqa: F401
     PauliMomentumOperator,
     PauliSectorOperator,
     PauliSymmetricOperator,
+    PauliTorusOperator,
     StencilOperator,
     LambdaLanczos,
     continued_fraction,

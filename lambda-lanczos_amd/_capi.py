@@ -183,6 +183,8 @@ PROTOTYPES = {
                                                  P(vp)]),
     "ll_op_create_pauli_symmetric_z": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, P(PauliTerm),
                                                  P(vp)]),
+    "ll_op_create_pauli_torus": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64, P(PauliTerm),
+                                           P(vp)]),  # untyped: storage is an argument
     "ll_op_create_host_d": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_host_z": (C.c_int, [vp, i64, HOST_MV_FN, vp, P(vp)]),
     "ll_op_create_device_d": (C.c_int, [vp, i64, DEV_MV_FN, vp, P(vp)]),

@@ -258,6 +258,13 @@ LL_CAPI_TYPES(LL_DEF_OP_CREATE_PAULI_MOMENTUM_FULL)
                                            create_pauli_symmetric<T>(ctx, n_sites, n_down, momentum, parity, inversion,    \
                                                n_terms, terms, out))
 LL_CAPI_TYPES(LL_DEF_OP_CREATE_PAULI_SYMMETRIC)
+// untyped: the storage type is named by a character, as the untyped primitives name it
+int ll_op_create_pauli_torus(ll_context* ctx, int32_t storage, int32_t lx, int32_t ly, int32_t n_down, int32_t mx, int32_t my,
+                             int64_t n_terms, const ll_pauli_term* terms, ll_operator** out) {
+  return guarded([&] {
+    for_storage_char(storage, [&](auto t) { create_pauli_torus<decltype(t)>(ctx, lx, ly, n_down, mx, my, n_terms, terms, out); });
+  });
+}
 // every host callback is stored under the void* signature (same ABI, only the pointee types differ): an identity cast for _z / _c
 #define LL_DEF_OP_CREATE_HOST(sfx, T, P, H)                                                        \
   LL_TYPED(op_create_host, sfx, (ll_context* ctx, int64_t n, H fn, void* user, ll_operator** out), \

@@ -30,6 +30,7 @@ int Tuning::*pauli_bits_key(const std::string& key) {
       {"pauli_momentum_block_bits", &Tuning::pauli_momentum_block_bits},
       {"pauli_momentum_full_block_bits", &Tuning::pauli_momentum_full_block_bits},
       {"pauli_symmetric_block_bits", &Tuning::pauli_symmetric_block_bits},
+      {"pauli_torus_block_bits", &Tuning::pauli_torus_block_bits},
       {"pauli_block_expand_block_bits", &Tuning::pauli_block_expand_block_bits},
       {"pauli_block_project_block_bits", &Tuning::pauli_block_project_block_bits},
       {"pauli_rdm_tile_bits", &Tuning::pauli_rdm_tile_bits}, {"pauli_rdm_block_bits", &Tuning::pauli_rdm_block_bits}};

@@ -263,6 +263,7 @@ struct Tuning {
   int pauli_tile_bits = -1;        // key pauli_tile_bits = b: the Pauli-string kernel's tiles hold 2^b states (-1: what fills kPauliTileBytes of LDS); tests force remote groups on small problems
   int pauli_momentum_block_bits = -1;  // key pauli_momentum_block_bits = b: the same for the momentum-block kernel (-1: kPauliMomentumBlockBits)
   int pauli_momentum_full_block_bits = -1;  // key pauli_momentum_full_block_bits = b: the same for the full-space momentum-block kernel (-1: kPauliMomentumFullBlockBits)
+  int pauli_torus_block_bits = -1;  // key pauli_torus_block_bits = b: the same for the torus kernel (-1: kPauliTorusBlockBits)
   int pauli_symmetric_block_bits = -1;  // key pauli_symmetric_block_bits = b: the same for the momentum / reflection / spin-inversion kernel (-1: kPauliSymmetricBlockBits)
   int pauli_block_expand_block_bits = -1;   // key pauli_block_expand_block_bits = b: ll_pauli_block_expand's workgroups take blocks of 2^b output indices (-1: kPauliBlockExpandBlockBits, pauli_block_embed_plan.hpp); tests force several trips of the grid-stride loop
   int pauli_block_project_block_bits = -1;  // key pauli_block_project_block_bits = b: ll_pauli_block_project's take blocks of 2^b representatives (-1: kPauliBlockProjectBlockBits)
@@ -565,12 +566,19 @@ struct PauliRepImage {
 constexpr int kPauliMomentumFullBlockBits = 8;   // indices of a workgroup's block: one state per lane, as kPauliMomentumBlockBits
 constexpr int kPauliSymmetricBlockBits = kPauliMomentumFullBlockBits;  // taken over from the full-momentum kernel, unmeasured
 constexpr unsigned kPauliSymmetricRatioStride = 121;
+// PAULI_TORUS (pauli_torus.hip): an Lx x Ly torus, site (x, y) = bit x + Lx y, n_sites = Lx Ly; G = the Lx Ly translations
+// T_x^a T_y^b (code a + Lx b), parity = inversion = 0, group_size = n_sites; momentum = m_x, momentum_y = m_y;
+// phase[code] = e^(-2 pi i (m_x a Ly + m_y b Lx) / (Lx Ly)) as (re, im); ratio[R_a * kPauliTorusRatioStride + c] as PAULI_SYMMETRIC
+// (R <= |G| <= 30).  lx = ly = 0 for the two ring kinds.
+constexpr int kPauliTorusBlockBits = kPauliSymmetricBlockBits;  // the symmetric kernel's: the same search form and as many images; unmeasured
+constexpr unsigned kPauliTorusRatioStride = 32;
 struct PauliBlockImage {
   int n_sites = 0, n_down = -1, momentum = 0, parity = 0, inversion = 0, group_size = 0;
+  int lx = 0, ly = 0, momentum_y = 0;  // PAULI_TORUS only
   int64_t dim = 0;
   PauliTermImage terms;
   PauliRepImage basis;
-  DevArray<double> ratio;        // [121 * 121] (PAULI_SYMMETRIC) / [32 * 32] (PAULI_MOMENTUM_FULL)
+  DevArray<double> ratio;        // [121 * 121] (PAULI_SYMMETRIC) / [32 * 32] (PAULI_MOMENTUM_FULL, PAULI_TORUS)
   DevArray<double> phase;        // [n_sites][2]
   int64_t device_bytes() const { return terms.device_bytes() + basis.device_bytes() + ratio.bytes() + phase.bytes(); }
 };
@@ -578,7 +586,7 @@ struct PauliBlockImage {
 
 // ---------------------------------------------------------------- operator
 struct ll_operator {
-  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM, PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC } kind = CSR;
+  enum Kind { CSR, HOST_CB, DEV_CB, DENSE, STENCIL, PAULI, PAULI_SECTOR, PAULI_MOMENTUM, PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC, PAULI_TORUS } kind = CSR;
   bool is_complex = false;
   int elem_bytes = 8;  // sizeof(T): 4 float, 8 double / complex float, 16 complex double
   ll_context* ctx = nullptr;
@@ -608,10 +616,11 @@ struct ll_operator {
   ll::PauliImage pauli;              // sum of Pauli strings (kind PAULI)
   ll::PauliSectorImage pauli_sector; // the same on one S_z sector (kind PAULI_SECTOR)
   ll::PauliMomentumImage pauli_momentum;  // one momentum block of an S_z sector of a ring (kind PAULI_MOMENTUM)
-  ll::PauliBlockImage pauli_block;   // one symmetry block of a ring by a searched basis (kinds PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC)
+  ll::PauliBlockImage pauli_block;   // one symmetry block of a ring or a torus by a searched basis (kinds PAULI_MOMENTUM_FULL, PAULI_SYMMETRIC, PAULI_TORUS)
   static_assert(PAULI_SECTOR == PAULI + 1 && PAULI_MOMENTUM == PAULI + 2 && PAULI_MOMENTUM_FULL == PAULI + 3 &&
-                    PAULI_SYMMETRIC == PAULI + 4, "is_pauli: the five Pauli kinds are one range of Kind (a sixth goes inside it)");
-  static bool is_pauli(int kind) { return kind >= PAULI && kind <= PAULI_SYMMETRIC; }
+                    PAULI_SYMMETRIC == PAULI + 4 && PAULI_TORUS == PAULI + 5,
+                "is_pauli: the six Pauli kinds are one range of Kind (a seventh goes inside it)");
+  static bool is_pauli(int kind) { return kind >= PAULI && kind <= PAULI_TORUS; }
   bool is_pauli() const { return is_pauli(kind); }
   // device bytes the operator holds (the caller's borrowed arrays excluded)
   int64_t device_bytes() const {
@@ -693,6 +702,11 @@ void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t moment
 template <typename T>
 void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, int32_t momentum, int32_t parity, int32_t inversion,
                             int64_t n_terms, const ll_pauli_term* terms, ll_operator** out);
+// n = D: the block (m_x, m_y) of an Lx x Ly torus (site (x, y) = bit x + Lx y) under its Lx Ly translations — of all 2^(Lx Ly)
+// states (n_down = -1) or of the sector n_down — for an H that commutes with both one-site translations
+template <typename T>
+void create_pauli_torus(ll_context* ctx, int32_t lx, int32_t ly, int32_t n_down, int32_t mx, int32_t my, int64_t n_terms,
+                        const ll_pauli_term* terms, ll_operator** out);
 // a host callback (every one under the void* signature: same ABI, only the pointee types differ) or a device callback
 template <typename T>
 void create_cb(ll_context* ctx, int64_t n, ll_host_mv_mul_z host_fn, ll_dev_mv_mul dev_fn, void* user, ll_operator** out);
@@ -702,7 +716,7 @@ void set_op_accuracy(ll_operator* op, int accuracy);
 int op_accuracy(const ll_operator* op);
 
 // ---------------------------------------------------------------- kernel launchers
-// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_block_transfer.hip, pauli_rdm.hip, pauli_rdm_tiled.hip; everything
+// Operator kernels: op_kernels.hip (CSR-stream, column split, dense, lattice), spmv_pb.hip, spmv_tiled.hip, spmv_image_build.hip, spmv_sym.hip, pauli.hip, pauli_basis.hpp (through pauli_sector.hip, pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip, pauli_torus.hip), pauli_expect.hip, pauli_expect_block.hip, pauli_block_embed.hip, pauli_block_transfer.hip, pauli_rdm.hip, pauli_rdm_tiled.hip; everything
 // from launch_reduce_cols down: kernels.hip, except the pair form (gs_pair.hip; launch_pair_sweep_small, pair_small_fits and
 // launch_maxpy_folding: gs_small.hip) and the two-pass recurrence (launch_recur_*: recur.hip).
 // All launchers enqueue on `s` and return immediately.
@@ -793,7 +807,7 @@ int launch_stencil(const ll_operator& op, const T* x_local, const T* halo_lo, co
 template <typename T>
 int launch_pauli(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                  const ScaleIn<T>* sc = nullptr);
-// The four indexed-basis kernels (pauli_basis.hpp) take 2^b indices per workgroup block: the context's key if set (at most
+// The five indexed-basis kernels (pauli_basis.hpp) take 2^b indices per workgroup block: the context's key if set (at most
 // 2^30), else the kernel's default
 inline int pauli_block_bits(const ll_operator& op, int ll::Tuning::*key, int dflt) {
   const int forced = op.ctx ? op.ctx->tune.*key : -1;
@@ -815,7 +829,11 @@ int launch_pauli_momentum_full(const ll_operator& op, const T* x, T* y, double o
 template <typename T>
 int launch_pauli_symmetric(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
                            const ScaleIn<T>* sc = nullptr);
-template <typename T>  // whichever of the five op.kind names (pauli_operators.cpp): what Engine::apply calls
+// One translation block of a torus (op.kind == PAULI_TORUS; pauli_torus.hip): x, y hold D elements.
+template <typename T>
+int launch_pauli_torus(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s,
+                       const ScaleIn<T>* sc = nullptr);
+template <typename T>  // whichever of the six op.kind names (pauli_operators.cpp): what Engine::apply calls
 int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, double* dot_partials, hipStream_t s, const ScaleIn<T>* sc);
 // string j of a list of terms or observables (`what`): its masks below n_sites, its coefficient finite (pauli_operators.cpp)
 void check_pauli_string(const char* what, int64_t j, const ll_pauli_term& q, int n_sites);

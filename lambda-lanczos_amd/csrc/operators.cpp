@@ -344,6 +344,7 @@ const char* operator_kind_name(int kind) {
     case ll_operator::PAULI_MOMENTUM: return "a momentum block of an S_z sector";
     case ll_operator::PAULI_MOMENTUM_FULL: return "a momentum block of the full space";
     case ll_operator::PAULI_SYMMETRIC: return "a momentum / reflection / spin-inversion block";
+    case ll_operator::PAULI_TORUS: return "a translation block of a torus";
     default: return "an operator of an unknown kind";
   }
 }

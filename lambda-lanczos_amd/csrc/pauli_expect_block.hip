@@ -1,4 +1,4 @@
-// Expectation values of Pauli strings on a state of a ring's symmetry block, for gfx950 (ll_pauli_expect_block, lanczos_hip.h):
+// Expectation values of Pauli strings on a state of a ring's (or a torus's) symmetry block, for gfx950 (ll_pauli_expect_block, lanczos_hip.h):
 // the state is given by its coefficients c on the block's representatives, Psi = B c with B the block's isometry, and
 //   out = coef * Re <Psi| P |Psi> = coef * sum_a Re[ conj(c_a) (Pbar c)(a) ],      Pbar = (1 / |G|) sum_{h in G} h P h^-1
 // (nothing is divided by <c|c>): Psi transforms by a one-dimensional character of the block's group G, so P may be replaced by
@@ -19,7 +19,7 @@
 // not on where it lives, not on the slot's number or its batch: the same bits run to run.
 //
 // Bytes per sweep: (sizeof(T) + 5) D (c, reps, orbit lengths) when every gather is found in cache, plus per slot and group with
-// X != 0 what the policy's own apply gathers (pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip).  The searched
+// X != 0 what the policy's own apply gathers (pauli_momentum.hip, pauli_momentum_full.hip, pauli_symmetric.hip, pauli_torus.hip).  The searched
 // policies are bound by the rotation search's integer work and the bucket search's dependent loads, once per slot, group and
 // state — slots with equal x masks repeat it (open).
 //
@@ -36,6 +36,7 @@
 #include "pauli_momentum_partner.hpp"
 #include "pauli_shared.hpp"
 #include "pauli_symmetric_partner.hpp"
+#include "pauli_torus_partner.hpp"
 
 namespace ll {
 
@@ -141,7 +142,10 @@ int launch_pauli_expect_block_op(const ll_operator& op, int count, const ExpectB
     case ll_operator::PAULI_MOMENTUM_FULL:
       return launch_pauli_expect_block(pauli_block_bits(op, &Tuning::pauli_momentum_full_block_bits, kPauliMomentumFullBlockBits),
                                        op.pauli_block.dim, count, tb, pauli_momentum_full_partner(op.pauli_block), x, partials, s);
-    default:  // PAULI_SYMMETRIC: pauli_expect_block admits the three kinds only
+    case ll_operator::PAULI_TORUS:
+      return launch_pauli_expect_block(pauli_block_bits(op, &Tuning::pauli_torus_block_bits, kPauliTorusBlockBits),
+                                       op.pauli_block.dim, count, tb, pauli_torus_partner(op.pauli_block), x, partials, s);
+    default:  // PAULI_SYMMETRIC: pauli_expect_block admits the four kinds only
       return launch_pauli_expect_block(pauli_block_bits(op, &Tuning::pauli_symmetric_block_bits, kPauliSymmetricBlockBits),
                                        op.pauli_block.dim, count, tb, pauli_symmetric_partner(op.pauli_block), x, partials, s);
   }
@@ -157,6 +161,10 @@ void pauli_expect_block_run(ll_context* ctx, const ll_operator* op, int64_t n_ob
   grp.n_sites = bv.n_sites;
   grp.reflection = bv.parity != 0;
   grp.flip = bv.inversion != 0;
+  if (op->kind == ll_operator::PAULI_TORUS) {
+    grp.lx = op->pauli_block.lx;
+    grp.ly = op->pauli_block.ly;
+  }
   check_observables(bv.n_sites, n_obs, obs);
   const PauliExpectBlockPlan plan = pauli_expect_block_plan(grp, scalar_traits<T>::is_complex, bv.n_down >= 0, n_obs, obs, B);
   for (int64_t j = 0; j < n_obs; ++j) out[j] = 0.0;  // what the identically zero observables keep: +0.0
@@ -208,10 +216,10 @@ void pauli_expect_block(ll_context* ctx, const ll_operator* op, int64_t n_obs, c
     LL_REQUIRE(false, std::string("the operator is ") + operator_kind_name(op->kind) +
                           ": its basis is not a symmetry block; measure with ll_pauli_expect");
   LL_REQUIRE(op->kind == ll_operator::PAULI_MOMENTUM || op->kind == ll_operator::PAULI_MOMENTUM_FULL ||
-                 op->kind == ll_operator::PAULI_SYMMETRIC,
+                 op->kind == ll_operator::PAULI_SYMMETRIC || op->kind == ll_operator::PAULI_TORUS,
              std::string("the operator is ") + operator_kind_name(op->kind) +
                  ": expectation values on a symmetry block need a momentum, full-momentum or momentum / reflection / "
-                 "spin-inversion block of a sum of Pauli strings");
+                 "spin-inversion block of a sum of Pauli strings");  // (the text callers match on; a torus block is admitted too)
   if (sweeps_out) *sweeps_out = 0;
   if (n_obs == 0) return;
   for_storage_type(*op, [&](auto t) { pauli_expect_block_run<decltype(t)>(ctx, op, n_obs, obs, psi, out, sweeps_out); });

@@ -1,9 +1,11 @@
 // The host side of the matrix-free spin-1/2 family H = sum_t c_t P_t: the term tables, the checks that H commutes with what a
-// block assumes, the bases, the five create_pauli* that capi.cpp calls, and launch_pauli_op, the dispatch to the five launchers.
+// block assumes, the bases, the six create_pauli* that capi.cpp calls, and launch_pauli_op, the dispatch to the six launchers.
 #include <cmath>
+#include <thread>
 #include <utility>
 
 #include "ll_internal.hpp"
+#include "pauli_torus_plan.hpp"
 
 namespace ll {
 void check_pauli_string(const char* what, int64_t j, const ll_pauli_term& q, int n_sites) {
@@ -158,6 +160,16 @@ struct PauliInvariance {
             " does not commute with the one-site translation of the ring: shifted by one site it meets a different coefficient (an "
             "open chain, or bonds that differ); a momentum sector needs a translation-invariant H");
   }
+  // the one-site translation of an Lx x Ly torus along x (dir 0) or y (dir 1)
+  void require_torus_translation(const PauliTorus& g, int dir) const {
+    require([&](uint64_t v) { return (uint64_t)(dir == 0 ? g.tx((uint32_t)v) : g.ty((uint32_t)v)); },
+            dir == 0 ? " does not commute with T_x, the one-site translation of the torus along x (site (x, y) -> (x + 1 mod Lx, y)): "
+                       "shifted by one site along x it meets a different coefficient (open boundaries along x, bonds that differ, "
+                       "or a ring's Hamiltonian given as a torus); a translation block needs an H invariant under T_x and T_y"
+                     : " does not commute with T_y, the one-site translation of the torus along y (site (x, y) -> (x, y + 1 mod Ly)): "
+                       "shifted by one site along y it meets a different coefficient (an open cylinder, or bonds that differ); a "
+                       "translation block needs an H invariant under T_x and T_y");
+  }
   void require_reflection(int L) const {
     require([&](uint64_t v) { return ring_rev(v, L); },
             " does not commute with the reflection of the ring (site j -> n_sites - 1 - j): reflected it meets a different "
@@ -240,19 +252,25 @@ std::vector<double> momentum_ratio_table() {
   return ratio;
 }
 // phase[l] = e^(-2 pi i m l / n_sites) as (re, im), l < n_sites, exact on the axes: the table of the three momentum-block operators
-void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>& phase) {
-  for (int l = 0; l < n_sites; ++l) {
-    const int k = (int)(((int64_t)momentum * l) % n_sites);
-    const double th = 2.0 * M_PI * (double)k / (double)n_sites;
-    double c = std::cos(th), sn = -std::sin(th);
-    if (4 * k % n_sites == 0) {
-      const int quarter = 4 * k / n_sites;  // 0 .. 3
-      c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
-      sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
-    }
-    phase[2 * (size_t)l] = c;
-    phase[2 * (size_t)l + 1] = sn;
+// entry l of a table of n_sites phases: e^(-2 pi i k / n_sites), 0 <= k < n_sites
+void unit_phase_entry(int32_t n_sites, int k, int l, std::vector<double>& phase) {
+  const double th = 2.0 * M_PI * (double)k / (double)n_sites;
+  double c = std::cos(th), sn = -std::sin(th);
+  if (4 * k % n_sites == 0) {
+    const int quarter = 4 * k / n_sites;  // 0 .. 3
+    c = quarter == 0 ? 1.0 : quarter == 2 ? -1.0 : 0.0;
+    sn = quarter == 1 ? -1.0 : quarter == 3 ? 1.0 : 0.0;
   }
+  phase[2 * (size_t)l] = c;
+  phase[2 * (size_t)l + 1] = sn;
+}
+void momentum_phase_table(int32_t n_sites, int32_t momentum, std::vector<double>& phase) {
+  for (int l = 0; l < n_sites; ++l) unit_phase_entry(n_sites, (int)(((int64_t)momentum * l) % n_sites), l, phase);
+}
+// phase[code] = chi(T_x^a T_y^b) = e^(-2 pi i (m_x a Ly + m_y b Lx) / (Lx Ly)), code = a + Lx b: the table of the torus operator, by
+// the arithmetic of the ring's (with Ly = 1 or Lx = 1 the ring's bits)
+void torus_phase_table(const PauliTorus& g, int32_t mx, int32_t my, std::vector<double>& phase) {
+  for (int c = 0; c < g.sites(); ++c) unit_phase_entry(g.sites(), g.phase_num(mx, my, c), c, phase);
 }
 // The binary necklaces of n_sites bits in ascending order with their periods, by the Fredricksen-Kessler-Maiorana enumeration: a
 // string read from site n_sites - 1 down to site 0 that is the lexicographically smallest of its rotations is the smallest
@@ -346,15 +364,14 @@ RepBuckets rep_buckets(int L, const std::vector<uint32_t>& reps) {
   for (int64_t n = rb.max_bucket; n > 1; n -= n / 2) ++rb.trips;  // n -> n - n / 2
   return rb;
 }
-// The operator of either searched-basis kind from its representatives: bucket table, phases, the image and its tables on the
-// device, the allocations named "<who> ...".
+// The operator of a searched-basis kind from its representatives: bucket table, the image and its tables on the device, the
+// allocations named "<who> ...".  phase: the n_sites phases of the kind's group elements.
 template <typename T>
-void pauli_block_operator(ll_context* ctx, ll_operator::Kind kind, const PauliTables& pt, int n_sites, int n_down, int momentum,
-                          int parity, int inversion, const BlockReps& br, const std::vector<double>& ratio, const std::string& who,
-                          ll_operator** out) {
+std::unique_ptr<ll_operator> pauli_block_operator(ll_context* ctx, ll_operator::Kind kind, const PauliTables& pt, int n_sites, int n_down,
+                                                  int momentum, int parity, int inversion, const BlockReps& br,
+                                                  const std::vector<double>& ratio, const std::vector<double>& phase,
+                                                  const std::string& who) {
   const RepBuckets rb = rep_buckets(n_sites, br.reps);
-  std::vector<double> phase(2 * (size_t)n_sites);
-  momentum_phase_table(n_sites, momentum, phase);
   std::unique_ptr<ll_operator> op = pauli_operator<T>(ctx, kind, (int64_t)br.reps.size(), pt, &ll_operator::pauli_block);
   PauliBlockImage& im = op->pauli_block;
   im.n_sites = n_sites;
@@ -372,7 +389,13 @@ void pauli_block_operator(ll_context* ctx, ll_operator::Kind kind, const PauliTa
   pauli_upload(ctx, im.basis.start, rb.start, (who + " bucket table").c_str());
   pauli_upload(ctx, im.ratio, ratio, (who + " norm ratios").c_str());
   pauli_upload(ctx, im.phase, phase, (who + " phases").c_str());
-  *out = op.release();
+  return op;
+}
+// the phases of a ring's shifts
+std::vector<double> ring_phases(int n_sites, int momentum) {
+  std::vector<double> phase(2 * (size_t)n_sites);
+  momentum_phase_table(n_sites, momentum, phase);
+  return phase;
 }
 }  // namespace
 
@@ -484,8 +507,9 @@ void create_pauli_momentum_full(ll_context* ctx, int32_t n_sites, int32_t moment
   const BlockReps br = block_reps(n_sites, -1, momentum, 0, 0, "internal: a momentum block of 2^27 states or more");
   // never empty: the state 0..01 has the full period n_sites, which every m admits (n_sites = 1: m = 0, and both states have R = 1)
   LL_REQUIRE(!br.reps.empty(), "internal: an empty momentum block of the full space");
-  pauli_block_operator<T>(ctx, ll_operator::PAULI_MOMENTUM_FULL, pt, n_sites, -1, momentum, 0, 0, br, momentum_ratio_table(),
-                          "momentum block", out);
+  *out = pauli_block_operator<T>(ctx, ll_operator::PAULI_MOMENTUM_FULL, pt, n_sites, -1, momentum, 0, 0, br, momentum_ratio_table(),
+                                 ring_phases(n_sites, momentum), "momentum block")
+             .release();
 }
 
 // One block under momentum, reflection and spin inversion, of the full space or of one sector (pauli_symmetric.hip)
@@ -522,8 +546,80 @@ void create_pauli_symmetric(ll_context* ctx, int32_t n_sites, int32_t n_down, in
   for (int a = 1; a <= G; ++a)
     for (int c = 1; c <= G; ++c)
       if (G % c == 0) ratio[(size_t)a * kPauliSymmetricRatioStride + (size_t)c] = std::sqrt((double)a / (double)(G / c));
-  pauli_block_operator<T>(ctx, ll_operator::PAULI_SYMMETRIC, pt, n_sites, n_down, momentum, parity, inversion, br, ratio,
-                          "symmetry block", out);
+  *out = pauli_block_operator<T>(ctx, ll_operator::PAULI_SYMMETRIC, pt, n_sites, n_down, momentum, parity, inversion, br, ratio,
+                                 ring_phases(n_sites, momentum), "symmetry block")
+             .release();
+}
+
+// One translation block of an Lx x Ly torus, of the full space or of one sector (pauli_torus.hip).  The representatives are
+// enumerated on the host in slices of equal top bits (pauli_torus_plan.hpp), at most 16 threads, each state left at its first
+// smaller image.
+template <typename T>
+void create_pauli_torus(ll_context* ctx, int32_t lx, int32_t ly, int32_t n_down, int32_t mx, int32_t my, int64_t n_terms,
+                        const ll_pauli_term* terms, ll_operator** out) {
+  LL_REQUIRE(lx >= 1 && ly >= 1, "lx and ly must be at least 1 (the extents of the torus)");
+  LL_REQUIRE((int64_t)lx * ly <= kPauliMaxSites, "lx * ly must be at most " + std::to_string(kPauliMaxSites) +
+                                                     " (the sites of the torus: 2^(lx ly) states, 32-bit local indices)");
+  const int n_sites = lx * ly;
+  const PauliTables pt = pauli_tables<T>(ctx, n_sites, n_terms, terms, out);
+  LL_REQUIRE(n_down >= -1 && n_down <= n_sites,
+             "n_down must lie in [-1, lx * ly] (-1: the full space; else the number of flipped spins of the sector)");
+  LL_REQUIRE(mx >= 0 && mx < lx, "mx must lie in [0, lx) (the block of k_x = 2 pi mx / lx)");
+  LL_REQUIRE(my >= 0 && my < ly, "my must lie in [0, ly) (the block of k_y = 2 pi my / ly)");
+  LL_REQUIRE(scalar_traits<T>::is_complex || ((2 * mx) % lx == 0 && (2 * my) % ly == 0),
+             "a real storage type takes mx = 0 or lx / 2 and my = 0 or ly / 2 only (the other blocks are complex Hermitian); use a "
+             "complex storage type");
+  const PauliTorus g(lx, ly);
+  const PauliInvariance inv(n_terms, terms);
+  inv.require_torus_translation(g, 0);
+  inv.require_torus_translation(g, 1);
+  if (n_down >= 0) pauli_require_sz_conserving(pt, scalar_traits<T>::is_complex ? 2 : 1);
+  // slices of equal top bits, handed out in ascending order and joined in that order
+  const int top_bits = std::min(n_sites, 10), low_bits = n_sites - top_bits;
+  const uint32_t nslices = (uint32_t)1 << top_bits;
+  std::vector<std::vector<uint32_t>> slice_reps(nslices);
+  std::vector<std::vector<uint8_t>> slice_len(nslices);
+  std::atomic<uint32_t> next{0};
+  auto work = [&]() {
+    for (uint32_t q; (q = next.fetch_add(1)) < nslices;) pauli_torus_slice(g, n_down, mx, my, q, low_bits, slice_reps[q], slice_len[q]);
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const int nthreads = n_sites < 20 ? 1 : (int)std::min<unsigned>(16u, std::max<unsigned>(1u, hw));
+  {
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nthreads; ++t) pool.emplace_back(work);
+    work();
+    for (std::thread& th : pool) th.join();
+  }
+  BlockReps br;
+  br.group_size = n_sites;
+  size_t total = 0;
+  for (uint32_t q = 0; q < nslices; ++q) total += slice_reps[q].size();
+  LL_REQUIRE(total < (((size_t)1 << 27) - 1), "a block of 2^27 - 1 states or more (32-bit indices with room for the search)");
+  LL_REQUIRE(total != 0, "the block (mx " + std::to_string(mx) + ", my " + std::to_string(my) + ", n_down " + std::to_string(n_down) +
+                             ") of the " + std::to_string(lx) + " x " + std::to_string(ly) +
+                             " torus is empty: no orbit carries this character");
+  br.reps.reserve(total);
+  br.orbit_len.reserve(total);
+  for (uint32_t q = 0; q < nslices; ++q) {
+    br.reps.insert(br.reps.end(), slice_reps[q].begin(), slice_reps[q].end());
+    br.orbit_len.insert(br.orbit_len.end(), slice_len[q].begin(), slice_len[q].end());
+    std::vector<uint32_t>().swap(slice_reps[q]);
+    std::vector<uint8_t>().swap(slice_len[q]);
+  }
+  // ratio[R_a][c] = sqrt(R_a / R_b) for the orbit length R_b = |G| / c of a stabiliser of c elements
+  std::vector<double> ratio((size_t)kPauliTorusRatioStride * kPauliTorusRatioStride, 0.0);
+  for (int a = 1; a <= n_sites; ++a)
+    for (int c = 1; c <= n_sites; ++c)
+      if (n_sites % c == 0) ratio[(size_t)a * kPauliTorusRatioStride + (size_t)c] = std::sqrt((double)a / (double)(n_sites / c));
+  std::vector<double> phase(2 * (size_t)n_sites);
+  torus_phase_table(g, mx, my, phase);
+  std::unique_ptr<ll_operator> op =
+      pauli_block_operator<T>(ctx, ll_operator::PAULI_TORUS, pt, n_sites, n_down, mx, 0, 0, br, ratio, phase, "torus block");
+  op->pauli_block.lx = lx;
+  op->pauli_block.ly = ly;
+  op->pauli_block.momentum_y = my;
+  *out = op.release();
 }
 
 template <typename T>
@@ -534,6 +630,7 @@ int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, doub
     case ll_operator::PAULI_MOMENTUM: return launch_pauli_momentum<T>(op, x, y, offset, dot_partials, s, sc);
     case ll_operator::PAULI_MOMENTUM_FULL: return launch_pauli_momentum_full<T>(op, x, y, offset, dot_partials, s, sc);
     case ll_operator::PAULI_SYMMETRIC: return launch_pauli_symmetric<T>(op, x, y, offset, dot_partials, s, sc);
+    case ll_operator::PAULI_TORUS: return launch_pauli_torus<T>(op, x, y, offset, dot_partials, s, sc);
     default: LL_REQUIRE(false, "internal: not a Pauli-sum operator"); return 0;
   }
 }
@@ -545,6 +642,8 @@ int launch_pauli_op(const ll_operator& op, const T* x, T* y, double offset, doub
   template void create_pauli_momentum_full<T>(ll_context*, int32_t, int32_t, int64_t, const ll_pauli_term*, ll_operator**);    \
   template void create_pauli_symmetric<T>(ll_context*, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*, \
                                           ll_operator**);                                                                      \
+  template void create_pauli_torus<T>(ll_context*, int32_t, int32_t, int32_t, int32_t, int32_t, int64_t, const ll_pauli_term*,   \
+                                      ll_operator**);                                                                          \
   template int launch_pauli_op<T>(const ll_operator&, const T*, T*, double, double*, hipStream_t, const ScaleIn<T>*);
 LL_FOR_EACH_SCALAR(LL_INST_PAULI_OPERATORS)
 

@@ -395,7 +395,7 @@ class StencilOperator(_Operator):
 
 
 class _PauliFamily(_Operator):
-    """What the five Pauli-sum operators share: the term array and the create call, ll_op_create_pauli<kind>_<suffix>(ctx,
+    """What the Pauli-sum operators with typed entry points share: the term array and the create call, ll_op_create_pauli<kind>_<suffix>(ctx,
     *args, n_terms, terms, out).  n is what creation counted."""
 
     def _create(self, ctx, kind, dtype, terms, *args):
@@ -460,8 +460,9 @@ def pauli_expect_block(op, psi, observables, return_sweeps=False):
     op.n_local coefficients `psi` on the representatives of a symmetry block stand for (B: generators.momentum_embedding,
     full_momentum_embedding or symmetric_embedding) — Psi is never formed: every observable is averaged over the block's group
     (generators.symmetrised_strings) and measured with the gather of the operator's own apply, up to 32 per sweep over psi;
-    nothing is divided by <psi|psi>.  psi and return_sweeps as pauli_expect.  The library refuses every operator but
-    PauliMomentumOperator, PauliMomentumFullOperator and PauliSymmetricOperator."""
+    nothing is divided by <psi|psi>.  psi and return_sweeps as pauli_expect.  A PauliTorusOperator averages over the torus's
+    translations (generators.torus_embedding, torus_symmetrised_strings).  The library refuses every operator but
+    PauliMomentumOperator, PauliMomentumFullOperator, PauliSymmetricOperator and PauliTorusOperator."""
     return _pauli_expect_call("ll_pauli_expect_block", op, psi, observables, return_sweeps)
 
 
@@ -764,6 +765,32 @@ class PauliSymmetricOperator(_PauliFamily):
     transfer = PauliMomentumOperator.transfer  # exists to surface the library's refusal: semi-momentum states are not built
     reduced_density_matrix = PauliMomentumOperator.reduced_density_matrix
     reduced_density_matrix_tiled = PauliMomentumOperator.reduced_density_matrix_tiled
+
+
+class PauliTorusOperator(_PauliFamily):
+    """One translation block of an lx x ly torus (ll_op_create_pauli_torus): the operator B^H H B with
+    B = generators.torus_embedding(lx, ly, mx, my, n_down) and H the PauliOperator (n_down None) or the PauliSectorOperator (n_down)
+    of the same terms; the basis is generators.torus_basis, ascending.  Site (x, y) is bit x + lx y; 0 <= mx < lx, 0 <= my < ly;
+    the real dtypes take mx = 0 or lx / 2 and my = 0 or ly / 2 only.  H must commute with both one-site translations — creation
+    refuses one that does not, naming the direction and the term at fault — and an empty block is refused.  The image is O(n):
+    no table over the states (device_bytes <= 8 n + 192 KiB).  The library refuses expand, project, transfer and the block
+    density matrices for this kind; `expectation` measures on the block."""
+
+    def __init__(self, ctx, lx, ly, mx, my, terms, dtype=np.float64, n_down=None):
+        self.lx, self.ly, self.mx, self.my = int(lx), int(ly), int(mx), int(my)
+        self.n_sites = self.lx * self.ly
+        self.n_down = None if n_down is None else int(n_down)
+        arr, n_terms = _term_array(terms)
+        self.ctx, self.dtype = ctx, np.dtype(dtype)
+        self.row_begin, self.nnz = 0, n_terms
+        h = C.c_void_p()
+        check(lib().ll_op_create_pauli_torus(ctx.handle, ord(_suffix(self.dtype)), self.lx, self.ly,
+                                             -1 if self.n_down is None else self.n_down, self.mx, self.my, n_terms, arr, C.byref(h)))
+        self.handle = h
+        self.n = self.n_local = self.info()[0]  # n = D
+
+    inf_norm = PauliMomentumOperator.inf_norm
+    expectation = PauliMomentumOperator.expectation
 
 
 class HostOperator(_Operator):

@@ -860,6 +860,214 @@ def pauli_symmetric_csr(n_sites, m, parity, inversion, terms, dtype=np.float64, 
     return _pauli_rows(reps, terms, dtype, merge, column_of)
 
 
+# ------------------------------------------------------------------ translation blocks of an Lx x Ly torus
+# Site (x, y) is bit x + Lx y, n = Lx Ly <= 30.  T_x rotates each of the Ly fields of Lx bits left by one (site (x, y) ->
+# (x + 1 mod Lx, y)), T_y rotates the n-bit word left by Lx bits (site (x, y) -> (x, y + 1 mod Ly)).  G = {T_x^a T_y^b}, the code of
+# an element is a + Lx b, its character e^(-2 pi i (m_x a / Lx + m_y b / Ly)).  The representative of a G-orbit is its smallest
+# integer; it is in the block iff the character is 1 on its stabiliser (ll_op_create_pauli_torus).
+def _check_torus(lx, ly, mx, my, n_down):
+    lx, ly, mx, my = int(lx), int(ly), int(mx), int(my)
+    n_down = None if n_down is None or int(n_down) < 0 else int(n_down)
+    if not (lx >= 1 and ly >= 1 and lx * ly <= 30):
+        raise ValueError("need lx, ly >= 1 and lx * ly <= 30")
+    if not (0 <= mx < lx and 0 <= my < ly):
+        raise ValueError("need 0 <= mx < lx and 0 <= my < ly")
+    if n_down is not None and not 0 <= n_down <= lx * ly:
+        raise ValueError("need 0 <= n_down <= lx * ly")
+    return lx, ly, mx, my, n_down
+
+
+def _torus_tx(lx, ly, v):
+    """T_x on a state or a mask: a Python int or a uint64 array."""
+    col0 = sum(1 << (lx * y) for y in range(ly))
+    keep = ((1 << (lx * ly)) - 1) & ~col0
+    if isinstance(v, np.ndarray):
+        return ((v << np.uint64(1)) & np.uint64(keep)) | ((v >> np.uint64(lx - 1)) & np.uint64(col0))
+    return ((v << 1) & keep) | ((v >> (lx - 1)) & col0)
+
+
+def _torus_ty(lx, ly, v):
+    """T_y on a state or a mask: a Python int or a uint64 array."""
+    n = lx * ly
+    if isinstance(v, np.ndarray):
+        return ((v << np.uint64(lx)) | (v >> np.uint64(n - lx))) & np.uint64((1 << n) - 1)
+    return ((v << lx) | (v >> (n - lx))) & ((1 << n) - 1)
+
+
+def torus_bonds(lx, ly, dx, dy):
+    """The distinct unordered pairs {(x, y), (x + dx mod lx, y + dy mod ly)} of two different sites of the lx x ly torus, as
+    sorted (site, site) tuples in ascending order, site (x, y) = x + lx y.  Deduplicated: lx = 2, dx = 1 gives one bond per
+    pair, and a displacement that maps every site onto itself gives none."""
+    lx, ly = int(lx), int(ly)
+    pairs = set()
+    for y in range(ly):
+        for x in range(lx):
+            a, b = x + lx * y, (x + int(dx)) % lx + lx * ((y + int(dy)) % ly)
+            if a != b:
+                pairs.add((min(a, b), max(a, b)))
+    return sorted(pairs)
+
+
+def heisenberg_torus_terms(lx, ly, j1=1.0, j2=0.0):
+    """The J1-J2 Heisenberg model on the lx x ly torus, j1 sum S_i . S_j over the nearest-neighbour bonds (displacements (1, 0) and
+    (0, 1)) + j2 sum over the diagonal ones ((1, 1) and (1, -1)), S = sigma / 2: three strings of 0.25 J per distinct bond, as
+    heisenberg_terms; no j2 strings where j2 = 0.  Conserves S_z and commutes with both translations."""
+    terms = []
+    for J, steps in ((float(j1), ((1, 0), (0, 1))), (float(j2), ((1, 1), (1, -1)))):
+        if J == 0.0 and steps[0] == (1, 1):
+            continue
+        for a, b in sorted(set(torus_bonds(lx, ly, *steps[0])) | set(torus_bonds(lx, ly, *steps[1]))):
+            m = (1 << a) | (1 << b)
+            terms += [(m, 0, 0.25 * J), (m, m, 0.25 * J), (0, m, 0.25 * J)]
+    return terms
+
+
+def tfim_torus_terms(lx, ly, J, h):
+    """Transverse-field Ising model on the lx x ly torus, -J sum Z_i Z_j over the distinct nearest-neighbour bonds - h sum X_i
+    (Pauli matrices)."""
+    bonds = sorted(set(torus_bonds(lx, ly, 1, 0)) | set(torus_bonds(lx, ly, 0, 1)))
+    return [(0, (1 << a) | (1 << b), -float(J)) for a, b in bonds] + [(1 << j, 0, -float(h)) for j in range(int(lx) * int(ly))]
+
+
+def _torus_phases(lx, ly, mx, my):
+    """chi(T_x^a T_y^b) = e^(-2 pi i (mx a ly + my b lx) / (lx ly)) by the code a + lx b, exact where it lies on an axis; with ly = 1
+    (or lx = 1) _momentum_phases of the ring."""
+    n = lx * ly
+    code = np.arange(n, dtype=np.int64)
+    k = (mx * (code % lx) * ly + my * (code // lx) * lx) % n
+    ph = np.exp(-2j * np.pi * k / n)
+    axis = (4 * k) % n == 0
+    ph[axis] = np.array([1.0, -1j, -1.0, 1j])[(4 * k[axis]) // n]
+    return ph
+
+
+def _orbits_torus(lx, ly, states, mx, my):
+    """For every state s of `states` (uint64, closed under G): (its representative b, the code l of g with s = g b, the orbit
+    length R = |G| / |stabiliser|, whether the character is 1 on the stabiliser).  lx ly passes over the array, b outer, a inner."""
+    n = lx * ly
+    cnt = states.shape[0]
+    rep = np.full(cnt, np.uint64(1 << n), np.uint64)
+    first = np.zeros(cnt, np.int64)
+    stab = np.zeros(cnt, np.int64)
+    admitted = np.ones(cnt, bool)
+    cur = states.copy()
+    for b in range(ly):
+        for a in range(lx):   # cur = T_x^a T_y^b s
+            fixed = cur == states
+            stab += fixed
+            if (mx * a * ly + my * b * lx) % n:
+                admitted &= ~fixed
+            less = cur < rep
+            rep = np.where(less, cur, rep)
+            first = np.where(less, a + lx * b, first)
+            cur = _torus_tx(lx, ly, cur)
+        cur = _torus_ty(lx, ly, cur)
+    # s = h^-1 b with h = T_x^a T_y^b the first minimiser: the code of h^-1
+    fa, fb = first % lx, first // lx
+    return rep, (lx - fa) % lx + lx * ((ly - fb) % ly), n // stab, admitted
+
+
+def _torus_columns(lx, ly, mx, my, n_down):
+    """(states, in the block, column of each state's representative, chi(g) for s = g b, R, reps, R of the reps)."""
+    states = _symmetric_states(lx * ly, n_down)
+    rep, l, R, adm = _orbits_torus(lx, ly, states, mx, my)
+    isrep = (states == rep) & adm
+    reps = states[isrep]
+    col = np.where(adm, np.searchsorted(reps, rep), 0).astype(np.int64)
+    col = np.minimum(col, max(reps.shape[0] - 1, 0))
+    return states, adm, col, _torus_phases(lx, ly, mx, my)[l], R, reps, R[isrep]
+
+
+def torus_basis(lx, ly, mx, my, n_down=None):
+    """(representatives, orbit lengths) of the block (mx, my) of the full space (n_down None) or of the sector n_down of the
+    lx x ly torus: the representatives r (uint32, ascending) of the orbits on whose stabiliser the character is 1, and R_r (int64).
+    With ly = 1 this is symmetric_basis(lx, mx, 0, 0, n_down)."""
+    lx, ly, mx, my, n_down = _check_torus(lx, ly, mx, my, n_down)
+    _, _, _, _, _, reps, ra = _torus_columns(lx, ly, mx, my, n_down)
+    return reps.astype(np.uint32), ra
+
+
+def torus_embedding(lx, ly, mx, my, n_down=None, dense=True):
+    """B: the basis vectors |r; mx my> = N_r^(-1/2) sum_{g in G} chi(g) g |r> as the columns of a matrix over all 2^(lx ly) states
+    (n_down None) or over sector_states(lx ly, n_down) — an isometry.  A row holds at most one entry, chi(g) / sqrt(R_b) for the
+    state g b: dense=False returns (column of each row or -1, its value)."""
+    lx, ly, mx, my, n_down = _check_torus(lx, ly, mx, my, n_down)
+    states, adm, col, chi, R, reps, _ = _torus_columns(lx, ly, mx, my, n_down)
+    col = np.where(adm, col, -1)
+    val = np.where(adm, chi / np.sqrt(R.astype(np.float64)), 0.0)
+    if not dense:
+        return col, val
+    B = np.zeros((states.shape[0], reps.shape[0]), np.complex128)
+    B[np.flatnonzero(adm), col[adm]] = val[adm]
+    return B
+
+
+def torus_translation_fault(lx, ly, terms):
+    """None when H = sum of `terms` commutes with T_x and with T_y of the lx x ly torus by the rule of ll_op_create_pauli_torus
+    (coefficients of equal masks merged in list order; the masks moved by one site meet exactly the same coefficient, a missing
+    term counting as 0); else (direction "x" or "y", the number of the first term at fault), T_x checked first."""
+    lx, ly = int(lx), int(ly)
+    merged = {}
+    for x, z, c in terms:
+        merged[(int(x), int(z))] = merged.get((int(x), int(z)), 0.0) + float(c)
+    for name, move in (("x", _torus_tx), ("y", _torus_ty)):
+        for t, (x, z, _) in enumerate(terms):
+            if merged.get((move(lx, ly, int(x)), move(lx, ly, int(z))), 0.0) != merged[(int(x), int(z))]:
+                return name, t
+    return None
+
+
+def torus_symmetrised_strings(lx, ly, term):
+    """The average of the string `term` = (x_mask, z_mask[, coef]) over the lx ly translations of the torus, as a list of
+    (x_mask, z_mask, weight) sorted by x mask, then z mask: symmetrised_strings for a torus block (both masks moved by the same
+    element; no signs, so nothing cancels).  The coefficient of `term` is not in the weights."""
+    lx, ly, x, z = int(lx), int(ly), int(term[0]), int(term[1])
+    n = lx * ly
+    if not (lx >= 1 and ly >= 1 and n <= 30) or (x | z) >> n:
+        raise ValueError("need lx, ly >= 1, lx * ly <= 30 and masks below 2^(lx ly)")
+    mult = {}
+    for b in range(ly):
+        for a in range(lx):
+            mult[(x, z)] = mult.get((x, z), 0) + 1
+            x, z = _torus_tx(lx, ly, x), _torus_tx(lx, ly, z)
+        x, z = _torus_ty(lx, ly, x), _torus_ty(lx, ly, z)
+    return [(kx, kz, mult[(kx, kz)] / n) for kx, kz in sorted(mult)]
+
+
+def pauli_torus_csr(lx, ly, mx, my, terms, dtype=np.float64, n_down=None, merge=True):
+    """The block B^H H B (B = torus_embedding; H = pauli_csr, or pauli_sector_csr with n_down) as CSR over torus_basis, from the
+    gather form, in double: row a holds, per x mask X whose partner a ^ X = g b has b in the block, w(a) sqrt(R_a / R_b) chi(g) in
+    the column of b, w as in pauli_csr.  merge as in pauli_symmetric_csr (merge=False: one entry per term and state).  A real
+    dtype needs 2 mx = 0 (mod lx) and 2 my = 0 (mod ly); H must commute with both translations."""
+    lx, ly, mx, my, n_down = _check_torus(lx, ly, mx, my, n_down)
+    terms = list(terms)
+    if np.dtype(dtype).kind != "c" and ((2 * mx) % lx or (2 * my) % ly):
+        raise ValueError("a real dtype takes mx = 0 or lx / 2 and my = 0 or ly / 2 only")
+    fault = torus_translation_fault(lx, ly, terms)
+    if fault is not None:
+        t = fault[1]
+        raise ValueError("term %d (x_mask 0x%x, z_mask 0x%x) does not commute with T_%s" % (t, terms[t][0], terms[t][1], fault[0]))
+    states, adm, col, chi, R, reps, ra = _torus_columns(lx, ly, mx, my, n_down)
+    if reps.shape[0] == 0:
+        raise ValueError("the block is empty")
+    ra = ra.astype(np.float64)
+    n_sites = lx * ly
+    if n_down is not None:
+        h = (n_sites + 1) // 2
+        lo, hi = sector_rank_tables(n_sites, n_down, h)
+
+    def column_of(p):
+        if n_down is None:
+            k = p.astype(np.int64)   # the state is its own number
+            return col[k], adm[k], np.sqrt(ra / R[k]) * chi[k]
+        inside = _popcount(p) == n_down
+        q = np.where(inside, p, states[0])
+        k = lo[q & np.uint64((1 << h) - 1)].astype(np.int64) + hi[q >> np.uint64(h)]
+        return col[k], inside & adm[k], np.sqrt(ra / R[k]) * chi[k]
+
+    return _pauli_rows(reps, terms, dtype, merge, column_of)
+
+
 # ------------------------------------------------------------------ a sum of Pauli strings between two momentum blocks of a ring
 # out = B_t^H (sum_j coef_j P_j) B_s c (ll_pauli_block_transfer): B_s, B_t the embeddings of two blocks of one kind,
 #   kind "momentum"       shape = (n_sites, n_down, m)    momentum_embedding
